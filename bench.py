@@ -17,13 +17,15 @@ fast-forward of a rollout's last episode (its "tail") is part of the rollout. Th
 therefore one ROLLOUT: --rollout-steps agent steps (default 1040 = 40 episodes; the reference collects
 n_steps = 1100, train_swing.py:49-50) written in place into the rank's rollout buffer, ended by the join
 of every outstanding fast-forward, and -- with N > 1 -- the exchange of the rollout shards that the PPO
-collect boundary needs (RCCL all-gather over xGMI). `--steps K` is rounded UP to whole rollouts:
-steps_timed = rollout_steps * ceil(K / rollout_steps) (so K = 20 times 1040 steps, not 20 one-substep
-steps between two episode ends), and to as many more whole rollouts as it takes to time --min-timed-ms
-(50 ms: the replay rate of a process wanders by +-5 % over seconds and is 8 % lower during its first
-second about every second time -- hence also --settle-seconds of untimed replays first); `steps` echoes K. The episode phase is aligned (warm-up rounded up to
-whole episodes) and the line carries substeps_per_agent_step; a value whose substeps per step are not
-the workload's (within 5 %) is refused (value = null, "invalid" says why).
+collect boundary needs (RCCL all-gather over xGMI). `--steps K` is the number of agent steps timed,
+exactly: K // rollout_steps whole rollouts and, when K is not a multiple of rollout_steps, one shorter
+rollout of the remaining K % rollout_steps steps (its own captured graph, ended by its join and ONE
+all-gather); steps_timed = K and ms_per_step = timed wall-clock / K. K a multiple of 26 times whole
+SwingRacket episodes; otherwise the last episode is cut short before its fast-forward, and the expected
+substeps per agent step are those of the K steps timed. The timed steps start at an episode start from
+the state that warm-up (--warmup, rounded up to whole episodes) and one untimed rollout left, restored
+after --settle-seconds of untimed replays (a fresh process replays ~8 % slower during its first second
+about every second time), so that the same arguments give the same outputs (--dump-outputs).
 Inputs (state, synthetic U(-1,1) actions from PCG64) are resident in HBM before the timed region.
 
 Also in that line:
@@ -57,6 +59,15 @@ ALGO_BYTES = {"swing": {"read": 145, "write": 122}, "tennis": {"read": 117, "wri
 EXPECTED_SUBSTEPS = {("swing", True): None, ("swing", False): 5.09, ("tennis", True): 1.0, ("tennis", False): 1.0}
 
 
+def substeps_over(per_step, env_name, k):
+    """substeps per agent step over k agent steps from an episode start, given `per_step` over whole episodes: a SwingRacket
+    episode cut short before its 26th step has run one substep per step and no fast-forward"""
+    if env_name != "swing":
+        return per_step
+    whole = k // 26 * 26
+    return (whole * per_step + (k - whole)) / k
+
+
 def pmc_traffic(env_name, n_envs):
     """HBM bytes per launch of the step kernel from the committed rocprofv3 PMC summary
     (profiles/*_pmc_traffic.json, produced by tools/run_pmc.sh + tools/summarize_pmc.py:
@@ -78,7 +89,7 @@ def pmc_traffic(env_name, n_envs):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1040, help="agent steps to time; rounded UP to whole rollouts (see --rollout-steps)")
+    ap.add_argument("--steps", type=int, default=13520, help="agent steps to time, exactly (default: 13 rollouts): whole rollouts (see --rollout-steps) and, if K is not a multiple of them, one shorter rollout of the rest")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps after reset (default 52 SwingRacket / 1040 Tennisbot: its envs are reset together and their first episode -- every ball still in flight -- steps 12 %% faster than the steady state); rounded up to whole episodes; the captured rollout is also replayed once before the clock starts")
     ap.add_argument("--rollout-steps", type=int, default=1040, help="agent steps per rollout = per hipGraph replay, ended by the join of the fast-forwards (and the exchange); SwingRacket: a multiple of 26")
     ap.add_argument("--env", choices=["swing", "tennis"], default="swing")
@@ -97,9 +108,12 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="launch every step from the host instead of replaying one captured hipGraph per rollout")
     ap.add_argument("--fast-forward", choices=["auto", "slots", "pool"], default="auto", help="pin the pipeline's form (TbOptions.ff_defer) for A/B runs: slots = one fast-forward kernel per episode end on a side stream, pool = every episode end parked, one launch at the join; auto = the library's choice by batch size")
     ap.add_argument("--no-pipeline", action="store_true", help="run the SwingRacket fast-forward inside the step kernel instead of a side stream")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0, help="time at least this long: more whole rollouts than --steps asks for if need be (the replay rate of one process wanders by +-5 %% over seconds, tools/diag/diag_ramp.py; one 6.5 ms rollout samples that, eight average it); steps_timed reports what was timed")
     ap.add_argument("--settle-seconds", type=float, default=1.5, help="untimed replays of the rollout before the clock starts, for this long: a fresh process replays the SwingRacket graph at 645-655 M env steps/s for its first 0.6-1.3 s about every second time and at 700+ M from then on (tools/diag/diag_ramp.py); counted in warmup_run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them returned (obs, reward, done of every env; a fixed, seeded sample of the envs "
+                    "past 60 MiB) to DIR/<name>.npy: the timed steps start from the same state with the same actions in every run, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.warmup is None:
         args.warmup = 52 if args.env == "swing" else 1040
     return args
@@ -132,6 +146,7 @@ class Rollouts:
         self.graph = None
         self.use_graph = use_graph
         self.note = ""
+        self.rest, self.rest_graph = 0, None
 
     def prepare(self):
         """capture the rollout (nothing runs), then run it once untimed: RCCL's first use of each collective
@@ -218,6 +233,33 @@ class Rollouts:
             self.steps_only()
             if self.collective:
                 buf.all_gather(force=self.force)  # collect boundary: one collective
+
+    def prepare_rest(self, n):
+        """the shorter last rollout of a timed region whose K is not a multiple of T: steps [0, n) of the buffer, captured like
+        the rollout (from the same episode phase) and replayed once untimed; its exchange is ONE all-gather"""
+        self.rest = n
+        if n and self.graph is not None:
+            self.rest_graph = self.env.capture(lambda: self.buf.step_range(self.env, 0, n))
+        if n:
+            self.run_rest()
+            self.torch.cuda.synchronize(self.env.device)
+
+    def run_rest(self):
+        env, buf = self.env, self.buf
+        if self.rest_graph is not None:
+            self.rest_graph.replay()
+        else:
+            buf.step_range(env, 0, self.rest)
+            env.flush()
+        if self.collective:
+            buf.all_gather(force=self.force)
+
+    def run_steps(self, rollouts):
+        """the timed region's work: K = rollouts * T + rest agent steps"""
+        for _ in range(rollouts):
+            self.run_once()
+        if self.rest:
+            self.run_rest()
 
     def timed(self, fn, reps):
         """reps x fn() bracketed by barrier + synchronize on both sides; (wall seconds, HIP-event seconds)"""
@@ -348,6 +390,34 @@ def init_distributed(torch, dev, world, rehearsal=False, force_collective=False)
             os.environ["MASTER_PORT"] = str(int(os.environ.get("MASTER_PORT", "29500")) + 1)  # rank 0 hosted the first store itself and it still holds the port
             dist.init_process_group(backend="gloo")
         return why
+
+
+DUMP_BYTES = 60 << 20  # (+ the .npy headers: under 64 MB)
+
+
+def last_step_outputs(buf, t, torch, dist_on):
+    """what the timed path returned in its last step (slot t of the rollout buffer) to a caller: obs, reward and done of every env
+    (every rank's, in global env id order), as float32 host arrays"""
+    import numpy as np
+    mine = (buf.obs[t].cpu().numpy(), buf.rewards[t].cpu().numpy(), buf.dones[t].cpu().numpy().astype(np.float32))
+    ranks = [mine]
+    if dist_on:
+        ranks = [None] * torch.distributed.get_world_size()
+        torch.distributed.all_gather_object(ranks, mine)
+    return {name: np.concatenate([r[k] for r in ranks]) for k, name in enumerate(("obs", "reward", "done"))}
+
+
+def dump_outputs(outputs, out_dir):
+    """DIR/<name>.npy; past DUMP_BYTES a fixed, seeded sample of the envs (their ids in env_id.npy)"""
+    import numpy as np
+    n = len(outputs["reward"])
+    per_env = sum(a[0].nbytes for a in outputs.values())
+    if n * per_env > DUMP_BYTES:
+        ids = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // (per_env + 8), replace=False))
+        outputs = dict({k: a[ids] for k, a in outputs.items()}, env_id=ids.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def warm_up(env, buf, warmup, period):
@@ -625,8 +695,8 @@ def main():
     env = BatchedEnv(kind, N, device=dev, seed=args.seed, env_id_base=rank * N, params=default_params(flags=flags, **ext),
                      track_terminal_obs=False, pipeline=pipeline, options=dict(ff_defer={"auto": None, "slots": False, "pool": "all"}[args.fast_forward]))
     T_roll = -(-max(1, args.rollout_steps) // period) * period
-    rollouts = -(-max(1, args.steps) // T_roll)
-    steps_timed = rollouts * T_roll
+    rollouts, rest = divmod(args.steps, T_roll)
+    steps_timed = args.steps
     buf = RolloutBuffer(kind, T_roll, N, dev)
     fill_actions(buf.actions, args.seed + rank, torch)
     buf.bind(env)
@@ -643,14 +713,9 @@ def main():
         buf.rehearsal_total_cycles = int(fake_us * cycles_per_us)
     R = Rollouts(env, buf, torch, dist_on, not args.no_graph, max(1, args.gather_chunks), force_collective, exchange=replicas_only is None)
     R.prepare()
+    # where the timed steps start, in every run with these arguments: settle() replays for a wall-clock time, not a count
+    start = env.get_state_words()
     warmup_run += R.settle(args.settle_seconds) * T_roll + T_roll  # (+ the one untimed rollout of prepare())
-    if args.min_timed_ms > 0:  # agreed on by all ranks: the slowest rank's untimed rollout decides
-        one_t = torch.tensor([R.timed(R.run_once, 1)[0]], dtype=torch.float64, device=dev)
-        if dist_on:
-            torch.distributed.all_reduce(one_t, op=torch.distributed.ReduceOp.MAX)
-        warmup_run += T_roll
-        rollouts = max(rollouts, min(256, int(args.min_timed_ms * 1e-3 / max(float(one_t.item()), 1e-6)) + 1))
-        steps_timed = rollouts * T_roll
     exch = None
     if R.collective:  # measured apart, untimed: what the rollout and the exchange cost on their own
         seen = torch.ones(1, device=dev)
@@ -661,8 +726,12 @@ def main():
         exch = {"ranks_seen": int(seen.item()), "bytes_per_rank": int(buf.nbytes), "rollout_ms": r_wall * 1e3, "exchange_ms": x_wall * 1e3,
                 "form": "%d step-chunks, each all-gathered on a high-priority side stream while later chunks step" % R.chunks if R.chunks > 1
                         else "ONE all-gather after the rollout"}
+    R.prepare_rest(rest)
+    warmup_run += rest
+    env.set_state_words(*start)
     env.counters_reset()  # from here on the counters hold the timed steps only
-    wall, ev_s = R.timed(R.run_once, rollouts)
+    wall, ev_s = R.timed(lambda: R.run_steps(rollouts), 1)
+    outputs = last_step_outputs(buf, (steps_timed - 1) % T_roll, torch, dist_on) if args.dump_outputs else None
     gather_ok = True
     if R.collective:  # after the clock: every rank must hold every shard, starting with its own
         ok = torch.tensor([1.0 if buf.check_gathered() else 0.0], device=dev)
@@ -676,18 +745,21 @@ def main():
         # north_star's wording of the exchange -- "a single RCCL all-gather at the PPO collect boundary" -- timed the same way next
         # to the default form: the same rollouts, then ONE all-gather of the whole rollout buffer, nothing overlapped
         R1 = Rollouts(env, buf, torch, dist_on, R.use_graph, 1, force_collective, exchange=True)
+        env.set_state_words(*start)  # (the episode phase its graph is captured at)
         R1.prepare()
         x1_wall, _ = R1.timed(R1.exchange_only, 1)
         r1_wall, _ = R1.timed(R1.steps_only, 1)  # (its own graph: no marks, one fast-forward launch at the join)
+        R1.prepare_rest(rest)
+        env.set_state_words(*start)
         env.counters_reset()
-        w1, ev1_s = R1.timed(R1.run_once, rollouts)
+        w1, ev1_s = R1.timed(lambda: R1.run_steps(rollouts), 1)
         ok1 = torch.tensor([1.0 if buf.check_gathered() else 0.0], device=dev)
         w1_t = torch.tensor([w1, x1_wall, r1_wall], dtype=torch.float64, device=dev)
         if dist_on:
             torch.distributed.all_reduce(w1_t, op=torch.distributed.ReduceOp.MAX)
             torch.distributed.all_reduce(ok1, op=torch.distributed.ReduceOp.MIN)
         single = {"form": "ONE all-gather after the rollout (--gather-chunks 1)", "value": world * N * steps_timed / float(w1_t[0].item()),
-                  "exchange_ms": float(w1_t[1].item()) * 1e3, "ms_per_rollout": float(w1_t[0].item()) / rollouts * 1e3, "rollouts_timed": rollouts,
+                  "exchange_ms": float(w1_t[1].item()) * 1e3, "ms_per_rollout": float(w1_t[0].item()) * T_roll / steps_timed * 1e3, "rollouts_timed": rollouts,
                   "rollout_ms": float(w1_t[2].item()) * 1e3}
         c1 = env.counters()
         del R1
@@ -700,7 +772,7 @@ def main():
     # figures stay beside it (pick_exchange_form: only a chunked run whose shards failed their check gives way).
     picked_single = single is not None and pick_exchange_form(float(wall_t.item()), gather_ok, float(w1_t[0].item()), bool(ok1.item() > 0.5)) == "single_all_gather"
     if picked_single:
-        chunked = {"form": exch["form"], "value": world * N * steps_timed / float(wall_t.item()), "ms_per_rollout": float(wall_t.item()) / rollouts * 1e3,
+        chunked = {"form": exch["form"], "value": world * N * steps_timed / float(wall_t.item()), "ms_per_rollout": float(wall_t.item()) * T_roll / steps_timed * 1e3,
                    "rollouts_timed": rollouts, "gather_ok": gather_ok}
         wall, ev_s, c, gather_ok = w1, ev1_s, c1, True
         wall_t = w1_t[:1].clone()
@@ -720,7 +792,7 @@ def main():
         cadence = None if (args.contact_off or args.racket_ground or args.rolling_friction) else cadence_profile(args.env, N)
         sps = timed_substeps / (world * N * steps_timed)
         if exch is not None:
-            exch["exposed_exchange_ms"] = max(0.0, wall_max / rollouts * 1e3 - exch["rollout_ms"])
+            exch["exposed_exchange_ms"] = max(0.0, wall_max * T_roll / steps_timed * 1e3 - exch["rollout_ms"])
             exch["note"] = R.note
             if single is not None:
                 single["exposed_exchange_ms"] = max(0.0, single["ms_per_rollout"] - single["rollout_ms"])
@@ -741,7 +813,7 @@ def main():
             "value": world * N * steps_timed / wall_max,
             "unit": "env steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "steps_timed": steps_timed, "rollout_steps": T_roll, "rollouts_timed": rollouts, "warmup_run": warmup_run,
+            "steps_timed": steps_timed, "rollout_steps": T_roll, "rollouts_timed": rollouts, "rest_steps": rest, "warmup_run": warmup_run,
             "timed_region_ms": wall_max * 1e3,
             "ms_per_step": wall_max / steps_timed * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -769,6 +841,9 @@ def main():
                          "note": "latency-bound at this batch size, not bandwidth-bound (see sweep / DESIGN.md)"},
             "parity": parity_text(),
         }
+        if rest:
+            result["config"]["workload"] += "; then ONE rollout of the remaining %d agent steps%s" % (
+                rest, " (its last episode cut short before its fast-forward)" if kind == ENV_SWING and steps_timed % 26 else "")
         if cadence is not None:
             cw, csrc = cadence
             # launch_us (HIP events over the whole rollouts / their steps) = kernel_us + gap_us (one step launch and the gap to the next
@@ -797,14 +872,14 @@ def main():
         want = EXPECTED_SUBSTEPS.get((args.env, bool(args.racket_ground)))
         if args.contact_off or args.magnus or args.spin_max or args.rolling_friction:
             want = None  # other workloads than the headline's: reported, not judged
+        if want is not None:
+            want = substeps_over(want, args.env, steps_timed)
         if want is not None and abs(sps / want - 1.0) > 0.05:
-            invalid.append("substeps per agent step %.3f, the workload's is %.3f: the timed region did not hold whole episodes" % (sps, want))
+            invalid.append("substeps per agent step %.3f, the workload's is %.3f over %d steps: the timed region did not hold the workload" % (sps, want, steps_timed))
         if bad_states:
             invalid.append("%d env states went non-finite or left the lockstep the pipelined kernels rely on" % bad_states)
         if not gather_ok:
             invalid.append("the gathered rollout does not match the local shard")
-        if kind == ENV_SWING and steps_timed % 26:
-            invalid.append("steps_timed is not a whole number of episodes")
         if invalid:
             result["invalid"] = "; ".join(invalid)
             result["value_refused"] = result["value"]
@@ -836,14 +911,16 @@ def main():
             "substeps_per_s_1core": cb["1core"]["substeps_per_s"],
             "reference_record": reference_record() if args.env == "swing" else None,
         }
-        sps = result["substeps_per_agent_step"]
-        if kind == ENV_SWING and abs(sps / best["substeps_per_agent_step"] - 1.0) > 0.05 and result["value"] is not None:
-            result["invalid"] = "GPU leg %.3f substeps per agent step, CPU leg %.3f: not the same workload" % (sps, best["substeps_per_agent_step"])
+        sps, cpu_sps = result["substeps_per_agent_step"], substeps_over(best["substeps_per_agent_step"], args.env, steps_timed)
+        if kind == ENV_SWING and abs(sps / cpu_sps - 1.0) > 0.05 and result["value"] is not None:
+            result["invalid"] = "GPU leg %.3f substeps per agent step, CPU leg %.3f over the same %d steps: not the same workload" % (sps, cpu_sps, steps_timed)
             result["value_refused"], result["value"] = result["value"], None
     if dist_on or force_collective:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(outputs, args.dump_outputs)
         print(json.dumps(result))
 
 

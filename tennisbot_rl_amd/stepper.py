@@ -51,6 +51,10 @@ def load_library():
         raise StepperError(
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % _LIB_PATH)
+    # torch first: the library must run on torch's HIP runtime, whose device memory and streams it is handed. torch's own
+    # libraries ask for "libamdhip64.so" by that name; loaded after ours, they would map a second HIP (and HSA) runtime into
+    # the process, and one of the two then finds no device. Loaded before, our "libamdhip64.so.7" resolves to torch's copy.
+    import torch  # noqa: F401
     L = ctypes.CDLL(_LIB_PATH)
     vp, i32, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
     L.tb_abi_version.restype = i32

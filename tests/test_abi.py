@@ -5,6 +5,7 @@ import ctypes
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -73,6 +74,19 @@ def test_no_device_means_loud_failure_not_fallback(lib):
     from tennisbot_rl_amd.stepper import BatchedEnv, StepperError
     with pytest.raises(StepperError):
         BatchedEnv(ENV_SWING, 16)
+
+
+def test_one_hip_runtime_whichever_is_loaded_first(lib):
+    """load_library() before anything imported torch, then torch: the process must still hold ONE HIP runtime (two, and the
+    library's finds no device on a GPU host while torch's does). A fresh interpreter: this one may have imported torch already."""
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from tennisbot_rl_amd.stepper import load_library\n"
+            "load_library()\n"
+            "import torch\n"
+            "print(len({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}))\n" % ROOT)
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert out.stdout.split()[-1] == "1", "HIP runtimes mapped: " + out.stdout
 
 
 def test_bad_arguments_are_rejected(lib):

@@ -31,17 +31,17 @@ def test_bench_json_contract(extra):
     assert d["n_gpus"] == 1 and d["steps"] == 52 and d["warmup"] == 20 and d["vs_baseline"] is None
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["dtype"] == "f32" and d["data"] == "synthetic"
     assert "workload" in d["config"] and "model" not in d["config"] and "invalid" not in d
-    # K = 52 is rounded up to whole rollouts (whole episodes): what is timed is the headline workload whatever K says
+    # K = 52 is timed exactly (two whole episodes): the whole rollouts K holds, then one rollout of the rest
     T = d["rollout_steps"]
-    assert d["steps_timed"] == T * d["rollouts_timed"] >= 52 and T == (104 if "--rollout-steps" in extra else 1040)
+    assert d["steps_timed"] == 52 == T * d["rollouts_timed"] + d["rest_steps"] and T == (104 if "--rollout-steps" in extra else 1040)
+    assert abs(d["ms_per_step"] * 52 / d["timed_region_ms"] - 1) < 1e-9
     assert abs(d["value"] - 4096 * d["steps_timed"] / (d["ms_per_step"] * d["steps_timed"] * 1e-3)) / d["value"] < 1e-6
     swing = "tennis" not in extra
     if swing:
         # warm-up: the 20 asked for rounded up to an episode, then whole untimed rollouts (one from prepare(), the rest until
-        # --settle-seconds have passed): the timed rollout starts at an episode start, in the process's steady state
-        assert d["steps_timed"] % 26 == 0 and d["warmup_run"] >= 26 + T and (d["warmup_run"] - 26) % T == 0
+        # --settle-seconds have passed) and one untimed run of the shorter last rollout: the timed steps start at an episode start
+        assert d["steps_timed"] % 26 == 0 and d["warmup_run"] >= 26 + T + d["rest_steps"] and (d["warmup_run"] - 26 - d["rest_steps"]) % T == 0
         assert abs(d["substeps_per_agent_step"] / 5.09 - 1) < 0.05
-        assert d["timed_region_ms"] >= 5.0 or T == 104
     else:
         assert d["substeps_per_agent_step"] == 1.0
     r = d["roofline"]
@@ -197,3 +197,49 @@ def test_rccl_failure_falls_back_to_labelled_replicas(tmp_path):
                           "--master-port", str(port), str(script)], capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert out.stdout.count("replicas only:") == 2
+
+
+@pytest.mark.gpu
+def test_bench_times_exactly_k_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """--steps K times K agent steps, also when K is neither whole rollouts nor whole episodes (137 = one 104-step rollout + 33:
+    the last episode cut short before its fast-forward), and --dump-outputs writes the last timed step's outputs: the same
+    arguments, the same arrays, bit for bit, although the untimed replays before the clock (--settle-seconds) differ in number"""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = run_bench("--steps", "137", "--rollout-steps", "104", "--no-cpu-baseline", "--no-sweep", "--settle-seconds", "0.2", "--dump-outputs", str(tmp_path / str(k)))
+        assert d["steps_timed"] == 137 == 104 * d["rollouts_timed"] + d["rest_steps"] and d["rest_steps"] == 33
+        assert abs(d["ms_per_step"] * 137 / d["timed_region_ms"] - 1) < 1e-9
+        assert "invalid" not in d and abs(d["substeps_per_agent_step"] / ((130 * 5.09 + 7) / 137) - 1) < 0.05
+        runs.append({f: np.load(tmp_path / str(k) / (f + ".npy")) for f in ("obs", "reward", "done")})
+    a, b = runs
+    assert a["obs"].shape == (4096, 6) and a["reward"].shape == a["done"].shape == (4096,)
+    assert all(x.dtype == np.float32 for x in a.values()) and set(np.unique(a["done"])) <= {0.0, 1.0}
+    assert np.isfinite(a["obs"]).all() and np.isfinite(a["reward"]).all()
+    for f in a:
+        assert np.array_equal(a[f].view(np.uint32), b[f].view(np.uint32)), f
+
+
+def test_bench_dump_is_bounded_and_seeded(tmp_path, monkeypatch):
+    """--dump-outputs past the size bound: the same seeded sample of envs every time, with their ids; and the substeps a
+    SwingRacket K-step timed region must show when K cuts its last episode short"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 5000
+    out = {"obs": np.arange(n * 6, dtype=np.float32).reshape(n, 6), "reward": np.arange(n, dtype=np.float32), "done": np.zeros(n, np.float32)}
+    bench.dump_outputs(out, str(tmp_path / "all"))
+    assert np.array_equal(np.load(tmp_path / "all" / "obs.npy"), out["obs"]) and not (tmp_path / "all" / "env_id.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40 * 1000)
+    for k in range(2):
+        bench.dump_outputs(out, str(tmp_path / str(k)))
+    ids = np.load(tmp_path / "0" / "env_id.npy")
+    assert ids.dtype == np.float64 and len(ids) == 40 * 1000 // (32 + 8) and np.all(np.diff(ids) > 0)
+    assert sum(os.path.getsize(tmp_path / "0" / f) - 128 for f in os.listdir(tmp_path / "0")) <= 40 * 1000
+    for f in ("obs", "reward", "done", "env_id"):
+        assert np.array_equal(np.load(tmp_path / "0" / (f + ".npy")), np.load(tmp_path / "1" / (f + ".npy")))
+    assert np.array_equal(np.load(tmp_path / "0" / "reward.npy"), ids.astype(np.float32))
+    assert bench.substeps_over(5.09, "swing", 52) == 5.09 and bench.substeps_over(5.09, "swing", 20) == 1.0
+    assert abs(bench.substeps_over(5.09, "swing", 137) - (130 * 5.09 + 7) / 137) < 1e-12 and bench.substeps_over(1.0, "tennis", 137) == 1.0

@@ -21,7 +21,7 @@ if [ "$PART" = "a" ]; then
   cd /tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o swing4096 -- python3 $R/bench.py --no-cpu-baseline --no-sweep > $OUT/prof_swing4096.log 2>&1 || exit 1
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o swing4096_contact_off -- python3 $R/bench.py --contact-off --no-cpu-baseline --no-sweep > $OUT/prof_swing4096_contact_off.log 2>&1 || exit 1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o swing4096_racket_ground -- python3 $R/bench.py --racket-ground --no-cpu-baseline --no-sweep --settle-seconds 0.3 --min-timed-ms 0 --steps 2080 > $OUT/prof_swing4096_racket_ground.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o swing4096_racket_ground -- python3 $R/bench.py --racket-ground --no-cpu-baseline --no-sweep --settle-seconds 0.3 --steps 2080 > $OUT/prof_swing4096_racket_ground.log 2>&1 || exit 1
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o swing1m -- python3 $R/bench.py --envs-per-gpu 1048576 --rollout-steps 104 --steps 104 --no-cpu-baseline --no-sweep > $OUT/prof_swing1m.log 2>&1 || exit 1
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o tennis4096 -- python3 $R/bench.py --env tennis --no-cpu-baseline --no-sweep > $OUT/prof_tennis4096.log 2>&1 || exit 1
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o ppo_fused -- python3 $R/train_swing.py --total-timesteps 4e6 --n-steps 1040 --save /tmp/ppo_%s.pt > $OUT/prof_ppo_fused.log 2>&1 || exit 1

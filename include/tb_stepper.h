@@ -174,8 +174,8 @@ typedef struct TbOptions {
   int32_t tennis_reg_rows;  /* Tennisbot static contact rows in registers: 1 on, -1 off (auto: on) */
   int32_t swing_reg_rows;   /* the same for the pipelined SwingRacket step kernel: 1 on, -1 off (auto: on) */
   int32_t ff_lanes_per_wave; /* parked envs per wave in the first fast-forward phase, 1..64 (auto: 64 from 4096 envs on, fewer below) */
-  int32_t ff_sort;          /* order parked envs by their ball's ballistic flight estimate before the fast-forward: 1 on (auto: off --
-                             * with random actions the flight lengths are decided by events inside the loop, not by the parked state) */
+  int32_t ff_sort;          /* accepted and ignored (was: an opt-in sort of the parked envs by flight estimate, which never changed a
+                             * result and no measured workload won with) */
   int32_t ff_phases;        /* the fast-forward as 1, 2 or 3 kernels: budgeted loop, then its compacted survivors (auto: 3 from 262144 envs on, else 1; from 131072 envs on the first of several also hands over every env whose ball reaches the racket) */
   int32_t ff_defer;         /* deferred fast-forwards (SwingRacket-v0 pipeline, up to 131072 envs). A fast-forward kernel lasts as long as its
                              * slowest env, at most four run at once (one per hardware queue), and every one is a FORK in a replayed graph that
@@ -229,7 +229,9 @@ int tb_destroy(TbHandle *h);
  * parameters travel in the kernel-argument block of each launch, so a hipGraph captured earlier keeps
  * the values it was captured with: tb_params_generation() goes up by one on every tb_set_params, and a
  * caller that replays captured steps compares it with the value at capture time and recaptures when it
- * differs (tennisbot_rl_amd.stepper.StepGraph does; a stale replay is refused, never silent). */
+ * differs (tennisbot_rl_amd.stepper.StepGraph does; a stale replay is refused, never silent). A call that
+ * fails (e.g. the pool the new block asks for cannot be allocated) leaves the handle as it was: old
+ * parameters, old generation. */
 int tb_set_params(TbHandle *h, const TbParams *params, void *stream);
 int tb_params_generation(TbHandle *h);
 /* set_racket_scale (tennisbot_env.py:213-215; the curriculum callback train.py:164-176 calls it at every
@@ -448,8 +450,8 @@ int tb_diag_stream_copy(const uint32_t *src_dev, uint32_t *dst_dev, int n, int r
  * the fast-forward waves without their arithmetic (tools/diag/r03_idle_probe.py: do resident waves shorten the dispatch gap between
  * the dependent launches of a graph?). */
 int tb_diag_idle(int waves, int microseconds, int device, void *stream);
-/* Test hook: the nth device allocation inside the NEXT tb_set_pipeline(h, 1) fails with hipErrorOutOfMemory
- * (0 = off). tb_set_pipeline is all-or-nothing: after a failure the handle is as if the pipeline had never
+/* Test hook: the nth device allocation of the pipeline or its pool from now on -- tb_set_pipeline(h, 1), or the pool that
+ * tb_set_params allocates -- fails with hipErrorOutOfMemory (0 = off). tb_set_pipeline is all-or-nothing: after a failure the handle is as if the pipeline had never
  * been enabled (nothing half-allocated for a later step to park into), and a second call starts over. */
 int tb_diag_fail_alloc(int nth);
 

@@ -6,7 +6,7 @@
 // /tmp and loaded through stepper.use_library(); they are never the in-tree libtb_stepper.so.
 //
 //   -DTB_DIAG_STAMPS         s_memtime stamps: cycles per substep segment and per kernel phase, summed per
-//                            wave into g_diag_cycles[16] (tools/diag/diag_stamps*.py, diag_ff_sort.py)
+//                            wave into g_diag_cycles[16] (tools/diag/diag_stamps*.py)
 //   -DTB_DIAG_TRACE          entry / exit real-time of every step-kernel launch into g_diag_trace (tools/diag/r03_cadence_probe.py)
 //   -DTB_DIAG_CADENCE        the lean launch trace: entry / exit real-time of every step-kernel launch without any atomic
 //                            (tools/diag/r04_cadence.py: the kernel_us / gap_us of bench.py's roofline)

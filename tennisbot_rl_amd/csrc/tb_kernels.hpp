@@ -1,6 +1,6 @@
 // tb_kernels.hpp -- the HIP kernels of libtb_stepper.so (gfx950 / MI355X): kernel arguments, state rows, reset, the env logic of both
-// gym envs around tb_device.hpp's substep, and the __global__ entry points (step / rollout, fused policy rollout, fast-forward with its
-// sort, reset, init, marks, diagnostics). Included once, by tb_stepper.hip, which holds the host side (handle, launches, C ABI).
+// gym envs around tb_device.hpp's substep, and the __global__ entry points (step / rollout, fused policy rollout, fast-forward, reset,
+// init, marks, diagnostics). Included once, by tb_stepper.hip, which holds the host side (handle, launches, C ABI).
 // Everything here lives in an anonymous namespace of that one translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,7 +36,7 @@ struct KArgs {
   // pipelined fast-forward (tb_set_pipeline): a step that starts a SwingRacket fast-forward parks
   // the env's pre-loop state in a slot and resets the env; tb_ff_kernel finishes it on a side stream
   float4* ff_rec;         // [n][ff_rec<RG>()] slot: one record per env (park_env)
-  uint8_t* ff_flag;       // [n] 1 = env i is parked in the slot (null for the compacted / sorted lists: their records' own tag says so)
+  uint8_t* ff_flag;       // [n] 1 = env i is parked in the slot (null for the compacted lists: their records' own tag says so)
   int ff_lanes;           // tb_ff_kernel: parked envs per wave (a few per wave at small batch sizes)
   float4* ff_next;        // tb_ff_kernel: where envs still running when their budget is spent are compacted to (null = last phase: no budget)
   int* ff_next_count;     // ... and how many there are so far
@@ -268,8 +268,8 @@ TB_DEV void reset_env(const KArgs& A, const float4* KP, int i, EnvRegs& e) {
 }
 
 // Parked SwingRacket envs travel as ONE record each (array of structures, unlike the SoA state): the fast-forward kernel
-// hands records to lanes in another order than the env index (compacted survivors, sorted by predicted flight length, or a
-// few per wave), and a lane that fetches whole 128-byte lines wastes nothing, where a gather from the SoA rows would pull a
+// hands records to lanes in another order than the env index (compacted survivors, the pool, or a few per
+// wave), and a lane that fetches whole 128-byte lines wastes nothing, where a gather from the SoA rows would pull a
 // 32-byte sector per word. The record is 8 float4 = 128 B = one line: the env's state. The RG instantiations (racket<->court
 // contact compiled in) append the contact cache: 12 float4 = 192 B. (Until round 3 every record was 192 B: a third of the
 // fast-forward's record traffic was a cache that the default kernels never look at.)
@@ -333,10 +333,9 @@ TB_DEV void unpark_env(const float4* r, EnvRegs& e, Manifold& M, int& env_index)
 }
 // How long will this parked env's fast-forward last? The ball's flight decides (the loop ends when it touches the court
 // or the goal): vertical motion under gravity and Bullet's v (k1 + k2 |v|) drag, integrated with 4 substeps per
-// iteration until the ball's lowest point reaches the court; the iteration count is the sort key. An ESTIMATE for
-// scheduling only -- which lane computes which env never changes a result -- so the hardware's approximate square
-// root is good enough, and a ball that is struck again, rolls onto the goal or the net first just lands in a
-// neighbouring bin.
+// iteration until the ball's lowest point reaches the court; the iteration count is the estimate. It sets budgets
+// only -- which kernel finishes which env never changes a result -- so the hardware's approximate square root is good
+// enough, and a ball that is struck again, rolls onto the goal or the net first just gets a budget that is off.
 TB_DEV int predict_flight(const KParams& P, vec3 bp, vec3 bv) {
   const float dt4 = 4.0f * P.dt, z_land = (P.ground_half[2] + P.ball_radius) + P.contact_threshold;
   float z = bp.z, vz = bv.z, vh = __builtin_amdgcn_sqrtf(FMA(bv.x, bv.x, bv.y * bv.y));
@@ -923,57 +922,6 @@ __global__ void tb_mark_kernel(unsigned long long* count) {
 // tb_set_racket_scale: one stream-ordered 4-byte store into the device-resident parameter block
 __global__ void tb_poke_kernel(float* dst, float v) { *dst = v; }
 
-// Orders the parked records of a slot by predicted flight length (predict_flight), 1024 at a time: counting sort over
-// 256 bins in LDS, each thread then writes its own record to its sorted place in a second buffer, which tb_ff_kernel
-// runs over 64 records per wave. Why: the fast-forward loop's cost is set by the slowest lane of a wave and by the contact
-// paths ANY lane enters (wave votes). 64 random envs: mean flight 108 substeps, maximum ~170, every lane landing in a
-// substep of its own (one contact solve per lane, paid by the whole wave). Sorted, the lanes of a wave finish together
-// and are in the same phase of the flight. A kernel of its own (not a prologue of tb_ff_kernel) so that the fast-forward
-// waves stay independent one-wave workgroups: a workgroup's registers are only released when its LAST wave ends, and
-// sorted workgroups would hold their short-flight waves' slots idle until their longest flight has landed (measured:
-// -20 % at 1 M envs). The source record's parked flag is cleared here; results never depend on which lane runs which env.
-#define TB_FF_SORT_BLOCK 1024
-template <bool RG>
-__global__ void __launch_bounds__(TB_FF_SORT_BLOCK) tb_ff_sort_kernel(KArgs A, float4* sorted) {
-  constexpr int TB_FF_REC = ff_rec<RG>();
-  __shared__ int s_hist[256];
-  const int lane = threadIdx.x & 63;
-  const int src = blockIdx.x * TB_FF_SORT_BLOCK + threadIdx.x;
-  if (threadIdx.x < 256) s_hist[threadIdx.x] = 0;
-  float4 r[TB_FF_REC];
-#pragma unroll
-  for (int k = 0; k < TB_FF_REC; ++k) r[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  int key = 255;  // not parked / beyond the batch: behind every real flight
-  if (src < A.n) {
-    float4* g = A.ff_rec + (size_t)src * TB_FF_REC;
-#pragma unroll
-    for (int k = 0; k < TB_FF_REC; ++k) r[k] = g[k];
-    const bool parked = A.ff_flag[src] != 0;
-    r[7].z = __uint_as_float(parked ? 1u : 0u);  // in `sorted` the record's own tag says whether it is parked
-    if (parked) {
-      A.ff_flag[src] = 0;  // the copy in `sorted` is the parked one from here on
-      const int it = predict_flight(A.P, mk(r[3].y, r[3].z, r[3].w), mk(r[4].x, r[4].y, r[4].z));
-      key = it < 254 ? it : 254;
-    }
-  }
-  __syncthreads();
-  const int rank = atomicAdd(&s_hist[key], 1);
-  __syncthreads();
-  if (threadIdx.x < 64) {  // exclusive scan of the 256 bins by one wave: 4 bins per lane
-    const int c0 = s_hist[4 * lane], c1 = s_hist[4 * lane + 1], c2 = s_hist[4 * lane + 2], c3 = s_hist[4 * lane + 3];
-    const int sum = c0 + c1 + c2 + c3;
-    int inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { int o = __shfl_up(inc, off, 64); if (lane >= off) inc += o; }
-    const int base = inc - sum;
-    s_hist[4 * lane] = base; s_hist[4 * lane + 1] = base + c0; s_hist[4 * lane + 2] = base + c0 + c1; s_hist[4 * lane + 3] = base + c0 + c1 + c2;
-  }
-  __syncthreads();
-  float4* d = sorted + ((size_t)blockIdx.x * TB_FF_SORT_BLOCK + (size_t)(s_hist[key] + rank)) * TB_FF_REC;  // (the buffer is padded to whole groups)
-#pragma unroll
-  for (int k = 0; k < TB_FF_REC; ++k) d[k] = r[k];
-}
-
 // Finishes parked SwingRacket fast-forwards (side stream): same device code as the in-step loop, lane by lane.
 // What this kernel adds is lane utilisation. A wave loops until its slowest lane is done, and with random actions the
 // flights are 103 substeps for 80 % of the envs (balls that were never struck drop from the same height) but 111 at the
@@ -1087,7 +1035,7 @@ __global__ void __launch_bounds__(64, (ESC && !RG) ? 4 : 1) tb_ff_kernel(KArgs A
         else A.reward[i] = rew;
         if (A.substeps) A.substeps[i] = ns;
       }
-      if (A.ff_flag) A.ff_flag[src] = 0;  // the record is free again (lists and sorted copies are rewritten whole before their next use)
+      if (A.ff_flag) A.ff_flag[src] = 0;  // the record is free again (lists are rewritten whole before their next use)
       // the pool run: a consumed record says so itself. A region's records are expected to be rewritten whole by the next launch that
       // parks into it -- but an env that does NOT park there (the lockstep invariant broken: counters[8]) would leave this record, with
       // its destination pointer, to be run once more by the next pool run. One 4-byte store per episode end.

@@ -149,12 +149,11 @@ struct TbHandle {
   int last_slot;
   float4* d_ff_rec[TB_FF_SLOTS];  // [n][ff_rec<RG>()] parked records (park_env), allocated for TB_FF_REC_MAX
   uint8_t* d_ff_flag[TB_FF_SLOTS];  // [n] parked flags
-  float4* d_ff_sorted[TB_FF_SLOTS];  // ff_sort: the slot's records in the order tb_ff_sort_kernel gives them, padded to whole sort groups
   float4* d_ff_list[TB_FF_SLOTS][2];  // survivors of fast-forward phases 1 and 2 (worst case: every env), compacted
   int* d_ff_count[TB_FF_SLOTS];       // [2] their numbers
   int ff_phases;                      // 1 = one kernel runs every loop to its end; 2, 3 = budgeted phases + survivor kernels
   unsigned long long first_substeps;  // counters[6], the host's share: n envs x agent steps of every launch that RAN (see count_first_substeps)
-  int ff_lanes, ff_sort;          // how tb_ff_kernel hands records to lanes (TbOptions.ff_lanes_per_wave / ff_sort, or chosen from n)
+  int ff_lanes;                   // parked envs per wave of tb_ff_kernel's first phase (TbOptions.ff_lanes_per_wave, or chosen from n)
   // deferred stragglers (tb_ff_kernel<.., POOL>; TbOptions.ff_defer): one pool for all episodes between two flushes
   float4* d_pool;                 // [pool_cap + pool_slack][TB_FF_REC_MAX]
   float** d_pool_dst;             // [pool_cap + pool_slack] where each deferred env's terminal reward goes
@@ -255,31 +254,96 @@ bool extended_contacts(const KParams& kp) {
   return (kp.flags & TB_F_RACKET_GROUND) || kp.roll_racket > 0.0f || kp.roll_court > 0.0f || kp.roll_goal > 0.0f;
 }
 
+// a pool record's size in float4s under the handle's contact set: the host side of ff_rec<RG>() (allocated for TB_FF_REC_MAX)
+size_t pool_rec(const TbHandle* h) { return extended_contacts(h->kp) ? ff_rec<true>() : ff_rec<false>(); }
+
+// Kernel selectors: the instantiation that runs a launch's variant. They reach exactly the variants the launches below ask for;
+// any other is null (nothing is built for it) and its launch fails.
+using StepKernel = void (*)(const uint32_t*, const uint8_t*, const float*, const float4*, int, int, KArgs);
+using ArgsKernel = void (*)(KArgs);
+
+// tb_step_kernel<KIND, LEAN, MULTI, RG, POLICY> with the static rows in LDS; the fused policy step runs one step per launch
+template <int KIND, bool LEAN>
+StepKernel step_kernel_lds_rows(bool multi, bool rg, bool pol) {
+  if (pol) return multi ? nullptr : rg ? tb_step_kernel<KIND, LEAN, false, true, true> : tb_step_kernel<KIND, LEAN, false, false, true>;
+  if (multi) return rg ? tb_step_kernel<KIND, LEAN, true, true> : tb_step_kernel<KIND, LEAN, true, false>;
+  return rg ? tb_step_kernel<KIND, LEAN, false, true> : tb_step_kernel<KIND, LEAN, false, false>;
+}
+// ... and REGROWS (static rows in registers): never with RG; Tennisbot, and the one-step pipelined SwingRacket kernel without the policy
+StepKernel step_kernel(int kind, bool lean, bool multi, bool rg, bool pol, bool regrows) {
+  if (regrows && rg) return nullptr;
+  if (kind == TB_ENV_TENNIS) {
+    if (lean) return nullptr;
+    if (!regrows) return step_kernel_lds_rows<TB_ENV_TENNIS, false>(multi, rg, pol);
+    if (pol) return multi ? nullptr : tb_step_kernel<TB_ENV_TENNIS, false, false, false, true, true>;
+    return multi ? tb_step_kernel<TB_ENV_TENNIS, false, true, false, false, true> : tb_step_kernel<TB_ENV_TENNIS, false, false, false, false, true>;
+  }
+  if (regrows) return lean && !multi && !pol ? tb_step_kernel<TB_ENV_SWING, true, false, false, false, true> : nullptr;
+  return lean ? step_kernel_lds_rows<TB_ENV_SWING, true>(multi, rg, pol) : step_kernel_lds_rows<TB_ENV_SWING, false>(multi, rg, pol);
+}
+
+// tb_ff_kernel<RG, BIG, ESC, POOL>: ESC only as the first of a BIG fast-forward's phases; a BIG POOL only without RG
+ArgsKernel ff_kernel(bool rg, bool big, bool esc, bool pool) {
+  if (esc) return !big || pool ? nullptr : rg ? tb_ff_kernel<true, true, true> : tb_ff_kernel<false, true, true>;
+  if (pool) return rg ? (big ? nullptr : tb_ff_kernel<true, false, false, true>) : big ? tb_ff_kernel<false, true, false, true> : tb_ff_kernel<false, false, false, true>;
+  if (rg) return big ? tb_ff_kernel<true, true> : tb_ff_kernel<true, false>;
+  return big ? tb_ff_kernel<false, true> : tb_ff_kernel<false, false>;
+}
+
+// tb_policy_rollout_kernel<KIND, S, RG>: every combination (S = 1 or 3 env slices per workgroup)
+template <int KIND>
+ArgsKernel policy_rollout_kernel(int slices, bool rg) {
+  if (slices == 1) return rg ? tb_policy_rollout_kernel<KIND, 1, true> : tb_policy_rollout_kernel<KIND, 1, false>;
+  return slices == 3 ? (rg ? tb_policy_rollout_kernel<KIND, 3, true> : tb_policy_rollout_kernel<KIND, 3, false>) : nullptr;
+}
+
+// the fast-forward family's one launch: one-wave workgroups on stream q
+int launch_ff_kernel(bool rg, bool big, bool esc, bool pool, dim3 grid, size_t lds, hipStream_t q, const KArgs& k) {
+  const ArgsKernel kern = ff_kernel(rg, big, esc, pool);
+  if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_ff_kernel instantiation for this variant");
+  hipLaunchKernelGGL(kern, grid, dim3(64), lds, q, k);
+  HIP_TRY(hipGetLastError());
+  return TB_OK;
+}
+
+// Work on the side stream of `slot` forks from `s` (it runs after everything issued to `s` so far) ...
+int fork_side(TbHandle* h, int slot, hipStream_t s) {
+  HIP_TRY(hipEventRecord(h->ev_step[slot], s));
+  HIP_TRY(hipStreamWaitEvent(h->side[slot], h->ev_step[slot], 0));
+  return TB_OK;
+}
+// ... and closes with its progress-mark count, the slot's event and the bookkeeping that later launches order themselves by;
+// `term` / `substeps`: the late-written buffers that the work writes (or null)
+int close_side(TbHandle* h, int slot, const void* term, const void* substeps, hipStream_t s) {
+  hipStream_t side = h->side[slot];
+  if (h->h_marks && h->marks_on) {  // progress marks: count this fast-forward as finished, in stream order behind it
+    hipLaunchKernelGGL(tb_mark_kernel, dim3(1), dim3(1), 0, side, h->h_marks + TB_MAX_MARKS + slot);
+    HIP_TRY(hipGetLastError());
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(s, &st));
+    if (st == hipStreamCaptureStatusActive) h->ff_cap[slot]++; else h->ff_eager[slot]++;
+  }
+  HIP_TRY(hipEventRecord(h->ev_ff[slot], side));
+  h->ff_busy[slot] = 1; h->last_slot = slot; h->last_term = term; h->last_sub = substeps;
+  return TB_OK;
+}
+
 // finish the lanes parked in `slot` on that slot's side stream, ordered after everything issued to `s` so far
 // (Measured and dropped in round 3: enqueueing the fast-forward one launch LATE, so that under stream capture the next step -- not
 //  the fast-forward -- is the parking node's first successor. It does what was hoped for the chain -- all 2132 step kernels of two
 //  replays on ONE hardware queue instead of 572 / 520 / 520 / 520 -- but a replayed graph then puts every second successor on the same
 //  second queue: 79 of 82 fast-forwards in line behind each other, 209 M env steps/s instead of 700.)
 int defer_mode(const TbHandle* h);
-int launch_ff(TbHandle* h, int slot, const KArgs& a_in, const void* term, const void* substeps, hipStream_t s) {
-  KArgs a = a_in;
+int launch_ff(TbHandle* h, int slot, KArgs a, hipStream_t s) {
+  const void *term = a.term_obs, *substeps = a.substeps;
   hipStream_t side = h->side[slot];
-  // lockstep episodes (every env parks in the same launch): sorted, or a few envs per wave; without the host knowing the
+  // lockstep episodes (every env parks in the same launch): a few envs per wave; without the host knowing the
   // phase every step is followed by this kernel and nearly every record is idle: plain 64 per wave, one flag test each
-  const bool sort = h->ff_sort && h->phase_valid;
-  a.ff_lanes = sort || !h->phase_valid ? 64 : h->ff_lanes;
-  const int groups = (h->n + TB_FF_SORT_BLOCK - 1) / TB_FF_SORT_BLOCK;
-  HIP_TRY(hipEventRecord(h->ev_step[slot], s));
-  HIP_TRY(hipStreamWaitEvent(side, h->ev_step[slot], 0));
+  a.ff_lanes = h->phase_valid ? h->ff_lanes : 64;
+  if (int rc = fork_side(h, slot, s)) return rc;
   // two fast-forwards that write the same terminal-obs / substeps buffer must finish in order
   if (h->last_slot >= 0 && h->last_slot != slot && ((term && term == h->last_term) || (substeps && substeps == h->last_sub)))
     HIP_TRY(hipStreamWaitEvent(side, h->ev_ff[h->last_slot], 0));
-  if (sort) {
-    if (extended_contacts(h->kp)) hipLaunchKernelGGL(tb_ff_sort_kernel<true>, dim3((unsigned)groups), dim3(TB_FF_SORT_BLOCK), 0, side, a, h->d_ff_sorted[slot]);
-    else hipLaunchKernelGGL(tb_ff_sort_kernel<false>, dim3((unsigned)groups), dim3(TB_FF_SORT_BLOCK), 0, side, a, h->d_ff_sorted[slot]);
-    HIP_TRY(hipGetLastError());
-    a.ff_rec = h->d_ff_sorted[slot]; a.ff_flag = nullptr; a.n = groups * TB_FF_SORT_BLOCK;  // (outputs are addressed by the env index each record carries)
-  }
   // phases: budgeted loop + survivor kernels (see tb_ff_kernel). Without the host knowing the episode phase nearly every
   // record is idle: one plain kernel.
   const int phases = h->phase_valid ? h->ff_phases : 1;
@@ -287,11 +351,11 @@ int launch_ff(TbHandle* h, int slot, const KArgs& a_in, const void* term, const 
   // deferred stragglers: on request (TbOptions.ff_defer > 0), or by default with racket<->court contact, whose resting stacks run
   // to the 800-substep limit. Not with progress marks (a mark promises that the steps before it are FINAL), not with late-written
   // terminal observations / substep counts (the pool keeps one destination per record: the reward's)
-  const bool defer = h->d_pool && phases == 1 && h->phase_valid && !sort && !term && !substeps && defer_mode(h) == 1;
+  const bool defer = h->d_pool && phases == 1 && h->phase_valid && !term && !substeps && defer_mode(h) == 1;
   if (phases > 1) HIP_TRY(hipMemsetAsync(h->d_ff_count[slot], 0, 2 * sizeof(int), side));
   for (int ph = 0; ph < phases; ++ph) {
     KArgs k = a;
-    dim3 grid((unsigned)((a.n + a.ff_lanes - 1) / a.ff_lanes)), block(64);
+    dim3 grid((unsigned)((a.n + a.ff_lanes - 1) / a.ff_lanes));
     if (ph > 0) {  // survivors of phase ph: a compacted list of unknown length, walked by a fixed grid
       k.ff_rec = h->d_ff_list[slot][ph - 1]; k.ff_flag = nullptr; k.ff_src_count = h->d_ff_count[slot] + (ph - 1); k.ff_lanes = TB_PHASE_LANES;
       int g = h->n / TB_PHASE_GRID_DIV; g = g < 64 ? 64 : g;  // (1 M envs, same box: / 512 9.37, / 256 9.56, / 128 9.41, / 1024 9.19 G env steps/s)
@@ -307,30 +371,13 @@ int launch_ff(TbHandle* h, int slot, const KArgs& a_in, const void* term, const 
       k.ff_extra = h->opt.ff_defer_margin ? h->opt.ff_defer_margin : 16;
       h->pool_pending = 1;
       if (h->pool_ev_valid) HIP_TRY(hipStreamWaitEvent(side, h->ev_pool, 0));  // append behind the last pool run and its counter reset
-      if (rg) hipLaunchKernelGGL((tb_ff_kernel<true, false, false, true>), grid, block, dyn_lds(false, true, 64), side, k);
-      else hipLaunchKernelGGL((tb_ff_kernel<false, false, false, true>), grid, block, dyn_lds(false, false, 64), side, k);
-      HIP_TRY(hipGetLastError());
-      continue;
     }
-    const bool big = h->n >= 131072;
+    const bool big = !defer && h->n >= 131072;  // (the deferring kernel is the small-batch POOL instantiation at any size)
     const bool esc = big && ph == 0 && phases > 1;
     const size_t lds = esc && !rg ? sizeof(float) * 64 * TB_ROWS_LDS_TWO : dyn_lds(false, rg, 64);
-    if (esc) { if (rg) hipLaunchKernelGGL((tb_ff_kernel<true, true, true>), grid, block, lds, side, k); else hipLaunchKernelGGL((tb_ff_kernel<false, true, true>), grid, block, lds, side, k); }
-    else if (rg) { if (big) hipLaunchKernelGGL((tb_ff_kernel<true, true>), grid, block, lds, side, k); else hipLaunchKernelGGL((tb_ff_kernel<true, false>), grid, block, lds, side, k); }
-    else { if (big) hipLaunchKernelGGL((tb_ff_kernel<false, true>), grid, block, lds, side, k); else hipLaunchKernelGGL((tb_ff_kernel<false, false>), grid, block, lds, side, k); }
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_ff_kernel(rg, big, esc, defer, grid, lds, side, k)) return rc;
   }
-  HIP_TRY(hipGetLastError());
-  if (h->h_marks && h->marks_on) {  // progress marks: count this fast-forward as finished, in stream order behind it
-    hipLaunchKernelGGL(tb_mark_kernel, dim3(1), dim3(1), 0, side, h->h_marks + TB_MAX_MARKS + slot);
-    HIP_TRY(hipGetLastError());
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &st));
-    if (st == hipStreamCaptureStatusActive) h->ff_cap[slot]++; else h->ff_eager[slot]++;
-  }
-  HIP_TRY(hipEventRecord(h->ev_ff[slot], side));
-  h->ff_busy[slot] = 1; h->last_slot = slot; h->last_term = term; h->last_sub = substeps;
-  return TB_OK;
+  return close_side(h, slot, term, substeps, s);
 }
 
 // ONE launch for what the pool holds: the whole episodes parked straight into it (ff_defer = 2) that no launch has been given to yet
@@ -346,7 +393,7 @@ int run_pool(TbHandle* h, hipStream_t q) {
     const size_t first = (size_t)h->pool_run_upto * h->n;
     records = (long long)(h->pool_episodes - h->pool_run_upto) * h->n;
     k.ff_src_count = nullptr; k.n = (int)records;
-    k.ff_rec = h->d_pool + first * (rg ? TB_FF_REC_MAX : 8); k.pool_dst_in = h->d_pool_dst + first;
+    k.ff_rec = h->d_pool + first * pool_rec(h); k.pool_dst_in = h->d_pool_dst + first;
   }
   long long g = (records + 63) / 64;
   g = g < 1024 ? 1024 : g > 16384 ? 16384 : g;  // (workgroups beyond the pool's fill exit at once; grid-stride beyond 1 M records)
@@ -355,10 +402,7 @@ int run_pool(TbHandle* h, hipStream_t q) {
   // (153 VGPRs, three waves per SIMD, wave-shared outline sweep) holds them all at once, the small-batch one (188 VGPRs, two per
   // SIMD) ran them in two rounds
   const bool big = !rg && h->pool_episodes > 0 && records >= 131072;
-  if (rg) hipLaunchKernelGGL((tb_ff_kernel<true, false, false, true>), dim3((unsigned)g), dim3(64), dyn_lds(false, true, 64), q, k);
-  else if (big) hipLaunchKernelGGL((tb_ff_kernel<false, true, false, true>), dim3((unsigned)g), dim3(64), dyn_lds(false, false, 64), q, k);
-  else hipLaunchKernelGGL((tb_ff_kernel<false, false, false, true>), dim3((unsigned)g), dim3(64), dyn_lds(false, false, 64), q, k);
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch_ff_kernel(rg, big, false, true, dim3((unsigned)g), dyn_lds(false, rg, 64), q, k)) return rc;
   h->pool_run_upto = h->pool_episodes;
   return TB_OK;
 }
@@ -385,26 +429,11 @@ int run_pool_for_mark(TbHandle* h, hipStream_t s) {
   if (!(h->pool_episodes > h->pool_run_upto)) return TB_OK;
   const int slot = h->next_slot;
   h->next_slot = (slot + 1) % TB_FF_SLOTS;
-  hipStream_t side = h->side[slot];
-  HIP_TRY(hipEventRecord(h->ev_step[slot], s));
-  HIP_TRY(hipStreamWaitEvent(side, h->ev_step[slot], 0));
-  if (int rc = run_pool(h, side)) return rc;
-  if (h->h_marks && h->marks_on) {
-    hipLaunchKernelGGL(tb_mark_kernel, dim3(1), dim3(1), 0, side, h->h_marks + TB_MAX_MARKS + slot);
-    HIP_TRY(hipGetLastError());
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &st));
-    if (st == hipStreamCaptureStatusActive) h->ff_cap[slot]++; else h->ff_eager[slot]++;
-  }
-  HIP_TRY(hipEventRecord(h->ev_ff[slot], side));
-  h->ff_busy[slot] = 1; h->last_slot = slot; h->last_term = nullptr; h->last_sub = nullptr;
-  return TB_OK;
+  if (int rc = fork_side(h, slot, s)) return rc;
+  if (int rc = run_pool(h, h->side[slot])) return rc;
+  return close_side(h, slot, nullptr, nullptr, s);
 }
 
-// TbOptions.ff_defer = 2: the launch that ends the episodes parks them STRAIGHT into the pool -- region [k n, (k + 1) n) for the
-// k-th such launch since the last flush -- and no fast-forward kernel of its own follows: the pool run at the join does all of
-// them at once. Returns whether `a` was set up that way (not with progress marks / late-written outputs / a full pool: then the
-// ordinary slot + tb_ff_kernel path serves the launch).
 // What TbOptions.ff_defer = 0 (auto) means for this handle: 2 -- every episode end straight into the pool -- up to 16384 envs, where
 // the rollout is a chain of launch-bound step kernels and every fork of a replayed graph costs the CHAIN (the next step moves to
 // another hardware queue: ~10 us per episode end, and 1.7-2.8 us between all other steps instead of ~1.2 us in a graph that is one
@@ -422,22 +451,38 @@ int defer_mode(const TbHandle* h) {
   return (h->kp.flags & TB_F_RACKET_GROUND) ? 1 : 0;
 }
 
-bool park_direct(TbHandle* h, KArgs& a, const void* term, const void* substeps, hipStream_t s, int* rc) {
-  *rc = TB_OK;
-  if (!(h->d_pool && defer_mode(h) == 2 && h->phase_valid && !term && !substeps && h->pool_episodes < h->pool_cap / h->n)) return false;
-  if (h->pool_ev_valid) {  // behind the last pool run (which may have been enqueued on another stream)
-    hipError_t e = hipStreamWaitEvent(s, h->ev_pool, 0);
-    if (e != hipSuccess) { *rc = fail((int)e, "hipStreamWaitEvent(s, h->ev_pool, 0)"); return false; }
+// Where a launch that may end the episodes parks them. TbOptions.ff_defer = 2: STRAIGHT into the pool -- region [k n, (k + 1) n) for
+// the k-th such launch since the last flush -- and no fast-forward kernel of its own follows: the pool run at the join does all of
+// them at once (not with progress marks / late-written outputs / a full pool). Otherwise a slot, whose fast-forward follows the launch.
+struct Park { bool direct; int slot; };  // into the pool, or into `slot` (-1 and not direct: the launch parks nothing)
+int claim_park(TbHandle* h, bool may_park, KArgs& a, hipStream_t s, Park* p) {
+  *p = Park{false, -1};
+  if (!may_park) return TB_OK;
+  a.defer = 1;
+  if (h->d_pool && defer_mode(h) == 2 && h->phase_valid && !a.term_obs && !a.substeps && h->pool_episodes < h->pool_cap / h->n) {
+    if (h->pool_ev_valid) HIP_TRY(hipStreamWaitEvent(s, h->ev_pool, 0));  // behind the last pool run (which may have been enqueued on another stream)
+    a.ff_rec = h->d_pool + (size_t)h->pool_episodes * h->n * pool_rec(h); a.ff_flag = nullptr;
+    a.pool_dst_out = h->d_pool_dst + (size_t)h->pool_episodes * h->n;
+    p->direct = true;
+    return TB_OK;
   }
-  const size_t rec = extended_contacts(h->kp) ? TB_FF_REC_MAX : 8;
-  a.defer = 1; a.ff_rec = h->d_pool + (size_t)h->pool_episodes * h->n * rec; a.ff_flag = nullptr;
-  a.pool_dst_out = h->d_pool_dst + (size_t)h->pool_episodes * h->n;
-  return true;
-}
-int parked_direct(TbHandle* h, hipStream_t s) {
-  HIP_TRY(hipEventRecord(h->ev_direct, s));
-  h->direct_ev_valid = 1; h->pool_episodes++; h->pool_pending = 1;
+  p->slot = h->next_slot;
+  h->next_slot = (p->slot + 1) % TB_FF_SLOTS;
+  if (h->ff_busy[p->slot]) HIP_TRY(hipStreamWaitEvent(s, h->ev_ff[p->slot], 0));  // slot still in use by an older fast-forward
+  a.ff_rec = h->d_ff_rec[p->slot]; a.ff_flag = h->d_ff_flag[p->slot];
   return TB_OK;
+}
+// after the launch `a` describes: a pool region is counted (the next flush or mark runs it); a slot gets its fast-forward, which owes
+// its reward to the step that parked -- the launch's last, `reward_step_stride` elements per step
+int finish_park(TbHandle* h, const Park& p, KArgs a, size_t reward_step_stride, hipStream_t s) {
+  if (p.direct) {
+    HIP_TRY(hipEventRecord(h->ev_direct, s));
+    h->direct_ev_valid = 1; h->pool_episodes++; h->pool_pending = 1;
+    return TB_OK;
+  }
+  if (p.slot < 0) return TB_OK;
+  a.reward += (size_t)(a.T - 1) * reward_step_stride;
+  return launch_ff(h, p.slot, a, s);
 }
 
 // The substep counter's host share. Every agent step runs at least one substep of every env: n x T per launch, known to the host --
@@ -475,59 +520,25 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
   // envs were reset together; episodes are exactly 26 steps) only the 26th call can park anything, so
   // only that call is followed by tb_ff_kernel; when it does not (masked reset, injected state), every
   // call gets a slot and a (then mostly idle) tb_ff_kernel.
+  // With the phase known and not at the 26th step, every env has step_count = phase < 25 (all were reset
+  // together and every library call that could break lockstep clears phase_valid), so no lane can start a
+  // fast-forward in this launch and the lean kernel needs no slot (a.ff_rec stays null). Should the
+  // invariant ever be broken, the lane is counted in counters[8] (lockstep violations) instead of being dropped silently.
   const bool piped = (T == 1 || lean_multi) && h->pipeline && h->kind == TB_ENV_SWING && (h->kp.flags & TB_F_AUTO_RESET);
   const bool may_park = piped && (T == 1 ? (!h->phase_valid || h->phase == 25) : h->phase + T - 1 == 25);
-  int slot = -1, rc_direct = TB_OK;
-  const bool direct = may_park && park_direct(h, a, term, substeps, s, &rc_direct);
-  if (rc_direct) return rc_direct;
-  if (may_park && !direct) {
-    slot = h->next_slot;
-    h->next_slot = (slot + 1) % TB_FF_SLOTS;
-    if (h->ff_busy[slot]) HIP_TRY(hipStreamWaitEvent(s, h->ev_ff[slot], 0));  // slot still in use by an older fast-forward
-    a.defer = 1; a.ff_rec = h->d_ff_rec[slot]; a.ff_flag = h->d_ff_flag[slot];
-  }
+  Park park;
+  if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
   const bool rg = extended_contacts(h->kp);  // selects the instantiation that contains the rolling-friction rows
+  // the static contact rows in registers (h->reg_rows / swing_reg_rows, see tb_create): Tennisbot, and the one-step pipelined
+  // SwingRacket kernel without the policy
+  const bool regrows = !rg && (h->kind == TB_ENV_TENNIS ? h->reg_rows : h->swing_reg_rows && piped && T == 1 && !pol);
+  const StepKernel kern = step_kernel(h->kind, piped, T > 1, rg, pol != nullptr, regrows);
+  if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_step_kernel instantiation for this variant");
   const unsigned lanes = pol ? 64u : block.x;
-  const size_t lds_rows = dyn_lds(false, rg, lanes), lds_regs = dyn_lds(true, false, lanes);  // instantiations with the static rows in LDS / in registers
   (void)hipGetLastError();  // the check below is about THIS launch, not about whatever another library left behind
-#define TB_LAUNCH_STEP(KIND, LEAN, MULTI)                                                                      \
-  do {                                                                                                         \
-    if (pol && rg) hipLaunchKernelGGL((tb_step_kernel<KIND, LEAN, false, true, true>), grid, block, lds_rows, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);   \
-    else if (pol) hipLaunchKernelGGL((tb_step_kernel<KIND, LEAN, false, false, true>), grid, block, lds_rows, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);   \
-    else if (rg) hipLaunchKernelGGL((tb_step_kernel<KIND, LEAN, MULTI, true>), grid, block, lds_rows, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);           \
-    else hipLaunchKernelGGL((tb_step_kernel<KIND, LEAN, MULTI, false>), grid, block, lds_rows, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);                  \
-  } while (0)
-  if (T > 1) {
-    if (h->kind == TB_ENV_TENNIS) {
-      if (h->reg_rows && !pol && !rg) hipLaunchKernelGGL((tb_step_kernel<TB_ENV_TENNIS, false, true, false, false, true>), grid, block, lds_regs, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
-      else TB_LAUNCH_STEP(TB_ENV_TENNIS, false, true);
-    } else if (piped) {
-      if (!may_park) a.ff_rec = nullptr;
-      TB_LAUNCH_STEP(TB_ENV_SWING, true, true);
-    } else TB_LAUNCH_STEP(TB_ENV_SWING, false, true);
-  } else if (h->kind == TB_ENV_TENNIS) {
-    if (h->reg_rows && !rg && pol) hipLaunchKernelGGL((tb_step_kernel<TB_ENV_TENNIS, false, false, false, true, true>), grid, block, lds_regs, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
-    else if (h->reg_rows && !rg) hipLaunchKernelGGL((tb_step_kernel<TB_ENV_TENNIS, false, false, false, false, true>), grid, block, lds_regs, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
-    else TB_LAUNCH_STEP(TB_ENV_TENNIS, false, false);
-  } else if (piped && h->swing_reg_rows && !pol && !rg) {
-    if (!may_park) a.ff_rec = nullptr;  // (see the comment of the next branch but one)
-    hipLaunchKernelGGL((tb_step_kernel<TB_ENV_SWING, true, false, false, false, true>), grid, block, lds_regs, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
-  } else if (may_park) TB_LAUNCH_STEP(TB_ENV_SWING, true, false);
-  else if (piped) {
-    // phase known and not the 26th step: every env has step_count = phase < 25 (all were reset
-    // together and every library call that could break lockstep clears phase_valid), so no lane
-    // can start a fast-forward in this launch and the lean kernel needs no slot. Should the
-    // invariant ever be broken, the lane is counted in counters[8] (lockstep violations) instead of being dropped silently.
-    a.ff_rec = nullptr;
-    TB_LAUNCH_STEP(TB_ENV_SWING, true, false);
-  } else TB_LAUNCH_STEP(TB_ENV_SWING, false, false);
-#undef TB_LAUNCH_STEP
+  hipLaunchKernelGGL(kern, grid, block, dyn_lds(regrows, rg, lanes), s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
   HIP_TRY(hipGetLastError());
-  if (direct) { if (int rc = parked_direct(h, s)) return rc; }
-  else if (may_park) {
-    if (T > 1) a.reward = reward + (size_t)(T - 1) * h->n;  // the fast-forward owes its reward to the step that parked: the last one
-    if (int rc = launch_ff(h, slot, a, term, substeps, s)) return rc;
-  }
+  if (int rc = finish_park(h, park, a, h->n, s)) return rc;
   if (h->phase_valid) h->phase = (h->phase + T) % 26;
   return TB_OK;
 }
@@ -543,36 +554,20 @@ int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, f
   a.st_act = st[0]; a.st_raw = st[1]; a.st_logp = st[2]; a.st_val = st[3]; a.st_obs = st[4]; a.st_rew = st[5]; a.st_done = st[6];
   const bool swing = h->kind == TB_ENV_SWING;
   const bool may_park = swing && h->phase + T - 1 == 25;  // (the caller checked pipeline, lockstep phase and phase + T <= 26)
-  int slot = -1, rc_direct = TB_OK;
-  const bool direct = may_park && park_direct(h, a, nullptr, nullptr, s, &rc_direct);
-  if (rc_direct) return rc_direct;
-  if (may_park && !direct) {
-    slot = h->next_slot;
-    h->next_slot = (slot + 1) % TB_FF_SLOTS;
-    if (h->ff_busy[slot]) HIP_TRY(hipStreamWaitEvent(s, h->ev_ff[slot], 0));
-    a.defer = 1; a.ff_rec = h->d_ff_rec[slot]; a.ff_flag = h->d_ff_flag[slot];
-  }
+  Park park;
+  if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
   // 16 envs per workgroup (3 waves) while every workgroup still gets a CU of its own, else 48 (7 waves): see the kernel
   const bool narrow = h->opt.policy_slices ? h->opt.policy_slices == 1 : h->n <= 4096;
   const int E = narrow ? TB_POLICY_SLICE : 3 * TB_POLICY_SLICE;
   dim3 grid((unsigned)((h->n + E - 1) / E)), block(narrow ? 192 : 448);
-  (void)hipGetLastError();
   const bool rg = extended_contacts(h->kp);
-  const size_t lds = dyn_lds(!swing, rg, 64);  // the env wave's columns: static rows (SwingRacket) + the racket<->court cache (RG)
-#define TB_LAUNCH_PR(KIND, SL)                                                                                 \
-  do {                                                                                                         \
-    if (rg) hipLaunchKernelGGL((tb_policy_rollout_kernel<KIND, SL, true>), grid, block, lds, s, a);            \
-    else hipLaunchKernelGGL((tb_policy_rollout_kernel<KIND, SL, false>), grid, block, lds, s, a);              \
-  } while (0)
-  if (swing) { if (narrow) TB_LAUNCH_PR(TB_ENV_SWING, 1); else TB_LAUNCH_PR(TB_ENV_SWING, 3); }
-  else { if (narrow) TB_LAUNCH_PR(TB_ENV_TENNIS, 1); else TB_LAUNCH_PR(TB_ENV_TENNIS, 3); }
-#undef TB_LAUNCH_PR
+  const ArgsKernel kern = swing ? policy_rollout_kernel<TB_ENV_SWING>(narrow ? 1 : 3, rg) : policy_rollout_kernel<TB_ENV_TENNIS>(narrow ? 1 : 3, rg);
+  if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_rollout_kernel instantiation for this variant");
+  (void)hipGetLastError();
+  // dynamic LDS: the env wave's columns -- static rows (SwingRacket) + the racket<->court cache (RG)
+  hipLaunchKernelGGL(kern, grid, block, dyn_lds(!swing, rg, 64), s, a);
   HIP_TRY(hipGetLastError());
-  if (direct) { if (int rc = parked_direct(h, s)) return rc; }
-  else if (may_park) {
-    a.reward = reward + (size_t)(T - 1) * st[5];  // the fast-forward owes its reward to the step that parked: the last one
-    if (int rc = launch_ff(h, slot, a, nullptr, nullptr, s)) return rc;
-  }
+  if (int rc = finish_park(h, park, a, st[5], s)) return rc;
   if (h->phase_valid) h->phase = (h->phase + T) % 26;
   return TB_OK;
 }
@@ -625,11 +620,9 @@ int tb_create(const TbParams* params, const TbOptions* options, int env_kind, in
   // (with the unpacked build of round 3 the register-row step kernel is 154 VGPRs, three waves per SIMD: it wins at every size now --
   //  131072 envs 8.13 against 7.68 G env steps/s, 262144: 8.35 / 8.21, 1 M: 11.64 / 11.11; until then it was chosen up to 131072 envs)
   h->swing_reg_rows = env_kind == TB_ENV_SWING && (opt.swing_reg_rows ? opt.swing_reg_rows > 0 : 1);
-  // fast-forward: sort the lanes of large batches by predicted flight length; below 4096 envs a few envs per wave
-  h->ff_sort = opt.ff_sort > 0;  // opt-in: pays when flight lengths can be told from the parked state (a trained policy's struck balls)
   // measured on one box: 3 phases +11 % at 1 M envs, +-0 at 256 K, -16 % at 32 K and 4096 (two more kernels in every episode's chain)
   h->ff_phases = opt.ff_phases >= 1 && opt.ff_phases <= 3 ? opt.ff_phases : (n_envs >= 262144 ? 3 : 1);
-  h->ff_lanes = opt.ff_lanes_per_wave;
+  h->ff_lanes = opt.ff_lanes_per_wave;  // fast-forward: 64 envs per wave from 4096 envs on, a few per wave below
   if (!h->ff_lanes) { h->ff_lanes = 4; while (h->ff_lanes < 64 && (long long)h->ff_lanes * 64 < n_envs) h->ff_lanes <<= 1; }
   const int nw = words_of(env_kind);
   hipError_t err;
@@ -678,21 +671,20 @@ static void release_pipeline(TbHandle* h) {
   for (int k = 0; k < TB_FF_SLOTS; ++k) {
     if (h->d_ff_rec[k]) (void)hipFree(h->d_ff_rec[k]);
     if (h->d_ff_flag[k]) (void)hipFree(h->d_ff_flag[k]);
-    if (h->d_ff_sorted[k]) (void)hipFree(h->d_ff_sorted[k]);
     if (h->d_ff_list[k][0]) (void)hipFree(h->d_ff_list[k][0]);
     if (h->d_ff_list[k][1]) (void)hipFree(h->d_ff_list[k][1]);
     if (h->d_ff_count[k]) (void)hipFree(h->d_ff_count[k]);
     if (h->ev_step[k]) (void)hipEventDestroy(h->ev_step[k]);
     if (h->ev_ff[k]) (void)hipEventDestroy(h->ev_ff[k]);
     if (h->side[k]) (void)hipStreamDestroy(h->side[k]);
-    h->d_ff_rec[k] = nullptr; h->d_ff_flag[k] = nullptr; h->d_ff_sorted[k] = nullptr; h->d_ff_list[k][0] = nullptr; h->d_ff_list[k][1] = nullptr;
+    h->d_ff_rec[k] = nullptr; h->d_ff_flag[k] = nullptr; h->d_ff_list[k][0] = nullptr; h->d_ff_list[k][1] = nullptr;
     h->d_ff_count[k] = nullptr; h->ev_step[k] = nullptr; h->ev_ff[k] = nullptr; h->side[k] = nullptr; h->ff_busy[k] = 0;
   }
   release_pool(h);
   h->pipeline = 0;
 }
 
-// test hook (tb_diag_fail_alloc): the n-th device allocation of the next tb_set_pipeline fails with hipErrorOutOfMemory
+// test hook (tb_diag_fail_alloc): the n-th device allocation of the pipeline or the pool (tb_set_pipeline, tb_set_params) fails with hipErrorOutOfMemory
 static int g_fail_alloc_countdown = 0;
 static hipError_t pipeline_malloc(void** p, size_t bytes) {
   if (g_fail_alloc_countdown > 0 && --g_fail_alloc_countdown == 0) { *p = nullptr; return hipErrorOutOfMemory; }
@@ -702,12 +694,12 @@ static hipError_t pipeline_malloc(void** p, size_t bytes) {
 // The pool (TbOptions.ff_defer): 64 n records (two reference-sized rollouts of 1100 steps with EVERY episode end in it) + the slack
 // all resident fast-forward waves could overshoot it by (slots x n), 192 B each + an 8-byte destination pointer: 14 KB per env.
 // Allocated only for handles whose defer_mode can be non-zero: on request, up to 16384 envs, or above that (to 131072) once the
-// parameter block turns racket<->court contact on -- tb_set_params calls this again. (Until round 4 every pipelined handle up
+// parameter block turns racket<->court contact on -- tb_set_params asks again, with the new flags, before it commits them. (Until round 4 every pipelined handle up
 // to 131072 envs got one: 1.9 GB at that size that the default kernels never touched.) Zeroed: a record's tag word says whether
 // it holds a parked env, and no launch may ever find a tag it did not write.
-static bool pool_wanted(const TbHandle* h) {
+static bool pool_wanted(const TbHandle* h, uint32_t flags) {
   if (h->n > TB_DEFER_MAX_ENVS || h->opt.ff_defer < 0) return false;
-  return h->opt.ff_defer > 0 || h->n <= 16384 || (h->kp.flags & TB_F_RACKET_GROUND);
+  return h->opt.ff_defer > 0 || h->n <= 16384 || (flags & TB_F_RACKET_GROUND);
 }
 static void release_pool(TbHandle* h) {
   if (h->d_pool) (void)hipFree(h->d_pool);
@@ -729,8 +721,8 @@ static int alloc_pool_parts(TbHandle* h, float4** pool, float*** dst, int** coun
   HIP_TRY(hipEventCreateWithFlags(ev_direct, hipEventDisableTiming));
   return TB_OK;
 }
-static int alloc_pool(TbHandle* h) {  // all of it or none: defer_mode takes a non-null d_pool for a usable pool
-  if (h->d_pool || !pool_wanted(h)) return TB_OK;
+static int alloc_pool(TbHandle* h, uint32_t flags) {  // all of it or none: defer_mode takes a non-null d_pool for a usable pool
+  if (h->d_pool || !pool_wanted(h, flags)) return TB_OK;
   const size_t recs = (size_t)64 * h->n + (size_t)TB_FF_SLOTS * h->n;
   float4* pool = nullptr; float** dst = nullptr; int* count = nullptr; hipEvent_t e1 = nullptr, e2 = nullptr;
   if (int rc = alloc_pool_parts(h, &pool, &dst, &count, &e1, &e2, recs)) {
@@ -757,15 +749,10 @@ static int alloc_pipeline(TbHandle* h) {
     for (int ph = 0; ph + 1 < h->ff_phases; ++ph) HIP_TRY(pipeline_malloc((void**)&h->d_ff_list[k][ph], wb));
     HIP_TRY(pipeline_malloc((void**)&h->d_ff_count[k], 2 * sizeof(int)));
     HIP_TRY(hipMemset(h->d_ff_count[k], 0, 2 * sizeof(int)));
-    if (h->ff_sort) {
-      const size_t sb = sizeof(float4) * (size_t)TB_FF_REC_MAX * TB_FF_SORT_BLOCK * ((h->n + TB_FF_SORT_BLOCK - 1) / TB_FF_SORT_BLOCK);
-      HIP_TRY(pipeline_malloc((void**)&h->d_ff_sorted[k], sb));
-      HIP_TRY(hipMemset(h->d_ff_sorted[k], 0, sb));
-    }
     HIP_TRY(hipEventCreateWithFlags(&h->ev_step[k], hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_ff[k], hipEventDisableTiming));
   }
-  if (int rc = alloc_pool(h)) return rc;
+  if (int rc = alloc_pool(h, h->kp.flags)) return rc;
   HIP_TRY(hipDeviceSynchronize());
   return TB_OK;
 }
@@ -854,7 +841,7 @@ int tb_pipeline_form(TbHandle* h) {
   if (!h) return fail(TB_E_INVAL, "tb_pipeline_form: null handle");
   if (h->kind != TB_ENV_SWING || !h->pipeline) return 0;
   const int mode = defer_mode(h);
-  return mode == 2 ? 3 : mode == 1 && h->ff_phases == 1 && !h->ff_sort ? 2 : 1;
+  return mode == 2 ? 3 : mode == 1 && h->ff_phases == 1 ? 2 : 1;
 }
 
 int tb_phase_advance(TbHandle* h, int n_steps) {
@@ -929,15 +916,24 @@ int tb_set_params(TbHandle* h, const TbParams* params, void* stream) {
   // the staging buffer may still feed an earlier async copy on another stream: settle it first
   if (int rc = flush_all(h, s)) return rc;
   HIP_TRY(hipStreamSynchronize(s));
+  KParams kp = h->kp;  // (what to_kparams leaves alone stays as it was)
+  float planes[TB_N_CULL][3];
+  to_kparams(params, &kp, &planes[0][0]);
+  // Nothing in flight and nothing parked from here on. The pool first, so that a failure leaves the handle as it was: a pipelined
+  // handle whose new parameter block asks for one (racket<->court contact above 16384 envs) gets it now; one that has it and
+  // switches the contact set, and with it the record stride (pool_rec), starts from a zeroed pool -- no tag word of one stride can
+  // land on the payload of a record of the other.
+  if (h->side[0] && !h->d_pool) {
+    if (int rc = alloc_pool(h, params->flags)) { (void)hipGetLastError(); return rc; }
+    HIP_TRY(hipDeviceSynchronize());
+  } else if (h->d_pool && extended_contacts(kp) != extended_contacts(h->kp)) {
+    HIP_TRY(hipMemsetAsync(h->d_pool, 0, sizeof(float4) * (size_t)TB_FF_REC_MAX * (h->pool_cap + h->pool_slack), s));
+  }
   if ((params->flags ^ h->params.flags) & TB_F_AUTO_RESET) h->phase_valid = 0;  // episodes may stop / start restarting
-  h->params = *params;
-  to_kparams(params, &h->kp, &h->cull_planes[0][0]);
+  h->params = *params; h->kp = kp;
+  memcpy(h->cull_planes, planes, sizeof planes);
   if (int rc = upload_hull(h, s)) return rc;
   HIP_TRY(hipStreamSynchronize(s));
-  if (h->side[0]) {  // a pipelined handle whose new parameter block asks for the pool (racket<->court contact above 16384 envs)
-    if (int rc = alloc_pool(h)) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-  }
   h->params_generation++;
   return TB_OK;
 }
@@ -967,8 +963,7 @@ int tb_reset(TbHandle* h, const uint8_t* mask_dev, float* obs_dev, void* stream)
   KArgs a = base_args(h);
   a.mask = mask_dev; a.obs = obs_dev;
   dim3 grid((unsigned)((h->n + 255) / 256)), block(256);
-  if (h->kind == TB_ENV_SWING) hipLaunchKernelGGL(tb_reset_kernel<TB_ENV_SWING>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(tb_reset_kernel<TB_ENV_TENNIS>, grid, block, 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(h->kind == TB_ENV_SWING ? tb_reset_kernel<TB_ENV_SWING> : tb_reset_kernel<TB_ENV_TENNIS>, grid, block, 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return TB_OK;
 }

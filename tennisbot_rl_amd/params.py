@@ -89,7 +89,7 @@ class TbOptions(ctypes.Structure):
 
 def make_options(block=0, tennis_reg_rows=None, swing_reg_rows=None, ff_lanes_per_wave=0, ff_sort=None, ff_phases=0, policy_slices=0, ff_defer=None, ff_defer_margin=0,
                  ff_seal=None):
-    """None = auto; True / False force a variant on / off"""
+    """None = auto; True / False force a variant on / off (ff_sort: accepted and ignored, the sort was removed)"""
     def tri(x):
         return 0 if x is None else (1 if x else -1)
     o = TbOptions()

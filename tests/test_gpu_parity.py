@@ -494,7 +494,7 @@ def test_randomised_engine_parameters_stay_bit_exact(torch, kind):
 @pytest.mark.parametrize("kind,steps,piped,options,flags", [
     (ENV_SWING, 30, False, None, F_DEFAULT), (ENV_SWING, 30, True, None, F_DEFAULT), (ENV_TENNIS, 120, False, None, F_DEFAULT),
     (ENV_SWING, 30, True, dict(ff_phases=3), F_DEFAULT), (ENV_SWING, 30, True, dict(ff_phases=2), F_DEFAULT | F_RACKET_GROUND),
-    (ENV_SWING, 30, True, dict(ff_phases=3, ff_sort=True, ff_lanes_per_wave=16), F_DEFAULT),
+    (ENV_SWING, 30, True, dict(ff_phases=3, ff_lanes_per_wave=16), F_DEFAULT),
     (ENV_SWING, 30, True, dict(swing_reg_rows=False), F_DEFAULT)])  # (the step kernel with its static rows in LDS: the automatic choice until round 3's build flags)
 def test_large_batch_instantiations_in_lockstep_with_the_oracle(torch, kind, steps, piped, options, flags):
     """above 131 072 envs tb_create picks other launch shapes and kernel variants (128-thread workgroups, the fast-forward
@@ -660,15 +660,16 @@ def test_float32_drift_vs_float64_truth(torch):
 
 @pytest.mark.parametrize("n,reg_rows,ff", [(4096, True, {}), (1000, True, {}), (1000, False, {}),
                                            (1000, None, dict(ff_lanes_per_wave=1)), (1000, None, dict(ff_lanes_per_wave=7)), (4096, None, dict(ff_lanes_per_wave=64, ff_sort=False)),
-                                           (1000, None, dict(ff_sort=True)), (4096, None, dict(ff_sort=True, ff_phases=2)), (40000, None, {}),
-                                           (4096, None, dict(ff_phases=1)), (4096, None, dict(ff_phases=2)), (70000, None, dict(ff_phases=3, ff_sort=True))])
+                                           (1000, None, dict(ff_sort=True)), (4096, None, dict(ff_phases=2, ff_lanes_per_wave=16)), (40000, None, {}),
+                                           (4096, None, dict(ff_phases=1)), (4096, None, dict(ff_phases=2)), (70000, None, dict(ff_phases=3))])
 def test_pipelined_fast_forward_is_bit_identical(torch, n, reg_rows, ff):
     """tb_set_pipeline: the fast-forward runs on a side stream and writes the terminal step's
     reward late; after flush() every output equals the unpipelined path bit for bit (both builds
     of the pipelined step kernel: static contact rows in registers, as small batches run it, and in
-    scratch; every way tb_ff_kernel hands parked envs to lanes, TbOptions.ff_lanes_per_wave / ff_sort:
-    1, 7 or 64 per wave, sorted by predicted flight length in 1024-env groups; the loop in one kernel or cut into
-    budgeted phases whose survivors are compacted for the next kernel, TbOptions.ff_phases)"""
+    scratch; every way tb_ff_kernel hands parked envs to lanes, TbOptions.ff_lanes_per_wave: 1, 7, 16 or 64 per
+    wave; the loop in one kernel or cut into budgeted phases whose survivors are compacted for the next kernel,
+    TbOptions.ff_phases). TbOptions.ff_sort is accepted and ignored since the sort of parked envs was removed: setting
+    it changes nothing."""
     from tennisbot_rl_amd.rollout import RolloutBuffer
     from tennisbot_rl_amd.stepper import BatchedEnv
     T = 26 * 4 + 7
@@ -1440,6 +1441,49 @@ def test_nonfinite_states_are_counted_like_the_oracle_counts_them(torch, kind):
         got, want = env.counters(), [int(x) for x in ref.counters()]
         assert list(got.values()) == want, (t, got, want)
     assert got["nonfinite_states"] >= poisoned  # (every poisoned env is still non-finite one step later: counted in both steps)
+    env.close()
+
+
+def test_set_params_failure_leaves_the_handle_as_it_was(torch):
+    """tb_set_params allocates the pool that the new parameter block asks for (racket<->court contact above 16384 envs) BEFORE it
+    commits anything: when that allocation fails the handle keeps its parameters, their generation and its pipeline form, and
+    steps on under the OLD parameters in lockstep with the oracle; the same call then succeeds. (the new parameters
+    used to be live already, so a graph captured under the old ones still passed StepGraph.valid().)"""
+    from tennisbot_rl_amd.stepper import BatchedEnv, StepperError
+    n = 20000
+    env = BatchedEnv(ENV_SWING, n, device="cuda:0", seed=4, pipeline=True, track_terminal_obs=False)
+    assert env.pipeline_form() == "slots"
+    L, h = env.L, env._h
+    gen = L.tb_params_generation(h)
+    p = default_params(flags=F_DEFAULT | F_RACKET_GROUND)
+    assert L.tb_diag_fail_alloc(1) == 0
+    try:
+        with pytest.raises(StepperError, match="pipeline_malloc|hipErrorOutOfMemory|out of memory"):
+            env.set_params(p)
+    finally:
+        L.tb_diag_fail_alloc(0)
+    assert L.tb_params_generation(h) == gen
+    assert env.pipeline_form() == "slots"
+    pf = default_params(flags=F_DEFAULT); pf.flags |= F_AUTO_RESET
+    ref = OracleBatch(pf, ENV_SWING, n, seed=4, precision="f32")
+    ref.L.tbo_set_threads(ref.h, 16)
+    rng = np.random.default_rng(12)
+    same(env.reset().cpu().numpy(), ref.reset(), "reset obs")
+    outs = []
+    for t in range(26):  # one episode, its end included: the racket lands during the fast-forward
+        a = rng.uniform(-1, 1, (n, 6)).astype(np.float32)
+        obs, rew, done = env.step(torch.from_numpy(a).cuda())
+        o2, r2, d2, s2 = ref.step(a)
+        same(done.cpu().numpy(), d2, "done %d" % t); same(obs.cpu().numpy(), o2, "obs %d" % t)
+        outs.append((rew, r2))
+    env.flush()
+    for t, (rew, r2) in enumerate(outs):
+        same(rew.cpu().numpy(), r2, "reward %d" % t)
+    got, want = env.counters(), ref.counters()
+    assert list(got.values()) == [int(x) for x in want], (got, want)
+    env.set_params(p)
+    assert L.tb_params_generation(h) == gen + 1
+    assert env.pipeline_form() == "slots+pool"
     env.close()
 
 

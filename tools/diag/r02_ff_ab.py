@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of the fast-forward kernel's lane assignment on ONE box (boxes differ by several percent): whole-rollout
-rate of SwingRacket-v0 for TbOptions.ff_lanes_per_wave / ff_sort variants, plus the one-episode rollout (26 steps +
+rate of SwingRacket-v0 for TbOptions.ff_lanes_per_wave / ff_phases variants, plus the one-episode rollout (26 steps +
 join) that exposes the fast-forward kernel's own duration."""
 import json
 import os

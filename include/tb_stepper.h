@@ -201,6 +201,10 @@ typedef struct TbOptions {
                              * Only without the Magnus extension and the extended contact set, with parameters inside the limits the
                              * argument needs (tb_kernels.hpp, fate_sealed), and never for launches that write terminal observations.
                              * tb_sealed_substeps reports how many substeps were booked this way. */
+  int32_t step_waves;       /* waves per 64 envs of the pipelined SwingRacket-v0 one-step kernel: 0 = auto (2 up to 16384 envs, where most
+                             * SIMDs are idle, else 1), 1, or 2 (the racket's update on one wave, the ball's on the other,
+                             * for launches where no env nears a contact or ends its short steps). Only with the static rows in registers
+                             * (swing_reg_rows). tb_step_waves reports the choice. (Appended after ABI v4's fields: an older caller's shorter struct reads as auto.) */
 } TbOptions;
 
 /* library identity / shape queries (host only, no device touched) */
@@ -403,6 +407,8 @@ int tb_phase_advance(TbHandle *h, int n_steps);
  * to the pool, 3 = every episode end parked into the pool, one fast-forward launch at the join (and at each progress mark). For
  * reports (bench.py names it). */
 int tb_pipeline_form(TbHandle *h);
+/* waves per 64 envs of the pipelined SwingRacket-v0 one-step kernel (TbOptions.step_waves): 2 or 1; 0 for a handle without that kernel */
+int tb_step_waves(TbHandle *h);
 /* After a capture that contained tb_step calls was ABANDONED (it failed, e.g. because something else
  * in it was not capturable): the handle's side streams were forked into that capture and stay
  * invalidated, and the host's episode-phase hint ran ahead of the device. Replaces the side streams
@@ -450,6 +456,9 @@ int tb_diag_stream_copy(const uint32_t *src_dev, uint32_t *dst_dev, int n, int r
  * the fast-forward waves without their arithmetic (tools/diag/r03_idle_probe.py: do resident waves shorten the dispatch gap between
  * the dependent launches of a graph?). */
 int tb_diag_idle(int waves, int microseconds, int device, void *stream);
+/* Diagnostics: out_dev[i] = 1 if SwingRacket-v0 env i's next step, from its current state, leaves the common path of the two-wave
+ * step kernel (TbOptions.step_waves: the very test that kernel runs, tb_kernels.hpp two_wave_rare), else 0. n_envs bytes, on `stream`. */
+int tb_diag_two_wave_gate(TbHandle *h, uint8_t *out_dev, void *stream);
 /* Test hook: the nth device allocation of the pipeline or its pool from now on -- tb_set_pipeline(h, 1), or the pool that
  * tb_set_params allocates -- fails with hipErrorOutOfMemory (0 = off). tb_set_pipeline is all-or-nothing: after a failure the handle is as if the pipeline had never
  * been enabled (nothing half-allocated for a later step to park into), and a second call starts over. */

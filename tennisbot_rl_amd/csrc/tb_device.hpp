@@ -1075,62 +1075,68 @@ TB_DEV void solve_contacts(const KParams& P, Rows<RG>& R, const Manifold& M, int
 #undef TB_EACH_GROUND_ROW
 
 // ---------------------------------------------------------------- one 1/240 s substep
-// wb_pre = rotate_inv(rk.q, rk.w), computed by the caller (rotate_inv2)
+// The racket's and the ball's updates below touch nothing of each other: integrate_velocities / integrate_pose call them one after
+// the other, and the two-wave step kernel (tb_kernels.hpp, two_wave_step) runs each on a wave of its own -- the same functions, so
+// the same operations in the same order.
+// wb_pre = rotate_inv(rk.q, rk.w), computed by the caller (rotate_inv2); speed_r = |rk.v|
+TB_DEV void racket_velocity(const KParams& P, Racket& rk, vec3 Fr, vec3 Tr, vec3 wb_pre, float speed_r) {
+  const float dt = P.dt, g = P.gravity;
+  float kd = FMA(P.lin_damp_quad, speed_r, P.lin_damp);
+  vec3 a = mk(FMA(Fr.x, P.racket_inv_mass, -(rk.v.x * kd)), FMA(Fr.y, P.racket_inv_mass, -(rk.v.y * kd)),
+              FMA(Fr.z, P.racket_inv_mass, -(rk.v.z * kd)) - g);
+  rk.v = fma3(dt, a, rk.v);
+  // a racket that neither spins nor is torqued has zero angular acceleration: skip the
+  // body-frame round trip (Tennisbot rackets until they are hit; every fast-forward substep
+  // of a racket that was never torqued)
+  const bool torqued = nonzero3(Tr);
+  bool active = nonzero3(rk.w) | torqued;
+  TB_DIAG_ABLATE_ANGULAR(active);
+  if (active) {
+    vec3 wb = wb_pre, Tb = mk(0.0f, 0.0f, 0.0f);
+    if (torqued) Tb = rotate_inv(rk.q, Tr);
+    vec3 L = mk(P.racket_inertia[0] * wb.x, P.racket_inertia[1] * wb.y, P.racket_inertia[2] * wb.z);
+    vec3 gy = cross(wb, L);
+    float ka = FMA(P.ang_damp_quad, sqrtf(dot(wb, wb)), P.ang_damp);
+    vec3 ab = mk(P.racket_inv_inertia[0] * ((Tb.x - gy.x) - L.x * ka), P.racket_inv_inertia[1] * ((Tb.y - gy.y) - L.y * ka),
+                 P.racket_inv_inertia[2] * ((Tb.z - gy.z) - L.z * ka));
+    rk.w = fma3(dt, rotate(rk.q, ab), rk.w);
+  }
+}
+// speed_b = |b.v|; spin_b = |b.w|, or anything if LAZY
+template <bool LAZY = false>
+TB_DEV void ball_velocity(const KParams& P, Ball& b, vec3 Fb, float speed_b, float spin_b) {
+  const float dt = P.dt, g = P.gravity;
+  if (P.magnus_k != 0.0f) Fb = fma3(P.magnus_k, cross(b.w, b.v), Fb);
+  float kd = FMA(P.lin_damp_quad, speed_b, P.lin_damp);
+  vec3 a = mk(FMA(Fb.x, P.ball_inv_mass, -(b.v.x * kd)), FMA(Fb.y, P.ball_inv_mass, -(b.v.y * kd)),
+              FMA(Fb.z, P.ball_inv_mass, -(b.v.z * kd)) - g);
+  b.v = fma3(dt, a, b.v);
+  bool spinning = nonzero3(b.w);
+  if (spinning) {
+    if constexpr (LAZY) spin_b = sqrtf(dot(b.w, b.w));
+    float ka = FMA(P.ang_damp_quad, spin_b, P.ang_damp);
+    vec3 aw = mk(-(b.w.x * ka), -(b.w.y * ka), -(b.w.z * ka));
+    b.w = fma3(dt, aw, b.w);
+  }
+}
 // LAZY (the large-batch fast-forward instantiations, where VALU issue slots count and not latency): the ball's spin rate is
 // only taken where a ball spins -- after a contact, i.e. for a few lanes -- instead of next to the two speeds
 template <bool LAZY = false>
 TB_DEV void integrate_velocities(const KParams& P, Racket& rk, Ball& b, vec3 Fr, vec3 Tr, vec3 Fb, vec3 wb_pre) {
-  const float dt = P.dt, g = P.gravity;
   // the three speeds that do not wait for anything are taken first, side by side: a correctly rounded sqrtf is a
   // ~16-instruction dependent chain, and three independent chains in one block interleave where three chains behind
   // three branches queue (the values and every operation on them are the same as before: bit-identical)
   const float speed_r = sqrtf(dot(rk.v, rk.v)), speed_b = sqrtf(dot(b.v, b.v));
   float spin_b = 0.0f;
   if constexpr (!LAZY) spin_b = sqrtf(dot(b.w, b.w));
-  {
-    float kd = FMA(P.lin_damp_quad, speed_r, P.lin_damp);
-    vec3 a = mk(FMA(Fr.x, P.racket_inv_mass, -(rk.v.x * kd)), FMA(Fr.y, P.racket_inv_mass, -(rk.v.y * kd)),
-                FMA(Fr.z, P.racket_inv_mass, -(rk.v.z * kd)) - g);
-    rk.v = fma3(dt, a, rk.v);
-    // a racket that neither spins nor is torqued has zero angular acceleration: skip the
-    // body-frame round trip (Tennisbot rackets until they are hit; every fast-forward substep
-    // of a racket that was never torqued)
-    const bool torqued = nonzero3(Tr);
-    bool active = nonzero3(rk.w) | torqued;
-    TB_DIAG_ABLATE_ANGULAR(active);
-    if (active) {
-      vec3 wb = wb_pre, Tb = mk(0.0f, 0.0f, 0.0f);
-      if (torqued) Tb = rotate_inv(rk.q, Tr);
-      vec3 L = mk(P.racket_inertia[0] * wb.x, P.racket_inertia[1] * wb.y, P.racket_inertia[2] * wb.z);
-      vec3 gy = cross(wb, L);
-      float ka = FMA(P.ang_damp_quad, sqrtf(dot(wb, wb)), P.ang_damp);
-      vec3 ab = mk(P.racket_inv_inertia[0] * ((Tb.x - gy.x) - L.x * ka), P.racket_inv_inertia[1] * ((Tb.y - gy.y) - L.y * ka),
-                   P.racket_inv_inertia[2] * ((Tb.z - gy.z) - L.z * ka));
-      rk.w = fma3(dt, rotate(rk.q, ab), rk.w);
-    }
-  }
-  {
-    if (P.magnus_k != 0.0f) Fb = fma3(P.magnus_k, cross(b.w, b.v), Fb);
-    float kd = FMA(P.lin_damp_quad, speed_b, P.lin_damp);
-    vec3 a = mk(FMA(Fb.x, P.ball_inv_mass, -(b.v.x * kd)), FMA(Fb.y, P.ball_inv_mass, -(b.v.y * kd)),
-                FMA(Fb.z, P.ball_inv_mass, -(b.v.z * kd)) - g);
-    b.v = fma3(dt, a, b.v);
-    bool spinning = nonzero3(b.w);
-    if (spinning) {
-      if constexpr (LAZY) spin_b = sqrtf(dot(b.w, b.w));
-      float ka = FMA(P.ang_damp_quad, spin_b, P.ang_damp);
-      vec3 aw = mk(-(b.w.x * ka), -(b.w.y * ka), -(b.w.z * ka));
-      b.w = fma3(dt, aw, b.w);
-    }
-  }
+  racket_velocity(P, rk, Fr, Tr, wb_pre, speed_r);
+  ball_velocity<LAZY>(P, b, Fb, speed_b, spin_b);
 }
 
 // exponential-map orientation update with Bullet's pi/4 clamp quirk (w is not rescaled, only
 // z = x^2 is clamped); unclamped |q'|^2 = 1 + O(eps): one Newton step of 1/sqrt normalises
-TB_DEV void integrate_pose(const KParams& P, Racket& rk, Ball& b) {
+TB_DEV void racket_orientation(const KParams& P, Racket& rk) {
   const float dt = P.dt;
-  rk.p = fma3(dt, rk.v, rk.p);
-  b.p = fma3(dt, b.v, b.p);
   float w2 = dot(rk.w, rk.w);
   TB_DIAG_ABLATE_ORIENT(w2);
   if (w2 > 0.0f) {
@@ -1147,6 +1153,12 @@ TB_DEV void integrate_pose(const KParams& P, Racket& rk, Ball& b) {
     else inv = FMA(-0.5f, n2, 1.5f);
     rk.q.x = q.x * inv; rk.q.y = q.y * inv; rk.q.z = q.z * inv; rk.q.w = q.w * inv;
   }
+}
+TB_DEV void integrate_pose(const KParams& P, Racket& rk, Ball& b) {
+  const float dt = P.dt;
+  rk.p = fma3(dt, rk.v, rk.p);
+  b.p = fma3(dt, b.v, b.p);
+  racket_orientation(P, rk);
 }
 
 // Per-shape culls in front of the exact static tests (1 mm of slack against rounding: each is implied by the test's own early-out):

@@ -542,6 +542,117 @@ TB_DEV void stage_hull(float4* s_hull, const KArgs& A) {
 }
 static_assert(sizeof(KParams) <= sizeof(float4) * TB_KP_ROWS, "the LDS copy of the parameter block needs more rows");
 
+// THE TWO-WAVE STEP (tb_step_kernel<.., TWO_WAVE>: the pipelined SwingRacket one-step kernel at small batch sizes).
+// A workgroup of two waves steps 64 envs. At 4096 envs one-wave workgroups leave ~94 % of the SIMDs idle, and a lone wave issues the
+// racket's update and the ball's one after the other although neither reads the other: in a substep without a contact they meet only
+// in the culls (before either update: poses only) and in the observation. Here wave 0 integrates the rackets and wave 1 the balls.
+// What the ball wave's observation needs of the racket (its new x, y) goes through LDS; what the racket wave's non-finite-state count
+// needs of the ball (one flag) comes back the same way, behind the same barrier.
+// The common path only: no lane of the 64 may be past the racket's slab test, near a static shape (one test against the highest), at
+// the end of its short steps (step_count 25: this substep starts the fast-forward and parks the env) or done (a pending restoring
+// force, a reset). Both waves hold the poses the test reads, run the same test and take the same branch. Otherwise the function
+// returns false before anything is written, and wave 0 steps all 64 envs with the one-wave code (the census of a random-action
+// episode: never in the 25 short steps, always in the 26th; profiles/r03_lane_census_1m.txt).
+// Wave 1 holds only what it reads: the racket's position and orientation (the test), the ball, goal, step count and done byte.
+TB_DEV void load_ball_side(const uint32_t* w, const uint8_t* done_state, int n, int i, EnvRegs& e) {
+  constexpr int K = TB_ENV_SWING;
+  e.r.p = mk(ld<K>(w, TB_W_RP, n, i), ld<K>(w, TB_W_RP + 1, n, i), ld<K>(w, TB_W_RP + 2, n, i));
+  e.r.q.x = ld<K>(w, TB_W_RQ, n, i); e.r.q.y = ld<K>(w, TB_W_RQ + 1, n, i); e.r.q.z = ld<K>(w, TB_W_RQ + 2, n, i); e.r.q.w = ld<K>(w, TB_W_RQ + 3, n, i);
+  e.b.p = mk(ld<K>(w, TB_W_BP, n, i), ld<K>(w, TB_W_BP + 1, n, i), ld<K>(w, TB_W_BP + 2, n, i));
+  e.b.v = mk(ld<K>(w, TB_W_BV, n, i), ld<K>(w, TB_W_BV + 1, n, i), ld<K>(w, TB_W_BV + 2, n, i));
+  e.b.w = mk(ld<K>(w, TB_W_BW, n, i), ld<K>(w, TB_W_BW + 1, n, i), ld<K>(w, TB_W_BW + 2, n, i));
+  e.aux[0] = ld<K>(w, 22, n, i); e.aux[1] = ld<K>(w, 23, n, i);
+  e.step_count = (int)row_word<true>(w, Dims<K>::W - 2, n, i);
+  e.done = done_state[i];
+}
+// true: this env's next SwingRacket step may leave the common path. substep's culls on the poses before the substep, in the same
+// order (d, then the slab on the rotated d: rotate_inv2 computes the very operations of rotate_inv); conservative for NaN states.
+TB_DEV bool two_wave_rare(const KParams& P, const EnvRegs& e) {
+  bool rare = e.done != TB_DONE_NO || e.step_count >= 25;  // swingracket_env.py:105-106 would go on to the fast-forward, or a reset is due
+  const vec3 d = e.b.p - e.r.p;
+  if ((P.flags & TB_F_RACKET_BALL) && racket_in_reach(P, d, 1.0f)) {
+    vec3 ql;
+    float qax;
+    rare |= racket_slab<false>(P, rotate_inv(e.r.q, d), 1.0f, ql, qax);
+  }
+  rare |= !(ball_low_point(P, e.b) >= P.static_top + 1.0e-3f);
+  return rare;
+}
+// true: this launch's step of the wave's envs is done (both waves return it alike)
+TB_DEV bool two_wave_step(const KArgs& A, EnvRegs& e, const float* a, int i, bool live) {
+  constexpr int K = TB_ENV_SWING;
+  const KParams& P = A.P;
+  const bool racket_wave = threadIdx.x < 64;
+  const int lane = (int)(threadIdx.x & 63);
+  __shared__ float2 s_rp[64];     // the racket's new x, y (wave 0 -> wave 1)
+  __shared__ float s_ball_fin[64];  // the ball's new state is finite: 1 (wave 1 -> wave 0)
+  if (__any(live && two_wave_rare(P, e))) return false;
+  if (racket_wave) {
+    uint32_t cnt[TB_N_COUNTERS];
+#pragma unroll
+    for (int k = 0; k < TB_N_COUNTERS; ++k) cnt[k] = 0u;
+    if (live) {
+      // swing_step and substep without a contact: the forces of :76-78, the velocity update, the pose update
+      const vec3 F = mk(a[0] * 400.0f, a[1] * 400.0f, FMA(a[2], 400.0f, 4.0f * 9.81f));
+      const vec3 T = mk(a[3] * 5.0f, a[4] * 5.0f, a[5] * 5.0f);
+      const float speed_r = sqrtf(dot(e.r.v, e.r.v));
+      racket_velocity(P, e.r, F, T, rotate_inv(e.r.q, e.r.w), speed_r);
+      e.r.p = fma3(P.dt, e.r.v, e.r.p);
+      s_rp[lane] = make_float2(e.r.p.x, e.r.p.y);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (LDS only: the state stores of either wave are not waited for)
+    if (live) {
+      racket_orientation(P, e.r);
+      st<K>(A.words, TB_W_RP, A.n, i, e.r.p.x); st<K>(A.words, TB_W_RP + 1, A.n, i, e.r.p.y); st<K>(A.words, TB_W_RP + 2, A.n, i, e.r.p.z);
+      st<K>(A.words, TB_W_RQ, A.n, i, e.r.q.x); st<K>(A.words, TB_W_RQ + 1, A.n, i, e.r.q.y); st<K>(A.words, TB_W_RQ + 2, A.n, i, e.r.q.z);
+      st<K>(A.words, TB_W_RQ + 3, A.n, i, e.r.q.w);
+      st<K>(A.words, TB_W_RV, A.n, i, e.r.v.x); st<K>(A.words, TB_W_RV + 1, A.n, i, e.r.v.y); st<K>(A.words, TB_W_RV + 2, A.n, i, e.r.v.z);
+      st<K>(A.words, TB_W_RW, A.n, i, e.r.w.x); st<K>(A.words, TB_W_RW + 1, A.n, i, e.r.w.y); st<K>(A.words, TB_W_RW + 2, A.n, i, e.r.w.z);
+      // state_is_finite's verdict on all 22 values: the racket's 13 here, the ball's 9 from wave 1
+      float a0 = e.r.p.x * 0.0f, a1 = e.r.p.y * 0.0f, a2 = e.r.p.z * 0.0f, a3 = e.r.q.x * 0.0f;
+      a0 = FMA(e.r.q.y, 0.0f, a0); a1 = FMA(e.r.q.z, 0.0f, a1); a2 = FMA(e.r.q.w, 0.0f, a2); a3 = FMA(e.r.v.x, 0.0f, a3);
+      a0 = FMA(e.r.v.y, 0.0f, a0); a1 = FMA(e.r.v.z, 0.0f, a1); a2 = FMA(e.r.w.x, 0.0f, a2); a3 = FMA(e.r.w.y, 0.0f, a3);
+      a0 = FMA(e.r.w.z, 0.0f, a0);
+      const float t = (a0 + a1) + (a2 + a3);
+      if (!(t == t && s_ball_fin[lane] != 0.0f)) cnt[7]++;
+    }
+    flush_counters(A.counters, cnt);
+  } else {
+    if (live) {
+      const float speed_b = sqrtf(dot(e.b.v, e.b.v)), spin_b = sqrtf(dot(e.b.w, e.b.w));
+      ball_velocity(P, e.b, mk(0.0f, 0.0f, 0.0f), speed_b, spin_b);
+      e.b.p = fma3(P.dt, e.b.v, e.b.p);
+      e.step_count += 1;  // :83; no contact: reward 0, not done (:98-106)
+      st<K>(A.words, TB_W_BP, A.n, i, e.b.p.x); st<K>(A.words, TB_W_BP + 1, A.n, i, e.b.p.y); st<K>(A.words, TB_W_BP + 2, A.n, i, e.b.p.z);
+      st<K>(A.words, TB_W_BV, A.n, i, e.b.v.x); st<K>(A.words, TB_W_BV + 1, A.n, i, e.b.v.y); st<K>(A.words, TB_W_BV + 2, A.n, i, e.b.v.z);
+      st<K>(A.words, TB_W_BW, A.n, i, e.b.w.x); st<K>(A.words, TB_W_BW + 1, A.n, i, e.b.w.y); st<K>(A.words, TB_W_BW + 2, A.n, i, e.b.w.z);
+      row_store<true>(A.words, Dims<K>::W - 2, A.n, i, (uint32_t)e.step_count);
+      float a0 = e.b.p.x * 0.0f, a1 = e.b.p.y * 0.0f, a2 = e.b.p.z * 0.0f, a3 = e.b.v.x * 0.0f;
+      a0 = FMA(e.b.v.y, 0.0f, a0); a1 = FMA(e.b.v.z, 0.0f, a1); a2 = FMA(e.b.w.x, 0.0f, a2); a3 = FMA(e.b.w.y, 0.0f, a3);
+      a0 = FMA(e.b.w.z, 0.0f, a0);
+      const float t = (a0 + a1) + (a2 + a3);
+      s_ball_fin[lane] = t == t ? 1.0f : 0.0f;
+      float2* o = reinterpret_cast<float2*>(A.obs + (size_t)i * 6);  // write_obs's rows; the racket's pair after the barrier
+      o[1] = make_float2(e.b.p.x, e.b.p.y); o[2] = make_float2(e.aux[0], e.aux[1]);
+      A.reward[i] = 0.0f;
+      A.done_out[i] = 0;
+      if (A.substeps) A.substeps[i] = 1;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (live) reinterpret_cast<float2*>(A.obs + (size_t)i * 6)[0] = s_rp[lane];
+  }
+  return true;
+}
+
+// diagnostics: two_wave_rare of every env's current state (1 = its next step leaves the two-wave kernel's common path)
+__global__ void __launch_bounds__(64) tb_diag_two_wave_gate_kernel(KArgs A, uint8_t* out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= A.n) return;
+  EnvRegs e;
+  load_env<TB_ENV_SWING>(A.words, A.done_state, A.n, i, e);
+  out[i] = two_wave_rare(A.P, e) ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // step / rollout kernel: T agent steps of every env, state in registers throughout
 // ------------------------------------------------------------------------------------------
@@ -572,7 +683,9 @@ namespace {
 #ifndef TB_HINT_POLICY_VGPR_PARAMS
 #define TB_HINT_POLICY_VGPR_PARAMS 1 // policy rollout kernels: the substep's constants pinned in vector registers for the whole launch
 #endif
-template <int KIND, bool LEAN, bool MULTI, bool RG, bool POLICY = false, bool REGROWS = false>
+// TWO_WAVE: two waves per 64 envs, the racket's update on one and the ball's on the other (two_wave_step; the pipelined SwingRacket
+// one-step kernel, REGROWS, at small batch sizes). A launch whose 64 envs are not all on the common path runs them on wave 0 below.
+template <int KIND, bool LEAN, bool MULTI, bool RG, bool POLICY = false, bool REGROWS = false, bool TWO_WAVE = false>
 __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict__ k_words, const uint8_t* __restrict__ k_done, const float* __restrict__ k_actions,
                                                       const float4* __restrict__ k_hull, int k_n, int k_nhull, KArgs A) {
   // The leading arguments repeat A.words / done_state / actions / hull / n / P.n_hull as separate,
@@ -587,13 +700,14 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
   // pays more for the table's addresses than the copy costs it (918 -> 899 M, 32768 envs 5.17 -> 4.80 G): it keeps the LDS copy,
   // like every kernel that loops (fast-forward, tb_rollout, the fused policy).
   constexpr bool TABLE_IN_MEMORY = !POLICY && !MULTI && KIND == TB_ENV_TENNIS;
+  static_assert(!TWO_WAVE || (KIND == TB_ENV_SWING && LEAN && !MULTI && !RG && !POLICY && REGROWS), "the two-wave form is the pipelined SwingRacket one-step kernel's");
   // LAZYTAB (tb_step on pipelined SwingRacket without the extended contact set): the LDS copy is made by the first wave that reads it (substep's SF_LAZYTAB form)
   constexpr bool LAZYTAB = !POLICY && !MULTI && KIND == TB_ENV_SWING && LEAN && !RG;
   constexpr unsigned FORM = (RG ? SF_RG : 0u) | (REGROWS ? SF_REGROWS : 0u) | (LAZYTAB ? SF_LAZYTAB : 0u);
   __shared__ float4 s_lds_hull[TABLE_IN_MEMORY ? 1 : TB_HULL_LDS];
   __shared__ __attribute__((aligned(16))) float s_mean[POLICY ? 64 * 8 : 4];
   // POLICY: 256-thread workgroups, four waves per 64 envs, each running both towers of a 16-env slice (see policy_towers); wave 0 steps the envs
-  const int i = POLICY ? blockIdx.x * 64 + (threadIdx.x & 63) : blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = POLICY || TWO_WAVE ? blockIdx.x * 64 + (threadIdx.x & 63) : blockIdx.x * blockDim.x + threadIdx.x;
   // measured at 4096 envs: Tennisbot +5.6 % (687 -> 726 M env steps/s); SwingRacket -6 % if it uses them too
   // (its kernels sit at the SGPR limit), so SwingRacket keeps reading the struct
   constexpr bool SEP = KIND == TB_ENV_TENNIS;
@@ -614,8 +728,20 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
   // the outline table -- so that their latencies overlap instead of queueing behind the barrier
   float a[NA];
   if (live && !(POLICY && threadIdx.x >= 64)) {
-    load_env<KIND>(w_words, w_done, w_n, i, e);
-    if (!POLICY) load_actions<KIND>(w_actions, (size_t)i, a);
+    if (TWO_WAVE && threadIdx.x >= 64) {
+      load_ball_side(w_words, w_done, w_n, i, e);
+    } else {
+      load_env<KIND>(w_words, w_done, w_n, i, e);
+      if (!POLICY) load_actions<KIND>(w_actions, (size_t)i, a);
+    }
+  }
+  if constexpr (TWO_WAVE) {
+    if (two_wave_step(A, e, a, i, live)) {
+      TB_DIAG_TRACE_EXIT(trace_slot);
+      TB_DIAG_CADENCE_EXIT(cad_t0, cad_n);
+      return;
+    }
+    if (threadIdx.x >= 64) return;  // a rare-path launch: wave 0 steps the 64 envs below (no barrier there)
   }
 #if TB_HINT_TENNIS_CONSTANTS
   if constexpr (KIND == TB_ENV_TENNIS && !POLICY && !MULTI) {

@@ -122,12 +122,14 @@ void to_kparams(const TbParams* p, KParams* k, float* planes) {
 #define TB_FF_SLOTS 8  // parked-state buffers + side streams: ~2.5 fast-forwards are in flight in steady state
 #define TB_PIPELINE_MAX_ENVS (1 << 24)
 #define TB_DEFER_MAX_ENVS 131072  // deferred stragglers: a small-batch scheme (large batches run the fast-forward in phases)
+#define TB_TWO_WAVE_MAX_ENVS 16384  // the two-wave step kernel up to here (auto)
 
 struct TbHandle {
   int device, kind, n, block;
   TbOptions opt;  // as given to tb_create (0 = auto)
   int reg_rows;  // Tennisbot step kernel with the static contact rows in registers
   int swing_reg_rows;  // the same for the pipelined SwingRacket step kernel (+2.7 % at 4096 envs; NOT for tb_ff_kernel)
+  int two_wave;  // ... and that kernel in its two-wave form (tb_kernels.hpp, two_wave_step)
   uint64_t seed, env_id_base;
   TbParams params;
   KParams kp;
@@ -532,8 +534,11 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
   // the static contact rows in registers (h->reg_rows / swing_reg_rows, see tb_create): Tennisbot, and the one-step pipelined
   // SwingRacket kernel without the policy
   const bool regrows = !rg && (h->kind == TB_ENV_TENNIS ? h->reg_rows : h->swing_reg_rows && piped && T == 1 && !pol);
-  const StepKernel kern = step_kernel(h->kind, piped, T > 1, rg, pol != nullptr, regrows);
+  const bool two_wave = regrows && h->kind == TB_ENV_SWING && h->two_wave;  // (regrows here: the pipelined one-step kernel)
+  const StepKernel kern = two_wave ? tb_step_kernel<TB_ENV_SWING, true, false, false, false, true, true>
+                                   : step_kernel(h->kind, piped, T > 1, rg, pol != nullptr, regrows);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_step_kernel instantiation for this variant");
+  if (two_wave) { grid = dim3((unsigned)((h->n + 63) / 64)); block = dim3(128); }  // two waves per 64 envs
   const unsigned lanes = pol ? 64u : block.x;
   (void)hipGetLastError();  // the check below is about THIS launch, not about whatever another library left behind
   hipLaunchKernelGGL(kern, grid, block, dyn_lds(regrows, rg, lanes), s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
@@ -600,6 +605,7 @@ int tb_create(const TbParams* params, const TbOptions* options, int env_kind, in
     if (opt.ff_defer < -1 || opt.ff_defer > 2) return fail(TB_E_INVAL, "tb_create: TbOptions.ff_defer must be -1, 0, 1 or 2");
     if (opt.ff_defer_margin < 0 || opt.ff_defer_margin > 800) return fail(TB_E_INVAL, "tb_create: TbOptions.ff_defer_margin must be in [0, 800]");
     if (opt.ff_seal < -1 || opt.ff_seal > 1) return fail(TB_E_INVAL, "tb_create: TbOptions.ff_seal must be -1, 0 or 1");
+    if (opt.step_waves < 0 || opt.step_waves > 2) return fail(TB_E_INVAL, "tb_create: TbOptions.step_waves must be 0, 1 or 2");
   }
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
@@ -620,6 +626,8 @@ int tb_create(const TbParams* params, const TbOptions* options, int env_kind, in
   // (with the unpacked build of round 3 the register-row step kernel is 154 VGPRs, three waves per SIMD: it wins at every size now --
   //  131072 envs 8.13 against 7.68 G env steps/s, 262144: 8.35 / 8.21, 1 M: 11.64 / 11.11; until then it was chosen up to 131072 envs)
   h->swing_reg_rows = env_kind == TB_ENV_SWING && (opt.swing_reg_rows ? opt.swing_reg_rows > 0 : 1);
+  // two waves per 64 envs where SIMDs are idle anyway: 4096 envs, same box, see profiles/r05_two_wave_ab.txt
+  h->two_wave = h->swing_reg_rows && (opt.step_waves ? opt.step_waves == 2 : n_envs <= TB_TWO_WAVE_MAX_ENVS);
   // measured on one box: 3 phases +11 % at 1 M envs, +-0 at 256 K, -16 % at 32 K and 4096 (two more kernels in every episode's chain)
   h->ff_phases = opt.ff_phases >= 1 && opt.ff_phases <= 3 ? opt.ff_phases : (n_envs >= 262144 ? 3 : 1);
   h->ff_lanes = opt.ff_lanes_per_wave;  // fast-forward: 64 envs per wave from 4096 envs on, a few per wave below
@@ -842,6 +850,12 @@ int tb_pipeline_form(TbHandle* h) {
   if (h->kind != TB_ENV_SWING || !h->pipeline) return 0;
   const int mode = defer_mode(h);
   return mode == 2 ? 3 : mode == 1 && h->ff_phases == 1 ? 2 : 1;
+}
+
+int tb_step_waves(TbHandle* h) {
+  if (!h) return fail(TB_E_INVAL, "tb_step_waves: null handle");
+  if (h->kind != TB_ENV_SWING || !h->pipeline || !h->swing_reg_rows) return 0;
+  return h->two_wave ? 2 : 1;
 }
 
 int tb_phase_advance(TbHandle* h, int n_steps) {
@@ -1145,6 +1159,15 @@ int tb_diag_stream_copy(const uint32_t* src_dev, uint32_t* dst_dev, int n, int r
   DeviceGuard g(device);
   if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
   hipLaunchKernelGGL(tb_diag_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src_dev, dst_dev, n, rows);
+  HIP_TRY(hipGetLastError());
+  return TB_OK;
+}
+
+int tb_diag_two_wave_gate(TbHandle* h, uint8_t* out_dev, void* stream) {
+  if (!h || !out_dev || h->kind != TB_ENV_SWING) return fail(TB_E_INVAL, "tb_diag_two_wave_gate: bad argument");
+  DeviceGuard g(h->device);
+  if (int rc = flush_all(h, (hipStream_t)stream)) return rc;
+  hipLaunchKernelGGL(tb_diag_two_wave_gate_kernel, dim3((unsigned)((h->n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, base_args(h), out_dev);
   HIP_TRY(hipGetLastError());
   return TB_OK;
 }

@@ -93,6 +93,8 @@ def load_library():
     L.tb_phase_advance.restype = i32
     L.tb_pipeline_form.argtypes = [vp]
     L.tb_pipeline_form.restype = i32
+    L.tb_step_waves.argtypes = [vp]
+    L.tb_step_waves.restype = i32
     L.tb_params_generation.argtypes = [vp]
     L.tb_params_generation.restype = i32
     L.tb_set_racket_scale.argtypes = [vp, ctypes.c_float, vp]
@@ -113,6 +115,8 @@ def load_library():
     L.tb_diag_stream_copy.restype = i32
     L.tb_diag_idle.argtypes = [i32, i32, i32, vp]
     L.tb_diag_idle.restype = i32
+    L.tb_diag_two_wave_gate.argtypes = [vp, vp, vp]
+    L.tb_diag_two_wave_gate.restype = i32
     L.tb_diag_fail_alloc.argtypes = [i32]
     L.tb_diag_fail_alloc.restype = i32
     for f in ("tb_create", "tb_destroy", "tb_set_params", "tb_reset", "tb_step", "tb_rollout", "tb_get_state",
@@ -527,6 +531,11 @@ class BatchedEnv:
         """tb_pipeline_form as a word: "none" (fast-forward inside the 26th step), "slots" (one fast-forward kernel per episode end on a
         side stream), "slots+pool" (its stragglers deferred to the join), "pool" (every episode end parked, ONE fast-forward at the join)"""
         return self.PIPELINE_FORMS[int(self.L.tb_pipeline_form(self._h))]
+
+    def step_waves(self):
+        """tb_step_waves: waves per 64 envs of the pipelined SwingRacket one-step kernel, 2 (racket and ball on waves of their own) or 1;
+        0 without that kernel"""
+        return int(self.L.tb_step_waves(self._h))
 
     # ------------------------------------------------------------------ state save / restore
     def get_state_words(self):

@@ -1,0 +1,138 @@
+"""The pipelined SwingRacket one-step kernel in its two-wave form (TbOptions.step_waves = 2: the racket's update on one wave, the
+ball's on the other; tb_kernels.hpp, two_wave_step) in lockstep with the float32 oracle, bit for bit (TOL = 0 as in
+test_gpu_parity.py): whole episodes with their parking, the pool's fast-forward at the join and auto-reset; partial last
+workgroups; balls moved past the racket's slab test or next to the court in the short steps, where a launch falls back to the
+one-wave code for its 64 envs; randomised engine parameters with the Magnus force and spin on."""
+import numpy as np
+import pytest
+
+from oracle import OracleBatch
+from tennisbot_rl_amd.params import ENV_SWING, F_AUTO_RESET, F_DEFAULT, STATE_WORDS, default_params
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch
+
+
+def same(a, b, what):
+    a, b = np.asarray(a), np.asarray(b)
+    ok = np.array_equal(a.view(np.uint32), b.view(np.uint32)) if a.dtype.kind == "f" else np.array_equal(a, b)
+    if not ok:
+        bad = np.argwhere(a != b) if a.shape == b.shape else [[0]]
+        raise AssertionError("%s: %d mismatches, first at %s" % (what, len(bad), bad[0]))
+
+
+def compare_state(env, ref, what):
+    w_gpu, d_gpu = env.get_state_words()
+    w_cpu, d_cpu = ref.get_state_words()
+    same(w_gpu.cpu().numpy().view(np.uint32), w_cpu.view(np.uint32), what + " state words")
+    same(d_gpu.cpu().numpy(), d_cpu, what + " done byte")
+
+
+def disturb(env, ref, rng, n):
+    """in the short steps: a seventh of the envs get their ball next to the racket's face (past the slab, most of them into a
+    contact), a few more their ball just above the court (the static-shape vote)"""
+    w, d = env.get_state_words()
+    w = w.cpu().numpy().copy().view(np.uint32)
+    f = w.view(np.float32)
+    face = np.arange(0, n, 7)
+    f[13, face] = f[0, face] - (float(env.params.racket_half_thick) + float(env.params.ball_radius)) * rng.uniform(0.8, 3.0, face.size).astype(np.float32)
+    f[14, face] = f[1, face]
+    f[15, face] = f[2, face]
+    low = np.arange(3, n, 29)
+    f[15, low] = np.float32(0.05)
+    dn = d.cpu().numpy()
+    env.set_state_words(w.view(np.int32), dn)
+    ref.set_state_words(w, dn)
+
+
+def run(torch, n, seed, steps=57, over=None, disturb_at=None):
+    from tennisbot_rl_amd.stepper import BatchedEnv
+    p = default_params(flags=F_DEFAULT, **(over or {}))
+    env = BatchedEnv(ENV_SWING, n, device="cuda:0", seed=seed, params=p, pipeline=True, track_terminal_obs=False, options=dict(step_waves=2))
+    assert env.step_waves() == 2
+    pf = p.copy(); pf.flags |= F_AUTO_RESET
+    ref = OracleBatch(pf, ENV_SWING, n, seed=seed, precision="f32")
+    ref.L.tbo_set_threads(ref.h, 8)
+    rng = np.random.default_rng(seed)
+    same(env.reset().cpu().numpy(), ref.reset(), "reset obs")
+    rewards = []
+    for t in range(steps):
+        if disturb_at is not None and t == disturb_at:
+            disturb(env, ref, rng, n)
+        a = rng.uniform(-1, 1, (n, 6)).astype(np.float32)
+        obs, rew, done = env.step(torch.from_numpy(a).cuda())
+        o2, r2, d2, s2 = ref.step(a)
+        same(obs.cpu().numpy(), o2, "n=%d step %d obs" % (n, t))
+        same(done.cpu().numpy(), d2, "n=%d step %d done" % (n, t))
+        rewards.append((rew, r2))  # the terminal rewards arrive with the pool's fast-forward at the join
+    env.flush()
+    for t, (rew, r2) in enumerate(rewards):
+        same(rew.cpu().numpy(), r2, "n=%d step %d reward" % (n, t))
+    compare_state(env, ref, "n=%d final" % n)
+    got, want = env.counters(), ref.counters()
+    assert list(got.values()) == [int(x) for x in want], (got, want)
+    env.close()
+    return got
+
+
+@pytest.mark.parametrize("n", [4096, 1000, 3000])
+def test_two_wave_whole_episodes_in_lockstep(torch, n):
+    got = run(torch, n, seed=50 + n)
+    assert got["episodes_finished"] >= 2 * n and got["nonfinite_states"] == 0
+
+
+@pytest.mark.parametrize("n,at", [(4096, 13), (3000, 20)])
+def test_two_wave_falls_back_for_balls_at_the_racket_or_the_court(torch, n, at):
+    got = run(torch, n, seed=70 + n, steps=40, disturb_at=at)
+    assert got["racket_ball_contact_substeps"] > 0
+
+
+def test_two_wave_randomised_parameters_magnus_and_spin(torch):
+    rng = np.random.default_rng(4242)
+    for trial in range(3):
+        over = dict(gravity=rng.uniform(3.0, 15.0), lin_damp=rng.uniform(0.0, 0.1), ang_damp=rng.uniform(0.0, 0.1),
+                    max_ang_step=rng.uniform(0.3, 1.2), racket_mass=rng.uniform(1.0, 8.0), racket_inertia=tuple(rng.uniform(0.02, 0.3, 3)),
+                    ball_mass=rng.uniform(0.03, 0.2), lin_damp_quad=rng.uniform(0.0, 0.1), ang_damp_quad=rng.uniform(0.0, 0.1),
+                    contact_threshold=rng.uniform(2e-4, 3e-3), magnus_k=[1e-4, 5e-4, 2e-3][trial], ball_spin_max=[50.0, 200.0, 20.0][trial])
+        run(torch, 1000 + 24 * trial, seed=90 + trial, steps=30, over=over, disturb_at=15 if trial == 1 else None)
+
+
+def test_two_wave_equals_one_wave(torch):
+    """the same rollout through both forms of the kernel (TbOptions.step_waves = 2 and 1): every output and the state bit-identical"""
+    from tennisbot_rl_amd.rollout import RolloutBuffer
+    from tennisbot_rl_amd.stepper import BatchedEnv
+    n, T = 2000, 26 * 3 + 5
+    acts = torch.from_numpy(np.random.default_rng(5).uniform(-1, 1, (T, n, 6)).astype(np.float32)).cuda()
+    envs = [BatchedEnv(ENV_SWING, n, seed=8, pipeline=True, track_terminal_obs=False, options=dict(step_waves=w)) for w in (2, 1)]
+    assert [e.step_waves() for e in envs] == [2, 1]
+    bufs = [RolloutBuffer(ENV_SWING, T, n, "cuda:0") for _ in envs]
+    for e, b in zip(envs, bufs):
+        b.actions.copy_(acts)
+        e.reset()
+        for t in range(T):
+            b.step_into(e, t)
+        e.flush()
+    torch.cuda.synchronize()
+    a, b = bufs
+    assert torch.equal(a.obs, b.obs) and torch.equal(a.rewards, b.rewards) and torch.equal(a.dones, b.dones)
+    wa, da = envs[0].get_state_words(); wb, db = envs[1].get_state_words()
+    assert torch.equal(wa, wb) and torch.equal(da, db)
+    assert envs[0].counters() == envs[1].counters()
+    for e in envs:
+        e.close()
+
+
+def test_step_waves_auto_choice(torch):
+    from tennisbot_rl_amd.stepper import BatchedEnv
+    for n, piped, opts, want in [(4096, True, {}, 2), (16384, True, {}, 2), (16385, True, {}, 1), (4096, True, dict(step_waves=1), 1),
+                                 (40000, True, dict(step_waves=2), 2), (4096, True, dict(swing_reg_rows=False), 0), (4096, False, {}, 0)]:
+        env = BatchedEnv(ENV_SWING, n, seed=1, pipeline=piped, track_terminal_obs=False, options=opts)
+        assert env.step_waves() == want, (n, piped, opts)
+        env.close()

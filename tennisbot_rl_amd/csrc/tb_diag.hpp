@@ -78,6 +78,10 @@ TB_DEV void diag_flush_stamps(const Stamps& st) {
 #define TB_DIAG_ADD_LANE0(slot, expr) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_diag_cycles[slot], (unsigned long long)(expr)); } while (0)
 #define TB_DIAG_ADD_LEADER(slot, expr) do { if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)__ballot(1)) - 1u) atomicAdd(&g_diag_cycles[slot], (unsigned long long)(expr)); } while (0)
 #define TB_DIAG_ADD_EACH(slot, expr) atomicAdd(&g_diag_cycles[slot], (unsigned long long)(expr))
+// the two-wave step's marks (tools/diag/r06_two_wave_stamps.py): g_diag_cycles[slot] += cycles since the kernel's entry stamp, per wave
+#define TB_DIAG_T0_ARG , unsigned long long t_entry
+#define TB_DIAG_T0_PASS , t_entry
+#define TB_DIAG_MARK(slot) TB_DIAG_ADD_LANE0(slot, stamp_now() - t_entry)
 #else
 #define TB_STAMP(st, k) do { } while (0)
 #define TB_STAMP_ARG
@@ -90,6 +94,9 @@ TB_DEV void diag_flush_stamps(const Stamps& st) {
 #define TB_DIAG_ADD_LANE0(slot, expr) do { } while (0)
 #define TB_DIAG_ADD_LEADER(slot, expr) do { } while (0)
 #define TB_DIAG_ADD_EACH(slot, expr) do { } while (0)
+#define TB_DIAG_T0_ARG
+#define TB_DIAG_T0_PASS
+#define TB_DIAG_MARK(slot) do { } while (0)
 #endif
 
 // ---- launch trace (-DTB_DIAG_TRACE, also part of -DTB_DIAG_STAMPS) ---------------------------

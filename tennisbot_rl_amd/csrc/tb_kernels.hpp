@@ -546,14 +546,16 @@ static_assert(sizeof(KParams) <= sizeof(float4) * TB_KP_ROWS, "the LDS copy of t
 // A workgroup of two waves steps 64 envs. At 4096 envs one-wave workgroups leave ~94 % of the SIMDs idle, and a lone wave issues the
 // racket's update and the ball's one after the other although neither reads the other: in a substep without a contact they meet only
 // in the culls (before either update: poses only) and in the observation. Here wave 0 integrates the rackets and wave 1 the balls.
-// What the ball wave's observation needs of the racket (its new x, y) goes through LDS; what the racket wave's non-finite-state count
-// needs of the ball (one flag) comes back the same way, behind the same barrier.
 // The common path only: no lane of the 64 may be past the racket's slab test, near a static shape (one test against the highest), at
 // the end of its short steps (step_count 25: this substep starts the fast-forward and parks the env) or done (a pending restoring
-// force, a reset). Both waves hold the poses the test reads, run the same test and take the same branch. Otherwise the function
-// returns false before anything is written, and wave 0 steps all 64 envs with the one-wave code (the census of a random-action
-// episode: never in the 25 short steps, always in the 26th; profiles/r03_lane_census_1m.txt).
-// Wave 1 holds only what it reads: the racket's position and orientation (the test), the ball, goal, step count and done byte.
+// force, a reset). The last two are read straight from the loaded state, and both waves test them first: such a launch (the parking
+// step, resets) speculates nothing and wave 0 steps all 64 envs with the one-wave code (the census of a random-action episode: never
+// in the 25 short steps, always in the 26th; profiles/r03_lane_census_1m.txt). The geometric tests (two_wave_rare) are the ball
+// wave's alone, and the racket wave does not wait for them: it integrates into a copy of the racket, the ball wave updates its ball,
+// then runs the tests for the 64 envs. One barrier hands over what the other side needs: the verdict and the ball's finite flag
+// (wave 1 -> wave 0), the racket's new x, y for the observation (wave 0 -> wave 1). Stores come after it, on the common path only.
+// On a rare verdict nothing has been written: the ball wave returns and wave 0 steps the 64 envs from the loaded state, which it kept.
+// Wave 1 holds only what it reads: the racket's position and orientation (the tests), the ball, goal, step count and done byte.
 TB_DEV void load_ball_side(const uint32_t* w, const uint8_t* done_state, int n, int i, EnvRegs& e) {
   constexpr int K = TB_ENV_SWING;
   e.r.p = mk(ld<K>(w, TB_W_RP, n, i), ld<K>(w, TB_W_RP + 1, n, i), ld<K>(w, TB_W_RP + 2, n, i));
@@ -578,69 +580,85 @@ TB_DEV bool two_wave_rare(const KParams& P, const EnvRegs& e) {
   rare |= !(ball_low_point(P, e.b) >= P.static_top + 1.0e-3f);
   return rare;
 }
-// true: this launch's step of the wave's envs is done (both waves return it alike)
-TB_DEV bool two_wave_step(const KArgs& A, EnvRegs& e, const float* a, int i, bool live) {
+// true: this launch's step of the wave's envs is done (both waves return it alike). e is not modified: on false it is the loaded state.
+TB_DEV bool two_wave_step(const KArgs& A, const EnvRegs& e, const float* a, int i, bool live TB_DIAG_T0_ARG) {
   constexpr int K = TB_ENV_SWING;
   const KParams& P = A.P;
   const bool racket_wave = threadIdx.x < 64;
   const int lane = (int)(threadIdx.x & 63);
-  __shared__ float2 s_rp[64];     // the racket's new x, y (wave 0 -> wave 1)
+  __shared__ float2 s_rp[64];       // the racket's new x, y (wave 0 -> wave 1)
   __shared__ float s_ball_fin[64];  // the ball's new state is finite: 1 (wave 1 -> wave 0)
-  if (__any(live && two_wave_rare(P, e))) return false;
+  __shared__ int s_rare;            // some env of the 64 fails the geometric tests (wave 1 -> wave 0)
+  [[maybe_unused]] const int mk0 = racket_wave ? 0 : 8;  // (diagnostic marks, tools/diag/r06_two_wave_stamps.py)
+  TB_DIAG_WAIT_LOADS(live);
+  TB_DIAG_MARK(mk0);
+  if (__any(live && (e.done != TB_DONE_NO || e.step_count >= 25))) return false;  // two_wave_rare's first line: both waves hold these
   if (racket_wave) {
+    TB_DIAG_MARK(mk0 + 1);
+    // swing_step and substep without a contact: the forces of :76-78, the velocity update, the pose update. Into a copy, and in
+    // every lane (a lane past n computes on what its registers hold and stores nothing): no merge with the loaded state, no moves.
+    Racket r = e.r;
+    const vec3 F = mk(a[0] * 400.0f, a[1] * 400.0f, FMA(a[2], 400.0f, 4.0f * 9.81f));
+    const vec3 T = mk(a[3] * 5.0f, a[4] * 5.0f, a[5] * 5.0f);
+    const float speed_r = sqrtf(dot(r.v, r.v));
+    racket_velocity(P, r, F, T, rotate_inv(r.q, r.w), speed_r);
+    r.p = fma3(P.dt, r.v, r.p);
+    s_rp[lane] = make_float2(r.p.x, r.p.y);
+    racket_orientation(P, r);
+    TB_DIAG_MARK(mk0 + 2);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (LDS only: no global store has been issued yet)
+    TB_DIAG_MARK(mk0 + 3);
+    if (__builtin_amdgcn_readfirstlane(s_rare)) return false;
     uint32_t cnt[TB_N_COUNTERS];
 #pragma unroll
     for (int k = 0; k < TB_N_COUNTERS; ++k) cnt[k] = 0u;
     if (live) {
-      // swing_step and substep without a contact: the forces of :76-78, the velocity update, the pose update
-      const vec3 F = mk(a[0] * 400.0f, a[1] * 400.0f, FMA(a[2], 400.0f, 4.0f * 9.81f));
-      const vec3 T = mk(a[3] * 5.0f, a[4] * 5.0f, a[5] * 5.0f);
-      const float speed_r = sqrtf(dot(e.r.v, e.r.v));
-      racket_velocity(P, e.r, F, T, rotate_inv(e.r.q, e.r.w), speed_r);
-      e.r.p = fma3(P.dt, e.r.v, e.r.p);
-      s_rp[lane] = make_float2(e.r.p.x, e.r.p.y);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (LDS only: the state stores of either wave are not waited for)
-    if (live) {
-      racket_orientation(P, e.r);
-      st<K>(A.words, TB_W_RP, A.n, i, e.r.p.x); st<K>(A.words, TB_W_RP + 1, A.n, i, e.r.p.y); st<K>(A.words, TB_W_RP + 2, A.n, i, e.r.p.z);
-      st<K>(A.words, TB_W_RQ, A.n, i, e.r.q.x); st<K>(A.words, TB_W_RQ + 1, A.n, i, e.r.q.y); st<K>(A.words, TB_W_RQ + 2, A.n, i, e.r.q.z);
-      st<K>(A.words, TB_W_RQ + 3, A.n, i, e.r.q.w);
-      st<K>(A.words, TB_W_RV, A.n, i, e.r.v.x); st<K>(A.words, TB_W_RV + 1, A.n, i, e.r.v.y); st<K>(A.words, TB_W_RV + 2, A.n, i, e.r.v.z);
-      st<K>(A.words, TB_W_RW, A.n, i, e.r.w.x); st<K>(A.words, TB_W_RW + 1, A.n, i, e.r.w.y); st<K>(A.words, TB_W_RW + 2, A.n, i, e.r.w.z);
+      st<K>(A.words, TB_W_RP, A.n, i, r.p.x); st<K>(A.words, TB_W_RP + 1, A.n, i, r.p.y); st<K>(A.words, TB_W_RP + 2, A.n, i, r.p.z);
+      st<K>(A.words, TB_W_RQ, A.n, i, r.q.x); st<K>(A.words, TB_W_RQ + 1, A.n, i, r.q.y); st<K>(A.words, TB_W_RQ + 2, A.n, i, r.q.z);
+      st<K>(A.words, TB_W_RQ + 3, A.n, i, r.q.w);
+      st<K>(A.words, TB_W_RV, A.n, i, r.v.x); st<K>(A.words, TB_W_RV + 1, A.n, i, r.v.y); st<K>(A.words, TB_W_RV + 2, A.n, i, r.v.z);
+      st<K>(A.words, TB_W_RW, A.n, i, r.w.x); st<K>(A.words, TB_W_RW + 1, A.n, i, r.w.y); st<K>(A.words, TB_W_RW + 2, A.n, i, r.w.z);
       // state_is_finite's verdict on all 22 values: the racket's 13 here, the ball's 9 from wave 1
-      float a0 = e.r.p.x * 0.0f, a1 = e.r.p.y * 0.0f, a2 = e.r.p.z * 0.0f, a3 = e.r.q.x * 0.0f;
-      a0 = FMA(e.r.q.y, 0.0f, a0); a1 = FMA(e.r.q.z, 0.0f, a1); a2 = FMA(e.r.q.w, 0.0f, a2); a3 = FMA(e.r.v.x, 0.0f, a3);
-      a0 = FMA(e.r.v.y, 0.0f, a0); a1 = FMA(e.r.v.z, 0.0f, a1); a2 = FMA(e.r.w.x, 0.0f, a2); a3 = FMA(e.r.w.y, 0.0f, a3);
-      a0 = FMA(e.r.w.z, 0.0f, a0);
+      float a0 = r.p.x * 0.0f, a1 = r.p.y * 0.0f, a2 = r.p.z * 0.0f, a3 = r.q.x * 0.0f;
+      a0 = FMA(r.q.y, 0.0f, a0); a1 = FMA(r.q.z, 0.0f, a1); a2 = FMA(r.q.w, 0.0f, a2); a3 = FMA(r.v.x, 0.0f, a3);
+      a0 = FMA(r.v.y, 0.0f, a0); a1 = FMA(r.v.z, 0.0f, a1); a2 = FMA(r.w.x, 0.0f, a2); a3 = FMA(r.w.y, 0.0f, a3);
+      a0 = FMA(r.w.z, 0.0f, a0);
       const float t = (a0 + a1) + (a2 + a3);
       if (!(t == t && s_ball_fin[lane] != 0.0f)) cnt[7]++;
     }
     flush_counters(A.counters, cnt);
+    TB_DIAG_MARK(mk0 + 4);
   } else {
+    Ball b = e.b;  // (as the racket: a copy, every lane)
+    const float speed_b = sqrtf(dot(b.v, b.v)), spin_b = sqrtf(dot(b.w, b.w));
+    ball_velocity(P, b, mk(0.0f, 0.0f, 0.0f), speed_b, spin_b);
+    b.p = fma3(P.dt, b.v, b.p);
+    float a0 = b.p.x * 0.0f, a1 = b.p.y * 0.0f, a2 = b.p.z * 0.0f, a3 = b.v.x * 0.0f;
+    a0 = FMA(b.v.y, 0.0f, a0); a1 = FMA(b.v.z, 0.0f, a1); a2 = FMA(b.w.x, 0.0f, a2); a3 = FMA(b.w.y, 0.0f, a3);
+    a0 = FMA(b.w.z, 0.0f, a0);
+    const float t = (a0 + a1) + (a2 + a3);
+    s_ball_fin[lane] = t == t ? 1.0f : 0.0f;
+    const bool rare = __any(live && two_wave_rare(P, e));
+    if (lane == 0) s_rare = rare ? 1 : 0;
+    TB_DIAG_MARK(mk0 + 1);
+    TB_DIAG_MARK(mk0 + 2);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    TB_DIAG_MARK(mk0 + 3);
+    if (rare) return false;
     if (live) {
-      const float speed_b = sqrtf(dot(e.b.v, e.b.v)), spin_b = sqrtf(dot(e.b.w, e.b.w));
-      ball_velocity(P, e.b, mk(0.0f, 0.0f, 0.0f), speed_b, spin_b);
-      e.b.p = fma3(P.dt, e.b.v, e.b.p);
-      e.step_count += 1;  // :83; no contact: reward 0, not done (:98-106)
-      st<K>(A.words, TB_W_BP, A.n, i, e.b.p.x); st<K>(A.words, TB_W_BP + 1, A.n, i, e.b.p.y); st<K>(A.words, TB_W_BP + 2, A.n, i, e.b.p.z);
-      st<K>(A.words, TB_W_BV, A.n, i, e.b.v.x); st<K>(A.words, TB_W_BV + 1, A.n, i, e.b.v.y); st<K>(A.words, TB_W_BV + 2, A.n, i, e.b.v.z);
-      st<K>(A.words, TB_W_BW, A.n, i, e.b.w.x); st<K>(A.words, TB_W_BW + 1, A.n, i, e.b.w.y); st<K>(A.words, TB_W_BW + 2, A.n, i, e.b.w.z);
-      row_store<true>(A.words, Dims<K>::W - 2, A.n, i, (uint32_t)e.step_count);
-      float a0 = e.b.p.x * 0.0f, a1 = e.b.p.y * 0.0f, a2 = e.b.p.z * 0.0f, a3 = e.b.v.x * 0.0f;
-      a0 = FMA(e.b.v.y, 0.0f, a0); a1 = FMA(e.b.v.z, 0.0f, a1); a2 = FMA(e.b.w.x, 0.0f, a2); a3 = FMA(e.b.w.y, 0.0f, a3);
-      a0 = FMA(e.b.w.z, 0.0f, a0);
-      const float t = (a0 + a1) + (a2 + a3);
-      s_ball_fin[lane] = t == t ? 1.0f : 0.0f;
-      float2* o = reinterpret_cast<float2*>(A.obs + (size_t)i * 6);  // write_obs's rows; the racket's pair after the barrier
-      o[1] = make_float2(e.b.p.x, e.b.p.y); o[2] = make_float2(e.aux[0], e.aux[1]);
+      st<K>(A.words, TB_W_BP, A.n, i, b.p.x); st<K>(A.words, TB_W_BP + 1, A.n, i, b.p.y); st<K>(A.words, TB_W_BP + 2, A.n, i, b.p.z);
+      st<K>(A.words, TB_W_BV, A.n, i, b.v.x); st<K>(A.words, TB_W_BV + 1, A.n, i, b.v.y); st<K>(A.words, TB_W_BV + 2, A.n, i, b.v.z);
+      st<K>(A.words, TB_W_BW, A.n, i, b.w.x); st<K>(A.words, TB_W_BW + 1, A.n, i, b.w.y); st<K>(A.words, TB_W_BW + 2, A.n, i, b.w.z);
+      row_store<true>(A.words, Dims<K>::W - 2, A.n, i, (uint32_t)(e.step_count + 1));  // :83; no contact: reward 0, not done (:98-106)
+      float2* o = reinterpret_cast<float2*>(A.obs + (size_t)i * 6);  // write_obs's rows
+      o[0] = s_rp[lane]; o[1] = make_float2(b.p.x, b.p.y); o[2] = make_float2(e.aux[0], e.aux[1]);
       A.reward[i] = 0.0f;
       A.done_out[i] = 0;
       if (A.substeps) A.substeps[i] = 1;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (live) reinterpret_cast<float2*>(A.obs + (size_t)i * 6)[0] = s_rp[lane];
+    TB_DIAG_MARK(mk0 + 4);
   }
+  TB_DIAG_ADD_LANE0(mk0 + 5, 1);
   return true;
 }
 
@@ -736,12 +754,12 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
     }
   }
   if constexpr (TWO_WAVE) {
-    if (two_wave_step(A, e, a, i, live)) {
+    if (two_wave_step(A, e, a, i, live TB_DIAG_T0_PASS)) {
       TB_DIAG_TRACE_EXIT(trace_slot);
       TB_DIAG_CADENCE_EXIT(cad_t0, cad_n);
       return;
     }
-    if (threadIdx.x >= 64) return;  // a rare-path launch: wave 0 steps the 64 envs below (no barrier there)
+    if (threadIdx.x >= 64) return;  // a rare-path launch: wave 0 steps the 64 envs below from the loaded state (no barrier there)
   }
 #if TB_HINT_TENNIS_CONSTANTS
   if constexpr (KIND == TB_ENV_TENNIS && !POLICY && !MULTI) {

@@ -171,8 +171,10 @@ typedef struct TbHandle TbHandle;
 typedef struct TbOptions {
   uint32_t struct_size;     /* sizeof(TbOptions): lets a newer library read an older caller's struct */
   int32_t block;            /* threads per workgroup of the step kernels: 64, 128 or 256 (auto: 64 up to 16384 envs, above that 128; 64 for SwingRacket-v0 between 49152 and 131072 envs) */
-  int32_t tennis_reg_rows;  /* Tennisbot static contact rows in registers: 1 on, -1 off (auto: on) */
-  int32_t swing_reg_rows;   /* the same for the pipelined SwingRacket step kernel: 1 on, -1 off (auto: on) */
+  int32_t tennis_reg_rows;  /* accepted and ignored (was: an opt-out, -1, that moved the Tennisbot step kernels' static contact rows from
+                             * registers to LDS, which never changed a result and no default chose) */
+  int32_t swing_reg_rows;   /* accepted and ignored (was: the same for the pipelined SwingRacket one-step kernel; -1 also turned its
+                             * two-wave form off) */
   int32_t ff_lanes_per_wave; /* parked envs per wave in the first fast-forward phase, 1..64 (auto: 64 from 4096 envs on, fewer below) */
   int32_t ff_sort;          /* accepted and ignored (was: an opt-in sort of the parked envs by flight estimate, which never changed a
                              * result and no measured workload won with) */
@@ -203,8 +205,7 @@ typedef struct TbOptions {
                              * tb_sealed_substeps reports how many substeps were booked this way. */
   int32_t step_waves;       /* waves per 64 envs of the pipelined SwingRacket-v0 one-step kernel: 0 = auto (2 up to 16384 envs, where most
                              * SIMDs are idle, else 1), 1, or 2 (the racket's update on one wave, the ball's on the other,
-                             * for launches where no env nears a contact or ends its short steps). Only with the static rows in registers
-                             * (swing_reg_rows). tb_step_waves reports the choice. (Appended after ABI v4's fields: an older caller's shorter struct reads as auto.) */
+                             * for launches where no env nears a contact or ends its short steps). tb_step_waves reports the choice. (Appended after ABI v4's fields: an older caller's shorter struct reads as auto.) */
 } TbOptions;
 
 /* library identity / shape queries (host only, no device touched) */

@@ -525,10 +525,11 @@ struct RowS {  // ball vs static shape
   float mu, target, jn, jt1, jt2;
 };
 // a static row in its lane's LDS column (word w of row i at st[(14 i + w) * stride]).
-// TWO: two slots instead of three -- the net's row and the goal's share the second (substep's SF_ESC form hands an env that is near both
+// TWO (rows_in_two_slots): two slots instead of three -- the net's row and the goal's share the second (substep's SF_ESC form hands an env that is near both
 // to the next phase kernel before anything is stored): 28 words per lane instead of 42, a fourth wave per SIMD for the kernel
 // that runs nearly all of a large batch's fast-forward substeps.
 template <bool TWO> TB_DEV constexpr int row_slot(int i) { return TWO && i == 2 ? 1 : i; }
+constexpr bool rows_in_two_slots(bool esc, bool rg, bool regrows) { return esc && !rg && !regrows; }
 template <bool TWO = false, typename MANI> TB_DEV RowS load_row(const MANI& M, int i) {
   const float* p = M.st + 14 * row_slot<TWO>(i) * M.stride;
   const int s = M.stride;
@@ -1212,7 +1213,7 @@ TB_DEV int substep(const KParams& P, const float4* hull, Racket& rk, Ball& b, Ma
   static_assert(!WIDE || !RELOAD, "one form of shared sweep at a time");
   int bits = 0;
   TB_STAMP(st, 0);  // everything between two substeps (loop control, env logic)
-  constexpr bool TWO = ESC && !RG && !REGROWS;  // the static rows in two LDS slots, see load_row
+  constexpr bool TWO = rows_in_two_slots(ESC, RG, REGROWS);  // the static rows in two LDS slots, see load_row
   if constexpr (TWO) {  // (poses only, like the racket's culls: the very tests the static narrowphase below starts with)
     const float zl = ball_low_point(P, b);
     if (near_net(P, b, zl) && near_goal<KIND>(P, zl)) return CT_ESCAPE;  // both rows of the shared slot could be wanted

@@ -145,7 +145,9 @@ TB_DEV void store_env(uint32_t* w, uint8_t* done_state, int n, int i, const EnvR
 // behind it only by lanes that have cached points -- a racket on the ground.
 #define TB_MANI_WORDS 14
 // dynamic LDS of every kernel that steps envs, one column per lane: [TB_ROWS_LDS words: the static contact rows, unless the
-// instantiation keeps them in registers (REGROWS)] [TB_MANI_LDS words: the racket<->court cache, RG instantiations only]
+// instantiation keeps them in registers (REGROWS)] [TB_MANI_LDS words: the racket<->court cache, RG instantiations only];
+// each family's words per lane are stated next to its kernel (step_lds_words, policy_rollout_lds_words, ff_lds_words)
+constexpr int lds_words(bool rows_in_lds, bool rg) { return (rows_in_lds ? TB_ROWS_LDS : 0) + (rg ? TB_MANI_LDS : 0); }
 extern __shared__ float s_mani[];
 TB_DEV void init_manifold(Manifold& M, int lane_in_block, int lanes, bool rows_in_lds) {
   M.n = 0; M.deep = 0; M.stride = lanes;
@@ -685,7 +687,6 @@ namespace {
 // trip count of 1 is worth ~50-100 VGPRs (no loop-carried copies of the per-step bookkeeping), i.e.
 // one to two more waves per SIMD for the kernel every RL step launches.
 // POLICY: the actions are not read from memory but inferred in-kernel (tb_policy_step).
-// REGROWS (Tennisbot, small batches): the static contact rows in registers, see solve_contacts.
 // SCHEDULING HINTS. Three places below (and one in tb_device.hpp) steer where the compiler puts scalar argument loads, with empty
 // `asm volatile` statements that only NAME values. They change no result; each was chosen by a same-box A/B on AMD clang 22 / ROCm 7.2
 // (profiles/EXPERIMENTS.md) and is worth 1-4 % to a launch-bound kernel -- on THIS compiler. They are the only compile-time switches
@@ -701,9 +702,16 @@ namespace {
 #ifndef TB_HINT_POLICY_VGPR_PARAMS
 #define TB_HINT_POLICY_VGPR_PARAMS 1 // policy rollout kernels: the substep's constants pinned in vector registers for the whole launch
 #endif
+// REGROWS, where a step kernel keeps the three static contact rows (substep's SF_REGROWS form): registers for Tennisbot and the pipelined
+// SwingRacket one-step kernel without the policy, never with RG; its lane's LDS column otherwise. Registers won at every measured size in
+// the steady state: Tennisbot +8-28 % from 4096 to 4 M envs, SwingRacket (154 VGPRs) 131072 envs 8.13 against 7.68 G env steps/s, 1 M 11.64 / 11.11.
+constexpr bool step_rows_in_registers(int kind, bool lean, bool multi, bool rg, bool policy) { return !rg && (kind == TB_ENV_TENNIS || (lean && !multi && !policy)); }
+// the variant that has a two-wave form (TWO_WAVE below), and the step kernel's dynamic LDS in words per lane (init_manifold below)
+constexpr bool step_has_two_waves(int kind, bool lean, bool multi, bool rg, bool policy) { return kind == TB_ENV_SWING && lean && !multi && !rg && !policy; }
+constexpr int step_lds_words(int kind, bool lean, bool multi, bool rg, bool policy) { return lds_words(!step_rows_in_registers(kind, lean, multi, rg, policy), rg); }
 // TWO_WAVE: two waves per 64 envs, the racket's update on one and the ball's on the other (two_wave_step; the pipelined SwingRacket
-// one-step kernel, REGROWS, at small batch sizes). A launch whose 64 envs are not all on the common path runs them on wave 0 below.
-template <int KIND, bool LEAN, bool MULTI, bool RG, bool POLICY = false, bool REGROWS = false, bool TWO_WAVE = false>
+// one-step kernel at small batch sizes). A launch whose 64 envs are not all on the common path runs them on wave 0 below.
+template <int KIND, bool LEAN, bool MULTI, bool RG, bool POLICY = false, bool TWO_WAVE = false>
 __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict__ k_words, const uint8_t* __restrict__ k_done, const float* __restrict__ k_actions,
                                                       const float4* __restrict__ k_hull, int k_n, int k_nhull, KArgs A) {
   // The leading arguments repeat A.words / done_state / actions / hull / n / P.n_hull as separate,
@@ -718,7 +726,8 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
   // pays more for the table's addresses than the copy costs it (918 -> 899 M, 32768 envs 5.17 -> 4.80 G): it keeps the LDS copy,
   // like every kernel that loops (fast-forward, tb_rollout, the fused policy).
   constexpr bool TABLE_IN_MEMORY = !POLICY && !MULTI && KIND == TB_ENV_TENNIS;
-  static_assert(!TWO_WAVE || (KIND == TB_ENV_SWING && LEAN && !MULTI && !RG && !POLICY && REGROWS), "the two-wave form is the pipelined SwingRacket one-step kernel's");
+  static_assert(!TWO_WAVE || step_has_two_waves(KIND, LEAN, MULTI, RG, POLICY), "the two-wave form is the pipelined SwingRacket one-step kernel's");
+  constexpr bool REGROWS = step_rows_in_registers(KIND, LEAN, MULTI, RG, POLICY);
   // LAZYTAB (tb_step on pipelined SwingRacket without the extended contact set): the LDS copy is made by the first wave that reads it (substep's SF_LAZYTAB form)
   constexpr bool LAZYTAB = !POLICY && !MULTI && KIND == TB_ENV_SWING && LEAN && !RG;
   constexpr unsigned FORM = (RG ? SF_RG : 0u) | (REGROWS ? SF_REGROWS : 0u) | (LAZYTAB ? SF_LAZYTAB : 0u);
@@ -903,6 +912,9 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
 // lanes are parked for tb_ff_kernel exactly as in the pipelined step kernel. Same arithmetic per env as tb_policy_step,
 // step after step: identical results.
 // RG: the extended contact set compiled in (racket<->court manifold cache in the env wave's LDS columns, rolling-friction rows).
+// The static contact rows: registers for Tennisbot (with RG too), the env wave's LDS columns for SwingRacket; dynamic LDS per env lane:
+constexpr bool policy_rollout_rows_in_registers(int kind) { return kind == TB_ENV_TENNIS; }
+constexpr int policy_rollout_lds_words(int kind, bool rg) { return lds_words(!policy_rollout_rows_in_registers(kind), rg); }
 template <int KIND, int S, bool RG>
 __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KArgs A) {
   constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE * S;
@@ -953,7 +965,7 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   }
   if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);
   Manifold M;
-  init_manifold(M, lane, 64, KIND == TB_ENV_SWING);  // SwingRacket: static rows in LDS; Tennisbot keeps them in registers (REGROWS below)
+  init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
   bool had_contacts = false;
   if constexpr (RG) {
     if (live) { had_contacts = A.mflag[i] != 0; if (had_contacts) load_manifold(A, i, M); }
@@ -997,13 +1009,13 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
       //  env wave, 4096 envs: each lane sweeping for itself 570-574, one query at a time over 64 lanes 592-595 -> 622, four at a time 644 M env
       //  steps/s; 48 envs per wave, 16384 envs: for itself 1036 -> 1057 M -- there the one-query form had lost, 461 -> 426 M at 4096 envs)
       //  (not with 48 envs per wave AND the extended contact set: at that instantiation's 256-VGPR limit the shared sweep's edge records spill)
-      constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | (S == 1 || !RG ? SF_WIDE : 0u);
+      constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | (S == 1 || !RG ? SF_WIDE : 0u) | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);
 #ifdef TB_DIAG_NO_ENVSTEP  // timing-only (tools/diag/r04_policy_ablate.py): RESULTS ARE WRONG
       rew = a[0]; e.step_count += 1;
       if (KIND == TB_ENV_TENNIS) make_obs<KIND>(e, o);
 #else
       if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);  // never loops in here: see tb_step_kernel<LEAN>
-      else rew = tennis_step<FORM | SF_REGROWS>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
+      else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
 #endif
       if (live) {
         if (KIND == TB_ENV_SWING) {
@@ -1102,6 +1114,8 @@ __global__ void tb_poke_kernel(float* dst, float v) { *dst = v; }
 constexpr int TB_PHASE_LANES = 64;    // survivors per wave in the phase kernels behind the first (32 measured: EXPERIMENTS.md)
 constexpr int TB_PHASE_GRID_DIV = 256; // their grid: n / 256 one-wave workgroups (measured / 128 ... / 1024)
 constexpr int TB_BUDGET_MARGIN = 8;
+// its dynamic LDS in words per lane (init_manifold below: the static rows in LDS; ESC without RG keeps them in two slots, load_row<TWO>)
+constexpr int ff_lds_words(bool rg, bool esc) { return rows_in_two_slots(esc, rg, false) ? TB_ROWS_LDS_TWO : lds_words(true, rg); }
 template <bool RG, bool BIG, bool ESC = false, bool POOL = false>
 __global__ void __launch_bounds__(64, (ESC && !RG) ? 4 : 1) tb_ff_kernel(KArgs A) {
   static_assert(!POOL || !ESC, "the pool has no hand-over phase behind it");

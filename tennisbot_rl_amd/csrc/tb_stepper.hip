@@ -127,9 +127,7 @@ void to_kparams(const TbParams* p, KParams* k, float* planes) {
 struct TbHandle {
   int device, kind, n, block;
   TbOptions opt;  // as given to tb_create (0 = auto)
-  int reg_rows;  // Tennisbot step kernel with the static contact rows in registers
-  int swing_reg_rows;  // the same for the pipelined SwingRacket step kernel (+2.7 % at 4096 envs; NOT for tb_ff_kernel)
-  int two_wave;  // ... and that kernel in its two-wave form (tb_kernels.hpp, two_wave_step)
+  int two_wave;  // the pipelined SwingRacket one-step kernel in its two-wave form (tb_kernels.hpp, two_wave_step)
   uint64_t seed, env_id_base;
   TbParams params;
   KParams kp;
@@ -187,13 +185,13 @@ namespace {
 
 int words_of(int kind) { return kind == TB_ENV_SWING ? TB_SWING_WORDS : TB_TENNIS_WORDS; }
 
-// dynamic LDS of a stepping kernel (see init_manifold): per lane, the static rows unless in registers + the cache if RG
+// dynamic LDS of a stepping kernel: `words` per lane (the kernel family's *_lds_words, tb_kernels.hpp) for `lanes` lanes
 #ifdef TB_DIAG_LDS_PAD  // (tools/diag/r03_occupancy_probe.py: fewer workgroups per CU through a padded dynamic LDS request; tb_diag_set_lds_pad)
 size_t g_diag_lds_pad = 0;
 #else
 constexpr size_t g_diag_lds_pad = 0;
 #endif
-size_t dyn_lds(bool regrows, bool rg, unsigned lanes) { return g_diag_lds_pad + sizeof(float) * lanes * ((regrows ? 0 : TB_ROWS_LDS) + (rg ? TB_MANI_LDS : 0)); }
+size_t dyn_lds(int words, unsigned lanes) { return g_diag_lds_pad + sizeof(float) * lanes * words; }
 
 int ensure_marks(TbHandle* h) {
   if (h->h_marks) return TB_OK;
@@ -264,24 +262,18 @@ size_t pool_rec(const TbHandle* h) { return extended_contacts(h->kp) ? ff_rec<tr
 using StepKernel = void (*)(const uint32_t*, const uint8_t*, const float*, const float4*, int, int, KArgs);
 using ArgsKernel = void (*)(KArgs);
 
-// tb_step_kernel<KIND, LEAN, MULTI, RG, POLICY> with the static rows in LDS; the fused policy step runs one step per launch
+// tb_step_kernel<KIND, LEAN, MULTI, RG, POLICY>; the fused policy step runs one step per launch
 template <int KIND, bool LEAN>
-StepKernel step_kernel_lds_rows(bool multi, bool rg, bool pol) {
+StepKernel step_kernel_of(bool multi, bool rg, bool pol) {
   if (pol) return multi ? nullptr : rg ? tb_step_kernel<KIND, LEAN, false, true, true> : tb_step_kernel<KIND, LEAN, false, false, true>;
   if (multi) return rg ? tb_step_kernel<KIND, LEAN, true, true> : tb_step_kernel<KIND, LEAN, true, false>;
   return rg ? tb_step_kernel<KIND, LEAN, false, true> : tb_step_kernel<KIND, LEAN, false, false>;
 }
-// ... and REGROWS (static rows in registers): never with RG; Tennisbot, and the one-step pipelined SwingRacket kernel without the policy
-StepKernel step_kernel(int kind, bool lean, bool multi, bool rg, bool pol, bool regrows) {
-  if (regrows && rg) return nullptr;
-  if (kind == TB_ENV_TENNIS) {
-    if (lean) return nullptr;
-    if (!regrows) return step_kernel_lds_rows<TB_ENV_TENNIS, false>(multi, rg, pol);
-    if (pol) return multi ? nullptr : tb_step_kernel<TB_ENV_TENNIS, false, false, false, true, true>;
-    return multi ? tb_step_kernel<TB_ENV_TENNIS, false, true, false, false, true> : tb_step_kernel<TB_ENV_TENNIS, false, false, false, false, true>;
-  }
-  if (regrows) return lean && !multi && !pol ? tb_step_kernel<TB_ENV_SWING, true, false, false, false, true> : nullptr;
-  return lean ? step_kernel_lds_rows<TB_ENV_SWING, true>(multi, rg, pol) : step_kernel_lds_rows<TB_ENV_SWING, false>(multi, rg, pol);
+// ... and <.., TWO_WAVE> where the variant has that form (step_has_two_waves); LEAN is SwingRacket's only
+StepKernel step_kernel(int kind, bool lean, bool multi, bool rg, bool pol, bool two_wave) {
+  if (two_wave) return step_has_two_waves(kind, lean, multi, rg, pol) ? tb_step_kernel<TB_ENV_SWING, true, false, false, false, true> : nullptr;
+  if (kind == TB_ENV_TENNIS) return lean ? nullptr : step_kernel_of<TB_ENV_TENNIS, false>(multi, rg, pol);
+  return lean ? step_kernel_of<TB_ENV_SWING, true>(multi, rg, pol) : step_kernel_of<TB_ENV_SWING, false>(multi, rg, pol);
 }
 
 // tb_ff_kernel<RG, BIG, ESC, POOL>: ESC only as the first of a BIG fast-forward's phases; a BIG POOL only without RG
@@ -376,8 +368,7 @@ int launch_ff(TbHandle* h, int slot, KArgs a, hipStream_t s) {
     }
     const bool big = !defer && h->n >= 131072;  // (the deferring kernel is the small-batch POOL instantiation at any size)
     const bool esc = big && ph == 0 && phases > 1;
-    const size_t lds = esc && !rg ? sizeof(float) * 64 * TB_ROWS_LDS_TWO : dyn_lds(false, rg, 64);
-    if (int rc = launch_ff_kernel(rg, big, esc, defer, grid, lds, side, k)) return rc;
+    if (int rc = launch_ff_kernel(rg, big, esc, defer, grid, dyn_lds(ff_lds_words(rg, esc), 64), side, k)) return rc;
   }
   return close_side(h, slot, term, substeps, s);
 }
@@ -404,7 +395,7 @@ int run_pool(TbHandle* h, hipStream_t q) {
   // (153 VGPRs, three waves per SIMD, wave-shared outline sweep) holds them all at once, the small-batch one (188 VGPRs, two per
   // SIMD) ran them in two rounds
   const bool big = !rg && h->pool_episodes > 0 && records >= 131072;
-  if (int rc = launch_ff_kernel(rg, big, false, true, dim3((unsigned)g), dyn_lds(false, rg, 64), q, k)) return rc;
+  if (int rc = launch_ff_kernel(rg, big, false, true, dim3((unsigned)g), dyn_lds(ff_lds_words(rg, false), 64), q, k)) return rc;
   h->pool_run_upto = h->pool_episodes;
   return TB_OK;
 }
@@ -531,17 +522,14 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
   Park park;
   if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
   const bool rg = extended_contacts(h->kp);  // selects the instantiation that contains the rolling-friction rows
-  // the static contact rows in registers (h->reg_rows / swing_reg_rows, see tb_create): Tennisbot, and the one-step pipelined
-  // SwingRacket kernel without the policy
-  const bool regrows = !rg && (h->kind == TB_ENV_TENNIS ? h->reg_rows : h->swing_reg_rows && piped && T == 1 && !pol);
-  const bool two_wave = regrows && h->kind == TB_ENV_SWING && h->two_wave;  // (regrows here: the pipelined one-step kernel)
-  const StepKernel kern = two_wave ? tb_step_kernel<TB_ENV_SWING, true, false, false, false, true, true>
-                                   : step_kernel(h->kind, piped, T > 1, rg, pol != nullptr, regrows);
+  const bool multi = T > 1, policy = pol != nullptr;
+  const bool two_wave = h->two_wave && step_has_two_waves(h->kind, piped, multi, rg, policy);
+  const StepKernel kern = step_kernel(h->kind, piped, multi, rg, policy, two_wave);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_step_kernel instantiation for this variant");
   if (two_wave) { grid = dim3((unsigned)((h->n + 63) / 64)); block = dim3(128); }  // two waves per 64 envs
-  const unsigned lanes = pol ? 64u : block.x;
+  const size_t lds = dyn_lds(step_lds_words(h->kind, piped, multi, rg, policy), policy ? 64u : block.x);
   (void)hipGetLastError();  // the check below is about THIS launch, not about whatever another library left behind
-  hipLaunchKernelGGL(kern, grid, block, dyn_lds(regrows, rg, lanes), s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
+  hipLaunchKernelGGL(kern, grid, block, lds, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
   HIP_TRY(hipGetLastError());
   if (int rc = finish_park(h, park, a, h->n, s)) return rc;
   if (h->phase_valid) h->phase = (h->phase + T) % 26;
@@ -569,8 +557,7 @@ int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, f
   const ArgsKernel kern = swing ? policy_rollout_kernel<TB_ENV_SWING>(narrow ? 1 : 3, rg) : policy_rollout_kernel<TB_ENV_TENNIS>(narrow ? 1 : 3, rg);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_rollout_kernel instantiation for this variant");
   (void)hipGetLastError();
-  // dynamic LDS: the env wave's columns -- static rows (SwingRacket) + the racket<->court cache (RG)
-  hipLaunchKernelGGL(kern, grid, block, dyn_lds(!swing, rg, 64), s, a);
+  hipLaunchKernelGGL(kern, grid, block, dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a);  // (the env wave's columns)
   HIP_TRY(hipGetLastError());
   if (int rc = finish_park(h, park, a, st[5], s)) return rc;
   if (h->phase_valid) h->phase = (h->phase + T) % 26;
@@ -619,15 +606,8 @@ int tb_create(const TbParams* params, const TbOptions* options, int env_kind, in
   h->device = device; h->kind = env_kind; h->n = n_envs; h->seed = seed; h->env_id_base = env_id_base;
   h->params = *params; to_kparams(params, &h->kp, &h->cull_planes[0][0]); h->block = pick_block(env_kind, n_envs, opt);
   h->opt = opt;
-  // Tennisbot, measured in the steady state (envs past their first, synchronised episodes): +28 % at 4096 envs,
-  // +8 % at 256 K, +16 % at 1 M, +12 % at 4 M; only the contact-free first episode after a common reset, where the
-  // kernel runs at 70 % of HBM peak and occupancy counts, loses 3 % at 1 M envs
-  h->reg_rows = env_kind == TB_ENV_TENNIS && (opt.tennis_reg_rows ? opt.tennis_reg_rows > 0 : 1);
-  // (with the unpacked build of round 3 the register-row step kernel is 154 VGPRs, three waves per SIMD: it wins at every size now --
-  //  131072 envs 8.13 against 7.68 G env steps/s, 262144: 8.35 / 8.21, 1 M: 11.64 / 11.11; until then it was chosen up to 131072 envs)
-  h->swing_reg_rows = env_kind == TB_ENV_SWING && (opt.swing_reg_rows ? opt.swing_reg_rows > 0 : 1);
   // two waves per 64 envs where SIMDs are idle anyway: 4096 envs, same box, see profiles/r05_two_wave_ab.txt
-  h->two_wave = h->swing_reg_rows && (opt.step_waves ? opt.step_waves == 2 : n_envs <= TB_TWO_WAVE_MAX_ENVS);
+  h->two_wave = opt.step_waves ? opt.step_waves == 2 : n_envs <= TB_TWO_WAVE_MAX_ENVS;
   // measured on one box: 3 phases +11 % at 1 M envs, +-0 at 256 K, -16 % at 32 K and 4096 (two more kernels in every episode's chain)
   h->ff_phases = opt.ff_phases >= 1 && opt.ff_phases <= 3 ? opt.ff_phases : (n_envs >= 262144 ? 3 : 1);
   h->ff_lanes = opt.ff_lanes_per_wave;  // fast-forward: 64 envs per wave from 4096 envs on, a few per wave below
@@ -854,7 +834,7 @@ int tb_pipeline_form(TbHandle* h) {
 
 int tb_step_waves(TbHandle* h) {
   if (!h) return fail(TB_E_INVAL, "tb_step_waves: null handle");
-  if (h->kind != TB_ENV_SWING || !h->pipeline || !h->swing_reg_rows) return 0;
+  if (h->kind != TB_ENV_SWING || !h->pipeline) return 0;
   return h->two_wave ? 2 : 1;
 }
 

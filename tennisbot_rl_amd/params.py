@@ -89,7 +89,8 @@ class TbOptions(ctypes.Structure):
 
 def make_options(block=0, tennis_reg_rows=None, swing_reg_rows=None, ff_lanes_per_wave=0, ff_sort=None, ff_phases=0, policy_slices=0, ff_defer=None, ff_defer_margin=0,
                  ff_seal=None, step_waves=0):
-    """None = auto; True / False force a variant on / off (ff_sort: accepted and ignored, the sort was removed); step_waves: 0 = auto, 1 or 2"""
+    """None = auto; True / False force a variant on / off (ff_sort, tennis_reg_rows, swing_reg_rows: accepted and ignored, those variants
+    were removed); step_waves: 0 = auto, 1 or 2"""
     def tri(x):
         return 0 if x is None else (1 if x else -1)
     o = TbOptions()

@@ -102,7 +102,7 @@ def test_swing_lockstep_ragged_sizes(torch, n):
 
 @pytest.mark.parametrize("n,reg_rows", [(1, True), (65, True), (4096, True), (65, False), (4096, False)])
 def test_tennis_lockstep(torch, n, reg_rows):
-    # both builds of the Tennisbot step kernel (TbOptions.tennis_reg_rows): static contact rows in registers / in scratch
+    # TbOptions.tennis_reg_rows is accepted and ignored (the kernel keeps its static contact rows in registers): False changes nothing
     env, ref = make_pair(torch, ENV_TENNIS, n, options=dict(tennis_reg_rows=reg_rows))
     # 1010 steps: past the 1000-step timeout (tennisbot_env.py:201-203), so every env finishes at least once
     run_lockstep(torch, env, ref, 1010, np.random.default_rng(100 + n), "tennis n=%d" % n, check_state_every=50)
@@ -495,7 +495,7 @@ def test_randomised_engine_parameters_stay_bit_exact(torch, kind):
     (ENV_SWING, 30, False, None, F_DEFAULT), (ENV_SWING, 30, True, None, F_DEFAULT), (ENV_TENNIS, 120, False, None, F_DEFAULT),
     (ENV_SWING, 30, True, dict(ff_phases=3), F_DEFAULT), (ENV_SWING, 30, True, dict(ff_phases=2), F_DEFAULT | F_RACKET_GROUND),
     (ENV_SWING, 30, True, dict(ff_phases=3, ff_lanes_per_wave=16), F_DEFAULT),
-    (ENV_SWING, 30, True, dict(swing_reg_rows=False), F_DEFAULT)])  # (the step kernel with its static rows in LDS: the automatic choice until round 3's build flags)
+    (ENV_SWING, 30, True, dict(swing_reg_rows=False), F_DEFAULT)])  # (swing_reg_rows is accepted and ignored: setting it changes nothing)
 def test_large_batch_instantiations_in_lockstep_with_the_oracle(torch, kind, steps, piped, options, flags):
     """above 131 072 envs tb_create picks other launch shapes and kernel variants (128-thread workgroups, the fast-forward
     instantiation that re-reads its cull planes and shares the outline sweep): 200 003 envs -- ragged against every workgroup
@@ -664,12 +664,11 @@ def test_float32_drift_vs_float64_truth(torch):
                                            (4096, None, dict(ff_phases=1)), (4096, None, dict(ff_phases=2)), (70000, None, dict(ff_phases=3))])
 def test_pipelined_fast_forward_is_bit_identical(torch, n, reg_rows, ff):
     """tb_set_pipeline: the fast-forward runs on a side stream and writes the terminal step's
-    reward late; after flush() every output equals the unpipelined path bit for bit (both builds
-    of the pipelined step kernel: static contact rows in registers, as small batches run it, and in
-    scratch; every way tb_ff_kernel hands parked envs to lanes, TbOptions.ff_lanes_per_wave: 1, 7, 16 or 64 per
-    wave; the loop in one kernel or cut into budgeted phases whose survivors are compacted for the next kernel,
-    TbOptions.ff_phases). TbOptions.ff_sort is accepted and ignored since the sort of parked envs was removed: setting
-    it changes nothing."""
+    reward late; after flush() every output equals the unpipelined path bit for bit (every way tb_ff_kernel hands
+    parked envs to lanes, TbOptions.ff_lanes_per_wave: 1, 7, 16 or 64 per wave; the loop in one kernel or cut into
+    budgeted phases whose survivors are compacted for the next kernel, TbOptions.ff_phases). TbOptions.ff_sort and
+    swing_reg_rows are accepted and ignored since the sort of parked envs and the LDS-row step kernel were removed:
+    setting them changes nothing."""
     from tennisbot_rl_amd.rollout import RolloutBuffer
     from tennisbot_rl_amd.stepper import BatchedEnv
     T = 26 * 4 + 7
@@ -1366,7 +1365,7 @@ def test_pool_run_never_reruns_a_consumed_record(torch):
 @pytest.mark.parametrize("n,options,n_edges", [(3000, dict(block=128), 38), (3000, dict(block=256), 38), (3000, dict(block=256, ff_defer=False), 11),
                                                (1061, dict(block=128), 63), (3000, dict(block=128, swing_reg_rows=False), 38), (20011, None, 38),
                                                (20011, dict(block=256), 5)],
-                         ids=["block128", "block256", "block256-slots-11gon", "block128-63gon", "block128-lds-rows", "auto-block-20011", "block256-20011-5gon"])
+                         ids=["block128", "block256", "block256-slots-11gon", "block128-63gon", "block128-swing-reg-rows-ignored", "auto-block-20011", "block256-20011-5gon"])
 def test_lazily_copied_outline_table_in_multi_wave_workgroups(torch, n, options, n_edges):
     """The pipelined SwingRacket step kernel copies the outline table into LDS lazily: the first WAVE whose ball gets past the racket's
     slab test copies it for itself, without a workgroup barrier (substep<LAZYTAB>, tb_device.hpp). Up to 16384 envs workgroups are one

@@ -129,10 +129,11 @@ def test_two_wave_equals_one_wave(torch):
         e.close()
 
 
-def test_step_waves_auto_choice(torch):
+def test_step_waves_choice_ignores_swing_reg_rows(torch):
+    # the wave count follows step_waves and the batch size only: TbOptions.swing_reg_rows is accepted and ignored
     from tennisbot_rl_amd.stepper import BatchedEnv
     for n, piped, opts, want in [(4096, True, {}, 2), (16384, True, {}, 2), (16385, True, {}, 1), (4096, True, dict(step_waves=1), 1),
-                                 (40000, True, dict(step_waves=2), 2), (4096, True, dict(swing_reg_rows=False), 0), (4096, False, {}, 0)]:
+                                 (40000, True, dict(step_waves=2), 2), (4096, True, dict(swing_reg_rows=False), 2), (4096, False, {}, 0)]:
         env = BatchedEnv(ENV_SWING, n, seed=1, pipeline=piped, track_terminal_obs=False, options=opts)
         assert env.step_waves() == want, (n, piped, opts)
         env.close()

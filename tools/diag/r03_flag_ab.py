@@ -29,12 +29,9 @@ if len(sys.argv) > 2 and sys.argv[1] == "--child":
             torch.cuda.synchronize(); t0 = time.perf_counter(); tr.collect(); torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
         ts.sort()
         print(json.dumps({"rate_M": round(4096 * 1100 / ts[len(ts) // 2] / 1e6, 1)})); sys.exit(0)
-    opts = {}
-    if what.endswith("_ldsrows"):  # (the step kernel with its static rows in LDS: 103 instead of 154 VGPRs)
-        what, opts = what[:-len("_ldsrows")], dict(swing_reg_rows=False)
     k, n, T, rg = WORK[what]
     kind = ENV_TENNIS if k else ENV_SWING
-    env = BatchedEnv(kind, n, device=dev, seed=0, params=default_params(flags=F_DEFAULT | (F_RACKET_GROUND if rg else 0)), track_terminal_obs=False, pipeline=kind == ENV_SWING, options=opts)
+    env = BatchedEnv(kind, n, device=dev, seed=0, params=default_params(flags=F_DEFAULT | (F_RACKET_GROUND if rg else 0)), track_terminal_obs=False, pipeline=kind == ENV_SWING)
     buf = RolloutBuffer(kind, T, n, dev); torch.manual_seed(0); buf.actions.uniform_(-1, 1); buf.bind(env); env.reset()
     for t in range(T): buf.step_into(env, t)
     env.flush()

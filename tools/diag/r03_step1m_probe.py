@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The step kernels ALONE at 1 M envs (GPU box): steps 1..25 of a SwingRacket episode -- no fast-forward in flight, the last one joined
-before the clock starts -- timed with HIP events, per TbOptions variant (workgroup size, static rows in registers or LDS), and
+before the clock starts -- timed with HIP events, per workgroup size (TbOptions.block), and
 Tennisbot's step kernel beside them. usage: r03_step1m_probe.py [lib=<other build>] [n=<envs>]"""
 import json
 import os
@@ -54,7 +54,7 @@ def probe(kind, opts):
     torch.cuda.empty_cache()
 
 
-for o in ({}, dict(block=64), dict(block=256), dict(swing_reg_rows=False), dict(swing_reg_rows=False, block=256), {}):
+for o in ({}, dict(block=64), dict(block=256), {}):
     probe(ENV_SWING, o)
 for o in ({}, dict(block=256)):
     probe(ENV_TENNIS, o)

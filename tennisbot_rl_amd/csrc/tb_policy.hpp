@@ -193,6 +193,9 @@ TB_DEV void policy_draw(const KArgs& A, int i, const EnvRegs& e, float* eps) {
     for (int k = 0; k < NA; ++k) eps[k] = 0.0f;
   }
 }
+// np.clip / torch.clamp to [-1, 1], NaN kept: fminf / fmaxf alone (v_med3_f32, minnum / maxnum semantics) would turn a NaN
+// action into -1 and step a diverged policy's env as if it were finite, past the nonfinite_states counter
+TB_DEV float clip_action(float raw) { return raw != raw ? raw : fminf(fmaxf(raw, -1.0f), 1.0f); }
 template <int KIND>
 TB_DEV void policy_sample(const KArgs& A, const float* s_mean, int i, const EnvRegs& e, float* a, size_t t = 0, const float* drawn = nullptr,
                           const float* stdv = nullptr /* exp(log_std), when the caller keeps it across steps */) {
@@ -214,7 +217,7 @@ TB_DEV void policy_sample(const KArgs& A, const float* s_mean, int i, const EnvR
     float raw = FMA(stdv ? stdv[k] : expf(log_std[k]), ek, mean[k]);
     logp += FMA(-0.5f * ek, ek, -log_std[k]) - 0.9189385332046727f;  // -(eps^2)/2 - log_std - ln(2 pi)/2
     out_raw[(size_t)i * NA + k] = raw;
-    a[k] = fminf(fmaxf(raw, -1.0f), 1.0f);  // SB3 clips Box actions before env.step
+    a[k] = clip_action(raw);  // SB3 clips Box actions before env.step
     out_act[(size_t)i * NA + k] = a[k];
   }
   A.pol_logp[t * A.st_logp + i] = logp;
@@ -233,7 +236,7 @@ TB_DEV float policy_sample_regs(const float* mean, const float* eps, const float
     const float ek = eps[k];
     raw[k] = FMA(stdv[k], ek, mean[k]);
     logp += FMA(-0.5f * ek, ek, -lstd[k]) - 0.9189385332046727f;
-    a[k] = fminf(fmaxf(raw[k], -1.0f), 1.0f);
+    a[k] = clip_action(raw[k]);
   }
   return logp;
 }

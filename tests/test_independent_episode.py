@@ -12,21 +12,9 @@ import numpy as np
 import pytest
 
 from oracle import OracleBatch
+from policy_reference import M32, philox4x32
 from tennisbot_rl_amd.params import ENV_SWING, F_AUTO_RESET, F_DEFAULT, default_params, load_scene
 from test_oracle_independent import DT, f64, rotmat, substep_dense
-
-M32 = 0xFFFFFFFF
-
-
-def philox4x32(ctr, key):
-    """Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), from the paper"""
-    c0, c1, c2, c3 = ctr
-    k0, k1 = key
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & M32, p1 & M32, ((p0 >> 32) ^ c3 ^ k1) & M32, p0 & M32
-        k0, k1 = (k0 + 0x9E3779B9) & M32, (k1 + 0xBB67AE85) & M32
-    return c0, c1, c2, c3
 
 
 def uniform(lo, span, u):  # random.uniform(a, b) = a + (b - a) * random(); 24 random bits

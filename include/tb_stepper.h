@@ -336,6 +336,38 @@ int tb_policy_rollout(TbHandle *h, int n_steps, const float *weights_dev, const 
                       uint64_t noise_seed, int deterministic, void *stream);
 
 /*
+ * Evolution-strategies population evaluation: the reference's fitness_static (tennisbot/ES/fitness_functions.py:17-159,
+ * evolution_strategy_static.py:25-44) for every env at once, one launch for every env's whole episode. Each env runs one episode
+ * with a fresh float64 observation normaliser and its member's GatedCNN (tennisbot/ES/policies.py:59-130) on the last 8
+ * normalised observations; action = clip(net, -1, 1) with NaN kept; the return is the float64 sum of the float32 step rewards in
+ * step order through the first done.
+ *   weights_dev: n_members rows of tb_es_floats(kind) floats in nn.utils.parameters_to_vector order (conv_0.w [8][O][2], conv_0.b,
+ *     conv_gate_0.w/b, conv_1.w [12][8][2], conv_1.b, conv_gate_1.w/b, conv_2.w [A][12][2], conv_2.b), weights_stride_floats apart:
+ *     a multiple of 4 and >= tb_es_floats(kind); base 16-byte aligned. Env i uses member i / envs_per_member, and
+ *     n_members * envs_per_member must equal n_envs.
+ *   return_dev [n_envs] doubles, length_dev [n_envs] agent steps (SwingRacket: always 26; Tennisbot: <= 1001).
+ * Every call first resets every env exactly as tb_reset(h, NULL, ...) does: env i evaluates the episode whose index is one past
+ * the one it was in (on a fresh handle the k-th call, counted from 0 and with no other reset in between, evaluates episode k),
+ * and on return every env holds that episode's freshly reset state again (the episode phase is 0). SwingRacket-v0 requires
+ * tb_set_pipeline(h, 1) (TB_E_UNSUPPORTED otherwise): the 26th step's fast-forward runs on the pipeline's kernels, and the
+ * return is complete in stream order on `stream` when the call returns -- no tb_flush is needed. The trace never changes a result.
+ * Counters: episodes finished and substeps are counted by the kernel (no host share).
+ */
+typedef struct TbEsTrace {
+  size_t struct_size;  /* sizeof(TbEsTrace) */
+  int max_steps;       /* rows [max_steps][n_envs]; steps beyond are not recorded; rows after an env's last step are not written */
+  float *net_in;       /* [T][N][O] the normalised float32 row the network appended at step t (the newest of the 8 it saw) */
+  float *obs;          /* [T][N][O] the observation that row was normalised from: the reset observation at t = 0, else step t-1's */
+  float *actions;      /* [T][N][A] the clipped action step t was taken with */
+  float *raw;          /* [T][N][A] the network's output before the clip */
+  float *reward;       /* [T][N] step t's float32 reward (SwingRacket's step 25: the fast-forward's terminal reward) */
+  uint8_t *done;       /* [T][N] */
+} TbEsTrace;
+int tb_es_floats(int env_kind); /* GatedCNN parameters: 766 (SwingRacket-v0) / 858 (Tennisbot-v0) */
+int tb_es_evaluate(TbHandle *h, const float *weights_dev, int n_members, size_t weights_stride_floats, int envs_per_member,
+                   double *return_dev, int32_t *length_dev, const TbEsTrace *trace_or_null, void *stream);
+
+/*
  * Pipelined fast-forward (SwingRacket-v0 with TB_F_AUTO_RESET; HIP streams, no reference
  * counterpart). The <= 775-substep fast-forward of swingracket_env.py:105-141 takes no
  * agent input, and the next episode does not depend on its outcome. With the pipeline

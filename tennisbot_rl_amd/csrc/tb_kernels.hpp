@@ -914,6 +914,17 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
 // RG: the extended contact set compiled in (racket<->court manifold cache in the env wave's LDS columns, rolling-friction rows).
 // The static contact rows: registers for Tennisbot (with RG too), the env wave's LDS columns for SwingRacket; dynamic LDS per env lane:
 constexpr bool policy_rollout_rows_in_registers(int kind) { return kind == TB_ENV_TENNIS; }
+// the DUMMY a lane without an env steps (see below; also tb_es_rollout_kernel's lanes whose episode is over)
+TB_DEV void idle_env(EnvRegs& e) {
+  const vec3 z3 = mk(0.0f, 0.0f, 0.0f);
+  e.r.p = mk(0.0f, 0.0f, 10.0f); e.r.q.x = 0.0f; e.r.q.y = 0.0f; e.r.q.z = 0.0f; e.r.q.w = 1.0f; e.r.v = z3; e.r.w = z3;
+  e.b.p = mk(100.0f, 100.0f, 1000.0f); e.b.v = z3; e.b.w = z3;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) e.aux[k] = 0.0f;
+  e.aux[3] = 1.0f;  // (Tennisbot: the racket scale; SwingRacket: spawn y)
+  e.aux[5] = 1.0f;  // (SwingRacket: d0)
+  e.step_count = -(1 << 30); e.episode = 0u; e.done = TB_DONE_NO;
+}
 constexpr int policy_rollout_lds_words(int kind, bool rg) { return lds_words(!policy_rollout_rows_in_registers(kind), rg); }
 template <int KIND, int S, bool RG>
 __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KArgs A) {
@@ -953,16 +964,7 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   // never reaches an episode end. It touches nothing, asks for nothing and is never stored -- but its lane is IN the substep, so the
   // racket narrowphase can share the outline sweeps of the asking envs among all 64 lanes (outline_sweep_rows).
   EnvRegs e;
-  {
-    const vec3 z3 = mk(0.0f, 0.0f, 0.0f);
-    e.r.p = mk(0.0f, 0.0f, 10.0f); e.r.q.x = 0.0f; e.r.q.y = 0.0f; e.r.q.z = 0.0f; e.r.q.w = 1.0f; e.r.v = z3; e.r.w = z3;
-    e.b.p = mk(100.0f, 100.0f, 1000.0f); e.b.v = z3; e.b.w = z3;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) e.aux[k] = 0.0f;
-    e.aux[3] = 1.0f;  // (Tennisbot: the racket scale; SwingRacket: spawn y)
-    e.aux[5] = 1.0f;  // (SwingRacket: d0)
-    e.step_count = -(1 << 30); e.episode = 0u; e.done = TB_DONE_NO;
-  }
+  idle_env(e);
   if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);
   Manifold M;
   init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));

@@ -25,6 +25,7 @@
 #include "tb_device.hpp"
 
 #include "tb_kernels.hpp"
+#include "tb_es.hpp"
 
 using namespace tb;
 
@@ -179,6 +180,7 @@ struct TbHandle {
   long long ff_cap[TB_FF_SLOTS], ff_eager[TB_FF_SLOTS];
   long long mark_ff_before[TB_MAX_MARKS][TB_FF_SLOTS];  // fast-forwards enqueued per slot before the mark: inside a capture ff_cap at that point, eagerly ff_eager (mark_in_capture says which)
   int mark_in_capture[TB_MAX_MARKS];
+  float* d_es_rew;  // [n] tb_es_evaluate: where the fast-forward writes the 26th step's reward (allocated on first use)
 };
 
 namespace {
@@ -261,6 +263,7 @@ size_t pool_rec(const TbHandle* h) { return extended_contacts(h->kp) ? ff_rec<tr
 // any other is null (nothing is built for it) and its launch fails.
 using StepKernel = void (*)(const uint32_t*, const uint8_t*, const float*, const float4*, int, int, KArgs);
 using ArgsKernel = void (*)(KArgs);
+using ArgsKernel2 = void (*)(KArgs, EsArgs);
 
 // tb_step_kernel<KIND, LEAN, MULTI, RG, POLICY>; the fused policy step runs one step per launch
 template <int KIND, bool LEAN>
@@ -647,6 +650,7 @@ int tb_destroy(TbHandle* h) {
   if (h->d_counters) (void)hipFree(h->d_counters);
   if (h->d_mani) (void)hipFree(h->d_mani);
   if (h->d_mflag) (void)hipFree(h->d_mflag);
+  if (h->d_es_rew) (void)hipFree(h->d_es_rew);
   release_pipeline(h);
   if (h->h_marks) (void)hipHostFree(h->h_marks);
   free(h);
@@ -1034,6 +1038,54 @@ int tb_policy_rollout(TbHandle* h, int n_steps, const float* weights_dev, const 
     obs_in = obs_dev + (size_t)(t - 1) * st[4];  // the next launch acts on what this one observed last
   }
   return TB_OK;
+}
+
+int tb_es_floats(int env_kind) {
+  return env_kind == TB_ENV_SWING ? es_floats<TB_ENV_SWING>() : env_kind == TB_ENV_TENNIS ? es_floats<TB_ENV_TENNIS>() : TB_E_INVAL;
+}
+
+int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t weights_stride_floats, int envs_per_member, double* return_dev,
+                   int32_t* length_dev, const TbEsTrace* trace, void* stream) {
+  if (!h || !weights_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_es_evaluate: null argument");
+  if (n_members < 1 || envs_per_member < 1 || (long long)n_members * envs_per_member != h->n)
+    return fail(TB_E_INVAL, "tb_es_evaluate: n_members * envs_per_member must equal n_envs (both >= 1)");
+  const bool swing = h->kind == TB_ENV_SWING;
+  if (weights_stride_floats % 4 || weights_stride_floats < (size_t)tb_es_floats(h->kind) || reinterpret_cast<uintptr_t>(weights_dev) % 16)
+    return fail(TB_E_INVAL, "tb_es_evaluate: the weights' row stride must be a multiple of 4 floats and >= tb_es_floats, the base 16-byte aligned");
+  if (swing && !h->pipeline)
+    return fail(TB_E_UNSUPPORTED, "tb_es_evaluate on SwingRacket-v0 needs tb_set_pipeline(h, 1): the 26th step's fast-forward runs on the pipeline's kernels");
+  EsArgs E;
+  memset(&E, 0, sizeof E);
+  E.weights = weights_dev; E.stride = weights_stride_floats; E.per_member = envs_per_member; E.ret = return_dev; E.len = length_dev;
+  if (trace && trace->max_steps > 0) {
+    if (trace->struct_size < sizeof(TbEsTrace)) return fail(TB_E_INVAL, "tb_es_evaluate: TbEsTrace.struct_size too small");
+    if (!trace->net_in || !trace->obs || !trace->actions || !trace->raw || !trace->reward || !trace->done)
+      return fail(TB_E_INVAL, "tb_es_evaluate: a TbEsTrace array is null");
+    E.t_max = trace->max_steps; E.t_net_in = trace->net_in; E.t_obs = trace->obs; E.t_act = trace->actions; E.t_raw = trace->raw;
+    E.t_rew = trace->reward; E.t_done = trace->done;
+  }
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (swing && !h->d_es_rew) HIP_TRY(hipMalloc((void**)&h->d_es_rew, sizeof(float) * (size_t)h->n));
+  if (int rc = tb_reset(h, nullptr, nullptr, stream)) return rc;  // (flushes the pipeline; every env in lockstep at phase 0)
+  KArgs a = base_args(h);
+  a.reward = h->d_es_rew;  // (SwingRacket: the fast-forward's destination for the 26th step's reward)
+  Park park;
+  if (int rc = claim_park(h, swing, a, s, &park)) return rc;
+  const bool rg = extended_contacts(h->kp);
+  ArgsKernel2 kern = swing ? (rg ? tb_es_rollout_kernel<TB_ENV_SWING, true> : tb_es_rollout_kernel<TB_ENV_SWING, false>)
+                           : (rg ? tb_es_rollout_kernel<TB_ENV_TENNIS, true> : tb_es_rollout_kernel<TB_ENV_TENNIS, false>);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kern, dim3((unsigned)((h->n + 63) / 64)), dim3(64), dyn_lds(es_lds_words(h->kind, rg), 64), s, a, E);
+  HIP_TRY(hipGetLastError());
+  if (swing) {
+    if (int rc = finish_park(h, park, a, 0, s)) return rc;
+    if (int rc = flush_all(h, s)) return rc;  // every fast-forward's reward is in d_es_rew once `s` gets past here
+    hipLaunchKernelGGL(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n,
+                       E.t_max > 25 ? E.t_rew : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
 }
 
 int tb_rollout(TbHandle* h, int n_steps, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,

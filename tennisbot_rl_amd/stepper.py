@@ -87,6 +87,10 @@ def load_library():
     L.tb_policy_floats.restype = i32
     L.tb_policy_step.argtypes = [vp] * 10 + [u64, i32, vp]
     L.tb_policy_step.restype = i32
+    L.tb_es_floats.argtypes = [i32]
+    L.tb_es_floats.restype = i32
+    L.tb_es_evaluate.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, vp, vp, ctypes.POINTER(TbEsTrace), vp]
+    L.tb_es_evaluate.restype = i32
     L.tb_phase.argtypes = [vp]
     L.tb_phase.restype = i32
     L.tb_phase_advance.argtypes = [vp, i32]
@@ -129,6 +133,12 @@ def load_library():
         assert L.tb_state_words(kind) == STATE_WORDS[kind]
     _LIB = L
     return L
+
+
+class TbEsTrace(ctypes.Structure):
+    """include/tb_stepper.h TbEsTrace: optional per-step record of tb_es_evaluate"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("max_steps", ctypes.c_int), ("net_in", ctypes.c_void_p), ("obs", ctypes.c_void_p),
+                ("actions", ctypes.c_void_p), ("raw", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p)]
 
 
 def _check(L, rc, what):
@@ -425,6 +435,45 @@ class BatchedEnv:
         if self.pipeline:
             self._inflight.append(rew)
         return (obs, rew, done), (act, raw, logp, value)
+
+    def es_floats(self):
+        """GatedCNN parameters per member for this env kind (766 SwingRacket-v0, 858 Tennisbot-v0)"""
+        return int(self.L.tb_es_floats(self.kind))
+
+    def es_evaluate(self, weights, envs_per_member, trace=False, max_steps=None):
+        """One episode per env with its member's GatedCNN and a fresh float64 normaliser (tb_es_evaluate; the reference's
+        fitness_static). weights: [M, stride] float32 on this device, stride a multiple of 4 and >= es_floats() (pack_population
+        in tennisbot_rl_amd/es.py), M * envs_per_member == num_envs; env i uses member i // envs_per_member. Every call resets
+        every env first (the episode after the one it was in). Returns (returns float64 [M, R], lengths int32 [M, R]) with
+        R = envs_per_member, complete in stream order; with trace=True also a dict of the per-step record
+        (net_in / obs [T, N, O], actions / raw [T, N, A], reward [T, N], done [T, N]; rows after an env's last step stay zero),
+        T = max_steps or the longest episode (26 / 1001)."""
+        t, n = self.torch, self.num_envs
+        R = int(envs_per_member)
+        if R < 1 or n % R:
+            raise ValueError("envs_per_member must divide num_envs (%d)" % n)
+        M, P = n // R, self.es_floats()
+        if not isinstance(weights, t.Tensor) or weights.dim() != 2 or weights.shape[0] != M:
+            raise ValueError("weights must be a [%d, stride] tensor" % M)
+        if weights.device != self.device or weights.dtype != t.float32:
+            raise ValueError("weights must be float32 on %s" % self.device)
+        if weights.shape[1] < P or weights.shape[1] % 4 or not weights.is_contiguous() or weights.data_ptr() % 16:
+            w = t.zeros((M, (P + 3) // 4 * 4), dtype=t.float32, device=self.device)
+            w[:, :P] = weights[:, :P]
+            weights = w
+        ret = t.empty(n, dtype=t.float64, device=self.device)
+        length = t.empty(n, dtype=t.int32, device=self.device)
+        tr, rec = None, None
+        if trace:
+            T = int(max_steps) if max_steps is not None else (26 if self.kind == ENV_SWING else 1001)
+            f = dict(dtype=t.float32, device=self.device)
+            rec = dict(net_in=t.zeros((T, n, self.obs_dim), **f), obs=t.zeros((T, n, self.obs_dim), **f), actions=t.zeros((T, n, self.act_dim), **f),
+                       raw=t.zeros((T, n, self.act_dim), **f), reward=t.zeros((T, n), **f), done=t.zeros((T, n), dtype=t.uint8, device=self.device))
+            tr = TbEsTrace(ctypes.sizeof(TbEsTrace), T, *(rec[k].data_ptr() for k in ("net_in", "obs", "actions", "raw", "reward", "done")))
+        _check(self.L, self.L.tb_es_evaluate(self._h, weights.data_ptr(), M, weights.shape[1], R, ret.data_ptr(), length.data_ptr(),
+                                             None if tr is None else ctypes.byref(tr), self._stream()), "tb_es_evaluate")
+        out = (ret.view(M, R), length.view(M, R))
+        return out + (rec,) if trace else out
 
     def capture(self, fn):
         """Capture `fn()` -- a fixed sequence of step()/step_ptrs()/RolloutBuffer.step_into calls on

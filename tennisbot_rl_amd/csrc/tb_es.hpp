@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
         }
       }
       cnt[6] += (uint32_t)ns;  // every substep of the step: the host adds no share for this kernel
-      if (!state_is_finite(e)) cnt[7]++;
+      if (!parked && !state_is_finite(e)) cnt[7]++;  // (a parked step's state is judged once, by the fast-forward that ends it)
       if (!parked) ret += (double)rew;
       len = t + 1;
       if (rec) {

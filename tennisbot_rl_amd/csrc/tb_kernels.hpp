@@ -861,7 +861,7 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
       }
       cnt[6] += (uint32_t)(ns - 1);  // substeps beyond the first of each agent step
       ns_total += ns;
-      if (!state_is_finite(e))
+      if (!parked && !state_is_finite(e))  // (a parked step's state is judged once, by the fast-forward that ends it)
         cnt[7]++;
       if (d && (A.P.flags & TB_F_AUTO_RESET)) {
         cnt[5]++;
@@ -1035,7 +1035,7 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
           }
         }
         cnt[6] += (uint32_t)(ns - 1);
-        if (!state_is_finite(e))
+        if (!parked && !state_is_finite(e))  // (judged by the fast-forward that ends a parked step)
           cnt[7]++;
         if (d) {  // (rollouts require TB_F_AUTO_RESET)
           cnt[5]++;

@@ -7,17 +7,14 @@ step path and the float64 restatement of tests/es_reference.py:
     bit for bit (NaN kept);
   * the return is the float64 sum of the traced rewards through the first done, bit for bit, and the length is that step + 1;
   * the return does not depend on the trace, on the SwingRacket fast-forward form or on the run."""
-import os
-
 import numpy as np
 import pytest
 
 import es_reference as er
-from tennisbot_rl_amd.params import ACT_DIM, ENV_SWING, ENV_TENNIS, F_AUTO_RESET, F_DEFAULT, F_RACKET_GROUND, OBS_DIM, default_params
+from helpers import check_es_trace, es_evaluate, es_member_weights, es_params, same_bits
+from tennisbot_rl_amd.params import ENV_SWING, ENV_TENNIS
 
 pytestmark = pytest.mark.gpu
-
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "es_swing_policy.npz")
 
 
 @pytest.fixture(scope="module")
@@ -28,104 +25,19 @@ def torch():
     return torch
 
 
-def member_weights(kind, name, M):
-    """[M, P] float32: torch's default init (a seed per member), the shipped ES policy (+ small noise per member), saturating
-    N(0, 2^2), all zero, or the default init with a NaN weight in member 1"""
-    from tennisbot_rl_amd import es
-    O, A = OBS_DIM[kind], ACT_DIM[kind]
-    P = er.es_floats(O, A)
-    rng = np.random.default_rng(7)
-    if name in ("default", "nan"):
-        W = np.stack([es.initial_weights(kind, 100 + m).numpy() for m in range(M)])
-        if name == "nan":
-            W[min(1, M - 1), 37] = np.nan
-    elif name == "golden":
-        W = np.load(GOLD)["weights"][None, :] + rng.normal(0.0, 0.02, (M, P)).astype(np.float32)
-        W[0] = np.load(GOLD)["weights"]
-    elif name == "saturating":
-        W = rng.normal(0.0, 2.0, (M, P))
-    else:
-        W = np.zeros((M, P))
-    return np.ascontiguousarray(W, dtype=np.float32)
-
-
-def same_bits(a, b):
-    """bit for bit, any NaN matching any NaN (a NaN's payload is not part of the contract)"""
-    a, b = np.asarray(a), np.asarray(b)
-    u = np.uint64 if a.dtype == np.float64 else np.uint32
-    return bool(np.all((a.view(u) == b.view(u)) | (np.isnan(a) & np.isnan(b))))
+member_weights = es_member_weights
 
 
 def make_params(rg):
-    return default_params(flags=F_DEFAULT | F_AUTO_RESET | (F_RACKET_GROUND if rg else 0))
+    return es_params(rg)
 
 
 def evaluate(torch, kind, n, epm, W, rg=False, ff=None, trace=True, seed=5):
-    from tennisbot_rl_amd.stepper import BatchedEnv
-    opts = {} if ff is None else dict(ff_defer=ff)
-    env = BatchedEnv(kind, n, device="cuda:0", seed=seed, params=make_params(rg), pipeline=kind == ENV_SWING, options=opts)
-    M = n // epm
-    pop = torch.zeros((M, (W.shape[1] + 3) // 4 * 4), device="cuda:0")
-    pop[:, :W.shape[1]] = torch.from_numpy(W).to("cuda:0")
-    out = env.es_evaluate(pop, epm, trace=trace)
-    torch.cuda.synchronize()
-    res = [x.reshape(-1).cpu().numpy() for x in out[:2]]
-    if trace:
-        res.append({k: v.cpu().numpy() for k, v in out[2].items()})
-    env.close()
-    return res
+    return es_evaluate(torch, kind, n, epm, W, make_params(rg), ff=ff, trace=trace, seed=seed)
 
 
 def check_trace(torch, kind, n, epm, W, ret, length, tr, rg, seed=5):
-    from oracle import OracleBatch
-    from tennisbot_rl_amd.stepper import BatchedEnv
-    O, A = OBS_DIM[kind], ACT_DIM[kind]
-    T = tr["reward"].shape[0]
-    assert length.min() >= 1 and length.max() <= T
-    if kind == ENV_SWING:
-        assert (length == 26).all()
-    steps = np.arange(T)[:, None]
-    act = steps < length[None, :]  # [T, n] the env's episode ran step t
-    # 1. the first observation is the oracle's reset of episode 0
-    ref = OracleBatch(make_params(rg), kind, n, seed=seed, precision="f32")
-    assert np.array_equal(tr["obs"][0].view(np.uint32), ref.reset().view(np.uint32))
-    # 2. replay through the env's own step path
-    env = BatchedEnv(kind, n, device="cuda:0", seed=seed, params=make_params(rg))
-    env.reset()
-    obs_r, rew_r, done_r = [], [], []
-    for t in range(int(length.max())):
-        o, r, d = env.step(torch.from_numpy(np.ascontiguousarray(tr["actions"][t])).to("cuda:0"))
-        obs_r.append(o.cpu().numpy()); rew_r.append(r.cpu().numpy()); done_r.append(d.cpu().numpy())
-    env.close()
-    Tl = len(obs_r)
-    obs_r, rew_r, done_r = np.stack(obs_r), np.stack(rew_r), np.stack(done_r)
-    a = act[:Tl]
-    assert same_bits(rew_r[a], tr["reward"][:Tl][a]), "rewards differ from the replay"
-    assert np.array_equal(done_r[a], tr["done"][:Tl][a]), "done flags differ from the replay"
-    nxt = (steps[:Tl - 1] + 1) < length[None, :]  # obs[t + 1] recorded: step t was not the last
-    assert same_bits(obs_r[:Tl - 1][nxt], tr["obs"][1:Tl][nxt]), "observations differ from the replay"
-    # 3. the normaliser, bit for bit
-    rows = er.normalised_rows(tr["obs"])
-    assert same_bits(rows[act], tr["net_in"][act]), "net_in is not the float64 normaliser rounded"
-    # 4. the network within twice its forward error bound; actions = clip(raw), NaN kept
-    clipped = np.clip(tr["raw"], -1.0, 1.0)
-    assert same_bits(clipped[act], tr["actions"][act])
-    M = n // epm
-    for m in range(M):
-        envs = slice(m * epm, (m + 1) * epm)
-        p = er.unpack(W[m], O, A)
-        Tm = int(length[envs].max())
-        want, bound = er.forward_bound(p, er.windows(tr["net_in"][:Tm, envs]))
-        got = np.where(act[:Tm, envs, None], tr["raw"][:Tm, envs], want)
-        er.assert_within("raw action of member %d" % m, got, want, 2.0 * bound)
-    # 5. the return: float64 sum through the first done; the length: that step + 1
-    done = tr["done"] != 0
-    first = np.where(done.any(0), done.argmax(0), -1)
-    assert np.array_equal(first + 1, length), "length is not the first done + 1"
-    s = np.zeros(n)
-    for t in range(T):
-        s = np.where(act[t], s + tr["reward"][t].astype(np.float64), s)
-    assert same_bits(s, ret), "return is not the float64 sum of the step rewards"
+    check_es_trace(torch, kind, n, epm, W, ret, length, tr, make_params(rg), seed=seed)
 
 
 CASES = [

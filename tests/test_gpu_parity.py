@@ -9,7 +9,7 @@ The float64 build measures how far float32 drifts from the "true" trajectory.
 import numpy as np
 import pytest
 
-from helpers import make_words
+from helpers import draw_engine_params, make_words
 from oracle import OracleBatch
 from outlines import with_outline
 from tennisbot_rl_amd.params import (ENV_SWING, ENV_TENNIS, F_AUTO_RESET, F_DEFAULT, F_NET, F_RACKET_GROUND, STATE_WORDS, default_params,
@@ -453,17 +453,7 @@ def test_randomised_engine_parameters_stay_bit_exact(torch, kind):
     rng = np.random.default_rng(1234 + kind)
     n = 1024
     for trial in range(6):
-        over = dict(
-            gravity=rng.uniform(3.0, 15.0), lin_damp=rng.uniform(0.0, 0.1), ang_damp=rng.uniform(0.0, 0.1),
-            max_ang_step=rng.uniform(0.3, 1.2), rest_vel_threshold=rng.uniform(0.0, 1.0), erp=rng.uniform(0.02, 0.4),
-            contact_threshold=rng.uniform(2e-4, 3e-3), solver_iters=int(rng.integers(4, 80)), solver_tol=10.0 ** rng.uniform(-7, -4),
-            racket_mass=rng.uniform(1.0, 8.0), racket_inertia=tuple(rng.uniform(0.02, 0.3, 3)), ball_mass=rng.uniform(0.03, 0.2),
-            ball_inertia=10.0 ** rng.uniform(-5, -3), rest_racket=rng.uniform(0.0, 1.0), rest_court=rng.uniform(0.0, 1.0),
-            rest_goal=rng.uniform(0.0, 0.9), fric_racket=rng.uniform(0.0, 0.8), fric_court=rng.uniform(0.0, 0.8), fric_goal=rng.uniform(0.0, 0.8),
-            magnus_k=rng.choice([0.0, 1e-4, 5e-4]), ball_spin_max=rng.choice([0.0, 50.0, 200.0]),
-            lin_damp_quad=rng.uniform(0.0, 0.1), ang_damp_quad=rng.uniform(0.0, 0.1))
-        if trial % 2:
-            over.update(roll_racket=rng.uniform(0, 2e-3), roll_court=rng.uniform(0, 2e-3), roll_goal=rng.uniform(0, 2e-3))
+        over = draw_engine_params(rng, rolling=bool(trial % 2))
         scale = float(rng.uniform(1.0, 3.0)) if kind == ENV_TENNIS else 1.0
         env, ref = make_pair(torch, kind, n, seed=100 + trial, racket_scale=scale, **over)
         ref.L.tbo_set_threads(ref.h, 8)
@@ -1440,6 +1430,42 @@ def test_nonfinite_states_are_counted_like_the_oracle_counts_them(torch, kind):
         got, want = env.counters(), [int(x) for x in ref.counters()]
         assert list(got.values()) == want, (t, got, want)
     assert got["nonfinite_states"] >= poisoned  # (every poisoned env is still non-finite one step later: counted in both steps)
+    env.close()
+
+
+@pytest.mark.parametrize("path", ["step", "policy_rollout"])
+def test_parked_nonfinite_episode_end_is_counted_once(torch, path):
+    """a SwingRacket episode whose state is non-finite when its 26th step parks it for the pipelined fast-forward: nonfinite_states
+    counts that step once, when the fast-forward ends it -- the oracle judges every agent step once, after its fast-forward. NaN
+    actions (every 8th env), fed as actions to tb_step or as a NaN observation to the fused policy rollout, whose policy acts on it."""
+    from tennisbot_rl_amd.ppo import SWING_DEFAULTS, build_actor_critic, pack_policy
+    from tennisbot_rl_amd.stepper import BatchedEnv
+    n = 128
+    p = default_params()
+    env = BatchedEnv(ENV_SWING, n, device="cuda:0", seed=3, params=p, pipeline=True, track_terminal_obs=False, options=dict(ff_defer="all"))
+    pf = p.copy(); pf.flags |= F_AUTO_RESET
+    ref = OracleBatch(pf, ENV_SWING, n, seed=3, precision="f32")
+    o = env.reset()
+    same(o.cpu().numpy(), ref.reset(), "reset obs")
+    rng = np.random.default_rng(12)
+    if path == "step":
+        acts = rng.uniform(-1, 1, (26, n, 6)).astype(np.float32)
+        acts[:, ::8] = np.nan
+        for a in acts:
+            env.step(torch.from_numpy(a).cuda())
+    else:
+        torch.manual_seed(4)
+        blob = pack_policy(build_actor_critic(6, 6, tuple(SWING_DEFAULTS["net_arch"])).to("cuda:0"))
+        o[::8] = float("nan")
+        (_, _, _), (act, _, _, _) = env.policy_rollout(blob, o, 26, seed=5)
+        acts = act.cpu().numpy()
+        assert np.isnan(acts[:, ::8]).all() and np.isfinite(acts[:, 1::8]).all()
+    env.flush()
+    for a in acts:
+        ref.step(a)
+    got, want = env.counters(), [int(x) for x in ref.counters()]
+    assert list(got.values()) == want, (got, want)
+    assert got["nonfinite_states"] >= 26 * (n // 8) and got["episodes_finished"] == n and got["lockstep_violations"] == 0
     env.close()
 
 

@@ -1,6 +1,6 @@
 // Evolution-strategies population evaluation (tb_es_evaluate): one lane per env runs a whole episode with its member's GatedCNN
 // inside the step loop. Device code only; included by tb_stepper.hip after tb_kernels.hpp (KArgs, EnvRegs, swing_step,
-// tennis_step, park_env, flush_counters, fast_tanh are defined there). Part of the library's single translation unit.
+// tennis_step, end_agent_step, flush_counters, fast_tanh are defined there). Part of the library's single translation unit.
 //
 // What one lane computes is the reference's fitness_static (tennisbot/ES/fitness_functions.py:17-159) for one episode:
 //   * a FRESH Normalizer(O) per episode (evolution_strategy_static.py:25-44; the pool pickles the generation's zero normaliser
@@ -37,7 +37,7 @@
 // most 8) stages those rows in LDS first; otherwise (envs_per_member = 1: 64 members) every lane reads its row from global memory.
 //
 // ENV STEP: tennis_step / swing_step exactly as the other kernels call them. SwingRacket episodes are exactly 26 agent steps and
-// the 26th always starts the fast-forward: that lane is PARKED (park_env) and tb_ff_kernel finishes it; the host folds the
+// the 26th always starts the fast-forward: that lane is PARKED (park_for_ff) and tb_ff_kernel finishes it; the host folds the
 // terminal reward into the return after the pipeline's flush (tb_es_fold_kernel). Lanes whose episode is over -- and lanes beyond
 // n -- step the idle dummy (idle_env) so that every lane stays in the shared substep; a wave runs until its last lane is done.
 #pragma once
@@ -173,7 +173,8 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
       reinterpret_cast<float4*>(s_w)[k] = *reinterpret_cast<const float4*>(E.weights + (size_t)(m0 + r) * E.stride + 4 * c);
     }
   }
-  stage_hull(s_hull, A);  // (its barrier covers the staged rows too)
+  stage_hull(s_hull, A.hull, A.P.n_hull);
+  __syncthreads();  // (the staged rows too)
   const int m = (live ? i : last) / E.per_member;
   const float* W = staged ? s_w + (m - m0) * N::PP : E.weights + (size_t)m * E.stride;
   float* ring = s_ring + lane;
@@ -183,9 +184,7 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
   if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);  // the state tb_reset just wrote: the episode's start, no contacts cached
   Manifold M;
   init_manifold(M, lane, 64, !es_rows_in_registers(KIND, RG));
-  uint32_t cnt[TB_N_COUNTERS];
-#pragma unroll
-  for (int k = 0; k < TB_N_COUNTERS; ++k) cnt[k] = 0u;
+  uint32_t cnt[TB_N_COUNTERS] = {};
   KParams Pl = A.P;
   double nrm = 0.0, mean[NO], mdiff[NO];
 #pragma unroll
@@ -222,24 +221,9 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
     if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
     else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
     if (active) {
-      if (KIND == TB_ENV_SWING) {
-        make_obs<TB_ENV_SWING>(e, o);
-        d = e.done != TB_DONE_NO;
-        if (parked) {  // the 26th step: its reward is the fast-forward's, folded in after the flush
-          if (A.ff_rec) {
-            park_env<RG>(A.ff_rec, i, e, M);
-            if (A.ff_flag) A.ff_flag[i] = 1;
-            if (A.pool_dst_out) A.pool_dst_out[i] = A.reward + i;
-          } else {
-            cnt[8]++;  // (cannot happen: tb_es_evaluate resets every env and claims a slot; reported, never silent)
-          }
-          d = true;
-          rew = 0.0f;
-        }
-      }
-      cnt[6] += (uint32_t)ns;  // every substep of the step: the host adds no share for this kernel
-      if (!parked && !state_is_finite(e)) cnt[7]++;  // (a parked step's state is judged once, by the fast-forward that ends it)
-      if (!parked) ret += (double)rew;
+      end_agent_step<KIND, RG, false>(A, i, e, M, parked, ns, (size_t)i, o, d, cnt);  // (tb_es_evaluate claims a slot for every env)
+      if (parked) rew = 0.0f;  // the 26th step: its reward is the fast-forward's, folded in after the flush
+      else ret += (double)rew;
       len = t + 1;
       if (rec) {
         E.t_rew[(size_t)t * A.n + i] = rew;

@@ -183,6 +183,19 @@ TB_DEV void store_manifold(const KArgs& A, int i, const Manifold& M, bool had) {
     A.mflag[i] = 0;
   }
 }
+// A launch's state round trip for a lane that steps env i: its contact cache in (RG; true = it had cached points), ...
+template <bool RG>
+TB_DEV bool load_contacts(const KArgs& A, int i, bool live, Manifold& M) {
+  if (!RG || !live || A.mflag[i] == 0) return false;
+  load_manifold(A, i, M);
+  return true;
+}
+// ... and the state and the cache out (`all`: see store_env)
+template <int KIND, bool RG>
+TB_DEV void save_env(const KArgs& A, int i, const EnvRegs& e, const Manifold& M, bool all, bool had_contacts) {
+  store_env<KIND>(A.words, A.done_state, A.n, i, e, all);
+  if (RG && (M.n > 0 || had_contacts)) store_manifold(A, i, M, had_contacts);
+}
 
 template <int KIND>
 TB_DEV void make_obs(const EnvRegs& e, float* o) {
@@ -277,9 +290,16 @@ TB_DEV void reset_env(const KArgs& A, const float4* KP, int i, EnvRegs& e) {
 // fast-forward's record traffic was a cache that the default kernels never look at.)
 #define TB_FF_REC_MAX 12  // what the handle allocates per env and slot (the parameter block may switch the extended contacts on later)
 template <bool RG> constexpr int ff_rec() { return RG ? TB_FF_REC_MAX : 8; }
+// The record's tag, word z of float4 #7 (word w is the env index): what tb_ff_kernel tells live records by where no flag bytes exist.
+constexpr uint32_t REC_CONSUMED = 0u;  // finished by the pool run: not to be run again
+constexpr uint32_t REC_PARKED = 1u;    // parked by a step kernel
+constexpr uint32_t REC_SURVIVOR = 2u;  // still running when its fast-forward phase's budget was spent: REC_SURVIVOR | substeps so far << 8
+TB_DEV constexpr uint32_t rec_survivor(int ns) { return REC_SURVIVOR | ((uint32_t)ns << 8); }
+TB_DEV float& rec_tag(float4* r) { return r[7].z; }  // (a float word: read and written through __float_as_uint / __uint_as_float)
+// `slot`: the record's place in `rec`, `env`: the env it belongs to
 template <bool RG>
-TB_DEV void park_env(float4* rec, int i, const EnvRegs& e, const Manifold& M) {
-  float4* r = rec + (size_t)i * ff_rec<RG>();
+TB_DEV void park_env(float4* rec, int slot, int env, uint32_t tag, const EnvRegs& e, const Manifold& M) {
+  float4* r = rec + (size_t)slot * ff_rec<RG>();
   r[0] = make_float4(e.r.p.x, e.r.p.y, e.r.p.z, e.r.q.x);
   r[1] = make_float4(e.r.q.y, e.r.q.z, e.r.q.w, e.r.v.x);
   r[2] = make_float4(e.r.v.y, e.r.v.z, e.r.w.x, e.r.w.y);
@@ -287,7 +307,7 @@ TB_DEV void park_env(float4* rec, int i, const EnvRegs& e, const Manifold& M) {
   r[4] = make_float4(e.b.v.x, e.b.v.y, e.b.v.z, e.b.w.x);
   r[5] = make_float4(e.b.w.y, e.b.w.z, e.aux[0], e.aux[1]);
   r[6] = make_float4(e.aux[2], e.aux[3], e.aux[4], e.aux[5]);
-  r[7] = make_float4(__int_as_float(e.step_count), __uint_as_float(e.episode), __uint_as_float(1u), __int_as_float(i));
+  r[7] = make_float4(__int_as_float(e.step_count), __uint_as_float(e.episode), __uint_as_float(tag), __int_as_float(env));
   if constexpr (!RG) return;
   // (statically indexed: registers; lanes without cached points -- nearly all -- skip the LDS reads)
   uint32_t ids = 0u;
@@ -537,12 +557,63 @@ TB_DEV void flush_counters(unsigned long long* counters, const uint32_t* cnt) {
   }
 }
 
-TB_DEV void stage_hull(float4* s_hull, const KArgs& A) {
-  for (int k = threadIdx.x; k < 2 * A.P.n_hull; k += blockDim.x) s_hull[k] = A.hull[k];
-  for (int k = TB_HULL_PLANES + threadIdx.x; k < TB_HULL_LDS; k += blockDim.x) s_hull[k] = A.hull[k];
-  __syncthreads();
+// the outline table's rows in use into LDS, by the whole workgroup; the caller places the barrier behind it
+TB_DEV void stage_hull(float4* s_hull, const float4* hull, int n_hull) {
+  for (int k = threadIdx.x; k < 2 * n_hull; k += blockDim.x) s_hull[k] = hull[k];
+  for (int k = TB_HULL_PLANES + threadIdx.x; k < TB_HULL_LDS; k += blockDim.x) s_hull[k] = hull[k];
 }
 static_assert(sizeof(KParams) <= sizeof(float4) * TB_KP_ROWS, "the LDS copy of the parameter block needs more rows");
+
+// ------------------------------------------------------------------------------------------
+// the end of an agent step: what every kernel that steps envs (tb_step_kernel, tb_policy_rollout_kernel, tb_es_rollout_kernel) does
+// for a live lane after swing_step / tennis_step
+
+// A SwingRacket step that starts the fast-forward (swing_step's `parked`) hands the env to tb_ff_kernel: its state goes into record i
+// of the launch's slot, and tb_ff_kernel writes this step's reward (to A.reward + rew_row), terminal observation and substep count
+// later. Every SwingRacket episode ends inside that step (the loop only exits through done), so done = 1 is known now and the env
+// restarts at once. counters[8]: a lane that parks with no slot claimed. The host claims one for every launch that can park (the
+// lockstep episode phase, see launch_step), so such a lane means that invariant was broken: reported, never silent.
+template <bool RG>
+TB_DEV void park_for_ff(const KArgs& A, int i, const EnvRegs& e, const Manifold& M, size_t rew_row, uint32_t* cnt) {
+  if (A.ff_rec) {
+    park_env<RG>(A.ff_rec, i, i, REC_PARKED, e, M);
+    if (A.ff_flag) A.ff_flag[i] = 1;  // (a byte array of its own: cleared by the fast-forward with one coalesced store per wave, where a 4-byte
+                                      //  store into each record cost a 64-byte memory write per env; the record's own tag says "parked" too)
+    if (A.pool_dst_out) A.pool_dst_out[i] = A.reward + rew_row;  // parked straight into the pool (TbOptions.ff_defer = 2): where its reward will go
+  } else {
+    cnt[8]++;
+  }
+}
+
+// The agent step's observation and done flag (SwingRacket; tennis_step wrote both for Tennisbot), its parking, and its counts:
+//   counters[6], substeps: HOST_COUNTS_FIRST kernels count only the substeps beyond each step's first -- the host adds n x T per launch
+//     (count_first_substeps; one atomic per launch from one lane was 2.7 % of the 4096-env rate); tb_es_rollout_kernel, whose lanes
+//     leave at their own episode ends, counts every substep;
+//   counters[7], non-finite states: the state after the step, unless it parked -- tb_ff_kernel judges a parked step once, when its
+//     flight ends.
+template <int KIND, bool RG, bool HOST_COUNTS_FIRST>
+TB_DEV void end_agent_step(const KArgs& A, int i, const EnvRegs& e, const Manifold& M, bool parked, int ns, size_t rew_row, float* o, bool& d,
+                           uint32_t* cnt) {
+  if (!parked && !state_is_finite(e)) cnt[7]++;
+  if (KIND == TB_ENV_SWING) {
+    make_obs<TB_ENV_SWING>(e, o);
+    d = e.done != TB_DONE_NO;  // swingracket_env.py:145 returns self.done
+    if (parked) {
+      park_for_ff<RG>(A, i, e, M, rew_row, cnt);
+      d = true;
+    }
+  }
+  cnt[6] += (uint32_t)(HOST_COUNTS_FIRST ? ns - 1 : ns);
+}
+
+// a new episode in env i's registers and its first observation (KP: see reset_env)
+template <int KIND>
+TB_DEV void restart_episode(const KArgs& A, const float4* KP, int i, EnvRegs& e, Manifold& M, float* o) {
+  e.episode += 1u;
+  reset_env<KIND>(A, KP, i, e);
+  M.n = 0; M.deep = 0;  // a rebuilt world has no contacts yet
+  make_obs<KIND>(e, o);
+}
 
 // THE TWO-WAVE STEP (tb_step_kernel<.., TWO_WAVE>: the pipelined SwingRacket one-step kernel at small batch sizes).
 // A workgroup of two waves steps 64 envs. At 4096 envs one-wave workgroups leave ~94 % of the SIMDs idle, and a lone wave issues the
@@ -611,9 +682,7 @@ TB_DEV bool two_wave_step(const KArgs& A, const EnvRegs& e, const float* a, int 
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (LDS only: no global store has been issued yet)
     TB_DIAG_MARK(mk0 + 3);
     if (__builtin_amdgcn_readfirstlane(s_rare)) return false;
-    uint32_t cnt[TB_N_COUNTERS];
-#pragma unroll
-    for (int k = 0; k < TB_N_COUNTERS; ++k) cnt[k] = 0u;
+    uint32_t cnt[TB_N_COUNTERS] = {};
     if (live) {
       st<K>(A.words, TB_W_RP, A.n, i, r.p.x); st<K>(A.words, TB_W_RP + 1, A.n, i, r.p.y); st<K>(A.words, TB_W_RP + 2, A.n, i, r.p.z);
       st<K>(A.words, TB_W_RQ, A.n, i, r.q.x); st<K>(A.words, TB_W_RQ + 1, A.n, i, r.q.y); st<K>(A.words, TB_W_RQ + 2, A.n, i, r.q.z);
@@ -786,10 +855,7 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
 #endif
   Manifold M;
   init_manifold(M, POLICY ? (int)(threadIdx.x & 63) : (int)threadIdx.x, POLICY ? 64 : (int)blockDim.x, !REGROWS);
-  bool had_contacts = false;
-  if constexpr (RG) {
-    if (live && !(POLICY && threadIdx.x >= 64)) { had_contacts = A.mflag[i] != 0; if (had_contacts) load_manifold(A, i, M); }
-  }
+  const bool had_contacts = load_contacts<RG>(A, i, live && !(POLICY && threadIdx.x >= 64), M);
   if (POLICY) {
     // one barrier for both hand-offs (outline table, action means); the outline rows are requested
     // before the towers' operands and parked in a register meanwhile
@@ -803,16 +869,13 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
     if (threadIdx.x >= 64) return;  // no barrier below this point
     if (live) policy_sample<KIND>(A, s_mean, i, e, a);
   } else if (!TABLE_IN_MEMORY && !LAZYTAB) {
-    for (int k = threadIdx.x; k < 2 * w_nhull; k += blockDim.x) s_lds_hull[k] = w_hull[k];
-    for (int k = TB_HULL_PLANES + threadIdx.x; k < TB_HULL_LDS; k += blockDim.x) s_lds_hull[k] = w_hull[k];
+    stage_hull(s_lds_hull, w_hull, w_nhull);
     __syncthreads();
   }
   TB_DIAG_WAIT_LOADS(live);
   TB_DIAG_NOW(t_loaded);
 
-  uint32_t cnt[TB_N_COUNTERS];
-#pragma unroll
-  for (int k = 0; k < TB_N_COUNTERS; ++k) cnt[k] = 0u;
+  uint32_t cnt[TB_N_COUNTERS] = {};
 
   TB_DIAG_STAMPS_BEGIN(st);
   TB_DIAG_NOW(t_kernel0);
@@ -838,38 +901,14 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
       int ns = 1;
       bool d, parked = false;
       float rew;
-      if (KIND == TB_ENV_SWING) {
-        rew = swing_step<FORM>(A.P, s_hull, e, M, a, ns, cnt, LEAN || A.defer != 0, parked TB_STAMP_PASS, w_hull);
-        make_obs<TB_ENV_SWING>(e, o);
-        d = e.done != TB_DONE_NO;  // swingracket_env.py:145 returns self.done
-        if (parked) {
-          // Every SwingRacket episode ends inside this step (the loop only exits through done), so
-          // done = 1 is known now; reward, terminal obs and substep count of this step are written
-          // later by tb_ff_kernel from the parked state. The env itself restarts immediately.
-          if (A.ff_rec) {
-            park_env<RG>(A.ff_rec, i, e, M);
-            if (A.ff_flag) A.ff_flag[i] = 1;  // (a byte array of its own: cleared by the fast-forward with one coalesced store per wave, where a 4-byte
-                                              //  store into each record cost a 64-byte memory write per env; the record's own tag says "parked" too)
-            if (A.pool_dst_out) A.pool_dst_out[i] = A.reward + row;  // parked straight into the pool (TbOptions.ff_defer = 2): where its reward will go
-          } else {
-            cnt[8]++;  // lockstep invariant broken (see launch_step): reported, never silent
-          }
-          d = true;
-        }
-      } else {
-        rew = tennis_step<FORM>(A.P, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
-      }
-      cnt[6] += (uint32_t)(ns - 1);  // substeps beyond the first of each agent step
+      if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(A.P, s_hull, e, M, a, ns, cnt, LEAN || A.defer != 0, parked TB_STAMP_PASS, w_hull);
+      else rew = tennis_step<FORM>(A.P, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
+      end_agent_step<KIND, RG, true>(A, i, e, M, parked, ns, row, o, d, cnt);
       ns_total += ns;
-      if (!parked && !state_is_finite(e))  // (a parked step's state is judged once, by the fast-forward that ends it)
-        cnt[7]++;
       if (d && (A.P.flags & TB_F_AUTO_RESET)) {
         cnt[5]++;
         if (A.term_obs && !parked) write_obs<KIND>(A.term_obs, (size_t)i, o);
-        e.episode += 1u;
-        reset_env<KIND>(A, s_hull + TB_HULL_KP, i, e);
-        M.n = 0; M.deep = 0;  // a rebuilt world has no contacts yet
-        make_obs<KIND>(e, o);
+        restart_episode<KIND>(A, s_hull + TB_HULL_KP, i, e, M, o);
         any_reset = true;
       }
       write_obs<KIND>(A.obs, row, o);
@@ -884,13 +923,10 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
     }
     TB_DIAG_ADD_LANE0(15, stamp_now() - t_loaded);  // compute + output stores issued
     if (A.substeps) A.substeps[i] = ns_total;
-    store_env<KIND>(A.words, A.done_state, A.n, i, e, any_reset);
-    if constexpr (RG) { if (M.n > 0 || had_contacts) store_manifold(A, i, M, had_contacts); }
+    save_env<KIND, RG>(A, i, e, M, any_reset, had_contacts);
   }
   TB_DIAG_ADD_LANE0(7, t_loaded - t_entry);  // state + outline loads landed
   flush_counters(A.counters, cnt);
-  // (the first substep of every env in every agent step is counted by the HOST, see count_first_substeps: one atomic per launch
-  //  from one lane was 2.7 % of the 4096-env rate)
   TB_DIAG_STAMPS_END(st);
   TB_DIAG_ADD_LANE0(8, stamp_now() - t_kernel0);  // per-wave scalars: cycles in the kernel, waves, 100 MHz ticks
   TB_DIAG_ADD_LANE0(9, 1);
@@ -933,8 +969,7 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   __shared__ __attribute__((aligned(16))) float s_mean[E * 8];
   __shared__ __attribute__((aligned(16))) float s_obs[E * NO];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int k = threadIdx.x; k < 2 * A.P.n_hull; k += blockDim.x) s_hull[k] = A.hull[k];
-  for (int k = TB_HULL_PLANES + threadIdx.x; k < TB_HULL_LDS; k += blockDim.x) s_hull[k] = A.hull[k];
+  stage_hull(s_hull, A.hull, A.P.n_hull);  // (behind the first barrier of each role below)
   if (wave < 2 * S) {
     const int tower = wave / S, slice = wave % S, grp = lane >> 4;
     const int slot = slice * TB_POLICY_SLICE + (lane & 15), env = blockIdx.x * E + slot;
@@ -968,13 +1003,8 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);
   Manifold M;
   init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
-  bool had_contacts = false;
-  if constexpr (RG) {
-    if (live) { had_contacts = A.mflag[i] != 0; if (had_contacts) load_manifold(A, i, M); }
-  }
-  uint32_t cnt[TB_N_COUNTERS];
-#pragma unroll
-  for (int k = 0; k < TB_N_COUNTERS; ++k) cnt[k] = 0u;
+  const bool had_contacts = load_contacts<RG>(A, i, live, M);
+  uint32_t cnt[TB_N_COUNTERS] = {};
   bool any_reset = false;
   TB_DIAG_STAMPS_BEGIN(st);
   __syncthreads();
@@ -1020,29 +1050,10 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
       else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
 #endif
       if (live) {
-        if (KIND == TB_ENV_SWING) {
-          make_obs<TB_ENV_SWING>(e, o);
-          d = e.done != TB_DONE_NO;
-          if (parked) {
-            if (A.ff_rec) {
-              park_env<RG>(A.ff_rec, i, e, M);
-              if (A.ff_flag) A.ff_flag[i] = 1;
-              if (A.pool_dst_out) A.pool_dst_out[i] = A.reward + (size_t)t * A.st_rew + i;
-            } else {
-              cnt[8]++;  // lockstep invariant broken (see launch_policy_rollout): reported, never silent
-            }
-            d = true;
-          }
-        }
-        cnt[6] += (uint32_t)(ns - 1);
-        if (!parked && !state_is_finite(e))  // (judged by the fast-forward that ends a parked step)
-          cnt[7]++;
+        end_agent_step<KIND, RG, true>(A, i, e, M, parked, ns, (size_t)t * A.st_rew + i, o, d, cnt);
         if (d) {  // (rollouts require TB_F_AUTO_RESET)
           cnt[5]++;
-          e.episode += 1u;
-          reset_env<KIND>(A, s_hull + TB_HULL_KP, i, e);
-          M.n = 0; M.deep = 0;
-          make_obs<KIND>(e, o);
+          restart_episode<KIND>(A, s_hull + TB_HULL_KP, i, e, M, o);
           any_reset = true;
         }
 #pragma unroll
@@ -1061,10 +1072,7 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
       }
     }
   }
-  if (live) {
-    store_env<KIND>(A.words, A.done_state, A.n, i, e, any_reset);
-    if constexpr (RG) { if (M.n > 0 || had_contacts) store_manifold(A, i, M, had_contacts); }
-  }
+  if (live) save_env<KIND, RG>(A, i, e, M, any_reset, had_contacts);
   flush_counters(A.counters, cnt);
   TB_DIAG_STAMPS_END(st);
   TB_DIAG_ADD_LANE0(9, 1);
@@ -1124,10 +1132,9 @@ __global__ void __launch_bounds__(64, (ESC && !RG) ? 4 : 1) tb_ff_kernel(KArgs A
   constexpr int TB_FF_REC = ff_rec<RG>();
   __shared__ float4 s_hull[TB_HULL_LDS];
   const int lane = threadIdx.x & 63;
-  stage_hull(s_hull, A);
-  uint32_t cnt[TB_N_COUNTERS];
-#pragma unroll
-  for (int k = 0; k < TB_N_COUNTERS; ++k) cnt[k] = 0u;
+  stage_hull(s_hull, A.hull, A.P.n_hull);
+  __syncthreads();
+  uint32_t cnt[TB_N_COUNTERS] = {};
   uint32_t n_sealed = 0u;
   TB_DIAG_STAMPS_BEGIN(st);
   int n_src = A.ff_src_count ? *A.ff_src_count : A.n;
@@ -1148,7 +1155,7 @@ __global__ void __launch_bounds__(64, (ESC && !RG) ? 4 : 1) tb_ff_kernel(KArgs A
       const float4* g = A.ff_rec + (size_t)src * TB_FF_REC;
 #pragma unroll
       for (int k = 0; k < TB_FF_REC; ++k) r[k] = g[k];
-      live = A.ff_flag ? A.ff_flag[src] != 0 : (__float_as_uint(r[7].z) & 255u) != 0u;
+      live = A.ff_flag ? A.ff_flag[src] != 0 : (__float_as_uint(rec_tag(r)) & 255u) != REC_CONSUMED;
     }
     bool unfinished = false;
     EnvRegs e;
@@ -1157,8 +1164,8 @@ __global__ void __launch_bounds__(64, (ESC && !RG) ? 4 : 1) tb_ff_kernel(KArgs A
     int i = 0, ns = 1;  // fresh from the step kernel: it ran the first substep of this agent step
     if (live) {
       unpark_env<RG>(r, e, M, i);
-      const uint32_t tag = __float_as_uint(r[7].z);
-      if ((tag & 255u) == 2u) ns = (int)(tag >> 8);  // a survivor of an earlier phase: substeps so far
+      const uint32_t tag = __float_as_uint(rec_tag(r));
+      if ((tag & 255u) == REC_SURVIVOR) ns = (int)(tag >> 8);  // a survivor of an earlier phase: substeps so far
       const vec3 zero = mk(0.0f, 0.0f, 0.0f);
       // the first loop substep runs without any force (the accumulators were cleared by the agent's substep), every later
       // one with the restoring force of the state before it (swingracket_env.py:135-141): what a resumed env recomputes
@@ -1199,7 +1206,7 @@ __global__ void __launch_bounds__(64, (ESC && !RG) ? 4 : 1) tb_ff_kernel(KArgs A
       // the pool run: a consumed record says so itself. A region's records are expected to be rewritten whole by the next launch that
       // parks into it -- but an env that does NOT park there (the lockstep invariant broken: counters[8]) would leave this record, with
       // its destination pointer, to be run once more by the next pool run. One 4-byte store per episode end.
-      if (POOL && A.pool_dst_in) reinterpret_cast<uint32_t*>(A.ff_rec + (size_t)src * TB_FF_REC + 7)[2] = 0u;
+      if (POOL && A.pool_dst_in) rec_tag(A.ff_rec + (size_t)src * TB_FF_REC) = __uint_as_float(REC_CONSUMED);
     }
     if (A.ff_next) {  // survivors: one atomic per wave reserves their places in the next phase's list
       const unsigned long long m = __ballot(unfinished);
@@ -1208,11 +1215,9 @@ __global__ void __launch_bounds__(64, (ESC && !RG) ? 4 : 1) tb_ff_kernel(KArgs A
         if (lane == 0) first = atomicAdd(A.ff_next_count, __popcll(m));
         first = __shfl(first, 0, 64);
         if (unfinished) {
-          park_env<RG>(A.ff_next, first + __popcll(m & ((1ull << lane) - 1ull)), e, M);
-          uint32_t* w = reinterpret_cast<uint32_t*>(A.ff_next + (size_t)(first + __popcll(m & ((1ull << lane) - 1ull))) * TB_FF_REC + 7);
-          w[2] = 2u | ((uint32_t)ns << 8);
-          w[3] = (uint32_t)i;
-          if (POOL && A.pool_dst_out) A.pool_dst_out[first + __popcll(m & ((1ull << lane) - 1ull))] = A.reward + i;
+          const int slot = first + __popcll(m & ((1ull << lane) - 1ull));
+          park_env<RG>(A.ff_next, slot, i, rec_survivor(ns), e, M);
+          if (POOL && A.pool_dst_out) A.pool_dst_out[slot] = A.reward + i;
         }
       }
     }
@@ -1236,15 +1241,13 @@ __global__ void __launch_bounds__(256) tb_reset_kernel(KArgs A) {
   if (i >= A.n) return;
   if (A.mask && !A.mask[i]) return;
   EnvRegs e;
-  e.episode = A.words[(size_t)(Dims<KIND>::W - 1) * A.n + i] + 1u;
-  reset_env<KIND>(A, A.hull + TB_HULL_KP, i, e);
+  Manifold M;  // (no cache in registers here: mflag below)
+  float o[Dims<KIND>::O];
+  e.episode = A.words[(size_t)(Dims<KIND>::W - 1) * A.n + i];
+  restart_episode<KIND>(A, A.hull + TB_HULL_KP, i, e, M, o);
   store_env<KIND>(A.words, A.done_state, A.n, i, e, true);
-  A.mflag[i] = 0;  // a rebuilt world has no contacts yet
-  if (A.obs) {
-    float o[Dims<KIND>::O];
-    make_obs<KIND>(e, o);
-    write_obs<KIND>(A.obs, (size_t)i, o);
-  }
+  A.mflag[i] = 0;
+  if (A.obs) write_obs<KIND>(A.obs, (size_t)i, o);
 }
 
 // identity orientation, episode = -1 so that the first reset starts episode 0

@@ -94,11 +94,12 @@ void to_kparams(const TbParams* p, KParams* k, float* planes) {
   k->static_top = top;
   {  // cull planes: 8 fixed directions + the 4 longest edges, each pushed out by its own rounding
     int np = 0;
-    for (int d = 0; d < 8; ++d) {
-      double ang = d * 0.78539816339744830962, ny = cos(ang), nz = sin(ang), hmax = -1e30;
+    auto put_plane = [&](double ny, double nz) {  // (ny, nz, the outline's support value along it)
+      double hmax = -1e30;
       for (int i = 0; i < p->n_hull; ++i) { double v = ny * p->hull_edges[i][0] + nz * p->hull_edges[i][1]; hmax = v > hmax ? v : hmax; }
       planes[3 * np] = (float)ny; planes[3 * np + 1] = (float)nz; planes[3 * np + 2] = (float)(hmax + 1e-6); ++np;
-    }
+    };
+    for (int d = 0; d < 8; ++d) { const double ang = d * 0.78539816339744830962; put_plane(cos(ang), sin(ang)); }
     bool used[TB_MAX_HULL] = {false};
     for (int pick = 0; pick < TB_N_CULL - 8; ++pick) {
       int best = -1; double bl = -1.0;
@@ -107,10 +108,8 @@ void to_kparams(const TbParams* p, KParams* k, float* planes) {
         if (!used[i] && l2 > bl) { bl = l2; best = i; }
       }
       used[best] = true;
-      double il = 1.0 / sqrt(bl), ny = p->hull_edges[best][3] * il, nz = -p->hull_edges[best][2] * il;  // outward normal of a CCW edge
-      double hmax = -1e30;
-      for (int i = 0; i < p->n_hull; ++i) { double v = ny * p->hull_edges[i][0] + nz * p->hull_edges[i][1]; hmax = v > hmax ? v : hmax; }
-      planes[3 * np] = (float)ny; planes[3 * np + 1] = (float)nz; planes[3 * np + 2] = (float)(hmax + 1e-6); ++np;
+      const double il = 1.0 / sqrt(bl);
+      put_plane(p->hull_edges[best][3] * il, -p->hull_edges[best][2] * il);  // outward normal of a CCW edge
     }
   }
   // same float operations as the rows would do per contact (oracle setup_row): bit-identical
@@ -118,12 +117,143 @@ void to_kparams(const TbParams* p, KParams* k, float* planes) {
   k->ball_kt = 1.0f / fmaf(p->ball_inv_inertia, p->ball_radius * p->ball_radius, p->ball_inv_mass);
 }
 
-}  // namespace
+// test hook (tb_diag_fail_alloc): the n-th device allocation of the pipeline or the pool (tb_set_pipeline, tb_set_params) fails with hipErrorOutOfMemory
+int g_fail_alloc_countdown = 0;
+hipError_t pipeline_malloc(void** p, size_t bytes) {
+  if (g_fail_alloc_countdown > 0 && --g_fail_alloc_countdown == 0) { *p = nullptr; return hipErrorOutOfMemory; }
+  return hipMalloc(p, bytes);
+}
+hipError_t pipeline_calloc(void** p, size_t bytes) { const hipError_t e = pipeline_malloc(p, bytes); return e == hipSuccess ? hipMemset(*p, 0, bytes) : e; }  // ... zeroed
+
+// a kernel launch and its check (the stepping launches clear a stale sticky error first: their check is about THIS launch)
+template <class... P, class... A>
+int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t q, const A&... args) {
+  hipLaunchKernelGGL(kern, grid, block, lds, q, args...);
+  HIP_TRY(hipGetLastError());
+  return TB_OK;
+}
+// free / destroy what is there, and forget it
+template <class T> void drop(T*& p) { if (p) (void)hipFree(p); p = nullptr; }
+void drop(hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+void drop(hipStream_t& q) { if (q) (void)hipStreamDestroy(q); q = nullptr; }
+// None: work issued to `s` runs; Active: it only becomes a node of the graph being captured
+int capture_status(hipStream_t s, hipStreamCaptureStatus* st) { *st = hipStreamCaptureStatusNone; HIP_TRY(hipStreamIsCapturing(s, st)); return TB_OK; }
 
 #define TB_FF_SLOTS 8  // parked-state buffers + side streams: ~2.5 fast-forwards are in flight in steady state
 #define TB_PIPELINE_MAX_ENVS (1 << 24)
 #define TB_DEFER_MAX_ENVS 131072  // deferred stragglers: a small-batch scheme (large batches run the fast-forward in phases)
 #define TB_TWO_WAVE_MAX_ENVS 16384  // the two-wave step kernel up to here (auto)
+constexpr int kEpisodeSteps = 26;  // a SwingRacket episode is exactly this many agent steps (the kernels keep their own 25 / 26)
+constexpr size_t kSealedWord = (size_t)TB_N_COUNTERS * TB_COUNTER_SHARDS;  // the counter block: [TB_COUNTER_SHARDS][TB_N_COUNTERS] ...
+constexpr size_t kCounterWords = kSealedWord + 1;  // ... + one word: substeps booked by the pool's sealed-fate exit
+
+// The scheduler's parts: plain data, all zero = never built (the handle is calloc'ed).
+// Episode phase: agent steps since the last full reset, known while every env is in lockstep
+struct Phase {
+  int at, valid, at_capture, valid_at_capture;  // ..._at_capture: snapshot taken by tb_pipeline_sync(h, 1), restored by tb_pipeline_sync(h, 0) / tb_pipeline_recover
+  void set(int steps) { valid = 1; at = steps; }
+  void invalidate() { valid = 0; }
+  void advance(int T) { if (valid) at = (at + T) % kEpisodeSteps; }
+  bool launch_ends_episode(int T) const { return at + T == kEpisodeSteps; }
+  int chunk(int left) const { const int room = kEpisodeSteps - at; return left < room ? left : room; }  // a launch ends where the episodes end
+  void save_for_capture() { at_capture = at; valid_at_capture = valid; }
+  void restore() { at = at_capture; valid = valid_at_capture; }
+};
+
+// One fast-forward slot: a side stream, the events that fork it from the caller's stream and close its work, the parking buffers
+struct FfSlot {
+  hipStream_t side;  // one stream per slot: consecutive fast-forwards overlap each other too
+  hipEvent_t ev_step, ev_ff;
+  int busy;
+  float4* rec;       // [n][ff_rec<RG>()] parked records (park_env), allocated for TB_FF_REC_MAX
+  uint8_t* flag;     // [n] parked flags
+  float4* list[2];   // survivors of fast-forward phases 1 and 2 (worst case: every env), compacted
+  int* count;        // [2] their numbers
+  // fast-forwards enqueued on this slot (= per side stream: only there is "the first k have finished" the same as "k have
+  // finished" -- fast-forwards of different episodes overtake each other, one with a ball at rest on a grounded racket
+  // runs five times as long as the next): inside the current / latest capture; eagerly since tb_mark_begin
+  long long in_capture, eager;
+  int open() {
+    HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&ev_step, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ev_ff, hipEventDisableTiming));
+    return TB_OK;
+  }
+  void close() { drop(side); drop(ev_step); drop(ev_ff); busy = 0; }
+  int build(int n, int phases) {
+    if (int rc = open()) return rc;
+    const size_t wb = sizeof(float4) * (size_t)TB_FF_REC_MAX * n;
+    HIP_TRY(pipeline_calloc((void**)&rec, wb));
+    HIP_TRY(pipeline_calloc((void**)&flag, (size_t)n));
+    for (int ph = 0; ph + 1 < phases; ++ph) HIP_TRY(pipeline_malloc((void**)&list[ph], wb));
+    HIP_TRY(pipeline_calloc((void**)&count, 2 * sizeof(int)));
+    return TB_OK;
+  }
+  void free_buffers() { drop(rec); drop(flag); drop(list[0]); drop(list[1]); drop(count); }
+};
+
+struct Slots {
+  FfSlot s[TB_FF_SLOTS];
+  int next, last;                    // the slot the next parking launch takes; the one that closed last (-1: none to order against)
+  const void *last_term, *last_sub;  // shared late-written buffers force ordering between fast-forwards
+  bool built() const { return s[0].side != nullptr; }
+  int claim() { const int k = next; next = (k + 1) % TB_FF_SLOTS; return k; }
+  // what was enqueued before no longer orders what comes next (joined by the host, or on the other side of a capture boundary)
+  void forget_ordering() { for (FfSlot& f : s) f.busy = 0; last = -1; last_term = nullptr; last_sub = nullptr; }
+  void forget_capture() { for (FfSlot& f : s) f.in_capture = 0; }
+};
+
+// Deferred stragglers (tb_ff_kernel<.., POOL>; TbOptions.ff_defer): one pool for all episodes between two flushes.
+// 64 n records (two reference-sized rollouts of 1100 steps with EVERY episode end in it) + the slack
+// all resident fast-forward waves could overshoot it by (slots x n), 192 B each + an 8-byte destination pointer: 14 KB per env.
+// Allocated only for handles whose defer_mode can be non-zero: on request, up to 16384 envs, or above that (to 131072) once the
+// parameter block turns racket<->court contact on -- tb_set_params asks again, with the new flags, before it commits them. (Until round 4 every pipelined handle up
+// to 131072 envs got one: 1.9 GB at that size that the default kernels never touched.) Zeroed: a record's tag word says whether
+// it holds a parked env, and no launch may ever find a tag it did not write.
+struct Pool {
+  float4* rec;             // [cap + slack][TB_FF_REC_MAX]; non-null = a usable pool (all of it or none)
+  float** dst;             // [cap + slack] where each deferred env's terminal reward goes
+  int* count;
+  int cap, slack, pending;  // pending: records may be waiting (the next flush runs the pool kernel)
+  int run_upto;            // ... of which the first run_upto have had their launch already (at a progress mark)
+  int episodes;            // ff_defer = 2: episodes parked straight into the pool since the last flush (records [k n, (k + 1) n) each)
+  hipEvent_t ev_direct;    // ... and the latest launch that did so (a flush on another stream waits for it)
+  hipEvent_t ev_run;       // the last pool run (+ the reset of its counter): later fast-forwards append behind it, whatever stream flushed
+  int run_ev_valid, direct_ev_valid;
+  size_t records() const { return (size_t)cap + (size_t)slack; }
+  void idle() { pending = 0; episodes = 0; run_upto = 0; }             // nothing is waiting for a pool run
+  void events_forgotten() { run_ev_valid = 0; direct_ev_valid = 0; }  // (an event recorded on one side of a capture boundary means nothing on the other)
+  int build(int n) {  // into a zeroed local value: the caller swaps it in on success and releases it otherwise
+    cap = 64 * n; slack = TB_FF_SLOTS * n;
+    HIP_TRY(pipeline_calloc((void**)&rec, sizeof(float4) * (size_t)TB_FF_REC_MAX * records()));
+    HIP_TRY(pipeline_calloc((void**)&dst, sizeof(float*) * records()));
+    HIP_TRY(pipeline_calloc((void**)&count, sizeof(int)));
+    HIP_TRY(hipEventCreateWithFlags(&ev_run, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ev_direct, hipEventDisableTiming));
+    return TB_OK;
+  }
+  void release() { drop(rec); drop(dst); drop(count); drop(ev_run); drop(ev_direct); *this = Pool{}; }
+};
+
+// Progress marks (tb_mark_record). h: pinned host counters written by tb_mark_kernel -- [k] firings of mark k
+// (a kernel on the caller's own stream), [TB_MAX_MARKS + slot] fast-forwards finished (a kernel behind every tb_ff_kernel on
+// its side stream). No extra streams, no extra graph edges: a mark never makes anything wait. What a mark still has
+// to wait for -- the fast-forwards enqueued before it -- is host arithmetic over these two kinds of counters.
+struct Marks {
+  unsigned long long* h;
+  unsigned long long snap_ff[TB_FF_SLOTS], snap_marks[TB_MAX_MARKS];  // the counters at tb_mark_begin (nothing of this handle in flight)
+  int on;                                       // tb_mark_enable: fast-forwards are followed by their counting kernel
+  long long ff_before[TB_MAX_MARKS][TB_FF_SLOTS];  // fast-forwards enqueued per slot before the mark: inside a capture FfSlot::in_capture at that point, eagerly FfSlot::eager (in_capture says which)
+  int in_capture[TB_MAX_MARKS];
+  int ensure() {
+    if (h) return TB_OK;
+    HIP_TRY(hipHostMalloc((void**)&h, sizeof(unsigned long long) * (TB_MAX_MARKS + TB_FF_SLOTS), hipHostMallocDefault));
+    memset(h, 0, sizeof(unsigned long long) * (TB_MAX_MARKS + TB_FF_SLOTS));
+    return TB_OK;
+  }
+};
+
+}  // namespace
 
 struct TbHandle {
   int device, kind, n, block;
@@ -137,50 +267,20 @@ struct TbHandle {
   float4* d_hull;
   float4* h_hull;  // pinned staging copy of the outline table
   float cull_planes[TB_N_CULL][3];  // derived from the outline (to_kparams); they travel behind it in the same table
-  unsigned long long* d_counters;     // [TB_COUNTER_SHARDS][TB_N_COUNTERS] + one word: substeps booked by the pool's sealed-fate exit
+  unsigned long long* d_counters;     // [kCounterWords]
   uint32_t* d_mani;                   // [TB_MANI_WORDS][n] racket<->court contact caches
   uint8_t* d_mflag;                   // [n]
-  // pipelined fast-forward
-  int pipeline;            // enabled by tb_set_pipeline
-  int phase, phase_valid;  // agent steps since the last full reset (SwingRacket episodes are exactly 26 steps)
-  int phase_at_capture, phase_valid_at_capture;  // snapshot taken by tb_pipeline_sync(h, 1), restored by tb_pipeline_sync(h, 0) / tb_pipeline_recover
   int params_generation;   // tb_set_params count: captured launches carry the parameter block they were captured with
-  hipStream_t side[TB_FF_SLOTS];  // one stream per slot: consecutive fast-forwards overlap each other too
-  const void *last_term, *last_sub;  // shared late-written buffers force ordering between fast-forwards
-  int last_slot;
-  float4* d_ff_rec[TB_FF_SLOTS];  // [n][ff_rec<RG>()] parked records (park_env), allocated for TB_FF_REC_MAX
-  uint8_t* d_ff_flag[TB_FF_SLOTS];  // [n] parked flags
-  float4* d_ff_list[TB_FF_SLOTS][2];  // survivors of fast-forward phases 1 and 2 (worst case: every env), compacted
-  int* d_ff_count[TB_FF_SLOTS];       // [2] their numbers
-  int ff_phases;                      // 1 = one kernel runs every loop to its end; 2, 3 = budgeted phases + survivor kernels
   unsigned long long first_substeps;  // counters[6], the host's share: n envs x agent steps of every launch that RAN (see count_first_substeps)
-  int ff_lanes;                   // parked envs per wave of tb_ff_kernel's first phase (TbOptions.ff_lanes_per_wave, or chosen from n)
-  // deferred stragglers (tb_ff_kernel<.., POOL>; TbOptions.ff_defer): one pool for all episodes between two flushes
-  float4* d_pool;                 // [pool_cap + pool_slack][TB_FF_REC_MAX]
-  float** d_pool_dst;             // [pool_cap + pool_slack] where each deferred env's terminal reward goes
-  int* d_pool_count;
-  int pool_cap, pool_slack, pool_pending;  // pending: records may be waiting (the next flush runs the pool kernel)
-  int pool_run_upto;              // ... of which the first pool_run_upto have had their launch already (at a progress mark)
-  int pool_episodes;              // ff_defer = 2: episodes parked straight into the pool since the last flush (records [k n, (k + 1) n) each)
-  hipEvent_t ev_direct;           // ... and the latest launch that did so (a flush on another stream waits for it)
-  hipEvent_t ev_pool;             // the last pool run (+ the reset of its counter): later fast-forwards append behind it, whatever stream flushed
-  int pool_ev_valid, direct_ev_valid;
-  hipEvent_t ev_step[TB_FF_SLOTS], ev_ff[TB_FF_SLOTS];
-  int ff_busy[TB_FF_SLOTS], next_slot;
-  // progress marks (tb_mark_record). h_marks: pinned host counters written by tb_mark_kernel -- [k] firings of mark k
-  // (a kernel on the caller's own stream), [TB_MAX_MARKS] fast-forwards finished (a kernel behind every tb_ff_kernel on
-  // its side stream). No extra streams, no extra graph edges: a mark never makes anything wait. What a mark still has
-  // to wait for -- the fast-forwards enqueued before it -- is host arithmetic over these two kinds of counters.
-  unsigned long long* h_marks;
-  unsigned long long snap_ff[TB_FF_SLOTS], snap_marks[TB_MAX_MARKS];  // the counters at tb_mark_begin (nothing of this handle in flight)
-  int marks_on;                               // tb_mark_enable: fast-forwards are followed by their counting kernel
-  // fast-forwards enqueued PER SLOT (= per side stream: only there is "the first k have finished" the same as "k have
-  // finished" -- fast-forwards of different episodes overtake each other, one with a ball at rest on a grounded racket
-  // runs five times as long as the next): inside the current / latest capture; eagerly since tb_mark_begin
-  long long ff_cap[TB_FF_SLOTS], ff_eager[TB_FF_SLOTS];
-  long long mark_ff_before[TB_MAX_MARKS][TB_FF_SLOTS];  // fast-forwards enqueued per slot before the mark: inside a capture ff_cap at that point, eagerly ff_eager (mark_in_capture says which)
-  int mark_in_capture[TB_MAX_MARKS];
   float* d_es_rew;  // [n] tb_es_evaluate: where the fast-forward writes the 26th step's reward (allocated on first use)
+  // pipelined fast-forward
+  int pipeline;                   // enabled by tb_set_pipeline
+  int ff_phases;                  // 1 = one kernel runs every loop to its end; 2, 3 = budgeted phases + survivor kernels
+  int ff_lanes;                   // parked envs per wave of tb_ff_kernel's first phase (TbOptions.ff_lanes_per_wave, or chosen from n)
+  Phase phase;
+  Slots slots;
+  Pool pool;
+  Marks marks;
 };
 
 namespace {
@@ -194,13 +294,6 @@ size_t g_diag_lds_pad = 0;
 constexpr size_t g_diag_lds_pad = 0;
 #endif
 size_t dyn_lds(int words, unsigned lanes) { return g_diag_lds_pad + sizeof(float) * lanes * words; }
-
-int ensure_marks(TbHandle* h) {
-  if (h->h_marks) return TB_OK;
-  HIP_TRY(hipHostMalloc((void**)&h->h_marks, sizeof(unsigned long long) * (TB_MAX_MARKS + TB_FF_SLOTS), hipHostMallocDefault));
-  memset(h->h_marks, 0, sizeof(unsigned long long) * (TB_MAX_MARKS + TB_FF_SLOTS));
-  return TB_OK;
-}
 
 // 128-thread workgroups, measured with 64 / 128 / 256 alternated in one process (tools/diag/diag_blocks2.py; M env steps/s):
 //   SwingRacket  4096: 662-679 / 673-684 / 657-682    32768: 4570 / 4760 / 3600    65536: 4900 / 4600 / 4250    131072: 5900 / 5760 / 5450
@@ -229,7 +322,7 @@ KArgs base_args(const TbHandle* h) {
   KArgs a;
   memset(&a, 0, sizeof a);
   a.P = h->kp; a.words = h->d_words; a.done_state = h->d_done; a.hull = h->d_hull; a.counters = h->d_counters;
-  a.ff_sealed = seal_params_ok(h) ? h->d_counters + TB_N_COUNTERS * TB_COUNTER_SHARDS : nullptr;
+  a.ff_sealed = seal_params_ok(h) ? h->d_counters + kSealedWord : nullptr;
   a.mani = h->d_mani; a.mflag = h->d_mflag;
   a.seed = h->seed; a.env_id_base = h->env_id_base; a.n = h->n; a.T = 1;
   return a;
@@ -246,8 +339,8 @@ int upload_hull(TbHandle* h, hipStream_t s) {
 
 // make `s` wait for every fast-forward still running on the side stream
 int wait_side(TbHandle* h, hipStream_t s) {
-  for (int k = 0; k < TB_FF_SLOTS; ++k)
-    if (h->ff_busy[k]) HIP_TRY(hipStreamWaitEvent(s, h->ev_ff[k], 0));
+  for (const FfSlot& f : h->slots.s)
+    if (f.busy) HIP_TRY(hipStreamWaitEvent(s, f.ev_ff, 0));
   return TB_OK;
 }
 
@@ -298,30 +391,27 @@ ArgsKernel policy_rollout_kernel(int slices, bool rg) {
 int launch_ff_kernel(bool rg, bool big, bool esc, bool pool, dim3 grid, size_t lds, hipStream_t q, const KArgs& k) {
   const ArgsKernel kern = ff_kernel(rg, big, esc, pool);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_ff_kernel instantiation for this variant");
-  hipLaunchKernelGGL(kern, grid, dim3(64), lds, q, k);
-  HIP_TRY(hipGetLastError());
-  return TB_OK;
+  return launch(kern, grid, dim3(64), lds, q, k);
 }
 
 // Work on the side stream of `slot` forks from `s` (it runs after everything issued to `s` so far) ...
-int fork_side(TbHandle* h, int slot, hipStream_t s) {
-  HIP_TRY(hipEventRecord(h->ev_step[slot], s));
-  HIP_TRY(hipStreamWaitEvent(h->side[slot], h->ev_step[slot], 0));
+int fork_side(FfSlot& f, hipStream_t s) {
+  HIP_TRY(hipEventRecord(f.ev_step, s));
+  HIP_TRY(hipStreamWaitEvent(f.side, f.ev_step, 0));
   return TB_OK;
 }
 // ... and closes with its progress-mark count, the slot's event and the bookkeeping that later launches order themselves by;
 // `term` / `substeps`: the late-written buffers that the work writes (or null)
 int close_side(TbHandle* h, int slot, const void* term, const void* substeps, hipStream_t s) {
-  hipStream_t side = h->side[slot];
-  if (h->h_marks && h->marks_on) {  // progress marks: count this fast-forward as finished, in stream order behind it
-    hipLaunchKernelGGL(tb_mark_kernel, dim3(1), dim3(1), 0, side, h->h_marks + TB_MAX_MARKS + slot);
-    HIP_TRY(hipGetLastError());
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &st));
-    if (st == hipStreamCaptureStatusActive) h->ff_cap[slot]++; else h->ff_eager[slot]++;
+  FfSlot& f = h->slots.s[slot];
+  if (h->marks.h && h->marks.on) {  // progress marks: count this fast-forward as finished, in stream order behind it
+    if (int rc = launch(tb_mark_kernel, dim3(1), dim3(1), 0, f.side, h->marks.h + TB_MAX_MARKS + slot)) return rc;
+    hipStreamCaptureStatus st;
+    if (int rc = capture_status(s, &st)) return rc;
+    if (st == hipStreamCaptureStatusActive) f.in_capture++; else f.eager++;
   }
-  HIP_TRY(hipEventRecord(h->ev_ff[slot], side));
-  h->ff_busy[slot] = 1; h->last_slot = slot; h->last_term = term; h->last_sub = substeps;
+  HIP_TRY(hipEventRecord(f.ev_ff, f.side));
+  f.busy = 1; h->slots.last = slot; h->slots.last_term = term; h->slots.last_sub = substeps;
   return TB_OK;
 }
 
@@ -333,41 +423,43 @@ int close_side(TbHandle* h, int slot, const void* term, const void* substeps, hi
 int defer_mode(const TbHandle* h);
 int launch_ff(TbHandle* h, int slot, KArgs a, hipStream_t s) {
   const void *term = a.term_obs, *substeps = a.substeps;
-  hipStream_t side = h->side[slot];
+  Pool& pool = h->pool;
+  FfSlot& f = h->slots.s[slot];
+  hipStream_t side = f.side;
   // lockstep episodes (every env parks in the same launch): a few envs per wave; without the host knowing the
   // phase every step is followed by this kernel and nearly every record is idle: plain 64 per wave, one flag test each
-  a.ff_lanes = h->phase_valid ? h->ff_lanes : 64;
-  if (int rc = fork_side(h, slot, s)) return rc;
+  a.ff_lanes = h->phase.valid ? h->ff_lanes : 64;
+  if (int rc = fork_side(f, s)) return rc;
   // two fast-forwards that write the same terminal-obs / substeps buffer must finish in order
-  if (h->last_slot >= 0 && h->last_slot != slot && ((term && term == h->last_term) || (substeps && substeps == h->last_sub)))
-    HIP_TRY(hipStreamWaitEvent(side, h->ev_ff[h->last_slot], 0));
+  if (const Slots& sl = h->slots; sl.last >= 0 && sl.last != slot && ((term && term == sl.last_term) || (substeps && substeps == sl.last_sub)))
+    HIP_TRY(hipStreamWaitEvent(side, sl.s[sl.last].ev_ff, 0));
   // phases: budgeted loop + survivor kernels (see tb_ff_kernel). Without the host knowing the episode phase nearly every
   // record is idle: one plain kernel.
-  const int phases = h->phase_valid ? h->ff_phases : 1;
+  const int phases = h->phase.valid ? h->ff_phases : 1;
   const bool rg = extended_contacts(h->kp);
   // deferred stragglers: on request (TbOptions.ff_defer > 0), or by default with racket<->court contact, whose resting stacks run
   // to the 800-substep limit. Not with progress marks (a mark promises that the steps before it are FINAL), not with late-written
   // terminal observations / substep counts (the pool keeps one destination per record: the reward's)
-  const bool defer = h->d_pool && phases == 1 && h->phase_valid && !term && !substeps && defer_mode(h) == 1;
-  if (phases > 1) HIP_TRY(hipMemsetAsync(h->d_ff_count[slot], 0, 2 * sizeof(int), side));
+  const bool defer = pool.rec && phases == 1 && h->phase.valid && !term && !substeps && defer_mode(h) == 1;
+  if (phases > 1) HIP_TRY(hipMemsetAsync(f.count, 0, 2 * sizeof(int), side));
   for (int ph = 0; ph < phases; ++ph) {
     KArgs k = a;
     dim3 grid((unsigned)((a.n + a.ff_lanes - 1) / a.ff_lanes));
     if (ph > 0) {  // survivors of phase ph: a compacted list of unknown length, walked by a fixed grid
-      k.ff_rec = h->d_ff_list[slot][ph - 1]; k.ff_flag = nullptr; k.ff_src_count = h->d_ff_count[slot] + (ph - 1); k.ff_lanes = TB_PHASE_LANES;
+      k.ff_rec = f.list[ph - 1]; k.ff_flag = nullptr; k.ff_src_count = f.count + (ph - 1); k.ff_lanes = TB_PHASE_LANES;
       int g = h->n / TB_PHASE_GRID_DIV; g = g < 64 ? 64 : g;  // (1 M envs, same box: / 512 9.37, / 256 9.56, / 128 9.41, / 1024 9.19 G env steps/s)
       grid = dim3((unsigned)g);
     }
-    if (ph + 1 < phases) { k.ff_next = h->d_ff_list[slot][ph]; k.ff_next_count = h->d_ff_count[slot] + ph; }
+    if (ph + 1 < phases) { k.ff_next = f.list[ph]; k.ff_next_count = f.count + ph; }
     if (defer) {
       // with racket<->court contact every lane is on a path of its own (rackets land at different times, manifolds of different
       // sizes, solves of different lengths) and a wave pays for the union: 16 envs per wave (4096 envs, same box: 84-86 M env
       // steps/s with 64, 92-96 with 32, 94-98 with 16, 93-97 with 8, 89 with 4)
       if (rg && !h->opt.ff_lanes_per_wave && k.ff_lanes > 16) { k.ff_lanes = 16; grid = dim3((unsigned)((a.n + 15) / 16)); }
-      k.ff_next = h->d_pool; k.ff_next_count = h->d_pool_count; k.ff_cap = h->pool_cap; k.pool_dst_out = h->d_pool_dst;
+      k.ff_next = pool.rec; k.ff_next_count = pool.count; k.ff_cap = pool.cap; k.pool_dst_out = pool.dst;
       k.ff_extra = h->opt.ff_defer_margin ? h->opt.ff_defer_margin : 16;
-      h->pool_pending = 1;
-      if (h->pool_ev_valid) HIP_TRY(hipStreamWaitEvent(side, h->ev_pool, 0));  // append behind the last pool run and its counter reset
+      pool.pending = 1;
+      if (pool.run_ev_valid) HIP_TRY(hipStreamWaitEvent(side, pool.ev_run, 0));  // append behind the last pool run and its counter reset
     }
     const bool big = !defer && h->n >= 131072;  // (the deferring kernel is the small-batch POOL instantiation at any size)
     const bool esc = big && ph == 0 && phases > 1;
@@ -381,39 +473,41 @@ int launch_ff(TbHandle* h, int slot, KArgs a, hipStream_t s) {
 // own fast-forward kernels moved on to it (ff_defer = 1: their number is the pool's device counter)
 int run_pool(TbHandle* h, hipStream_t q) {
   KArgs k = base_args(h);
+  Pool& pool = h->pool;
   const bool rg = extended_contacts(h->kp);
-  k.ff_rec = h->d_pool; k.ff_flag = nullptr; k.ff_src_count = h->d_pool_count; k.ff_lanes = 64;
-  k.ff_cap = h->pool_cap + h->pool_slack; k.pool_dst_in = h->d_pool_dst;
-  long long records = (long long)h->pool_cap + h->pool_slack;
-  if (h->pool_episodes > 0) {
-    const size_t first = (size_t)h->pool_run_upto * h->n;
-    records = (long long)(h->pool_episodes - h->pool_run_upto) * h->n;
+  k.ff_rec = pool.rec; k.ff_flag = nullptr; k.ff_src_count = pool.count; k.ff_lanes = 64;
+  k.ff_cap = (int)pool.records(); k.pool_dst_in = pool.dst;
+  long long records = (long long)pool.records();
+  if (pool.episodes > 0) {
+    const size_t first = (size_t)pool.run_upto * h->n;
+    records = (long long)(pool.episodes - pool.run_upto) * h->n;
     k.ff_src_count = nullptr; k.n = (int)records;
-    k.ff_rec = h->d_pool + first * pool_rec(h); k.pool_dst_in = h->d_pool_dst + first;
+    k.ff_rec = pool.rec + first * pool_rec(h); k.pool_dst_in = pool.dst + first;
   }
   long long g = (records + 63) / 64;
   g = g < 1024 ? 1024 : g > 16384 ? 16384 : g;  // (workgroups beyond the pool's fill exit at once; grid-stride beyond 1 M records)
-  (void)hipGetLastError();
   // whole episodes in the pool make it a LARGE batch -- 43 episodes x 4096 envs = 2752 waves: the instantiation built for occupancy
   // (153 VGPRs, three waves per SIMD, wave-shared outline sweep) holds them all at once, the small-batch one (188 VGPRs, two per
   // SIMD) ran them in two rounds
-  const bool big = !rg && h->pool_episodes > 0 && records >= 131072;
+  const bool big = !rg && pool.episodes > 0 && records >= 131072;
+  (void)hipGetLastError();
   if (int rc = launch_ff_kernel(rg, big, false, true, dim3((unsigned)g), dyn_lds(ff_lds_words(rg, false), 64), q, k)) return rc;
-  h->pool_run_upto = h->pool_episodes;
+  pool.run_upto = pool.episodes;
   return TB_OK;
 }
 
 // every result of every fast-forward is in place once `s` gets past this point
 int flush_all(TbHandle* h, hipStream_t s) {
   if (int rc = wait_side(h, s)) return rc;
-  if (h->pool_pending) {  // what the episodes since the last flush left in the pool, side by side in one launch
-    if (h->pool_episodes > 0 && h->direct_ev_valid) HIP_TRY(hipStreamWaitEvent(s, h->ev_direct, 0));  // (a flush on another stream than the steps')
-    if (h->pool_episodes == 0 || h->pool_run_upto < h->pool_episodes) {
+  Pool& pool = h->pool;
+  if (pool.pending) {  // what the episodes since the last flush left in the pool, side by side in one launch
+    if (pool.episodes > 0 && pool.direct_ev_valid) HIP_TRY(hipStreamWaitEvent(s, pool.ev_direct, 0));  // (a flush on another stream than the steps')
+    if (pool.episodes == 0 || pool.run_upto < pool.episodes) {
       if (int rc = run_pool(h, s)) return rc;
     }
-    HIP_TRY(hipMemsetAsync(h->d_pool_count, 0, sizeof(int), s));
-    HIP_TRY(hipEventRecord(h->ev_pool, s));
-    h->pool_pending = 0; h->pool_ev_valid = 1; h->pool_episodes = 0; h->pool_run_upto = 0;
+    HIP_TRY(hipMemsetAsync(pool.count, 0, sizeof(int), s));
+    HIP_TRY(hipEventRecord(pool.ev_run, s));
+    pool.idle(); pool.run_ev_valid = 1;
   }
   return TB_OK;
 }
@@ -422,11 +516,10 @@ int flush_all(TbHandle* h, hipStream_t s) {
 // (or flush) get their pool launch now -- on a side stream, beside the steps of the next chunk, counted like any fast-forward kernel.
 // A graph of C chunks forks C times instead of once per episode.
 int run_pool_for_mark(TbHandle* h, hipStream_t s) {
-  if (!(h->pool_episodes > h->pool_run_upto)) return TB_OK;
-  const int slot = h->next_slot;
-  h->next_slot = (slot + 1) % TB_FF_SLOTS;
-  if (int rc = fork_side(h, slot, s)) return rc;
-  if (int rc = run_pool(h, h->side[slot])) return rc;
+  if (!(h->pool.episodes > h->pool.run_upto)) return TB_OK;
+  const int slot = h->slots.claim();
+  if (int rc = fork_side(h->slots.s[slot], s)) return rc;
+  if (int rc = run_pool(h, h->slots.s[slot].side)) return rc;
   return close_side(h, slot, nullptr, nullptr, s);
 }
 
@@ -440,9 +533,9 @@ int run_pool_for_mark(TbHandle* h, hipStream_t s) {
 // all-gathered beside it (one rank, 4096 envs, same box) replays in 6.3 ms that way and in 6.6-7.1 ms with the pool run at each mark
 // (ff_defer = 2 asks for that); form 1 never runs under marks (a mark promises final steps).
 int defer_mode(const TbHandle* h) {
-  if (!h->d_pool || h->opt.ff_defer < 0) return 0;
-  if (h->opt.ff_defer > 0) return h->marks_on && h->opt.ff_defer == 1 ? 0 : h->opt.ff_defer;
-  if (h->marks_on) return 0;
+  if (!h->pool.rec || h->opt.ff_defer < 0) return 0;
+  if (h->opt.ff_defer > 0) return h->marks.on && h->opt.ff_defer == 1 ? 0 : h->opt.ff_defer;
+  if (h->marks.on) return 0;
   if (h->n <= 16384) return 2;
   return (h->kp.flags & TB_F_RACKET_GROUND) ? 1 : 0;
 }
@@ -455,25 +548,26 @@ int claim_park(TbHandle* h, bool may_park, KArgs& a, hipStream_t s, Park* p) {
   *p = Park{false, -1};
   if (!may_park) return TB_OK;
   a.defer = 1;
-  if (h->d_pool && defer_mode(h) == 2 && h->phase_valid && !a.term_obs && !a.substeps && h->pool_episodes < h->pool_cap / h->n) {
-    if (h->pool_ev_valid) HIP_TRY(hipStreamWaitEvent(s, h->ev_pool, 0));  // behind the last pool run (which may have been enqueued on another stream)
-    a.ff_rec = h->d_pool + (size_t)h->pool_episodes * h->n * pool_rec(h); a.ff_flag = nullptr;
-    a.pool_dst_out = h->d_pool_dst + (size_t)h->pool_episodes * h->n;
+  Pool& pool = h->pool;
+  if (pool.rec && defer_mode(h) == 2 && h->phase.valid && !a.term_obs && !a.substeps && pool.episodes < pool.cap / h->n) {
+    if (pool.run_ev_valid) HIP_TRY(hipStreamWaitEvent(s, pool.ev_run, 0));  // behind the last pool run (which may have been enqueued on another stream)
+    a.ff_rec = pool.rec + (size_t)pool.episodes * h->n * pool_rec(h); a.ff_flag = nullptr;
+    a.pool_dst_out = pool.dst + (size_t)pool.episodes * h->n;
     p->direct = true;
     return TB_OK;
   }
-  p->slot = h->next_slot;
-  h->next_slot = (p->slot + 1) % TB_FF_SLOTS;
-  if (h->ff_busy[p->slot]) HIP_TRY(hipStreamWaitEvent(s, h->ev_ff[p->slot], 0));  // slot still in use by an older fast-forward
-  a.ff_rec = h->d_ff_rec[p->slot]; a.ff_flag = h->d_ff_flag[p->slot];
+  p->slot = h->slots.claim();
+  const FfSlot& f = h->slots.s[p->slot];
+  if (f.busy) HIP_TRY(hipStreamWaitEvent(s, f.ev_ff, 0));  // slot still in use by an older fast-forward
+  a.ff_rec = f.rec; a.ff_flag = f.flag;
   return TB_OK;
 }
 // after the launch `a` describes: a pool region is counted (the next flush or mark runs it); a slot gets its fast-forward, which owes
 // its reward to the step that parked -- the launch's last, `reward_step_stride` elements per step
 int finish_park(TbHandle* h, const Park& p, KArgs a, size_t reward_step_stride, hipStream_t s) {
   if (p.direct) {
-    HIP_TRY(hipEventRecord(h->ev_direct, s));
-    h->direct_ev_valid = 1; h->pool_episodes++; h->pool_pending = 1;
+    HIP_TRY(hipEventRecord(h->pool.ev_direct, s));
+    h->pool.direct_ev_valid = 1; h->pool.episodes++; h->pool.pending = 1;
     return TB_OK;
   }
   if (p.slot < 0) return TB_OK;
@@ -486,8 +580,8 @@ int finish_park(TbHandle* h, const Park& p, KArgs a, size_t reward_step_stride, 
 // CAPTURED runs nothing: whoever replays the graph reports the replayed steps through tb_phase_advance, as it must for the episode
 // phase anyway. (tb_counters joins the stream before it reads: what was enqueued has run by then.)
 int count_first_substeps(TbHandle* h, int T, hipStream_t s) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  HIP_TRY(hipStreamIsCapturing(s, &st));
+  hipStreamCaptureStatus st;
+  if (int rc = capture_status(s, &st)) return rc;
   if (st == hipStreamCaptureStatusNone) h->first_substeps += (unsigned long long)h->n * (unsigned long long)T;
   return TB_OK;
 }
@@ -495,6 +589,10 @@ int count_first_substeps(TbHandle* h, int T, hipStream_t s) {
 struct PolicyIO {  // non-null weights = fused policy step
   const float* weights; const float* obs_in; float* actions; float* raw; float* logp; float* value;
   unsigned long long seed; int deterministic;
+  void apply(KArgs& a) const {
+    a.pol_weights = weights; a.pol_obs = obs_in; a.pol_actions = actions; a.pol_raw = raw; a.pol_logp = logp;
+    a.pol_value = value; a.pol_seed = seed; a.pol_deterministic = deterministic;
+  }
 };
 
 // lean_multi (T > 1): the caller guarantees lockstep episodes (phase_valid) and that an episode can only
@@ -504,10 +602,7 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
                 const PolicyIO* pol = nullptr, bool lean_multi = false) {
   if (int rc = count_first_substeps(h, T, s)) return rc;
   KArgs a = base_args(h);
-  if (pol) {
-    a.pol_weights = pol->weights; a.pol_obs = pol->obs_in; a.pol_actions = pol->actions; a.pol_raw = pol->raw; a.pol_logp = pol->logp;
-    a.pol_value = pol->value; a.pol_seed = pol->seed; a.pol_deterministic = pol->deterministic;
-  }
+  if (pol) pol->apply(a);
   a.actions = actions; a.obs = obs; a.reward = reward; a.done_out = done; a.term_obs = term; a.substeps = substeps; a.T = T;
   dim3 grid((unsigned)((h->n + h->block - 1) / h->block)), block((unsigned)h->block);
   if (pol) { grid = dim3((unsigned)((h->n + 63) / 64)); block = dim3(256); }  // four waves per 64 envs
@@ -521,7 +616,7 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
   // fast-forward in this launch and the lean kernel needs no slot (a.ff_rec stays null). Should the
   // invariant ever be broken, the lane is counted in counters[8] (lockstep violations) instead of being dropped silently.
   const bool piped = (T == 1 || lean_multi) && h->pipeline && h->kind == TB_ENV_SWING && (h->kp.flags & TB_F_AUTO_RESET);
-  const bool may_park = piped && (T == 1 ? (!h->phase_valid || h->phase == 25) : h->phase + T - 1 == 25);
+  const bool may_park = piped && ((T == 1 && !h->phase.valid) || h->phase.launch_ends_episode(T));
   Park park;
   if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
   const bool rg = extended_contacts(h->kp);  // selects the instantiation that contains the rolling-friction rows
@@ -532,10 +627,9 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
   if (two_wave) { grid = dim3((unsigned)((h->n + 63) / 64)); block = dim3(128); }  // two waves per 64 envs
   const size_t lds = dyn_lds(step_lds_words(h->kind, piped, multi, rg, policy), policy ? 64u : block.x);
   (void)hipGetLastError();  // the check below is about THIS launch, not about whatever another library left behind
-  hipLaunchKernelGGL(kern, grid, block, lds, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a);
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch(kern, grid, block, lds, s, a.words, a.done_state, a.actions, a.hull, a.n, a.P.n_hull, a)) return rc;
   if (int rc = finish_park(h, park, a, h->n, s)) return rc;
-  if (h->phase_valid) h->phase = (h->phase + T) % 26;
+  h->phase.advance(T);
   return TB_OK;
 }
 
@@ -544,12 +638,11 @@ int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, f
                           hipStream_t s) {
   if (int rc = count_first_substeps(h, T, s)) return rc;
   KArgs a = base_args(h);
-  a.pol_weights = pol.weights; a.pol_obs = pol.obs_in; a.pol_actions = pol.actions; a.pol_raw = pol.raw; a.pol_logp = pol.logp;
-  a.pol_value = pol.value; a.pol_seed = pol.seed; a.pol_deterministic = pol.deterministic;
+  pol.apply(a);
   a.obs = obs; a.reward = reward; a.done_out = done; a.T = T;
   a.st_act = st[0]; a.st_raw = st[1]; a.st_logp = st[2]; a.st_val = st[3]; a.st_obs = st[4]; a.st_rew = st[5]; a.st_done = st[6];
   const bool swing = h->kind == TB_ENV_SWING;
-  const bool may_park = swing && h->phase + T - 1 == 25;  // (the caller checked pipeline, lockstep phase and phase + T <= 26)
+  const bool may_park = swing && h->phase.launch_ends_episode(T);  // (the caller checked pipeline, lockstep phase and that T stays inside the episode)
   Park park;
   if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
   // 16 envs per workgroup (3 waves) while every workgroup still gets a CU of its own, else 48 (7 waves): see the kernel
@@ -560,10 +653,64 @@ int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, f
   const ArgsKernel kern = swing ? policy_rollout_kernel<TB_ENV_SWING>(narrow ? 1 : 3, rg) : policy_rollout_kernel<TB_ENV_TENNIS>(narrow ? 1 : 3, rg);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_rollout_kernel instantiation for this variant");
   (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, grid, block, dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a);  // (the env wave's columns)
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch(kern, grid, block, dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a)) return rc;  // (the env wave's columns)
   if (int rc = finish_park(h, park, a, st[5], s)) return rc;
-  if (h->phase_valid) h->phase = (h->phase + T) % 26;
+  h->phase.advance(T);
+  return TB_OK;
+}
+
+// every fast-forward's result in place, then `bytes` of device memory read back; the host has them on return
+int read_back(TbHandle* h, void* dst, const void* src_dev, size_t bytes, hipStream_t s) {
+  if (int rc = flush_all(h, s)) return rc;
+  HIP_TRY(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return TB_OK;
+}
+
+// tb_set_state with the pipeline on: the pipelined kernels need to know which launch ends the episodes. The injected envs are in
+// lockstep again when every one is running (done = 0) at the same step count below the episode length -- then the phase is that
+// count (e.g. a checkpoint of a training run restored into a fresh handle). Costs one small device-to-host copy and a stream
+// synchronisation (so: not capturable, and not asynchronous even with on_device); only paid with the pipeline on,
+// the one mode that uses the phase -- without it the call stays fully asynchronous for on_device buffers.
+int rederive_phase(TbHandle* h, hipStream_t s) {
+  const size_t n = (size_t)h->n;
+  uint32_t* steps = (uint32_t*)malloc(n * sizeof(uint32_t));
+  uint8_t* dn = (uint8_t*)malloc(n);
+  if (!steps || !dn) { free(steps); free(dn); return fail(TB_E_INVAL, "tb_set_state: out of host memory"); }
+  hipError_t e = hipMemcpyAsync(steps, h->d_words + (size_t)TB_W_SW_STEP * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(dn, h->d_done, n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) {
+    bool same = (int32_t)steps[0] >= 0 && (int32_t)steps[0] < kEpisodeSteps;
+    for (size_t i = 0; same && i < n; ++i) same = steps[i] == steps[0] && dn[i] == TB_DONE_NO;
+    if (same) h->phase.set((int)steps[0]);
+  }
+  free(steps); free(dn);
+  return e == hipSuccess ? TB_OK : fail((int)e, "tb_set_state: reading back the step counters");
+}
+
+// the pipeline's streams, events and buffers: all of them, or none (what release_pipeline leaves behind is the state of a
+// handle whose pipeline was never enabled)
+void release_pipeline(TbHandle* h) {
+  for (FfSlot& f : h->slots.s) { f.free_buffers(); f.close(); }
+  h->pool.release();
+  h->pipeline = 0;
+}
+
+int alloc_pool(TbHandle* h, uint32_t flags) {  // all of it or none: defer_mode takes a non-null pool.rec for a usable pool
+  if (h->pool.rec || h->n > TB_DEFER_MAX_ENVS || h->opt.ff_defer < 0) return TB_OK;
+  if (!(h->opt.ff_defer > 0 || h->n <= 16384 || (flags & TB_F_RACKET_GROUND))) return TB_OK;  // (see Pool: who can ever defer)
+  Pool p = {};
+  if (int rc = p.build(h->n)) { p.release(); return rc; }
+  h->pool = p;
+  return TB_OK;
+}
+
+int alloc_pipeline(TbHandle* h) {
+  for (FfSlot& f : h->slots.s)
+    if (int rc = f.build(h->n, h->ff_phases)) return rc;
+  if (int rc = alloc_pool(h, h->kp.flags)) return rc;
+  HIP_TRY(hipDeviceSynchronize());
   return TB_OK;
 }
 
@@ -622,13 +769,12 @@ int tb_create(const TbParams* params, const TbOptions* options, int env_kind, in
   CREATE_TRY(hipMalloc((void**)&h->d_done, (size_t)n_envs));
   CREATE_TRY(hipMalloc((void**)&h->d_hull, sizeof(float4) * TB_HULL_LDS));
   CREATE_TRY(hipHostMalloc((void**)&h->h_hull, sizeof(float4) * TB_HULL_LDS, hipHostMallocDefault));
-  CREATE_TRY(hipMalloc((void**)&h->d_counters, sizeof(unsigned long long) * (TB_N_COUNTERS * TB_COUNTER_SHARDS + 1)));
-  CREATE_TRY(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned long long) * (TB_N_COUNTERS * TB_COUNTER_SHARDS + 1), 0));
+  CREATE_TRY(hipMalloc((void**)&h->d_counters, sizeof(unsigned long long) * kCounterWords));
+  CREATE_TRY(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned long long) * kCounterWords, 0));
   CREATE_TRY(hipMalloc((void**)&h->d_mani, sizeof(uint32_t) * (size_t)TB_MANI_WORDS * n_envs));
   CREATE_TRY(hipMalloc((void**)&h->d_mflag, (size_t)n_envs));
   CREATE_TRY(hipMemsetAsync(h->d_mflag, 0, (size_t)n_envs, 0));
-  hipLaunchKernelGGL(tb_init_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, 0, h->d_words, h->d_done, n_envs, nw);
-  CREATE_TRY(hipGetLastError());
+  if (int rc = launch(tb_init_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, 0, h->d_words, h->d_done, n_envs, nw)) { tb_destroy(h); return rc; }
   if (int rc = upload_hull(h, 0)) { tb_destroy(h); return rc; }
   CREATE_TRY(hipStreamSynchronize(0));
 #undef CREATE_TRY
@@ -636,129 +782,28 @@ int tb_create(const TbParams* params, const TbOptions* options, int env_kind, in
   return TB_OK;
 }
 
-static void release_pipeline(TbHandle* h);
-static void release_pool(TbHandle* h);
-
 int tb_destroy(TbHandle* h) {
   if (!h) return TB_OK;
   DeviceGuard g(h->device);
   (void)hipDeviceSynchronize();
-  if (h->d_words) (void)hipFree(h->d_words);
-  if (h->d_done) (void)hipFree(h->d_done);
-  if (h->d_hull) (void)hipFree(h->d_hull);
+  drop(h->d_words); drop(h->d_done); drop(h->d_hull); drop(h->d_counters); drop(h->d_mani); drop(h->d_mflag); drop(h->d_es_rew);
   if (h->h_hull) (void)hipHostFree(h->h_hull);
-  if (h->d_counters) (void)hipFree(h->d_counters);
-  if (h->d_mani) (void)hipFree(h->d_mani);
-  if (h->d_mflag) (void)hipFree(h->d_mflag);
-  if (h->d_es_rew) (void)hipFree(h->d_es_rew);
   release_pipeline(h);
-  if (h->h_marks) (void)hipHostFree(h->h_marks);
+  if (h->marks.h) (void)hipHostFree(h->marks.h);
   free(h);
-  return TB_OK;
-}
-
-// the pipeline's streams, events and buffers: all of them, or none (what release_pipeline leaves behind is the state of a
-// handle whose pipeline was never enabled)
-static void release_pipeline(TbHandle* h) {
-  for (int k = 0; k < TB_FF_SLOTS; ++k) {
-    if (h->d_ff_rec[k]) (void)hipFree(h->d_ff_rec[k]);
-    if (h->d_ff_flag[k]) (void)hipFree(h->d_ff_flag[k]);
-    if (h->d_ff_list[k][0]) (void)hipFree(h->d_ff_list[k][0]);
-    if (h->d_ff_list[k][1]) (void)hipFree(h->d_ff_list[k][1]);
-    if (h->d_ff_count[k]) (void)hipFree(h->d_ff_count[k]);
-    if (h->ev_step[k]) (void)hipEventDestroy(h->ev_step[k]);
-    if (h->ev_ff[k]) (void)hipEventDestroy(h->ev_ff[k]);
-    if (h->side[k]) (void)hipStreamDestroy(h->side[k]);
-    h->d_ff_rec[k] = nullptr; h->d_ff_flag[k] = nullptr; h->d_ff_list[k][0] = nullptr; h->d_ff_list[k][1] = nullptr;
-    h->d_ff_count[k] = nullptr; h->ev_step[k] = nullptr; h->ev_ff[k] = nullptr; h->side[k] = nullptr; h->ff_busy[k] = 0;
-  }
-  release_pool(h);
-  h->pipeline = 0;
-}
-
-// test hook (tb_diag_fail_alloc): the n-th device allocation of the pipeline or the pool (tb_set_pipeline, tb_set_params) fails with hipErrorOutOfMemory
-static int g_fail_alloc_countdown = 0;
-static hipError_t pipeline_malloc(void** p, size_t bytes) {
-  if (g_fail_alloc_countdown > 0 && --g_fail_alloc_countdown == 0) { *p = nullptr; return hipErrorOutOfMemory; }
-  return hipMalloc(p, bytes);
-}
-
-// The pool (TbOptions.ff_defer): 64 n records (two reference-sized rollouts of 1100 steps with EVERY episode end in it) + the slack
-// all resident fast-forward waves could overshoot it by (slots x n), 192 B each + an 8-byte destination pointer: 14 KB per env.
-// Allocated only for handles whose defer_mode can be non-zero: on request, up to 16384 envs, or above that (to 131072) once the
-// parameter block turns racket<->court contact on -- tb_set_params asks again, with the new flags, before it commits them. (Until round 4 every pipelined handle up
-// to 131072 envs got one: 1.9 GB at that size that the default kernels never touched.) Zeroed: a record's tag word says whether
-// it holds a parked env, and no launch may ever find a tag it did not write.
-static bool pool_wanted(const TbHandle* h, uint32_t flags) {
-  if (h->n > TB_DEFER_MAX_ENVS || h->opt.ff_defer < 0) return false;
-  return h->opt.ff_defer > 0 || h->n <= 16384 || (flags & TB_F_RACKET_GROUND);
-}
-static void release_pool(TbHandle* h) {
-  if (h->d_pool) (void)hipFree(h->d_pool);
-  if (h->d_pool_dst) (void)hipFree(h->d_pool_dst);
-  if (h->d_pool_count) (void)hipFree(h->d_pool_count);
-  if (h->ev_pool) (void)hipEventDestroy(h->ev_pool);
-  if (h->ev_direct) (void)hipEventDestroy(h->ev_direct);
-  h->ev_pool = nullptr; h->ev_direct = nullptr; h->pool_ev_valid = 0; h->direct_ev_valid = 0; h->pool_episodes = 0; h->pool_run_upto = 0;
-  h->d_pool = nullptr; h->d_pool_dst = nullptr; h->d_pool_count = nullptr; h->pool_cap = 0; h->pool_slack = 0; h->pool_pending = 0;
-}
-static int alloc_pool_parts(TbHandle* h, float4** pool, float*** dst, int** count, hipEvent_t* ev_pool, hipEvent_t* ev_direct, size_t recs) {
-  HIP_TRY(pipeline_malloc((void**)pool, sizeof(float4) * (size_t)TB_FF_REC_MAX * recs));
-  HIP_TRY(hipMemset(*pool, 0, sizeof(float4) * (size_t)TB_FF_REC_MAX * recs));
-  HIP_TRY(pipeline_malloc((void**)dst, sizeof(float*) * recs));
-  HIP_TRY(hipMemset(*dst, 0, sizeof(float*) * recs));
-  HIP_TRY(pipeline_malloc((void**)count, sizeof(int)));
-  HIP_TRY(hipMemset(*count, 0, sizeof(int)));
-  HIP_TRY(hipEventCreateWithFlags(ev_pool, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(ev_direct, hipEventDisableTiming));
-  return TB_OK;
-}
-static int alloc_pool(TbHandle* h, uint32_t flags) {  // all of it or none: defer_mode takes a non-null d_pool for a usable pool
-  if (h->d_pool || !pool_wanted(h, flags)) return TB_OK;
-  const size_t recs = (size_t)64 * h->n + (size_t)TB_FF_SLOTS * h->n;
-  float4* pool = nullptr; float** dst = nullptr; int* count = nullptr; hipEvent_t e1 = nullptr, e2 = nullptr;
-  if (int rc = alloc_pool_parts(h, &pool, &dst, &count, &e1, &e2, recs)) {
-    if (pool) (void)hipFree(pool);
-    if (dst) (void)hipFree(dst);
-    if (count) (void)hipFree(count);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e2) (void)hipEventDestroy(e2);
-    return rc;
-  }
-  h->pool_cap = 64 * h->n; h->pool_slack = TB_FF_SLOTS * h->n;
-  h->d_pool = pool; h->d_pool_dst = dst; h->d_pool_count = count; h->ev_pool = e1; h->ev_direct = e2;
-  return TB_OK;
-}
-
-static int alloc_pipeline(TbHandle* h) {
-  const size_t wb = sizeof(float4) * (size_t)TB_FF_REC_MAX * h->n;
-  for (int k = 0; k < TB_FF_SLOTS; ++k) {
-    HIP_TRY(hipStreamCreateWithFlags(&h->side[k], hipStreamNonBlocking));
-    HIP_TRY(pipeline_malloc((void**)&h->d_ff_rec[k], wb));
-    HIP_TRY(hipMemset(h->d_ff_rec[k], 0, wb));
-    HIP_TRY(pipeline_malloc((void**)&h->d_ff_flag[k], (size_t)h->n));
-    HIP_TRY(hipMemset(h->d_ff_flag[k], 0, (size_t)h->n));
-    for (int ph = 0; ph + 1 < h->ff_phases; ++ph) HIP_TRY(pipeline_malloc((void**)&h->d_ff_list[k][ph], wb));
-    HIP_TRY(pipeline_malloc((void**)&h->d_ff_count[k], 2 * sizeof(int)));
-    HIP_TRY(hipMemset(h->d_ff_count[k], 0, 2 * sizeof(int)));
-    HIP_TRY(hipEventCreateWithFlags(&h->ev_step[k], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&h->ev_ff[k], hipEventDisableTiming));
-  }
-  if (int rc = alloc_pool(h, h->kp.flags)) return rc;
-  HIP_TRY(hipDeviceSynchronize());
   return TB_OK;
 }
 
 int tb_set_pipeline(TbHandle* h, int enable) {
   if (!h) return fail(TB_E_INVAL, "tb_set_pipeline: null handle");
   DeviceGuard g(h->device);
-  if (enable && !h->side[0]) {
+  if (enable && !h->slots.built()) {
     if (h->kind != TB_ENV_SWING) return fail(TB_E_UNSUPPORTED, "tb_set_pipeline: only SwingRacket-v0 has a fast-forward to overlap");
     // 8 slots x (records + up to two survivor lists) x 192 B per env: 4.6 KB per env, 77 GB at the cap (of 288)
     if (h->n > TB_PIPELINE_MAX_ENVS) return fail(TB_E_INVAL, "tb_set_pipeline: more than 2^24 envs (the parked-record slots would not fit next to the state)");
-    h->last_slot = -1;
+    h->slots.forget_ordering();
     if (int rc = alloc_pipeline(h)) {
-      // all or nothing: a half-built pipeline would pass the `side[0]` test above on the next call and the step kernel would
+      // all or nothing: a half-built pipeline would pass the `built()` test above on the next call and the step kernel would
       // then park into a null slot. fail() has already recorded what went wrong.
       release_pipeline(h);
       (void)hipGetLastError();
@@ -777,18 +822,14 @@ int tb_diag_fail_alloc(int nth) {
 int tb_pipeline_sync(TbHandle* h, int host_wait) {
   if (!h) return fail(TB_E_INVAL, "tb_pipeline_sync: null handle");
   DeviceGuard g(h->device);
-  for (int k = 0; k < TB_FF_SLOTS; ++k) {
-    if (host_wait && h->side[k]) HIP_TRY(hipStreamSynchronize(h->side[k]));
-    h->ff_busy[k] = 0;
-  }
-  h->pool_ev_valid = 0; h->direct_ev_valid = 0;  // (an event recorded on one side of a capture boundary means nothing on the other)
-  h->last_slot = -1;
   if (host_wait) {
-    memset(h->ff_cap, 0, sizeof h->ff_cap);
-    h->phase_at_capture = h->phase; h->phase_valid_at_capture = h->phase_valid;
-  } else {  // the captured tb_step calls advanced the host's episode phase, but none of them ran: the replays will (tb_phase_advance)
-    h->phase = h->phase_at_capture; h->phase_valid = h->phase_valid_at_capture;
-  }
+    for (FfSlot& f : h->slots.s)
+      if (f.side) HIP_TRY(hipStreamSynchronize(f.side));
+    h->slots.forget_capture();
+    h->phase.save_for_capture();
+  } else h->phase.restore();  // the captured tb_step calls advanced the host's episode phase, but none of them ran: the replays will (tb_phase_advance)
+  h->slots.forget_ordering();
+  h->pool.events_forgotten();
   return TB_OK;
 }
 
@@ -796,25 +837,18 @@ int tb_pipeline_recover(TbHandle* h) {
   if (!h) return fail(TB_E_INVAL, "tb_pipeline_recover: null handle");
   DeviceGuard g(h->device);
   (void)hipGetLastError();  // the abandoned capture leaves a sticky hipErrorStreamCaptureInvalidated behind
-  // the captured tb_step calls advanced the host's episode phase, but none of them ran
-  h->phase = h->phase_at_capture; h->phase_valid = h->phase_valid_at_capture;
-  h->pool_ev_valid = 0; h->direct_ev_valid = 0;
-  // episode ends that the abandoned capture "parked" into the pool never ran: nothing is pending on their account
-  h->pool_episodes = 0; h->pool_run_upto = 0; h->pool_pending = 0;
-  for (int k = 0; k < TB_FF_SLOTS; ++k) {
-    h->ff_busy[k] = 0;
-    if (!h->side[k]) continue;
+  h->phase.restore();  // the captured tb_step calls advanced the host's episode phase, but none of them ran
+  h->pool.events_forgotten();
+  h->pool.idle();  // episode ends that the abandoned capture "parked" into the pool never ran: nothing is pending on their account
+  h->slots.forget_ordering();
+  h->slots.forget_capture();  // nothing of the abandoned capture will ever run
+  for (FfSlot& f : h->slots.s) {
+    if (!f.side) continue;
     // a side stream that was forked into the capture stays invalidated: replace it and its events
-    (void)hipStreamDestroy(h->side[k]);
-    (void)hipEventDestroy(h->ev_step[k]);
-    (void)hipEventDestroy(h->ev_ff[k]);
+    f.close();
     (void)hipGetLastError();
-    HIP_TRY(hipStreamCreateWithFlags(&h->side[k], hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&h->ev_step[k], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&h->ev_ff[k], hipEventDisableTiming));
+    if (int rc = f.open()) return rc;
   }
-  h->last_slot = -1; h->last_term = nullptr; h->last_sub = nullptr;
-  memset(h->ff_cap, 0, sizeof h->ff_cap);  // nothing of the abandoned capture will ever run
   return TB_OK;
 }
 
@@ -826,7 +860,7 @@ int tb_flush(TbHandle* h, void* stream) {
 
 int tb_phase(TbHandle* h) {
   if (!h) return fail(TB_E_INVAL, "tb_phase: null handle");
-  return h->phase_valid ? h->phase : -1;
+  return h->phase.valid ? h->phase.at : -1;
 }
 
 int tb_pipeline_form(TbHandle* h) {
@@ -844,7 +878,7 @@ int tb_step_waves(TbHandle* h) {
 
 int tb_phase_advance(TbHandle* h, int n_steps) {
   if (!h || n_steps < 0) return fail(TB_E_INVAL, "tb_phase_advance: bad argument");
-  if (h->phase_valid) h->phase = (h->phase + n_steps) % 26;
+  h->phase.advance(n_steps);
   h->first_substeps += (unsigned long long)h->n * (unsigned long long)n_steps;  // the replayed steps' share of the substep counter
   return TB_OK;
 }
@@ -853,51 +887,49 @@ int tb_mark_record(TbHandle* h, int k, void* stream) {
   if (!h || k < 0 || k >= TB_MAX_MARKS) return fail(TB_E_INVAL, "tb_mark_record: bad handle or mark index");
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
-  if (!h->marks_on) return fail(TB_E_UNSUPPORTED, "tb_mark_record needs tb_mark_enable(h, 1) before the steps it covers (their fast-forwards must be counted)");
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  HIP_TRY(hipStreamIsCapturing(s, &st));
+  if (!h->marks.on) return fail(TB_E_UNSUPPORTED, "tb_mark_record needs tb_mark_enable(h, 1) before the steps it covers (their fast-forwards must be counted)");
+  hipStreamCaptureStatus st;
+  if (int rc = capture_status(s, &st)) return rc;
   if (int rc = run_pool_for_mark(h, s)) return rc;  // (counted among the fast-forwards enqueued before the mark)
-  hipLaunchKernelGGL(tb_mark_kernel, dim3(1), dim3(1), 0, s, h->h_marks + k);
-  HIP_TRY(hipGetLastError());
-  h->mark_in_capture[k] = st == hipStreamCaptureStatusActive;
-  for (int q = 0; q < TB_FF_SLOTS; ++q) h->mark_ff_before[k][q] = h->mark_in_capture[k] ? h->ff_cap[q] : h->ff_eager[q];
+  if (int rc = launch(tb_mark_kernel, dim3(1), dim3(1), 0, s, h->marks.h + k)) return rc;
+  h->marks.in_capture[k] = st == hipStreamCaptureStatusActive;
+  for (int q = 0; q < TB_FF_SLOTS; ++q) h->marks.ff_before[k][q] = h->marks.in_capture[k] ? h->slots.s[q].in_capture : h->slots.s[q].eager;
   return TB_OK;
 }
 
 int tb_mark_enable(TbHandle* h, int on) {
   if (!h) return fail(TB_E_INVAL, "tb_mark_enable: null handle");
-  if (on) { if (int rc = ensure_marks(h)) return rc; }
-  h->marks_on = on ? 1 : 0;
+  if (on) { if (int rc = h->marks.ensure()) return rc; }
+  h->marks.on = on ? 1 : 0;
   return TB_OK;
 }
 
 int tb_mark_begin(TbHandle* h) {
   if (!h) return fail(TB_E_INVAL, "tb_mark_begin: null handle");
-  if (int rc = ensure_marks(h)) return rc;
-  for (int q = 0; q < TB_FF_SLOTS; ++q) h->snap_ff[q] = __atomic_load_n(h->h_marks + TB_MAX_MARKS + q, __ATOMIC_ACQUIRE);
-  for (int k = 0; k < TB_MAX_MARKS; ++k) h->snap_marks[k] = __atomic_load_n(h->h_marks + k, __ATOMIC_ACQUIRE);
-  memset(h->ff_eager, 0, sizeof h->ff_eager);
+  if (int rc = h->marks.ensure()) return rc;
+  for (int q = 0; q < TB_FF_SLOTS; ++q) { h->marks.snap_ff[q] = __atomic_load_n(h->marks.h + TB_MAX_MARKS + q, __ATOMIC_ACQUIRE); h->slots.s[q].eager = 0; }
+  for (int k = 0; k < TB_MAX_MARKS; ++k) h->marks.snap_marks[k] = __atomic_load_n(h->marks.h + k, __ATOMIC_ACQUIRE);
   return TB_OK;
 }
 
 long long tb_mark_count(TbHandle* h, int k) {
   if (!h || k < 0 || k >= TB_MAX_MARKS) return fail(TB_E_INVAL, "tb_mark_count: bad handle or mark index");
-  if (!h->h_marks) return 0;
-  return (long long)__atomic_load_n(h->h_marks + k, __ATOMIC_ACQUIRE);
+  if (!h->marks.h) return 0;
+  return (long long)__atomic_load_n(h->marks.h + k, __ATOMIC_ACQUIRE);
 }
 
 int tb_mark_host_wait(TbHandle* h, int k, int timeout_ms) {
-  if (!h || k < 0 || k >= TB_MAX_MARKS || !h->h_marks) return fail(TB_E_INVAL, "tb_mark_host_wait: bad handle, mark index, or no mark recorded yet");
+  if (!h || k < 0 || k >= TB_MAX_MARKS || !h->marks.h) return fail(TB_E_INVAL, "tb_mark_host_wait: bad handle, mark index, or no mark recorded yet");
   // fired once more than at tb_mark_begin, and every fast-forward enqueued before the mark has finished: those of the
   // graph that holds it (counted at capture time) plus whatever was launched eagerly since (over-waiting at worst)
   unsigned long long ff_target[TB_FF_SLOTS];
   for (int q = 0; q < TB_FF_SLOTS; ++q)
-    ff_target[q] = h->snap_ff[q] + (unsigned long long)(h->mark_in_capture[k] ? h->mark_ff_before[k][q] + h->ff_eager[q] : h->mark_ff_before[k][q]);
-  const unsigned long long count = h->snap_marks[k] + 1;
+    ff_target[q] = h->marks.snap_ff[q] + (unsigned long long)(h->marks.in_capture[k] ? h->marks.ff_before[k][q] + h->slots.s[q].eager : h->marks.ff_before[k][q]);
+  const unsigned long long count = h->marks.snap_marks[k] + 1;
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spins = 0;; ++spins) {
-    bool ok = __atomic_load_n(h->h_marks + k, __ATOMIC_ACQUIRE) >= count;
-    for (int q = 0; ok && q < TB_FF_SLOTS; ++q) ok = __atomic_load_n(h->h_marks + TB_MAX_MARKS + q, __ATOMIC_ACQUIRE) >= ff_target[q];
+    bool ok = __atomic_load_n(h->marks.h + k, __ATOMIC_ACQUIRE) >= count;
+    for (int q = 0; ok && q < TB_FF_SLOTS; ++q) ok = __atomic_load_n(h->marks.h + TB_MAX_MARKS + q, __ATOMIC_ACQUIRE) >= ff_target[q];
     if (ok) return TB_OK;
     if ((spins & 1023u) == 1023u &&
         std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() > timeout_ms)
@@ -921,13 +953,13 @@ int tb_set_params(TbHandle* h, const TbParams* params, void* stream) {
   // handle whose new parameter block asks for one (racket<->court contact above 16384 envs) gets it now; one that has it and
   // switches the contact set, and with it the record stride (pool_rec), starts from a zeroed pool -- no tag word of one stride can
   // land on the payload of a record of the other.
-  if (h->side[0] && !h->d_pool) {
+  if (h->slots.built() && !h->pool.rec) {
     if (int rc = alloc_pool(h, params->flags)) { (void)hipGetLastError(); return rc; }
     HIP_TRY(hipDeviceSynchronize());
-  } else if (h->d_pool && extended_contacts(kp) != extended_contacts(h->kp)) {
-    HIP_TRY(hipMemsetAsync(h->d_pool, 0, sizeof(float4) * (size_t)TB_FF_REC_MAX * (h->pool_cap + h->pool_slack), s));
+  } else if (h->pool.rec && extended_contacts(kp) != extended_contacts(h->kp)) {
+    HIP_TRY(hipMemsetAsync(h->pool.rec, 0, sizeof(float4) * (size_t)TB_FF_REC_MAX * h->pool.records(), s));
   }
-  if ((params->flags ^ h->params.flags) & TB_F_AUTO_RESET) h->phase_valid = 0;  // episodes may stop / start restarting
+  if ((params->flags ^ h->params.flags) & TB_F_AUTO_RESET) h->phase.invalidate();  // episodes may stop / start restarting
   h->params = *params; h->kp = kp;
   memcpy(h->cull_planes, planes, sizeof planes);
   if (int rc = upload_hull(h, s)) return rc;
@@ -947,23 +979,19 @@ int tb_set_racket_scale(TbHandle* h, float scale, void* stream) {
   DeviceGuard g(h->device);
   h->params.racket_scale = scale; h->kp.racket_scale = scale;  // what a later tb_set_params re-uploads
   float* dst = reinterpret_cast<float*>(h->d_hull + TB_HULL_KP) + offsetof(KParams, racket_scale) / sizeof(float);
-  hipLaunchKernelGGL(tb_poke_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dst, scale);
-  HIP_TRY(hipGetLastError());
-  return TB_OK;
+  return launch(tb_poke_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dst, scale);
 }
 
 int tb_reset(TbHandle* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
   if (!h) return fail(TB_E_INVAL, "tb_reset: null handle");
   DeviceGuard g(h->device);
   if (int rc = flush_all(h, (hipStream_t)stream)) return rc;
-  if (mask_dev) h->phase_valid = 0;  // episodes are no longer in lockstep
-  else { h->phase_valid = 1; h->phase = 0; }
+  if (mask_dev) h->phase.invalidate();  // episodes are no longer in lockstep
+  else h->phase.set(0);
   KArgs a = base_args(h);
   a.mask = mask_dev; a.obs = obs_dev;
   dim3 grid((unsigned)((h->n + 255) / 256)), block(256);
-  hipLaunchKernelGGL(h->kind == TB_ENV_SWING ? tb_reset_kernel<TB_ENV_SWING> : tb_reset_kernel<TB_ENV_TENNIS>, grid, block, 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return TB_OK;
+  return launch(h->kind == TB_ENV_SWING ? tb_reset_kernel<TB_ENV_SWING> : tb_reset_kernel<TB_ENV_TENNIS>, grid, block, 0, (hipStream_t)stream, a);
 }
 
 int tb_step(TbHandle* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, float* terminal_obs_dev,
@@ -1010,7 +1038,7 @@ int tb_policy_rollout(TbHandle* h, int n_steps, const float* weights_dev, const 
   if (n_steps < 1) return fail(TB_E_INVAL, "tb_policy_rollout: n_steps must be >= 1");
   if (!(h->kp.flags & TB_F_AUTO_RESET)) return fail(TB_E_UNSUPPORTED, "tb_policy_rollout needs TB_F_AUTO_RESET (episodes must restart inside the launch)");
   const bool swing = h->kind == TB_ENV_SWING;
-  if (swing && !(h->pipeline && h->phase_valid))
+  if (swing && !(h->pipeline && h->phase.valid))
     return fail(TB_E_UNSUPPORTED, "tb_policy_rollout on SwingRacket-v0 needs tb_set_pipeline(h, 1) and episodes in lockstep (every env reset together): "
                                   "the fast-forward that ends an episode cannot run inside a multi-step launch");
   const size_t n = (size_t)h->n, A = swing ? TB_SWING_ACT_DIM : TB_TENNIS_ACT_DIM, O = swing ? TB_SWING_OBS_DIM : TB_TENNIS_OBS_DIM;
@@ -1029,8 +1057,7 @@ int tb_policy_rollout(TbHandle* h, int n_steps, const float* weights_dev, const 
   hipStream_t s = (hipStream_t)stream;
   const float* obs_in = obs_in_dev;
   for (int t = 0; t < n_steps;) {
-    int chunk = n_steps - t;
-    if (swing) { const int room = 26 - h->phase; chunk = chunk < room ? chunk : room; }
+    const int chunk = swing ? h->phase.chunk(n_steps - t) : n_steps - t;
     PolicyIO pol = {weights_dev, obs_in, actions_dev + (size_t)t * st[0], raw_actions_dev + (size_t)t * st[1], logp_dev + (size_t)t * st[2],
                     value_dev + (size_t)t * st[3], noise_seed, deterministic};
     if (int rc = launch_policy_rollout(h, chunk, pol, obs_dev + (size_t)t * st[4], reward_dev + (size_t)t * st[5], done_dev + (size_t)t * st[6], st, s)) return rc;
@@ -1076,14 +1103,12 @@ int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t 
   ArgsKernel2 kern = swing ? (rg ? tb_es_rollout_kernel<TB_ENV_SWING, true> : tb_es_rollout_kernel<TB_ENV_SWING, false>)
                            : (rg ? tb_es_rollout_kernel<TB_ENV_TENNIS, true> : tb_es_rollout_kernel<TB_ENV_TENNIS, false>);
   (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3((unsigned)((h->n + 63) / 64)), dim3(64), dyn_lds(es_lds_words(h->kind, rg), 64), s, a, E);
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch(kern, dim3((unsigned)((h->n + 63) / 64)), dim3(64), dyn_lds(es_lds_words(h->kind, rg), 64), s, a, E)) return rc;
   if (swing) {
     if (int rc = finish_park(h, park, a, 0, s)) return rc;
     if (int rc = flush_all(h, s)) return rc;  // every fast-forward's reward is in d_es_rew once `s` gets past here
-    hipLaunchKernelGGL(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n,
-                       E.t_max > 25 ? E.t_rew : nullptr);
-    HIP_TRY(hipGetLastError());
+    float* const last_rew = E.t_max >= kEpisodeSteps ? E.t_rew : nullptr;  // (a trace that reaches the episode's last step)
+    if (int rc = launch(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n, last_rew)) return rc;
   }
   return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
 }
@@ -1095,12 +1120,12 @@ int tb_rollout(TbHandle* h, int n_steps, const float* actions_dev, float* obs_de
   if (!(h->kp.flags & TB_F_AUTO_RESET)) return fail(TB_E_UNSUPPORTED, "tb_rollout needs TB_F_AUTO_RESET (episodes must restart inside the launch)");
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
-  if (h->pipeline && h->kind == TB_ENV_SWING && h->phase_valid && !substeps_total_dev) {
-    // pipelined: launches that end where the episodes end (<= 26 steps each), every one followed by its
+  if (h->pipeline && h->kind == TB_ENV_SWING && h->phase.valid && !substeps_total_dev) {
+    // pipelined: launches that end where the episodes end, every one followed by its
     // fast-forward on a side stream instead of stalling its waves on it
     const size_t n = (size_t)h->n;
     for (int t = 0; t < n_steps;) {
-      const int room = 26 - h->phase, chunk = n_steps - t < room ? n_steps - t : room;
+      const int chunk = h->phase.chunk(n_steps - t);
       if (int rc = launch_step(h, chunk, actions_dev + (size_t)t * n * TB_SWING_ACT_DIM, obs_dev + (size_t)t * n * TB_SWING_OBS_DIM, reward_dev + (size_t)t * n,
                                done_dev + (size_t)t * n, nullptr, nullptr, s, nullptr, chunk > 1))
         return rc;
@@ -1129,34 +1154,14 @@ int tb_set_state(TbHandle* h, const uint32_t* words, const uint8_t* done, int on
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   if (int rc = flush_all(h, s)) return rc;
-  h->phase_valid = 0;  // injected states need not be in lockstep
+  h->phase.invalidate();  // injected states need not be in lockstep
   const size_t wb = sizeof(uint32_t) * (size_t)words_of(h->kind) * h->n;
   hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(hipMemcpyAsync(h->d_words, words, wb, k, s));
   if (done) HIP_TRY(hipMemcpyAsync(h->d_done, done, (size_t)h->n, k, s));
   else HIP_TRY(hipMemsetAsync(h->d_done, 0, (size_t)h->n, s));
   HIP_TRY(hipMemsetAsync(h->d_mflag, 0, (size_t)h->n, s));  // the racket<->court contact caches are not part of the state words
-  if (h->kind == TB_ENV_SWING && h->pipeline) {
-    // the pipelined kernels need to know which launch ends the episodes: the injected envs are in lockstep again
-    // when every one is running (done = 0) at the same step count s < 26 -- then the phase is s (e.g. a checkpoint
-    // of a training run restored into a fresh handle). Costs one small device-to-host copy and a stream
-    // synchronisation (so: not capturable, and not asynchronous even with on_device); only paid with the pipeline on,
-    // the one mode that uses the phase -- without it the call stays fully asynchronous for on_device buffers.
-    const size_t n = (size_t)h->n;
-    uint32_t* steps = (uint32_t*)malloc(n * sizeof(uint32_t));
-    uint8_t* dn = (uint8_t*)malloc(n);
-    if (!steps || !dn) { free(steps); free(dn); return fail(TB_E_INVAL, "tb_set_state: out of host memory"); }
-    hipError_t e1 = hipMemcpyAsync(steps, h->d_words + (size_t)TB_W_SW_STEP * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(dn, h->d_done, n, hipMemcpyDeviceToHost, s) : e1;
-    hipError_t e3 = e2 == hipSuccess ? hipStreamSynchronize(s) : e2;
-    if (e3 == hipSuccess) {
-      bool same = (int32_t)steps[0] >= 0 && (int32_t)steps[0] < 26;
-      for (size_t i = 0; same && i < n; ++i) same = steps[i] == steps[0] && dn[i] == TB_DONE_NO;
-      if (same) { h->phase_valid = 1; h->phase = (int)steps[0]; }
-    }
-    free(steps); free(dn);
-    if (e3 != hipSuccess) return fail((int)e3, "tb_set_state: reading back the step counters");
-  }
+  if (h->kind == TB_ENV_SWING && h->pipeline) { if (int rc = rederive_phase(h, s)) return rc; }
   if (!on_device) HIP_TRY(hipStreamSynchronize(s));
   return TB_OK;
 }
@@ -1164,11 +1169,9 @@ int tb_set_state(TbHandle* h, const uint32_t* words, const uint8_t* done, int on
 int tb_counters(TbHandle* h, uint64_t* out, void* stream) {
   if (!h || !out) return fail(TB_E_INVAL, "tb_counters: null argument");
   DeviceGuard g(h->device);
-  if (int rc = flush_all(h, (hipStream_t)stream)) return rc;
   static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "counter width");
   uint64_t shards[TB_COUNTER_SHARDS][TB_N_COUNTERS];
-  HIP_TRY(hipMemcpyAsync(shards, h->d_counters, sizeof shards, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (int rc = read_back(h, shards, h->d_counters, sizeof shards, (hipStream_t)stream)) return rc;
   for (int k = 0; k < TB_N_COUNTERS; ++k) {
     out[k] = 0;
     for (int sh = 0; sh < TB_COUNTER_SHARDS; ++sh) out[k] += shards[sh][k];
@@ -1180,10 +1183,7 @@ int tb_counters(TbHandle* h, uint64_t* out, void* stream) {
 int tb_sealed_substeps(TbHandle* h, uint64_t* out, void* stream) {
   if (!h || !out) return fail(TB_E_INVAL, "tb_sealed_substeps: null argument");
   DeviceGuard g(h->device);
-  if (int rc = flush_all(h, (hipStream_t)stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(out, h->d_counters + TB_N_COUNTERS * TB_COUNTER_SHARDS, sizeof(uint64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return TB_OK;
+  return read_back(h, out, h->d_counters + kSealedWord, sizeof(uint64_t), (hipStream_t)stream);
 }
 
 int tb_diag_stream_copy(const uint32_t* src_dev, uint32_t* dst_dev, int n, int rows, int device, void* stream) {
@@ -1221,7 +1221,7 @@ int tb_diag_idle(int waves, int microseconds, int device, void* stream) {
 int tb_counters_reset(TbHandle* h, void* stream) {
   if (!h) return fail(TB_E_INVAL, "tb_counters_reset: null handle");
   DeviceGuard g(h->device);
-  HIP_TRY(hipMemsetAsync(h->d_counters, 0, sizeof(uint64_t) * (TB_N_COUNTERS * TB_COUNTER_SHARDS + 1), (hipStream_t)stream));
+  HIP_TRY(hipMemsetAsync(h->d_counters, 0, sizeof(uint64_t) * kCounterWords, (hipStream_t)stream));
   h->first_substeps = 0;
   return TB_OK;
 }

@@ -1028,6 +1028,23 @@ except Exception:
 # HIP (ROCm 7.2) keeps refusing work on the legacy default stream of a process whose capture was
 # invalidated -- torch's own ops included -- so the survivor continues on a stream of its own
 with torch.cuda.stream(torch.cuda.Stream()):
+    # what the recovered handle would ENQUEUE: its results cannot show a pool that still counts the abandoned episode end as pending
+    # (the pool kernel finds every record of that region consumed), the work of its next flush can -- captured on its own, a flush
+    # with nothing pending is a graph without nodes, like the twin's
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")  # (the runtime torch has mapped already)
+    def nodes_of_a_flush(e):
+        q, graph, count = e._stream(), ctypes.c_void_p(), ctypes.c_size_t(0)
+        torch.cuda.current_stream().synchronize()
+        if hip.hipStreamBeginCapture(q, 1): sys.exit("hipStreamBeginCapture failed")  # (1 = thread-local, as BatchedEnv.capture)
+        rc = e.L.tb_flush(e._h, q)
+        if hip.hipStreamEndCapture(q, ctypes.byref(graph)) or rc: sys.exit("capturing a lone flush failed (tb_flush: %d)" % rc)
+        if hip.hipGraphGetNodes(graph, None, ctypes.byref(count)): sys.exit("hipGraphGetNodes failed")
+        hip.hipGraphDestroy(graph)
+        return count.value
+    k_env, k_twin = nodes_of_a_flush(env), nodes_of_a_flush(twin)
+    if k_env != 0 or k_twin != 0:
+        sys.exit("a flush right after the abandoned capture enqueues %d graph nodes (twin: %d): something is still pending" % (k_env, k_twin))
     for t in range(20, 60):
         a, b = env.step(acts[t]), twin.step(acts[t])
         env.flush(); twin.flush()

@@ -1,0 +1,293 @@
+"""Plain float64 restatement of the PPO learner (PPOTrainer.advantages / PPOTrainer.update, tennisbot_rl_amd/ppo.py): numpy only.
+
+The rule is SB3 1.8.0's PPO as the reference scripts configure it (train_swing.py:80-91, train.py:104-110):
+
+  * GAE from its definition. done[k] is the flag after step k (the envs auto-reset), V[T] = last_value,
+        delta[k] = r[k] + gamma V[k+1] (1 - done[k]) - V[k]
+        A[k]     = sum_{l >= k} (gamma lambda)^(l-k) prod_{k <= j < l} (1 - done[j]) delta[l],      returns = A + V.
+    `gae` evaluates that sum forward, one offset l - k at a time for every (k, env) at once -- not the backward recursion
+    the learner runs -- and returns beside it a forward error bound for a float32 evaluation of the recursion.
+  * The minibatch loss: advantages normalised inside the minibatch with the unbiased std, logp of the UNCLIPPED sample under
+    a diagonal Gaussian with a state-independent log_std, the clipped surrogate, a plain mean squared value error, the
+    Gaussian's entropy; its gradient with respect to every parameter by a hand-written backward pass through the tanh towers.
+  * The optimiser: gradients averaged over the ranks, THEN clipped to a global norm (torch's clip_grad_norm_: factor
+    min(1, max_norm / (norm + 1e-6))), Adam with eps 1e-5 and betas 0.9 / 0.999. `replay_update` runs epochs x minibatches
+    from recorded permutations, ragged tail included.
+
+Every function takes a `dtype`: with np.float32 it is the float32 twin of itself -- the same formulas with every
+intermediate rounded to float32. |twin - float64| is the rounding scale of a float32 learner on those inputs, measured
+without the code under test: the tolerance of gradients, statistics and parameters is a fixed multiple of it (`check_tensors`).
+
+Error bound of the float32 GAE recursion g[k] = delta[k] + (c nt[k]) g[k+1], c = fl(gamma lambda), u = 2^-24. Per step the
+recursion commits, relative to the exact value of what it rounds:
+    gamma V[k+1]:         gamma's own rounding and the product's   2 u |gamma V[k+1] nt|
+    r + (...):            one sum                                  u |r + gamma V[k+1] nt|
+    (...) - V[k]:         one sum                                  u |delta[k]|
+    (c nt) g[k+1]:        c's own rounding and the product's       2 u |c nt A[k+1]|
+    delta + (...):        one sum                                  u |A[k]|
+Call the total local[k]. An error committed at step l reaches A[k] multiplied by (gamma lambda)^(l-k) prod (1 - done[j]), the
+weight of the definition itself, so  err(A[k]) <= (1 + 4 T u) sum_l weight(k, l) local[l];  the factor covers the second-order
+terms ((1 + 2 u)^T over at most T steps). returns = A + V is one more sum: err + u |returns|. Inputs are exact float32.
+"""
+import math
+
+import numpy as np
+
+from policy_reference import LN_SQRT_2PI, U32, UNDERFLOW, state_dict_arrays  # noqa: F401  (state_dict_arrays: how tests take weights)
+
+BETAS = (0.9, 0.999)
+ADAM_EPS = 1e-5
+NORM_EPS = 1e-6   # torch.nn.utils.clip_grad_norm_
+ADV_EPS = 1e-8
+MULTIPLE = 24.0   # float32-twin errors allowed per tensor (max norm): see tests/test_ppo_reference.py for the measurements and the reason
+
+
+class GAE:
+    """adv, returns [T, n] and the error bounds of a float32 recursion on the same inputs"""
+
+    def __init__(self, adv, returns, adv_bound, returns_bound, delta):
+        self.adv, self.returns, self.adv_bound, self.returns_bound, self.delta = adv, returns, adv_bound, returns_bound, delta
+
+
+def _forward_sum(x, nt, w):
+    """S[k] = sum_{l >= k} w^(l-k) prod_{k <= j < l} nt[j] x[l], offset by offset"""
+    T = x.shape[0]
+    out = np.zeros_like(x)
+    alive = np.ones_like(x)           # prod of nt[k .. k+m-1] for the current offset m
+    wm = x.dtype.type(1.0)
+    for m in range(T):
+        out[:T - m] += wm * alive[:T - m] * x[m:]
+        alive[:T - m] *= nt[m:]
+        wm = wm * w
+        if not alive[:T - m - 1].any():
+            break
+    return out
+
+
+def gae(rewards, values, dones, last_value, gamma, gae_lambda, dtype=np.float64):
+    dt = np.dtype(dtype).type
+    r, V = np.asarray(rewards).astype(dtype), np.asarray(values).astype(dtype)
+    nt = (np.asarray(dones) == 0).astype(dtype)
+    T = r.shape[0]
+    Vn = np.concatenate([V[1:], np.asarray(last_value).astype(dtype)[None]], 0)
+    boot = dt(gamma) * Vn * nt
+    delta = r + boot - V
+    w = dt(dt(gamma) * dt(gae_lambda)) if dtype == np.float32 else dt(gamma * gae_lambda)
+    adv = _forward_sum(delta, nt, w)
+    returns = adv + V
+    # the bound, always in float64 and from the float64 quantities
+    r6, V6, nt6 = r.astype(np.float64), V.astype(np.float64), nt.astype(np.float64)
+    boot6 = gamma * np.concatenate([V6[1:], np.asarray(last_value, np.float64)[None]], 0) * nt6
+    delta6 = r6 + boot6 - V6
+    w6 = gamma * gae_lambda
+    A6 = _forward_sum(delta6, nt6, w6)
+    A_next = np.concatenate([A6[1:], np.zeros_like(A6[:1])], 0)
+    local = U32 * (2.0 * np.abs(boot6) + np.abs(r6 + boot6) + np.abs(delta6) + 2.0 * np.abs(w6 * nt6 * A_next) + np.abs(A6)) + 4.0 * UNDERFLOW
+    adv_bound = (1.0 + 4.0 * T * U32) * _forward_sum(local, nt6, w6)
+    returns_bound = adv_bound + U32 * (np.abs(A6 + V6) + adv_bound)
+    return GAE(adv, returns, adv_bound, returns_bound, delta)
+
+
+# ---------------------------------------------------------------------------------------------------------- loss and gradient
+class Loss:
+    def __init__(self, loss, grads, stats, ratio, adv_norm, active):
+        self.loss, self.grads, self.stats, self.ratio, self.adv_norm, self.active = loss, grads, stats, ratio, adv_norm, active
+
+
+def cast_params(params, dtype):
+    return {k: np.asarray(v).astype(dtype) for k, v in params.items()}
+
+
+def _tower(P, body, head, x):
+    hs, k = [x], 0
+    while "%s.%d.weight" % (body, k) in P:
+        hs.append(np.tanh(hs[-1] @ P["%s.%d.weight" % (body, k)].T + P["%s.%d.bias" % (body, k)]))
+        k += 2
+    return hs, hs[-1] @ P[head + ".weight"].T + P[head + ".bias"]
+
+
+def _tower_backward(P, body, head, hs, d_out, grads):
+    """d_out [B, out]: the loss's derivative with respect to the head's output"""
+    grads[head + ".weight"], grads[head + ".bias"] = d_out.T @ hs[-1], d_out.sum(0)
+    dh = d_out @ P[head + ".weight"]
+    for i in reversed(range(len(hs) - 1)):
+        dz = dh * (1 - hs[i + 1] * hs[i + 1])   # tanh' = 1 - tanh^2
+        grads["%s.%d.weight" % (body, 2 * i)], grads["%s.%d.bias" % (body, 2 * i)] = dz.T @ hs[i], dz.sum(0)
+        dh = dz @ P["%s.%d.weight" % (body, 2 * i)]
+
+
+def loss_and_grads(params, obs, act, old_logp, adv, returns, hp, dtype=np.float64):
+    """one minibatch: the scalar loss, d loss / d parameter for every parameter, and the three reported statistics.
+    `adv` is the raw minibatch slice: it is normalised here. `act` is the unclipped sample."""
+    dt = np.dtype(dtype).type
+    P = cast_params(params, dtype)
+    obs, act, old_logp, adv, returns = (np.asarray(x).astype(dtype) for x in (obs, act, old_logp, adv, returns))
+    B = adv.shape[0]
+    c, vf, ent = dt(hp["clip_range"]), dt(hp["vf_coef"]), dt(hp["ent_coef"])
+    a = (adv - adv.mean(dtype=dtype)) / (adv.std(ddof=1, dtype=dtype) + dt(ADV_EPS))
+    hs_pi, mean = _tower(P, "policy_net", "action_net", obs)
+    hs_vf, value = _tower(P, "value_net_body", "value_net", obs)
+    value = value[:, 0]
+    log_std = P["log_std"]
+    inv_std = np.exp(-log_std)
+    zeta = (act - mean) * inv_std                      # the standardised sample
+    logp = (dt(-0.5) * zeta * zeta - log_std - dt(LN_SQRT_2PI)).sum(-1, dtype=dtype)
+    ratio = np.exp(logp - old_logp)
+    s1, s2 = a * ratio, a * np.clip(ratio, dt(1) - c, dt(1) + c)
+    pg = -np.minimum(s1, s2).mean(dtype=dtype)
+    verr = returns - value
+    vl = (verr * verr).mean(dtype=dtype)
+    entropy = (dt(0.5) + dt(LN_SQRT_2PI) + log_std).sum(dtype=dtype)
+    loss = pg + vf * vl - ent * entropy
+    # backward. The surrogate moves with the ratio where the unclipped term is the smaller one (or both agree: no clip)
+    active = s1 <= s2
+    d_logp = np.where(active, -a * ratio, dt(0)) / dt(B)
+    grads = {}
+    _tower_backward(P, "policy_net", "action_net", hs_pi, (d_logp[:, None] * zeta) * inv_std, grads)   # d logp / d mean = zeta / std
+    grads["log_std"] = (d_logp[:, None] * (zeta * zeta - dt(1))).sum(0, dtype=dtype) - ent                # d logp / d log_std = zeta^2 - 1
+    _tower_backward(P, "value_net_body", "value_net", hs_vf, (dt(-2) * vf / dt(B) * verr)[:, None], grads)
+    stats = {"policy_loss": float(pg), "value_loss": float(vl), "entropy": float(entropy)}
+    return Loss(float(loss), grads, stats, ratio, a, active)
+
+
+def scalar_loss(params, obs, act, old_logp, adv, returns, hp):
+    """the loss alone, in float64 (finite differences)"""
+    return loss_and_grads(params, obs, act, old_logp, adv, returns, hp).loss
+
+
+# ------------------------------------------------------------------------------------------------------------------ optimiser
+def global_norm(grads):
+    return math.sqrt(sum(float((np.asarray(g, np.float64) ** 2).sum()) for g in grads.values()))
+
+
+def clip_global_norm(grads, max_norm, dtype=np.float64):
+    """torch.nn.utils.clip_grad_norm_: every gradient times min(1, max_norm / (norm + 1e-6)); returns (clipped, norm)"""
+    dt = np.dtype(dtype).type
+    norm = dt(np.sqrt(sum((np.asarray(g).astype(dtype) ** 2).sum(dtype=dtype) for g in grads.values()), dtype=dtype))
+    coef = min(dt(1.0), dt(max_norm) / (norm + dt(NORM_EPS)))
+    return {k: np.asarray(g).astype(dtype) * dt(coef) for k, g in grads.items()}, float(norm)
+
+
+def adam_init(params, dtype=np.float64):
+    return {"t": 0, "m": {k: np.zeros_like(np.asarray(v), dtype=dtype) for k, v in params.items()},
+            "v": {k: np.zeros_like(np.asarray(v), dtype=dtype) for k, v in params.items()}}
+
+
+def adam_step(params, grads, state, lr, betas=BETAS, eps=ADAM_EPS, dtype=np.float64):
+    """Adam (Kingma & Ba, Algorithm 1, with eps added to sqrt(v_hat) as torch does). Returns new params; `state` is updated."""
+    dt = np.dtype(dtype).type
+    b1, b2 = dt(betas[0]), dt(betas[1])
+    state["t"] += 1
+    t = state["t"]
+    c1, c2 = dt(1.0 - betas[0] ** t), dt(1.0 - betas[1] ** t)
+    out = {}
+    for k, p in params.items():
+        g = np.asarray(grads[k]).astype(dtype)
+        m = state["m"][k] = b1 * np.asarray(state["m"][k]).astype(dtype) + (dt(1) - b1) * g
+        v = state["v"][k] = b2 * np.asarray(state["v"][k]).astype(dtype) + (dt(1) - b2) * g * g
+        out[k] = np.asarray(p).astype(dtype) - dt(lr) * (m / c1) / (np.sqrt(v / c2) + dt(eps))
+    return out
+
+
+class Update:
+    def __init__(self, params, grads, stats, norms):
+        self.params, self.grads, self.stats, self.norms = params, grads, stats, norms
+
+
+def replay_update(params, shards, perms, batch_size, hp, dtype=np.float64, adam_state=None):
+    """The whole of PPOTrainer.update for `len(shards)` ranks. shards[r] = (obs [n, O], act [n, A], old_logp [n], adv [n],
+    returns [n]) of rank r; perms[r][epoch]: the permutation rank r drew in that epoch. Returns the final parameters, the last
+    (averaged, clipped) gradients, per rank the statistics of the last minibatch, and the pre-clip norm of every step."""
+    dt = np.dtype(dtype).type
+    P = cast_params(params, dtype)
+    state = adam_state if adam_state is not None else adam_init(P, dtype)
+    world = len(shards)
+    n = len(shards[0][3])
+    grads, stats, norms = None, [None] * world, []
+    for epoch in range(len(perms[0])):
+        for s in range(0, n, batch_size):
+            total = None
+            for r, shard in enumerate(shards):
+                idx = np.asarray(perms[r][epoch])[s:s + batch_size]
+                res = loss_and_grads(P, *(np.asarray(x)[idx] for x in shard), hp, dtype)
+                stats[r] = res.stats
+                total = res.grads if total is None else {k: total[k] + res.grads[k] for k in total}
+            if world > 1:
+                total = {k: g / dt(world) for k, g in total.items()}
+            grads, norm = clip_global_norm(total, hp["max_grad_norm"], dtype)
+            norms.append(norm)
+            P = adam_step(P, grads, state, hp["learning_rate"], dtype=dtype)
+    return Update(P, grads, stats, norms)
+
+
+# -------------------------------------------------------------------------------------------------------------------- checking
+def twin_scale(want, twin):
+    """per tensor: max |float32 twin - float64|, and never below u max |float64| (no float32 result is expected to sit
+    closer to the exact one than half an ulp of its own size, whatever the twin achieved by chance)"""
+    out = {}
+    for k, w in want.items():
+        w, t = np.asarray(w, np.float64), np.asarray(twin[k], np.float64)
+        out[k] = max(float(np.abs(t - w).max()), U32 * float(np.abs(w).max()))
+    return out
+
+
+def tensor_ratios(got, want, twin):
+    """per tensor: max |got - float64| / twin_scale. Every element takes part; a non-finite one counts as infinitely far."""
+    scale = twin_scale(want, twin)
+    out = {}
+    for k, w in want.items():
+        g = np.asarray(got[k], np.float64)
+        if g.shape != np.shape(w):
+            raise AssertionError("%s: shape %s, want %s" % (k, g.shape, np.shape(w)))
+        d = np.abs(g - np.asarray(w, np.float64))
+        d = np.where(np.isfinite(d), d, np.inf)
+        out[k] = float(d.max()) / scale[k]
+    return out
+
+
+def check_tensors(name, got, want, twin, multiple):
+    """every tensor of `got` within `multiple` twin errors of the float64 result in the max norm; returns the largest ratio"""
+    ratios = tensor_ratios(got, want, twin)
+    worst = max(ratios, key=ratios.get)
+    if not ratios[worst] <= multiple:
+        raise AssertionError("%s: %s is %.3g float32-twin errors from the float64 reference (allowed %.3g)" % (name, worst, ratios[worst], multiple))
+    return ratios[worst]
+
+
+# ------------------------------------------------------------------------------------- reading a torch learner (duck-typed: no import)
+def named_grads(policy):
+    return {k: p.grad.detach().cpu().numpy().copy() for k, p in policy.named_parameters()}
+
+
+def named_params(policy):
+    return {k: p.detach().cpu().numpy().copy() for k, p in policy.named_parameters()}
+
+
+def adam_state_of(policy, opt):
+    """torch.optim.Adam's moments and step count as adam_step takes them (zeros before the first step)"""
+    state = adam_init(named_params(policy))
+    for k, p in policy.named_parameters():
+        st = opt.state.get(p, {})
+        if st:
+            state["t"] = int(st["step"])
+            state["m"][k] = st["exp_avg"].detach().cpu().numpy().astype(np.float64)
+            state["v"][k] = st["exp_avg_sq"].detach().cpu().numpy().astype(np.float64)
+    return state
+
+
+def copy_state(state):
+    return {"t": state["t"], "m": {k: v.copy() for k, v in state["m"].items()}, "v": {k: v.copy() for k, v in state["v"].items()}}
+
+
+def record_permutations(torch, seed, n, epochs, device="cpu"):
+    """what PPOTrainer.update will draw after torch.manual_seed(seed) -- it draws nothing else from the generator --, with the
+    generator put back to that seed"""
+    torch.manual_seed(seed)
+    perms = [torch.randperm(n, device=device).cpu().numpy() for _ in range(epochs)]
+    torch.manual_seed(seed)
+    return perms
+
+
+def param_change(P, P0, lr):
+    """(p - p0) / lr per tensor: the update in units of the learning rate"""
+    return {k: (np.asarray(P[k], np.float64) - np.asarray(P0[k], np.float64)) / lr for k in P0}

@@ -368,6 +368,54 @@ int tb_es_evaluate(TbHandle *h, const float *weights_dev, int n_members, size_t 
                    double *return_dev, int32_t *length_dev, const TbEsTrace *trace_or_null, void *stream);
 
 /*
+ * The PPO learner (csrc/tb_learner.hpp; tennisbot_rl_amd/learner.py is the caller): GAE, one minibatch's gradient, and the
+ * optimiser step, fp32, for the two policy architectures the fused policy kernels are instantiated for. These functions need
+ * no env: they take (env_kind, device, stream) instead of a TbHandle, every buffer is caller-owned device memory, and every
+ * output is complete in stream order on `stream` when the call returns. Nothing is read or written on the host.
+ *
+ * Flat parameter order (tb_ppo_param_floats(kind) floats: 9069 SwingRacket-v0, 10181 Tennisbot-v0): the order of
+ * build_actor_critic(...).named_parameters() in tennisbot_rl_amd/ppo.py, each tensor row-major as torch holds it
+ * (nn.Linear.weight is [out][in]):
+ *   log_std [A] | policy_net.{0,2,(4)}.weight, .bias interleaved per layer | value_net_body likewise |
+ *   action_net.weight [A][last], .bias [A] | value_net.weight [1][last], .bias [1]
+ * The gradient and both Adam moments use the same order. float arrays must be 4-byte aligned, idx_dev and the workspace 8-byte
+ * aligned; bad sizes, null or misaligned pointers are refused here (TB_E_INVAL, tb_last_error), before anything is launched.
+ *
+ * tb_ppo_gae: adv[k] = delta[k] + gamma lambda (1 - done[k]) adv[k+1], delta[k] = r[k] + gamma V[k+1] (1 - done[k]) - V[k],
+ * V[T] = last_value; returns = adv + V. One lane per env, one launch. rewards / dones are [T][n] with a distance of
+ * *_step_stride_bytes between steps (0 = contiguous; e.g. the record size of a packed rollout buffer); values, adv and returns
+ * are contiguous [T][n], last_value [n].
+ *
+ * tb_ppo_grad: the gradient of the clipped-surrogate loss (advantages normalised with the minibatch's mean and unbiased std,
+ * value loss vf_coef * mean squared error; the entropy term is added by tb_ppo_apply) over the rows idx[0 .. batch) of the
+ * flat rollout arrays obs [n_rows][O], raw_actions [n_rows][A] (the unclipped samples), old_logp, adv, returns [n_rows].
+ * Each workgroup gathers tb_ppo_rows_per_workgroup() consecutive entries of idx itself and leaves partial gradient vectors in
+ * the workspace (tb_ppo_workspace_bytes(kind, batch) bytes; its content is only meaningful to tb_ppo_apply). No float atomics:
+ * the same inputs give the same bits. batch >= 2; idx values outside [0, n_rows) are clamped.
+ *
+ * tb_ppo_apply, phases = TB_PPO_REDUCE: grad_dev = the partials summed in a fixed order, minus ent_coef on log_std; stats_dev
+ * [3] = policy loss, value loss, entropy of the minibatch. phases = TB_PPO_STEP: grad_dev /= world, then times torch's clip
+ * factor min(1, max_grad_norm / (norm + 1e-6)); Adam (bias correction from `step`, the 1-based count of this step) updates
+ * params_dev, exp_avg_dev and exp_avg_sq_dev in place. Both bits: the two in turn. With several ranks the caller all-reduces
+ * (sums) grad_dev between the two phases; identical grad_dev, parameters and moments give identical bits on every rank.
+ */
+#define TB_PPO_REDUCE 1
+#define TB_PPO_STEP 2
+int tb_ppo_param_floats(int env_kind);
+int tb_ppo_rows_per_workgroup(void);
+long long tb_ppo_workspace_bytes(int env_kind, int batch);
+int tb_ppo_gae(int env_kind, int device, void *stream, int n_steps, int n_envs, const float *rewards_dev,
+               size_t reward_step_stride_bytes, const uint8_t *dones_dev, size_t done_step_stride_bytes, const float *values_dev,
+               const float *last_value_dev, double gamma, double gae_lambda, float *adv_dev, float *returns_dev);
+int tb_ppo_grad(int env_kind, int device, void *stream, const float *obs_dev, const float *raw_actions_dev,
+                const float *old_logp_dev, const float *adv_dev, const float *returns_dev, long long n_rows,
+                const int64_t *idx_dev, int batch, const float *params_dev, int n_params, float clip_range, float vf_coef,
+                void *workspace_dev, size_t workspace_bytes);
+int tb_ppo_apply(int env_kind, int device, void *stream, int phases, const void *workspace_dev, size_t workspace_bytes, int batch,
+                 float *params_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev, int n_params, float *stats_dev,
+                 float ent_coef, float max_grad_norm, int world, float lr, float beta1, float beta2, float eps, long long step);
+
+/*
  * Pipelined fast-forward (SwingRacket-v0 with TB_F_AUTO_RESET; HIP streams, no reference
  * counterpart). The <= 775-substep fast-forward of swingracket_env.py:105-141 takes no
  * agent input, and the next episode does not depend on its outcome. With the pipeline

@@ -1,0 +1,467 @@
+// The PPO learner on the device (tb_ppo_gae, tb_ppo_grad, tb_ppo_apply): GAE, one minibatch's gradient, norm clip + Adam.
+// Device code only; included by tb_stepper.hip after tb_kernels.hpp (Dims, PolicyNet, fast_tanh, f32x4 of tb_policy.hpp).
+//
+// Parameters travel as ONE flat fp32 vector in the order of build_actor_critic(...).named_parameters(), every tensor
+// row-major as torch holds it (nn.Linear.weight is [out][in]):
+//     log_std [A] | policy_net: W0 b0 W1 b1 (W2 b2) | value_net_body: the same | action_net W b | value_net W b
+// (PpoLayout). The gradient, both Adam moments and every partial gradient use the same order.
+//
+// tb_ppo_grad_kernel. A workgroup of four waves takes TB_PPO_SHARE = 256 consecutive entries of the minibatch's index vector;
+// wave w runs ONE tower (w >> 1: 0 = pi, 1 = vf; the two towers share nothing but the observation) over one half (w & 1) of
+// them, 16 rows per tile, and never talks to the other waves: no barrier, no atomics. Per tile, on v_mfma_f32_16x16x4_f32 with
+// the fragment conventions of tb_policy.hpp (everything transposed: features on the M axis, the 16 rows on N):
+//   forward    Z^T[out][row]  = W[out][k] H^T[k][row]        A = weight fragment, B = the previous layer's C/D registers
+//   backward   dH^T[in][row]  = W^T[in][out] dZ^T[out][row]   A = transposed weight fragment, B = dZ's C/D registers
+//   weights    dW[out][in]   += dZ^T[out][row] H[row][in]     K = the rows: both operands need the row index on the lane
+//                                                             GROUP, not on the lane -- one 16 x 16 transpose each through
+//                                                             LDS (ppo_transpose: wave-private, no workgroup barrier)
+// Forward and transposed weight fragments and every dW / db / d log_std accumulator stay in registers over the wave's whole
+// share (128 rows: an fp32 chain of 128 per element at the most); at the end each wave writes its tower's slots of partial
+// vector 2 * workgroup + half. tb_ppo_reduce_kernel then adds the partials per parameter in float64 in a fixed order.
+// The minibatch's advantage mean / unbiased std come from tb_ppo_adv_stats_kernel (float64 sums of x and x^2 in 64 blocks,
+// combined in a fixed order by every wave that needs them).
+#pragma once
+
+namespace {
+
+constexpr int TB_PPO_SHARE = 256;       // rows of the index vector per workgroup
+constexpr int TB_PPO_HALF = TB_PPO_SHARE / 2;
+constexpr int TB_PPO_STAT_BLOCKS = 64;  // partial sums of the advantage statistics
+constexpr float TB_LN_SQRT_2PI = 0.9189385332046727f;
+
+template <int KIND> struct PpoLayout {
+  using N = PolicyNet<KIND>;
+  static constexpr int O = Dims<KIND>::O, A = Dims<KIND>::A, NH = N::NH, LAST = N::LAST;
+  static constexpr int BODY = N::H0 * (O + 1) + N::H1 * (N::H0 + 1) + (NH == 3 ? N::H2 * (N::H1 + 1) : 0);
+  static constexpr int LOG_STD = 0, PI = A, VF = PI + BODY, PI_HEAD = VF + BODY, VF_HEAD = PI_HEAD + A * (LAST + 1);
+  static constexpr int P = VF_HEAD + LAST + 1;
+  static constexpr int STRIDE = P + 2;  // a partial vector: the gradient, then sum(-min(s1, s2)) and sum(verr^2)
+  // within a body: W0, b0, W1, b1, W2, b2
+  static constexpr int W0 = 0, B0 = W0 + N::H0 * O, W1 = B0 + N::H0, B1 = W1 + N::H1 * N::H0, W2 = B1 + N::H1, B2 = W2 + N::H2 * N::H1;
+};
+
+// 16 x 16 transpose of one accumulator tile inside a wave. In: C/D layout (lane (g, e) = (lane >> 4, lane & 15), register r:
+// feature 4 g + r of row e). Out: "row on the group" layout (lane (g, f), register c: feature f of row 4 c + g) -- the A
+// operand (as dZ^T) and the B operand (as H) of the dW product, whose k index is the row. buf: 256 floats of this wave's own.
+TB_DEV f32x4 ppo_transpose(const f32x4 c, float* buf, int lane) {
+  const int g = lane >> 4, e = lane & 15;
+  *reinterpret_cast<f32x4*>(buf + e * 16 + 4 * g) = c;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  f32x4 t;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) t[k] = buf[(4 * k + g) * 16 + e];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  return t;
+}
+
+// one nn.Linear of a tower for this lane: forward fragments, transposed fragments, bias, and the gradient accumulators
+template <int IN, int OUT, bool FIRST>
+struct PpoLayer {
+  static constexpr int NT = (OUT + 15) / 16, NTI = (IN + 15) / 16, NC = FIRST ? (IN + 3) / 4 : IN / 4;
+  static_assert(FIRST || IN % 16 == 0, "hidden widths are multiples of 16");
+  float wf[NT * NC];                   // (t, c): W[16 t + j][k(c, g)], k as in tb_policy.hpp
+  float wb[FIRST ? 1 : NTI * NT * 4];  // (ti, t, r): W[16 t + 4 g + r][16 ti + j]
+  f32x4 bias[NT];
+  f32x4 dw[NT * NTI];                  // (t, ti), C/D layout: dW[16 t + 4 g + r][16 ti + j]
+  float db[NT];                        // feature 16 t + j, summed over the rows = g (mod 4) so far
+
+  TB_DEV void load(const float* W, const float* b, int lane) {
+    const int g = lane >> 4, j = lane & 15;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int o = 16 * t + j, k = FIRST ? 4 * c + g : 16 * (c >> 2) + 4 * g + (c & 3);
+        wf[t * NC + c] = (o < OUT && k < IN) ? W[o * IN + k] : 0.0f;
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = 16 * t + 4 * g + r;
+        bias[t][r] = o < OUT ? b[o] : 0.0f;
+      }
+      db[t] = 0.0f;
+#pragma unroll
+      for (int ti = 0; ti < NTI; ++ti) dw[t * NTI + ti] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    if (!FIRST) {
+#pragma unroll
+      for (int ti = 0; ti < NTI; ++ti) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int o = 16 * t + 4 * g + r, i = 16 * ti + j;
+            wb[(ti * NT + t) * 4 + r] = (o < OUT && i < IN) ? W[o * IN + i] : 0.0f;
+          }
+        }
+      }
+    }
+  }
+  // z = bias + W x. The first layer takes its k-chunks as floats, the later ones the previous layer's C/D registers
+  TB_DEV void forward_first(const float (&x)[NC], f32x4 (&z)[NT]) const {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) z[t] = bias[t];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t * NC + c], x[c], z[t], 0, 0, 0);
+    }
+  }
+  TB_DEV void forward(const f32x4 (&h)[NTI], f32x4 (&z)[NT]) const {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) z[t] = bias[t];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t * NC + c], h[c >> 2][c & 3], z[t], 0, 0, 0);
+    }
+  }
+  // dh = W^T dz, in the C/D layout of this layer's input
+  TB_DEV void backward_input(const f32x4 (&dz)[NT], f32x4 (&dh)[NTI]) const {
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti) dh[ti] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int ti = 0; ti < NTI; ++ti) dh[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[(ti * NT + t) * 4 + r], dz[t][r], dh[ti], 0, 0, 0);
+      }
+    }
+  }
+  // dW += dz^T h, db += dz^T 1 for the tile's 16 rows; both operands in ppo_transpose's layout
+  TB_DEV void accumulate(const f32x4 (&dzT)[NT], const f32x4 (&hT)[NTI]) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int ti = 0; ti < NTI; ++ti) dw[t * NTI + ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(dzT[t][c], hT[ti][c], dw[t * NTI + ti], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) db[t] += (dzT[t][0] + dzT[t][1]) + (dzT[t][2] + dzT[t][3]);
+  }
+  // this wave's sums into its partial vector (gW, gb: where this layer's weight and bias lie in it)
+  TB_DEV void store(float* gW, float* gb, int lane) const {
+    const int g = lane >> 4, j = lane & 15;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int ti = 0; ti < NTI; ++ti) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int o = 16 * t + 4 * g + r, i = 16 * ti + j;
+          if (o < OUT && i < IN) gW[o * IN + i] = dw[t * NTI + ti][r];
+        }
+      }
+      float s = db[t];  // the four lane groups hold the rows = 0, 1, 2, 3 (mod 4): (0 + 1) + (2 + 3) on every lane
+      s += __shfl_xor(s, 16);
+      s += __shfl_xor(s, 32);
+      if (g == 0 && 16 * t + j < OUT) gb[16 * t + j] = s;
+    }
+  }
+};
+
+template <int NTILES>
+TB_DEV void ppo_tanh(const f32x4 (&z)[NTILES], f32x4 (&h)[NTILES]) {
+#pragma unroll
+  for (int t = 0; t < NTILES; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h[t][r] = fast_tanh(z[t][r]);
+  }
+}
+// dz = dh (1 - h^2)
+template <int NTILES>
+TB_DEV void ppo_dtanh(const f32x4 (&dh)[NTILES], const f32x4 (&h)[NTILES], f32x4 (&dz)[NTILES]) {
+#pragma unroll
+  for (int t = 0; t < NTILES; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dz[t][r] = dh[t][r] * (1.0f - h[t][r] * h[t][r]);
+  }
+}
+template <int NTILES>
+TB_DEV void ppo_transpose_all(const f32x4 (&c)[NTILES], f32x4 (&t)[NTILES], float* buf, int lane) {
+#pragma unroll
+  for (int k = 0; k < NTILES; ++k) t[k] = ppo_transpose(c[k], buf + (k & 1) * 256, lane);
+}
+
+struct PpoGradArgs {
+  const float* obs;       // [N][O]
+  const float* act;       // [N][A] the unclipped samples
+  const float* old_logp;  // [N]
+  const float* adv;       // [N]
+  const float* ret;       // [N]
+  const long long* idx;   // [B] rows of the minibatch
+  const float* params;    // [P]
+  const double* adv_sums; // [TB_PPO_STAT_BLOCKS][2]: sum x, sum x^2 of adv[idx]
+  float* partials;        // [2 * workgroups][P + 2]
+  long long n_rows;
+  int batch;
+  float clip_range, vf_coef;
+};
+
+// sum and sum of squares of the minibatch's advantages, float64, one pair per block (fixed order inside a block)
+__global__ __launch_bounds__(256) void tb_ppo_adv_stats_kernel(const float* adv, const long long* idx, int batch, long long n_rows, double* out) {
+  __shared__ double s_x[256], s_q[256];
+  double x = 0.0, q = 0.0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < batch; i += TB_PPO_STAT_BLOCKS * 256) {
+    long long row = idx[i];
+    row = row < 0 ? 0 : row >= n_rows ? n_rows - 1 : row;
+    const double a = (double)adv[row];
+    x += a; q += a * a;
+  }
+  s_x[threadIdx.x] = x; s_q[threadIdx.x] = q;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { s_x[threadIdx.x] += s_x[threadIdx.x + w]; s_q[threadIdx.x] += s_q[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[2 * blockIdx.x] = s_x[0]; out[2 * blockIdx.x + 1] = s_q[0]; }
+}
+
+// one tower of one half share. PI: the policy tower (logp, ratio, clipped surrogate, d log_std); else the value tower
+template <int KIND, bool PI>
+TB_DEV void ppo_tower(const PpoGradArgs& a, float* buf, int lane, int first, float* part) {
+  using L = PpoLayout<KIND>;
+  using N = PolicyNet<KIND>;
+  constexpr int O = L::O, NA = L::A, NH = L::NH, HOUT = PI ? NA : 1;
+  const int g = lane >> 4, e = lane & 15, B = a.batch;
+  const float* body = a.params + (PI ? L::PI : L::VF);
+  const float* head = a.params + (PI ? L::PI_HEAD : L::VF_HEAD);
+  using L0 = PpoLayer<O, N::H0, true>;
+  using L1 = PpoLayer<N::H0, N::H1, false>;
+  using L2 = PpoLayer<N::H1, N::H2, false>;  // (untouched when NH == 2)
+  using LH = PpoLayer<N::LAST, HOUT, false>;
+  L0 l0;
+  L1 l1;
+  L2 l2;
+  LH lh;
+  l0.load(body + L::W0, body + L::B0, lane);
+  l1.load(body + L::W1, body + L::B1, lane);
+  if (NH == 3) l2.load(body + L::W2, body + L::B2, lane);
+  lh.load(head, head + HOUT * N::LAST, lane);
+
+  // the minibatch's advantage mean and unbiased std (PI), from the pre-pass' float64 sums in a fixed order
+  float adv_mean = 0.0f, adv_den = 1.0f;
+  float ls[4], inv_std[4], dls[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (PI) {
+    double sx = 0.0, sq = 0.0;
+    for (int k = 0; k < TB_PPO_STAT_BLOCKS; ++k) { sx += a.adv_sums[2 * k]; sq += a.adv_sums[2 * k + 1]; }
+    const double mean = sx / (double)B, var = (sq - sx * mean) / (double)(B - 1);
+    adv_mean = (float)mean;
+    adv_den = (float)sqrt(var > 0.0 ? var : 0.0) + 1e-8f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      ls[r] = 4 * g + r < NA ? a.params[L::LOG_STD + 4 * g + r] : 0.0f;
+      inv_std[r] = expf(-ls[r]);
+    }
+  }
+  const float fb = (float)B;
+  float stat = 0.0f;  // PI: sum of -min(s1, s2); else sum of verr^2 (this lane's rows; lanes of group 0 only)
+
+  for (int i0 = first; i0 < first + TB_PPO_HALF && i0 < B; i0 += 16) {
+    // rows of the tile: slot e for the C/D layout, slots 4 c + g for the transposed one
+    const bool valid = i0 + e < B;
+    long long row = a.idx[valid ? i0 + e : B - 1];
+    row = row < 0 ? 0 : row >= a.n_rows ? a.n_rows - 1 : row;
+    float x0[L0::NC];
+    const float* orow = a.obs + (size_t)row * O;
+#pragma unroll
+    for (int c = 0; c < L0::NC; ++c) x0[c] = 4 * c + g < O ? orow[4 * c + g] : 0.0f;
+    f32x4 obsT[1];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int s = i0 + 4 * c + g;
+      long long rc = a.idx[s < B ? s : B - 1];
+      rc = rc < 0 ? 0 : rc >= a.n_rows ? a.n_rows - 1 : rc;
+      obsT[0][c] = e < O ? a.obs[(size_t)rc * O + e] : 0.0f;
+    }
+    // forward
+    f32x4 z0[L0::NT], h0[L0::NT], z1[L1::NT], h1[L1::NT], z2[L2::NT], h2[L2::NT], zh[1];
+    l0.forward_first(x0, z0); ppo_tanh(z0, h0);
+    l1.forward(h0, z1); ppo_tanh(z1, h1);
+    if constexpr (NH == 3) {
+      l2.forward(h1, z2); ppo_tanh(z2, h2);
+      lh.forward(h2, zh);
+    } else {
+      lh.forward(h1, zh);
+    }
+    // the loss's derivative with respect to the head's output (C/D layout: register r = output 4 g + r of row e)
+    f32x4 dout[1] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+    if constexpr (PI) {
+      float zeta[4], lp = 0.0f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool on = 4 * g + r < NA;
+        const float raw = on ? a.act[(size_t)row * NA + 4 * g + r] : 0.0f;
+        zeta[r] = on ? (raw - zh[0][r]) * inv_std[r] : 0.0f;
+        if (on) lp += (-0.5f * zeta[r] * zeta[r] - ls[r]) - TB_LN_SQRT_2PI;
+      }
+      lp += __shfl_xor(lp, 16);
+      lp += __shfl_xor(lp, 32);
+      const float ratio = expf(lp - a.old_logp[row]);
+      const float an = (a.adv[row] - adv_mean) / adv_den;
+      const float s1 = an * ratio, s2 = an * fminf(fmaxf(ratio, 1.0f - a.clip_range), 1.0f + a.clip_range);
+      const bool active = s1 <= s2;
+      if (valid && g == 0) stat += -fminf(s1, s2);
+      const float d_logp = (valid && active) ? (-an * ratio) / fb : 0.0f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        dout[0][r] = (d_logp * zeta[r]) * inv_std[r];
+        dls[r] += d_logp * (zeta[r] * zeta[r] - 1.0f);
+      }
+    } else {
+      const float verr = valid ? a.ret[row] - zh[0][0] : 0.0f;
+      if (g == 0) {
+        stat += verr * verr;
+        dout[0][0] = (-2.0f * a.vf_coef / fb) * verr;
+      }
+    }
+    // backward
+    f32x4 doutT[1];
+    ppo_transpose_all(dout, doutT, buf, lane);
+    if constexpr (NH == 3) {
+      f32x4 dh2[L2::NT], dz2[L2::NT], dz2T[L2::NT], h2T[L2::NT], dh1[L1::NT], dz1[L1::NT], dz1T[L1::NT], h1T[L1::NT], dh0[L0::NT], dz0[L0::NT], dz0T[L0::NT], h0T[L0::NT];
+      lh.backward_input(dout, dh2);
+      ppo_transpose_all(h2, h2T, buf, lane);
+      lh.accumulate(doutT, h2T);
+      ppo_dtanh(dh2, h2, dz2);
+      l2.backward_input(dz2, dh1);
+      ppo_transpose_all(dz2, dz2T, buf, lane); ppo_transpose_all(h1, h1T, buf, lane);
+      l2.accumulate(dz2T, h1T);
+      ppo_dtanh(dh1, h1, dz1);
+      l1.backward_input(dz1, dh0);
+      ppo_transpose_all(dz1, dz1T, buf, lane); ppo_transpose_all(h0, h0T, buf, lane);
+      l1.accumulate(dz1T, h0T);
+      ppo_dtanh(dh0, h0, dz0);
+      ppo_transpose_all(dz0, dz0T, buf, lane);
+      l0.accumulate(dz0T, obsT);
+    } else {
+      f32x4 dh1[L1::NT], dz1[L1::NT], dz1T[L1::NT], h1T[L1::NT], dh0[L0::NT], dz0[L0::NT], dz0T[L0::NT], h0T[L0::NT];
+      lh.backward_input(dout, dh1);
+      ppo_transpose_all(h1, h1T, buf, lane);
+      lh.accumulate(doutT, h1T);
+      ppo_dtanh(dh1, h1, dz1);
+      l1.backward_input(dz1, dh0);
+      ppo_transpose_all(dz1, dz1T, buf, lane); ppo_transpose_all(h0, h0T, buf, lane);
+      l1.accumulate(dz1T, h0T);
+      ppo_dtanh(dh0, h0, dz0);
+      ppo_transpose_all(dz0, dz0T, buf, lane);
+      l0.accumulate(dz0T, obsT);
+    }
+  }
+
+  // this wave's slots of the partial vector
+  float* gbody = part + (PI ? L::PI : L::VF);
+  float* ghead = part + (PI ? L::PI_HEAD : L::VF_HEAD);
+  l0.store(gbody + L::W0, gbody + L::B0, lane);
+  l1.store(gbody + L::W1, gbody + L::B1, lane);
+  if (NH == 3) l2.store(gbody + L::W2, gbody + L::B2, lane);
+  lh.store(ghead, ghead + HOUT * N::LAST, lane);
+#pragma unroll
+  for (int w = 1; w < 16; w <<= 1) {  // over the 16 rows of a lane group
+    stat += __shfl_xor(stat, w);
+    if (PI) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dls[r] += __shfl_xor(dls[r], w);
+    }
+  }
+  if (PI && e == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (4 * g + r < NA) part[L::LOG_STD + 4 * g + r] = dls[r];
+    }
+  }
+  if (lane == 0) part[L::P + (PI ? 0 : 1)] = stat;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void tb_ppo_grad_kernel(const PpoGradArgs a) {
+  __shared__ __attribute__((aligned(16))) float s_buf[4 * 512];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = wave & 1;
+  const int first = blockIdx.x * TB_PPO_SHARE + half * TB_PPO_HALF;
+  float* part = a.partials + (size_t)(2 * blockIdx.x + half) * PpoLayout<KIND>::STRIDE;
+  if (wave < 2) ppo_tower<KIND, true>(a, s_buf + wave * 512, lane, first, part);
+  else ppo_tower<KIND, false>(a, s_buf + wave * 512, lane, first, part);
+}
+
+// gradient[p] = sum of the partials in a fixed order (float64: four runs of n_part / 4, then (0 + 1) + (2 + 3)); log_std's
+// entropy term; the minibatch's three statistics. 64 parameters per block.
+template <int KIND>
+__global__ __launch_bounds__(256) void tb_ppo_reduce_kernel(const float* partials, int n_part, int batch, const float* params, float ent_coef, float* grad,
+                                                            float* stats) {
+  using L = PpoLayout<KIND>;
+  __shared__ double s_sum[4][64];
+  const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;
+  double s = 0.0;
+  if (p < L::STRIDE) {
+    const int per = (n_part + 3) / 4, lo = q * per, hi = lo + per < n_part ? lo + per : n_part;
+    for (int k = lo; k < hi; ++k) s += (double)partials[(size_t)k * L::STRIDE + p];
+  }
+  s_sum[q][j] = s;
+  __syncthreads();
+  if (q == 0 && p < L::STRIDE) {
+    const double total = (s_sum[0][j] + s_sum[1][j]) + (s_sum[2][j] + s_sum[3][j]);
+    if (p < L::P) {
+      grad[p] = p < L::A ? (float)total - ent_coef : (float)total;
+    } else {
+      stats[p - L::P] = (float)(total / (double)batch);
+      if (p == L::P) {
+        float ent = 0.0f;
+        for (int k = 0; k < L::A; ++k) ent += (0.5f + TB_LN_SQRT_2PI) + params[L::LOG_STD + k];
+        stats[2] = ent;
+      }
+    }
+  }
+}
+
+// grad /= world; the global norm (float64, fixed-order tree); torch's clip factor; Adam. One workgroup.
+__global__ __launch_bounds__(1024) void tb_ppo_step_kernel(float* params, float* grad, float* m, float* v, int P, float world, float max_norm, float lr,
+                                                           float beta1, float beta2, float eps, float c1, float c2) {
+  __shared__ double s_sq[1024];
+  double sq = 0.0;
+  for (int p = threadIdx.x; p < P; p += 1024) {
+    const float g = world != 1.0f ? grad[p] / world : grad[p];
+    sq += (double)g * (double)g;
+  }
+  s_sq[threadIdx.x] = sq;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) s_sq[threadIdx.x] += s_sq[threadIdx.x + w];
+    __syncthreads();
+  }
+  const float norm = (float)sqrt(s_sq[0]);
+  const float coef = fminf(1.0f, max_norm / (norm + 1e-6f));
+  for (int p = threadIdx.x; p < P; p += 1024) {
+    const float g = (world != 1.0f ? grad[p] / world : grad[p]) * coef;
+    const float mk = beta1 * m[p] + (1.0f - beta1) * g;
+    const float vk = beta2 * v[p] + ((1.0f - beta2) * g) * g;
+    grad[p] = g; m[p] = mk; v[p] = vk;
+    params[p] = params[p] - lr * (mk / c1) / (sqrtf(vk / c2) + eps);
+  }
+}
+
+// GAE: one lane per env, backwards over the steps; a step's loads and stores coalesce across envs. Operation for operation
+// PPOTrainer.advantages: delta = r + (gamma V') nt - V, g = delta + (c nt) g with c = fl(gamma lambda), returns = g + V.
+__global__ __launch_bounds__(64) void tb_ppo_gae_kernel(int T, int n, const float* rew, size_t rew_stride, const unsigned char* done, size_t done_stride,
+                                                        const float* values, const float* last_value, float gamma, float c, float* adv, float* ret) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  float next = last_value[i], g = 0.0f;
+#pragma unroll 8
+  for (int k = T - 1; k >= 0; --k) {
+    const float nt = done[(size_t)k * done_stride + i] ? 0.0f : 1.0f;
+    const float V = values[(size_t)k * n + i];
+    const float delta = (rew[(size_t)k * rew_stride + i] + (gamma * next) * nt) - V;
+    g = delta + (c * nt) * g;
+    adv[(size_t)k * n + i] = g;
+    ret[(size_t)k * n + i] = g + V;
+    next = V;
+  }
+}
+
+}  // namespace

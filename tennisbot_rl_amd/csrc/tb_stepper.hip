@@ -26,6 +26,7 @@
 
 #include "tb_kernels.hpp"
 #include "tb_es.hpp"
+#include "tb_learner.hpp"
 
 using namespace tb;
 
@@ -1111,6 +1112,116 @@ int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t 
     if (int rc = launch(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n, last_rew)) return rc;
   }
   return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
+}
+
+// ------------------------------------------------------------------------------------------ the PPO learner (tb_learner.hpp)
+int tb_ppo_param_floats(int env_kind) {
+  return env_kind == TB_ENV_SWING ? PpoLayout<TB_ENV_SWING>::P : env_kind == TB_ENV_TENNIS ? PpoLayout<TB_ENV_TENNIS>::P : TB_E_INVAL;
+}
+int tb_ppo_rows_per_workgroup(void) { return TB_PPO_SHARE; }
+
+static size_t ppo_partials(int batch) { return 2 * (((size_t)batch + TB_PPO_SHARE - 1) / TB_PPO_SHARE); }
+static constexpr size_t kPpoStatBytes = sizeof(double) * 2 * TB_PPO_STAT_BLOCKS;
+
+long long tb_ppo_workspace_bytes(int env_kind, int batch) {
+  if (!kind_ok(env_kind) || batch < 2) return fail(TB_E_INVAL, "tb_ppo_workspace_bytes: unknown env kind, or batch < 2");
+  return (long long)(kPpoStatBytes + sizeof(float) * ppo_partials(batch) * ((size_t)tb_ppo_param_floats(env_kind) + 2));
+}
+
+static int ppo_device(int device, const char* what) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TB_E_NODEVICE, "tb_ppo: no HIP device available (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(TB_E_NODEVICE, what);
+  return TB_OK;
+}
+static bool misaligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+
+int tb_ppo_gae(int env_kind, int device, void* stream, int n_steps, int n_envs, const float* rewards_dev, size_t reward_step_stride_bytes,
+               const uint8_t* dones_dev, size_t done_step_stride_bytes, const float* values_dev, const float* last_value_dev, double gamma,
+               double gae_lambda, float* adv_dev, float* returns_dev) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_ppo_gae: unknown env kind");
+  if (!rewards_dev || !dones_dev || !values_dev || !last_value_dev || !adv_dev || !returns_dev) return fail(TB_E_INVAL, "tb_ppo_gae: null argument");
+  if (n_steps < 1 || n_envs < 1) return fail(TB_E_INVAL, "tb_ppo_gae: n_steps and n_envs must be >= 1");
+  if (misaligned(rewards_dev, 4) || misaligned(values_dev, 4) || misaligned(last_value_dev, 4) || misaligned(adv_dev, 4) || misaligned(returns_dev, 4))
+    return fail(TB_E_INVAL, "tb_ppo_gae: a float array is not 4-byte aligned");
+  size_t rs = (size_t)n_envs, ds = (size_t)n_envs;
+  if (reward_step_stride_bytes) {
+    if (reward_step_stride_bytes % sizeof(float) || reward_step_stride_bytes < sizeof(float) * (size_t)n_envs)
+      return fail(TB_E_INVAL, "tb_ppo_gae: the rewards' step stride must be a multiple of 4 bytes and hold n_envs floats");
+    rs = reward_step_stride_bytes / sizeof(float);
+  }
+  if (done_step_stride_bytes) {
+    if (done_step_stride_bytes < (size_t)n_envs) return fail(TB_E_INVAL, "tb_ppo_gae: the dones' step stride is shorter than n_envs bytes");
+    ds = done_step_stride_bytes;
+  }
+  if (int rc = ppo_device(device, "tb_ppo_gae: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  return launch(tb_ppo_gae_kernel, dim3((unsigned)((n_envs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n_steps, n_envs, rewards_dev, rs, dones_dev, ds,
+                values_dev, last_value_dev, (float)gamma, (float)(gamma * gae_lambda), adv_dev, returns_dev);
+}
+
+int tb_ppo_grad(int env_kind, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev, const float* adv_dev,
+                const float* returns_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* params_dev, int n_params, float clip_range,
+                float vf_coef, void* workspace_dev, size_t workspace_bytes) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_ppo_grad: unknown env kind");
+  if (!obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !returns_dev || !idx_dev || !params_dev || !workspace_dev)
+    return fail(TB_E_INVAL, "tb_ppo_grad: null argument");
+  if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_ppo_grad: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_rows < 1 || batch < 2) return fail(TB_E_INVAL, "tb_ppo_grad: n_rows must be >= 1 and batch >= 2 (the unbiased std of one row is undefined)");
+  if (misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) || misaligned(returns_dev, 4) ||
+      misaligned(params_dev, 4))
+    return fail(TB_E_INVAL, "tb_ppo_grad: a float array is not 4-byte aligned");
+  if (misaligned(idx_dev, 8) || misaligned(workspace_dev, 8)) return fail(TB_E_INVAL, "tb_ppo_grad: idx and the workspace must be 8-byte aligned");
+  if ((long long)workspace_bytes < tb_ppo_workspace_bytes(env_kind, batch)) return fail(TB_E_INVAL, "tb_ppo_grad: the workspace is smaller than tb_ppo_workspace_bytes");
+  if (int rc = ppo_device(device, "tb_ppo_grad: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  hipStream_t s = (hipStream_t)stream;
+  double* sums = (double*)workspace_dev;
+  PpoGradArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, (const long long*)idx_dev, params_dev, sums,
+                   (float*)((char*)workspace_dev + kPpoStatBytes), n_rows, batch, clip_range, vf_coef};
+  if (int rc = launch(tb_ppo_adv_stats_kernel, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
+  const dim3 grid((unsigned)(ppo_partials(batch) / 2));
+  return env_kind == TB_ENV_SWING ? launch(tb_ppo_grad_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a) : launch(tb_ppo_grad_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a);
+}
+
+int tb_ppo_apply(int env_kind, int device, void* stream, int phases, const void* workspace_dev, size_t workspace_bytes, int batch, float* params_dev,
+                 float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int n_params, float* stats_dev, float ent_coef, float max_grad_norm, int world,
+                 float lr, float beta1, float beta2, float eps, long long step) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_ppo_apply: unknown env kind");
+  if (!(phases & (TB_PPO_REDUCE | TB_PPO_STEP)) || (phases & ~(TB_PPO_REDUCE | TB_PPO_STEP))) return fail(TB_E_INVAL, "tb_ppo_apply: phases must be TB_PPO_REDUCE, TB_PPO_STEP or both");
+  if (!params_dev || !grad_dev) return fail(TB_E_INVAL, "tb_ppo_apply: null argument");
+  if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_ppo_apply: n_params is not tb_ppo_param_floats(env_kind)");
+  if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(stats_dev, 4))
+    return fail(TB_E_INVAL, "tb_ppo_apply: a float array is not 4-byte aligned");
+  if (phases & TB_PPO_REDUCE) {
+    if (!workspace_dev || !stats_dev) return fail(TB_E_INVAL, "tb_ppo_apply: TB_PPO_REDUCE needs the workspace and stats_dev");
+    if (batch < 2 || misaligned(workspace_dev, 8) || (long long)workspace_bytes < tb_ppo_workspace_bytes(env_kind, batch))
+      return fail(TB_E_INVAL, "tb_ppo_apply: batch < 2, or the workspace is misaligned or smaller than tb_ppo_workspace_bytes");
+  }
+  if (phases & TB_PPO_STEP) {
+    if (!exp_avg_dev || !exp_avg_sq_dev) return fail(TB_E_INVAL, "tb_ppo_apply: TB_PPO_STEP needs both moments");
+    if (world < 1 || step < 1) return fail(TB_E_INVAL, "tb_ppo_apply: world and step must be >= 1");
+  }
+  if (int rc = ppo_device(device, "tb_ppo_apply: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  hipStream_t s = (hipStream_t)stream;
+  if (phases & TB_PPO_REDUCE) {
+    const float* partials = (const float*)((const char*)workspace_dev + kPpoStatBytes);
+    const int n_part = (int)ppo_partials(batch);
+    const dim3 grid((unsigned)((n_params + 2 + 63) / 64));
+    if (int rc = env_kind == TB_ENV_SWING ? launch(tb_ppo_reduce_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev)
+                                          : launch(tb_ppo_reduce_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev))
+      return rc;
+  }
+  if (phases & TB_PPO_STEP) {
+    const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
+    return launch(tb_ppo_step_kernel, dim3(1), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, (float)world, max_grad_norm, lr,
+                  beta1, beta2, eps, c1, c2);
+  }
+  return TB_OK;
 }
 
 int tb_rollout(TbHandle* h, int n_steps, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,

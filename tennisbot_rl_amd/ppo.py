@@ -153,9 +153,11 @@ class PPOTrainer:
     """clipped-surrogate PPO over a BatchedEnv; one process per GPU when distributed"""
 
     def __init__(self, env_id="SwingRacket-v0", num_envs=4096, n_steps=104, device=None, seed=0, batch_size=None,
-                 pipeline=True, graph=True, fused=True, rollout_launch=True, params=None, ff_defer="all", options=None, **hp):
+                 pipeline=True, graph=True, fused=True, rollout_launch=True, params=None, ff_defer="all", options=None, learner="torch", **hp):
         import torch
         self.torch = torch
+        if learner not in ("torch", "fused"):
+            raise ValueError("learner must be 'torch' or 'fused', not %r" % (learner,))
         kind = ENV_IDS[env_id]
         d = dict(SWING_DEFAULTS if kind == ENV_SWING else TENNIS_DEFAULTS)
         d.update(COMMON)
@@ -211,6 +213,13 @@ class PPOTrainer:
         if self.fused:
             self.packed = pack_policy(self.policy)
             assert self.packed.numel() == self.env.policy_floats()
+        # learner="fused": advantages / update run as HIP kernels on the flat parameter vector (learner.py); "torch": the bodies below
+        self._learner = None
+        if learner == "fused":
+            if not self.fused:
+                raise ValueError("learner='fused' needs the architecture the kernels are instantiated for (fused=True and the env's default net_arch)")
+            from .learner import FusedLearner
+            self._learner = FusedLearner(kind, self.policy, self.opt, self.hp, self.device)
 
     # ------------------------------------------------------------------ collect
     def _collect_fused(self):
@@ -297,6 +306,9 @@ class PPOTrainer:
         return self.last_value
 
     def advantages(self, last_value):
+        learner = getattr(self, "_learner", None)
+        if learner is not None:
+            return learner.advantages(self.buf.rewards, self.values, self.buf.dones, last_value)
         t, hp = self.torch, self.hp
         rew, done = self.buf.rewards, self.buf.dones.float()
         adv = t.zeros_like(rew)
@@ -315,6 +327,10 @@ class PPOTrainer:
         t, hp = self.torch, self.hp
         dist = t.distributed
         n = self.n_steps * self.num_envs
+        learner = getattr(self, "_learner", None)
+        if learner is not None:
+            return learner.update(self.obs_seq.reshape(n, -1), self._raw_actions.reshape(n, -1), self.logps.reshape(n), adv.reshape(n), returns.reshape(n),
+                                  hp["n_epochs"], self.batch_size, self.world)
         obs = self.obs_seq.reshape(n, -1); act = self._raw_actions.reshape(n, -1)
         old_lp = self.logps.reshape(n); adv = adv.reshape(n); returns = returns.reshape(n)
         stats = {}

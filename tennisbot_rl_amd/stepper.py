@@ -91,6 +91,19 @@ def load_library():
     L.tb_es_floats.restype = i32
     L.tb_es_evaluate.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, vp, vp, ctypes.POINTER(TbEsTrace), vp]
     L.tb_es_evaluate.restype = i32
+    f32, f64, i64 = ctypes.c_float, ctypes.c_double, ctypes.c_longlong
+    L.tb_ppo_param_floats.argtypes = [i32]
+    L.tb_ppo_param_floats.restype = i32
+    L.tb_ppo_rows_per_workgroup.argtypes = []
+    L.tb_ppo_rows_per_workgroup.restype = i32
+    L.tb_ppo_workspace_bytes.argtypes = [i32, i32]
+    L.tb_ppo_workspace_bytes.restype = i64
+    L.tb_ppo_gae.argtypes = [i32, i32, vp, i32, i32, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, f64, f64, vp, vp]
+    L.tb_ppo_gae.restype = i32
+    L.tb_ppo_grad.argtypes = [i32, i32, vp] + [vp] * 5 + [i64, vp, i32, vp, i32, f32, f32, vp, ctypes.c_size_t]
+    L.tb_ppo_grad.restype = i32
+    L.tb_ppo_apply.argtypes = [i32, i32, vp, i32, vp, ctypes.c_size_t, i32] + [vp] * 4 + [i32, vp, f32, f32, i32, f32, f32, f32, f32, i64]
+    L.tb_ppo_apply.restype = i32
     L.tb_phase.argtypes = [vp]
     L.tb_phase.restype = i32
     L.tb_phase_advance.argtypes = [vp, i32]

@@ -46,6 +46,7 @@ def main():
     ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (court.urdf:19-24; TB_F_RACKET_GROUND, opt-in: DESIGN.md section 3)")
     ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact (rollingFriction=.001 in racket.py:43-45, objects.py:29-31,48-50)")
     ap.add_argument("--no-fused", action="store_true", help="run the policy as torch modules between env steps instead of inside the step kernel")
+    ap.add_argument("--learner", default="torch", choices=["torch", "fused"], help="fused: GAE, minibatch gradient and Adam as HIP kernels (tennisbot_rl_amd/learner.py)")
     ap.add_argument("--log-json", type=str, default=None)
     args = ap.parse_args()
     if args.select != "ppo":
@@ -66,7 +67,7 @@ def main():
         from tennisbot_rl_amd.params import F_DEFAULT, F_RACKET_GROUND, default_params, reference_rolling_friction
         params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
     tr = PPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed,
-                    fused=not args.no_fused, params=params)
+                    fused=not args.no_fused, params=params, learner=args.learner)
     if args.load_reference:
         import numpy as np
         tr.policy.load_sb3_arrays(dict(np.load(os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz"))))

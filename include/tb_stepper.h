@@ -398,9 +398,13 @@ int tb_es_evaluate(TbHandle *h, const float *weights_dev, int n_members, size_t 
  * factor min(1, max_grad_norm / (norm + 1e-6)); Adam (bias correction from `step`, the 1-based count of this step) updates
  * params_dev, exp_avg_dev and exp_avg_sq_dev in place. Both bits: the two in turn. With several ranks the caller all-reduces
  * (sums) grad_dev between the two phases; identical grad_dev, parameters and moments give identical bits on every rank.
+ * TB_PPO_VALUE_ONLY, added to either phase: the critic alone. TB_PPO_REDUCE then writes only the value slots of grad_dev
+ * (value_net_body, value_net); TB_PPO_STEP takes its norm over, clips and updates only those slots. The policy slots of the
+ * parameters, the gradient and both moments are not written.
  */
 #define TB_PPO_REDUCE 1
 #define TB_PPO_STEP 2
+#define TB_PPO_VALUE_ONLY 4
 int tb_ppo_param_floats(int env_kind);
 int tb_ppo_rows_per_workgroup(void);
 long long tb_ppo_workspace_bytes(int env_kind, int batch);
@@ -414,6 +418,37 @@ int tb_ppo_grad(int env_kind, int device, void *stream, const float *obs_dev, co
 int tb_ppo_apply(int env_kind, int device, void *stream, int phases, const void *workspace_dev, size_t workspace_bytes, int batch,
                  float *params_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev, int n_params, float *stats_dev,
                  float ent_coef, float max_grad_norm, int world, float lr, float beta1, float beta2, float eps, long long step);
+
+/*
+ * The TRPO learner's policy step (csrc/tb_trpo.hpp; tennisbot_rl_amd/trpo.py is the caller), in the conventions of the tb_ppo_*
+ * block above: (env_kind, device, stream), caller-owned device buffers, host-only workspace-size queries, refusals before any
+ * launch. Vectors over the parameters (vec, out, direction) are full flat vectors of tb_ppo_param_floats(kind) floats; only
+ * their policy slots (log_std, policy_net, action_net) are read, and the value slots of `out` are written as 0.
+ *
+ * tb_trpo_fvp: out = F vec + damping vec, F the Fisher matrix of the diagonal-Gaussian policy over the rows idx[0 .. n_idx) of
+ * obs [n_rows][O]: (1/n_idx) sum_rows J^T diag(sigma^-2) J on the network's slots (J = d mean / d theta), 2 on log_std. Each
+ * workgroup takes tb_trpo_rows_per_workgroup() entries of idx; per-wave partial vectors in the workspace
+ * (tb_trpo_fvp_workspace_bytes(kind, n_idx)), then a fixed-order float64 reduction: the same inputs give the same bits. The
+ * damping term is added in float32 after the sum is rounded: fvp(d) == fvp(0) + fl(d vec) bit for bit. out must not be vec.
+ *
+ * tb_trpo_search: for each candidate k < n_candidates (<= 64), theta_k = params + steps[k] * direction, over the rows
+ * idx[0 .. batch): out[2 k] = mean(ratio_k * A_hat) (ratio_k = exp(logp_k - old_logp); A_hat = adv normalised over those rows
+ * with mean and unbiased std + 1e-8, as tb_ppo_grad does) and out[2 k + 1] = mean KL(theta || theta_k). One launch over
+ * candidates x tb_trpo_search_rows_per_workgroup()-row shares, float64 partial sums, a fixed-order reduction. A zero step gives
+ * KL == 0.0 exactly. Workspace: tb_trpo_search_workspace_bytes(kind, batch, n_candidates). idx values outside [0, n_rows) are
+ * clamped in both functions.
+ */
+int tb_trpo_rows_per_workgroup(void);
+int tb_trpo_search_rows_per_workgroup(void);
+long long tb_trpo_fvp_workspace_bytes(int env_kind, int n_idx);
+long long tb_trpo_search_workspace_bytes(int env_kind, int batch, int n_candidates);
+int tb_trpo_fvp(int env_kind, int device, void *stream, const float *obs_dev, long long n_rows, const int64_t *idx_dev, int n_idx,
+                const float *params_dev, const float *vec_dev, int n_params, float damping, float *out_dev, void *workspace_dev,
+                size_t workspace_bytes);
+int tb_trpo_search(int env_kind, int device, void *stream, const float *obs_dev, const float *raw_actions_dev,
+                   const float *old_logp_dev, const float *adv_dev, long long n_rows, const int64_t *idx_dev, int batch,
+                   const float *params_dev, const float *direction_dev, int n_params, const float *steps_dev, int n_candidates,
+                   double *out_dev, void *workspace_dev, size_t workspace_bytes);
 
 /*
  * Pipelined fast-forward (SwingRacket-v0 with TB_F_AUTO_RESET; HIP streams, no reference

@@ -390,10 +390,11 @@ __global__ __launch_bounds__(256) void tb_ppo_grad_kernel(const PpoGradArgs a) {
 }
 
 // gradient[p] = sum of the partials in a fixed order (float64: four runs of n_part / 4, then (0 + 1) + (2 + 3)); log_std's
-// entropy term; the minibatch's three statistics. 64 parameters per block.
+// entropy term; the minibatch's three statistics. 64 parameters per block. value_only: grad's policy slots (log_std, PI,
+// PI_HEAD) are left as they are.
 template <int KIND>
 __global__ __launch_bounds__(256) void tb_ppo_reduce_kernel(const float* partials, int n_part, int batch, const float* params, float ent_coef, float* grad,
-                                                            float* stats) {
+                                                            float* stats, int value_only) {
   using L = PpoLayout<KIND>;
   __shared__ double s_sum[4][64];
   const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;
@@ -407,7 +408,8 @@ __global__ __launch_bounds__(256) void tb_ppo_reduce_kernel(const float* partial
   if (q == 0 && p < L::STRIDE) {
     const double total = (s_sum[0][j] + s_sum[1][j]) + (s_sum[2][j] + s_sum[3][j]);
     if (p < L::P) {
-      grad[p] = p < L::A ? (float)total - ent_coef : (float)total;
+      const bool value_slot = (p >= L::VF && p < L::PI_HEAD) || p >= L::VF_HEAD;
+      if (!value_only || value_slot) grad[p] = p < L::A ? (float)total - ent_coef : (float)total;
     } else {
       stats[p - L::P] = (float)(total / (double)batch);
       if (p == L::P) {
@@ -419,12 +421,14 @@ __global__ __launch_bounds__(256) void tb_ppo_reduce_kernel(const float* partial
   }
 }
 
-// grad /= world; the global norm (float64, fixed-order tree); torch's clip factor; Adam. One workgroup.
+// grad /= world; the global norm (float64, fixed-order tree); torch's clip factor; Adam. One workgroup. Only the slots in
+// [lo0, hi0) or [lo1, hi1) take part, in the norm too (every slot: 0, P, 0, 0; the critic alone: the VF and VF_HEAD slots).
 __global__ __launch_bounds__(1024) void tb_ppo_step_kernel(float* params, float* grad, float* m, float* v, int P, float world, float max_norm, float lr,
-                                                           float beta1, float beta2, float eps, float c1, float c2) {
+                                                           float beta1, float beta2, float eps, float c1, float c2, int lo0, int hi0, int lo1, int hi1) {
   __shared__ double s_sq[1024];
   double sq = 0.0;
   for (int p = threadIdx.x; p < P; p += 1024) {
+    if (!((p >= lo0 && p < hi0) || (p >= lo1 && p < hi1))) continue;
     const float g = world != 1.0f ? grad[p] / world : grad[p];
     sq += (double)g * (double)g;
   }
@@ -437,6 +441,7 @@ __global__ __launch_bounds__(1024) void tb_ppo_step_kernel(float* params, float*
   const float norm = (float)sqrt(s_sq[0]);
   const float coef = fminf(1.0f, max_norm / (norm + 1e-6f));
   for (int p = threadIdx.x; p < P; p += 1024) {
+    if (!((p >= lo0 && p < hi0) || (p >= lo1 && p < hi1))) continue;
     const float g = (world != 1.0f ? grad[p] / world : grad[p]) * coef;
     const float mk = beta1 * m[p] + (1.0f - beta1) * g;
     const float vk = beta2 * v[p] + ((1.0f - beta2) * g) * g;

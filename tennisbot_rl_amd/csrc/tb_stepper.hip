@@ -27,6 +27,7 @@
 #include "tb_kernels.hpp"
 #include "tb_es.hpp"
 #include "tb_learner.hpp"
+#include "tb_trpo.hpp"
 
 using namespace tb;
 
@@ -1190,7 +1191,9 @@ int tb_ppo_apply(int env_kind, int device, void* stream, int phases, const void*
                  float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int n_params, float* stats_dev, float ent_coef, float max_grad_norm, int world,
                  float lr, float beta1, float beta2, float eps, long long step) {
   if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_ppo_apply: unknown env kind");
-  if (!(phases & (TB_PPO_REDUCE | TB_PPO_STEP)) || (phases & ~(TB_PPO_REDUCE | TB_PPO_STEP))) return fail(TB_E_INVAL, "tb_ppo_apply: phases must be TB_PPO_REDUCE, TB_PPO_STEP or both");
+  if (!(phases & (TB_PPO_REDUCE | TB_PPO_STEP)) || (phases & ~(TB_PPO_REDUCE | TB_PPO_STEP | TB_PPO_VALUE_ONLY)))
+    return fail(TB_E_INVAL, "tb_ppo_apply: phases must be TB_PPO_REDUCE, TB_PPO_STEP or both, with or without TB_PPO_VALUE_ONLY");
+  const int value_only = (phases & TB_PPO_VALUE_ONLY) != 0;
   if (!params_dev || !grad_dev) return fail(TB_E_INVAL, "tb_ppo_apply: null argument");
   if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_ppo_apply: n_params is not tb_ppo_param_floats(env_kind)");
   if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(stats_dev, 4))
@@ -1212,16 +1215,95 @@ int tb_ppo_apply(int env_kind, int device, void* stream, int phases, const void*
     const float* partials = (const float*)((const char*)workspace_dev + kPpoStatBytes);
     const int n_part = (int)ppo_partials(batch);
     const dim3 grid((unsigned)((n_params + 2 + 63) / 64));
-    if (int rc = env_kind == TB_ENV_SWING ? launch(tb_ppo_reduce_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev)
-                                          : launch(tb_ppo_reduce_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev))
+    if (int rc = env_kind == TB_ENV_SWING ? launch(tb_ppo_reduce_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only)
+                                          : launch(tb_ppo_reduce_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only))
       return rc;
   }
   if (phases & TB_PPO_STEP) {
     const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
+    int lo0 = 0, hi0 = n_params, lo1 = 0, hi1 = 0;
+    if (value_only) {
+      const bool swing = env_kind == TB_ENV_SWING;
+      lo0 = swing ? PpoLayout<TB_ENV_SWING>::VF : PpoLayout<TB_ENV_TENNIS>::VF;
+      hi0 = swing ? PpoLayout<TB_ENV_SWING>::PI_HEAD : PpoLayout<TB_ENV_TENNIS>::PI_HEAD;
+      lo1 = swing ? PpoLayout<TB_ENV_SWING>::VF_HEAD : PpoLayout<TB_ENV_TENNIS>::VF_HEAD;
+      hi1 = n_params;
+    }
     return launch(tb_ppo_step_kernel, dim3(1), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, (float)world, max_grad_norm, lr,
-                  beta1, beta2, eps, c1, c2);
+                  beta1, beta2, eps, c1, c2, lo0, hi0, lo1, hi1);
   }
   return TB_OK;
+}
+
+// ------------------------------------------------------------------------------------------- the TRPO learner (tb_trpo.hpp)
+int tb_trpo_rows_per_workgroup(void) { return TB_PPO_SHARE; }
+int tb_trpo_search_rows_per_workgroup(void) { return TB_TRPO_SEARCH_SHARE; }
+
+static size_t trpo_search_shares(int batch) { return ((size_t)batch + TB_TRPO_SEARCH_SHARE - 1) / TB_TRPO_SEARCH_SHARE; }
+
+long long tb_trpo_fvp_workspace_bytes(int env_kind, int n_idx) {
+  if (!kind_ok(env_kind) || n_idx < 1) return fail(TB_E_INVAL, "tb_trpo_fvp_workspace_bytes: unknown env kind, or n_idx < 1");
+  return (long long)(sizeof(float) * ppo_partials(n_idx) * (size_t)tb_ppo_param_floats(env_kind));
+}
+long long tb_trpo_search_workspace_bytes(int env_kind, int batch, int n_candidates) {
+  if (!kind_ok(env_kind) || batch < 2 || n_candidates < 1 || n_candidates > TB_TRPO_MAX_CANDIDATES)
+    return fail(TB_E_INVAL, "tb_trpo_search_workspace_bytes: unknown env kind, batch < 2, or n_candidates outside 1 .. 64");
+  return (long long)(kPpoStatBytes + sizeof(double) * 2 * trpo_search_shares(batch) * (size_t)n_candidates);
+}
+
+int tb_trpo_fvp(int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int n_idx, const float* params_dev,
+                const float* vec_dev, int n_params, float damping, float* out_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_trpo_fvp: unknown env kind");
+  if (!obs_dev || !idx_dev || !params_dev || !vec_dev || !out_dev || !workspace_dev) return fail(TB_E_INVAL, "tb_trpo_fvp: null argument");
+  if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_trpo_fvp: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_rows < 1 || n_idx < 1) return fail(TB_E_INVAL, "tb_trpo_fvp: n_rows and n_idx must be >= 1");
+  if (misaligned(obs_dev, 4) || misaligned(params_dev, 4) || misaligned(vec_dev, 4) || misaligned(out_dev, 4))
+    return fail(TB_E_INVAL, "tb_trpo_fvp: a float array is not 4-byte aligned");
+  if (misaligned(idx_dev, 8) || misaligned(workspace_dev, 8)) return fail(TB_E_INVAL, "tb_trpo_fvp: idx and the workspace must be 8-byte aligned");
+  if (vec_dev == out_dev) return fail(TB_E_INVAL, "tb_trpo_fvp: out_dev must not be vec_dev");
+  if ((long long)workspace_bytes < tb_trpo_fvp_workspace_bytes(env_kind, n_idx)) return fail(TB_E_INVAL, "tb_trpo_fvp: the workspace is smaller than tb_trpo_fvp_workspace_bytes");
+  if (int rc = ppo_device(device, "tb_trpo_fvp: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  hipStream_t s = (hipStream_t)stream;
+  const int n_part = (int)ppo_partials(n_idx);
+  TrpoFvpArgs a = {obs_dev, (const long long*)idx_dev, params_dev, vec_dev, (float*)workspace_dev, n_rows, n_idx};
+  const dim3 grid((unsigned)(n_part / 2)), rgrid((unsigned)((n_params + 63) / 64));
+  const bool swing = env_kind == TB_ENV_SWING;
+  if (int rc = swing ? launch(tb_trpo_fvp_kernel<TB_ENV_SWING>, grid, dim3(128), 0, s, a) : launch(tb_trpo_fvp_kernel<TB_ENV_TENNIS>, grid, dim3(128), 0, s, a)) return rc;
+  return swing ? launch(tb_trpo_fvp_reduce_kernel<TB_ENV_SWING>, rgrid, dim3(256), 0, s, (const float*)workspace_dev, n_part, n_idx, vec_dev, damping, out_dev)
+               : launch(tb_trpo_fvp_reduce_kernel<TB_ENV_TENNIS>, rgrid, dim3(256), 0, s, (const float*)workspace_dev, n_part, n_idx, vec_dev, damping, out_dev);
+}
+
+int tb_trpo_search(int env_kind, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev, const float* adv_dev,
+                   long long n_rows, const int64_t* idx_dev, int batch, const float* params_dev, const float* direction_dev, int n_params,
+                   const float* steps_dev, int n_candidates, double* out_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_trpo_search: unknown env kind");
+  if (!obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !idx_dev || !params_dev || !direction_dev || !steps_dev || !out_dev || !workspace_dev)
+    return fail(TB_E_INVAL, "tb_trpo_search: null argument");
+  if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_trpo_search: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_rows < 1 || batch < 2) return fail(TB_E_INVAL, "tb_trpo_search: n_rows must be >= 1 and batch >= 2 (the unbiased std of one row is undefined)");
+  if (n_candidates < 1 || n_candidates > TB_TRPO_MAX_CANDIDATES) return fail(TB_E_INVAL, "tb_trpo_search: n_candidates must be 1 .. 64");
+  if (misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) || misaligned(params_dev, 4) ||
+      misaligned(direction_dev, 4) || misaligned(steps_dev, 4))
+    return fail(TB_E_INVAL, "tb_trpo_search: a float array is not 4-byte aligned");
+  if (misaligned(idx_dev, 8) || misaligned(workspace_dev, 8) || misaligned(out_dev, 8))
+    return fail(TB_E_INVAL, "tb_trpo_search: idx, out and the workspace must be 8-byte aligned");
+  if ((long long)workspace_bytes < tb_trpo_search_workspace_bytes(env_kind, batch, n_candidates))
+    return fail(TB_E_INVAL, "tb_trpo_search: the workspace is smaller than tb_trpo_search_workspace_bytes");
+  if (int rc = ppo_device(device, "tb_trpo_search: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  hipStream_t s = (hipStream_t)stream;
+  double* sums = (double*)workspace_dev;
+  double* partials = (double*)((char*)workspace_dev + kPpoStatBytes);
+  const int shares = (int)trpo_search_shares(batch);
+  TrpoSearchArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, (const long long*)idx_dev, params_dev, direction_dev, steps_dev, sums, partials, n_rows, batch};
+  if (int rc = launch(tb_ppo_adv_stats_kernel, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
+  const dim3 grid((unsigned)shares, (unsigned)n_candidates);
+  if (int rc = env_kind == TB_ENV_SWING ? launch(tb_trpo_search_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a) : launch(tb_trpo_search_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a))
+    return rc;
+  return launch(tb_trpo_search_reduce_kernel, dim3((unsigned)n_candidates), dim3(256), 0, s, (const double*)partials, shares, batch, out_dev);
 }
 
 int tb_rollout(TbHandle* h, int n_steps, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,

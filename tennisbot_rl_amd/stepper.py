@@ -104,6 +104,18 @@ def load_library():
     L.tb_ppo_grad.restype = i32
     L.tb_ppo_apply.argtypes = [i32, i32, vp, i32, vp, ctypes.c_size_t, i32] + [vp] * 4 + [i32, vp, f32, f32, i32, f32, f32, f32, f32, i64]
     L.tb_ppo_apply.restype = i32
+    L.tb_trpo_rows_per_workgroup.argtypes = []
+    L.tb_trpo_rows_per_workgroup.restype = i32
+    L.tb_trpo_search_rows_per_workgroup.argtypes = []
+    L.tb_trpo_search_rows_per_workgroup.restype = i32
+    L.tb_trpo_fvp_workspace_bytes.argtypes = [i32, i32]
+    L.tb_trpo_fvp_workspace_bytes.restype = i64
+    L.tb_trpo_search_workspace_bytes.argtypes = [i32, i32, i32]
+    L.tb_trpo_search_workspace_bytes.restype = i64
+    L.tb_trpo_fvp.argtypes = [i32, i32, vp, vp, i64, vp, i32, vp, vp, i32, f32, vp, vp, ctypes.c_size_t]
+    L.tb_trpo_fvp.restype = i32
+    L.tb_trpo_search.argtypes = [i32, i32, vp] + [vp] * 4 + [i64, vp, i32, vp, vp, i32, vp, i32, vp, vp, ctypes.c_size_t]
+    L.tb_trpo_search.restype = i32
     L.tb_phase.argtypes = [vp]
     L.tb_phase.restype = i32
     L.tb_phase_advance.argtypes = [vp, i32]

@@ -1,0 +1,229 @@
+"""TRPO on the batched envs: the trust-region policy step as HIP kernels (csrc/tb_trpo.hpp; C ABI tb_trpo_fvp / tb_trpo_search
+in include/tb_stepper.h), the collect, GAE and critic of the PPO trainer around it.
+
+`TRPOTrainer` collects exactly as `PPOTrainer` does (fused rollout, tb_ppo_gae) and has the same critic. `FusedTRPO.update`
+replaces the policy's minibatch epochs with ONE step whose structure and constants are the reference's agent.py (TRPOAgent):
+
+  1. g = grad_theta mean(ratio * A_hat), the surrogate of agent.py:99-107. theta = log_std, policy_net, action_net (the LOG_STD, PI
+     and PI_HEAD slots of the flat vector); A_hat = the rollout's advantages normalised over the whole batch (mean, unbiased
+     std + 1e-8). tb_ppo_grad computes exactly -g when its clip never binds (clip_range = inf), so it is reused unchanged.
+  2. Fisher-vector products on cg_state_percent = 0.1 of the rows, drawn by one torch.randperm (agent.py:18,218-220):
+     F v = (1/m) sum_rows J^T diag(sigma^-2) J v on the network's slots, 2 v on log_std, plus cg_damping * v (0.001). That is the
+     Hessian of KL(old || new) at theta, which agent.py:144-167 obtains by double backprop.
+  3. Conjugate gradient, agent.py:169-191: 10 iterations, x, r and the scalars in float64, p in float32; torch vector ops.
+  4. beta = sqrt(2 delta / (x^T F x)), delta = kl_delta = 0.01 (agent.py:110-111).
+  5. Line search: theta_k = theta + beta 1.5^-k x, k = 0 .. 9 (agent.py:112-113), all ten in one launch over all rows; the first
+     k whose L_k = mean(ratio_k A_hat) and KL_k (agent.py:92-97) are finite with KL_k <= delta and L_k >= 0 (agent.py:132) is
+     taken; if none qualifies theta stays as it is, bit for bit. The choice is made on the device.
+  6. The critic: n_epochs passes of minibatch Adam on the value loss alone (tb_ppo_apply with TB_PPO_VALUE_ONLY): the policy
+     slots of the parameters, the gradient and both Adam moments are not written.
+
+Deviations from agent.py, all of them:
+  * log_std is inside the natural gradient (its Fisher block is 2 I); agent.py:120,136 moves it by the raw gradient.
+  * CG's early exit at rdotr < 1e-10 (agent.py:189-190) is a device-side freeze (torch.where): nothing synchronises.
+  * x^T F x of the step size is taken over the CG rows, not over all rows (agent.py:110-111 uses all).
+  * agent.py has no critic: it weights by normalised discounted returns (agent.py:210,264-268). Here GAE and a critic, as
+    `-s trpo` of train_swing.py (a learner with a value function) implies.
+  * The ratio's old log-probability is the rollout's own (as in the PPO learner), and the CG rows are the first 0.1 n entries of
+    a device-side torch.randperm instead of numpy's choice.
+
+An update issues no host synchronisation before its single read of the statistics. One rank only, and only the env's default
+net_arch (the kernels are instantiated for it). There is no torch fallback: a refused call raises, as in learner.py.
+"""
+from .learner import TB_PPO_REDUCE, TB_PPO_STEP, FusedLearner, flatten_parameters, parameter_offsets
+from .ppo import SWING_DEFAULTS, TENNIS_DEFAULTS, PPOTrainer
+from .params import ENV_SWING
+from .stepper import ENV_IDS, StepperError, _check
+
+TB_PPO_VALUE_ONLY = 4
+TRPO_DEFAULTS = dict(kl_delta=0.01, cg_iterations=10, cg_damping=0.001, cg_tolerance=1e-10, cg_state_percent=0.1,   # agent.py:17-18
+                     search_candidates=10, search_decay=1.5)                                                      # agent.py:112-113
+
+
+def select_candidate(torch, table, delta):
+    """table [K, 2] = (L_k, KL_k), a tensor: the first k that is finite with KL_k <= delta and L_k >= 0 (agent.py:132), or -1;
+    a 0-d int64 tensor on the table's device"""
+    K = table.shape[0]
+    L, KL = table[:, 0], table[:, 1]
+    ok = torch.isfinite(L) & torch.isfinite(KL) & (KL <= delta) & (L >= 0)
+    first = torch.where(ok, torch.arange(K, device=table.device), torch.full((K,), K, device=table.device)).min()
+    return torch.where(first < K, first, torch.full_like(first, -1))
+
+
+class FusedTRPO(FusedLearner):
+    """GAE (inherited), the trust-region policy step and the critic's epochs on the device for one policy / optimiser pair"""
+
+    def __init__(self, kind, policy, opt, hp, device):
+        for k, v in TRPO_DEFAULTS.items():        # filled in place: hp stays the caller's dict, as with FusedLearner, so a later
+            hp.setdefault(k, v)                   # change of trainer.hp reaches the learner
+        super().__init__(kind, policy, opt, hp, device)
+        t = self.torch
+        if not 1 <= int(self.hp["search_candidates"]) <= 64 or int(self.hp["cg_iterations"]) < 1 or not 0.0 < float(self.hp["cg_state_percent"]) <= 1.0:
+            raise ValueError("FusedTRPO: search_candidates 1 .. 64, cg_iterations >= 1 and 0 < cg_state_percent <= 1 expected")
+        self.mask = t.zeros(self.n_params, dtype=t.float32, device=self.device)   # 1 on theta's slots
+        for name, (off, n) in parameter_offsets(policy).items():
+            if name == "log_std" or name.startswith("policy_net.") or name.startswith("action_net."):
+                self.mask[off:off + n] = 1.0
+        z = lambda n, dt=t.float32: t.zeros(n, dtype=dt, device=self.device)  # noqa: E731
+        self._g, self._gstats, self._fv, self._fx = z(self.n_params), z(3), z(self.n_params), z(self.n_params)
+        K = int(self.hp["search_candidates"])
+        self.table = z((K, 2), t.float64)
+        self._decay = t.tensor([float(self.hp["search_decay"]) ** -k for k in range(K)], dtype=t.float64, device=self.device)
+        self.report = z(5, t.float64)
+        self._fvp_ws = self._search_ws = self._rows = None
+
+    # ----------------------------------------------------------------------------------------------------------- the kernels
+    def _grow(self, ws, need, what):
+        if need < 0:
+            _check(self.lib, int(need), what)
+        if ws is None or ws.numel() * 8 < need:
+            ws = self.torch.zeros((need + 7) // 8, dtype=self.torch.float64, device=self.device)
+        return ws
+
+    def fvp(self, obs, idx_ptr, m, vec, out, damping=None):
+        """out = F vec + damping vec over the rows idx[0 .. m) (a device pointer to int64) of obs; returns out"""
+        obs, vec = self._float(obs, "obs"), self._float(vec, "vec")
+        if out.dtype != self.torch.float32 or out.device != self.flat.device or not out.is_contiguous() or out.numel() != self.n_params or vec.numel() != self.n_params:
+            raise ValueError("fvp: vec and out must be contiguous float32 vectors of %d floats on %s" % (self.n_params, self.flat.device))
+        self._fvp_ws = ws = self._grow(self._fvp_ws, self.lib.tb_trpo_fvp_workspace_bytes(self.kind, int(m)), "tb_trpo_fvp_workspace_bytes")
+        _check(self.lib, self.lib.tb_trpo_fvp(self.kind, self._dev(), self._stream(), obs.data_ptr(), int(obs.shape[0]), idx_ptr, int(m), self.flat.data_ptr(),
+                                              vec.data_ptr(), self.n_params, float(self.hp["cg_damping"] if damping is None else damping), out.data_ptr(),
+                                              ws.data_ptr(), ws.numel() * 8), "tb_trpo_fvp")
+        return out
+
+    def search(self, arrays, n_rows, idx_ptr, batch, direction, steps, out=None):
+        """(L_k, KL_k) of theta + steps[k] * direction over the rows idx[0 .. batch): a float64 [K, 2] tensor"""
+        t = self.torch
+        obs, act, old_logp, adv = arrays[:4]
+        direction, steps = self._float(direction, "direction"), self._float(steps, "steps")
+        K = int(steps.numel())
+        if direction.numel() != self.n_params:
+            raise ValueError("search: the direction must hold %d floats" % self.n_params)
+        out = out if out is not None else t.zeros((K, 2), dtype=t.float64, device=self.device)
+        self._search_ws = ws = self._grow(self._search_ws, self.lib.tb_trpo_search_workspace_bytes(self.kind, int(batch), K), "tb_trpo_search_workspace_bytes")
+        _check(self.lib, self.lib.tb_trpo_search(self.kind, self._dev(), self._stream(), obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), int(n_rows),
+                                                 idx_ptr, int(batch), self.flat.data_ptr(), direction.data_ptr(), self.n_params, steps.data_ptr(), K, out.data_ptr(),
+                                                 ws.data_ptr(), ws.numel() * 8), "tb_trpo_search")
+        return out
+
+    def surrogate_gradient(self, arrays, n_rows, idx_ptr, batch):
+        """g = grad_theta mean(ratio A_hat) over the rows idx[0 .. batch), 0 on the value slots: minus what tb_ppo_grad leaves
+        when its clip never binds. self.grad is not touched."""
+        L, dev, s = self.lib, self._dev(), self._stream()
+        obs, act, old_logp, adv, returns = arrays
+        ws = self.workspace(batch)
+        wb = ws.numel() * 8
+        _check(L, L.tb_ppo_grad(self.kind, dev, s, obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), returns.data_ptr(), n_rows, idx_ptr, batch,
+                                self.flat.data_ptr(), self.n_params, float("inf"), 0.0, ws.data_ptr(), wb), "tb_ppo_grad")
+        _check(L, L.tb_ppo_apply(self.kind, dev, s, TB_PPO_REDUCE, ws.data_ptr(), wb, batch, self.flat.data_ptr(), self._g.data_ptr(), None, None, self.n_params,
+                                 self._gstats.data_ptr(), 0.0, 1.0, 1, 0.0, 0.9, 0.999, 1e-5, 1), "tb_ppo_apply")
+        return -self._g * self.mask
+
+    def conjugate_gradient(self, b, obs, idx_ptr, m):
+        """x ~ (F + damping)^-1 b, agent.py:169-191; float64 [P]. Frozen (not left) once rdotr < cg_tolerance."""
+        t = self.torch
+        p, r = b.clone(), b.double()
+        x = t.zeros_like(r)
+        rdotr = r.dot(r)
+        live = t.ones((), dtype=t.bool, device=self.device)
+        tol = float(self.hp["cg_tolerance"])
+        for _ in range(int(self.hp["cg_iterations"])):
+            pd = p.double()
+            f = self.fvp(obs, idx_ptr, m, p, self._fv).double()
+            alpha = rdotr / pd.dot(f)
+            x = t.where(live, x + alpha * pd, x)
+            r_new = r - alpha * f
+            new_rdotr = r_new.dot(r_new)
+            p = t.where(live, (r_new + (new_rdotr / rdotr) * pd).float(), p)
+            r = t.where(live, r_new, r)
+            rdotr = t.where(live, new_rdotr, rdotr)
+            live = live & (rdotr >= tol)
+        return x
+
+    def policy_step(self, arrays, n_rows, all_ptr, cg_ptr, m):
+        """steps 1-5 of the module docstring; theta moves in place (or not at all). Returns (accepted k or -1, L, KL of the
+        accepted candidate -- of k = 0 when none is) as 0-d device tensors. No host synchronisation."""
+        t, hp = self.torch, self.hp
+        g = self.surrogate_gradient(arrays, n_rows, all_ptr, n_rows)
+        x = self.conjugate_gradient(g, arrays[0], cg_ptr, m)
+        xf = (x.float() * self.mask).contiguous()
+        xFx = xf.double().dot(self.fvp(arrays[0], cg_ptr, m, xf, self._fx).double())
+        beta = t.sqrt(2.0 * float(hp["kl_delta"]) / xFx)
+        steps = (beta * self._decay).float()
+        self.search(arrays, n_rows, all_ptr, n_rows, xf, steps, out=self.table)
+        k = select_candidate(t, self.table, float(hp["kl_delta"]))
+        accepted = k >= 0
+        kk = k.clamp(min=0).view(1)                   # (gather / index_select: indexing with a 0-d tensor would read it on the host)
+        moved = self.flat + steps.gather(0, kk) * xf  # the product and the sum rounded separately: what the search kernel evaluated
+        self.flat.copy_(t.where(accepted, moved, self.flat))
+        row = self.table.index_select(0, kk)[0]
+        return k, row[0], row[1]
+
+    def value_minibatch(self, arrays, n_rows, idx_ptr, batch, step):
+        """one Adam step of the critic alone on rows idx[0 .. batch)"""
+        L, hp, dev, s = self.lib, self.hp, self._dev(), self._stream()
+        obs, act, old_logp, adv, returns = arrays
+        ws = self.workspace(batch)
+        wb = ws.numel() * 8
+        _check(L, L.tb_ppo_grad(self.kind, dev, s, obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), returns.data_ptr(), n_rows, idx_ptr, batch,
+                                self.flat.data_ptr(), self.n_params, float(hp["clip_range"]), float(hp["vf_coef"]), ws.data_ptr(), wb), "tb_ppo_grad")
+        g = self.opt.param_groups[0]
+        _check(L, L.tb_ppo_apply(self.kind, dev, s, TB_PPO_REDUCE | TB_PPO_STEP | TB_PPO_VALUE_ONLY, ws.data_ptr(), wb, batch, self.flat.data_ptr(), self.grad.data_ptr(),
+                                 self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.n_params, self.stats.data_ptr(), float(hp["ent_coef"]),
+                                 float(hp["max_grad_norm"]), 1, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), int(step)), "tb_ppo_apply")
+
+    # ---------------------------------------------------------------------------------------------------------------- update
+    def update(self, obs, act, old_logp, adv, returns, n_epochs, batch_size, world=1):
+        """one trust-region step of the policy on the flat rollout [n, ...], then n_epochs of the critic in minibatches of
+        batch_size rows. Draws one torch.randperm(n) for the CG rows and one per critic epoch; reads the device once, at the end."""
+        t = self.torch
+        if int(world) != 1:
+            raise StepperError("FusedTRPO: one rank only (multi-rank TRPO is not provided)")
+        n = int(adv.shape[0])
+        arrays = tuple(self._float(x, name) for x, name in ((obs, "obs"), (act, "act"), (old_logp, "old_logp"), (adv, "adv"), (returns, "returns")))
+        if arrays[0].numel() * self.lib.tb_act_dim(self.kind) != arrays[1].numel() * self.lib.tb_obs_dim(self.kind) or arrays[0].shape[0] != n \
+                or any(int(x.numel()) != n for x in arrays[2:]):
+            raise ValueError("update: obs [n, O], act [n, A], old_logp / adv / returns [n] expected")
+        flatten_parameters(self.policy)
+        if self.policy._flat_params is not self.flat:
+            self.flat = self.policy._flat_params
+        step = self._adopt_optimizer_state()
+        if self._rows is None or self._rows.numel() != n:
+            self._rows = t.arange(n, device=self.device)
+        m = max(1, int(float(self.hp["cg_state_percent"]) * n))
+        cg_rows = t.randperm(n, device=self.device)
+        k, L, KL = self.policy_step(arrays, n, self._rows.data_ptr(), cg_rows.data_ptr(), m)
+        for _ in range(int(n_epochs)):
+            perm = t.randperm(n, device=self.device)
+            for s in range(0, n, int(batch_size)):
+                if n - s < 2:
+                    break  # (a tail of one row has no unbiased std; tb_ppo_grad refuses it)
+                step += 1
+                self.value_minibatch(arrays, n, perm.data_ptr() + 8 * s, min(int(batch_size), n - s), step)
+        for p, (gv, mv, vv) in zip(self.params, self._views):
+            st = self.opt.state[p]
+            st["step"] = t.tensor(float(step), dtype=st["step"].dtype, device=st["step"].device)
+            p.grad = gv
+        self.report[0], self.report[1], self.report[2] = k.double(), L, KL
+        self.report[3:5] = self.stats[1:3].double()
+        k, L, KL, vl, ent = self.report.tolist()  # the one device-to-host read
+        return {"accepted_k": int(k), "surrogate": L, "kl": KL, "policy_loss": -L, "value_loss": vl, "entropy": ent}
+
+
+class TRPOTrainer(PPOTrainer):
+    """TRPO over a BatchedEnv: PPOTrainer's collect, GAE and critic; the policy moves by FusedTRPO's trust-region step.
+    hp: kl_delta, cg_iterations, cg_damping, cg_state_percent (TRPO_DEFAULTS) beside PPOTrainer's."""
+
+    def __init__(self, env_id="SwingRacket-v0", num_envs=4096, n_steps=104, device=None, seed=0, batch_size=None, **kw):
+        import torch
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("TRPOTrainer runs on one rank (world size %d): multi-rank TRPO is not provided" % dist.get_world_size())
+        default_arch = tuple((SWING_DEFAULTS if ENV_IDS[env_id] == ENV_SWING else TENNIS_DEFAULTS)["net_arch"])
+        if tuple(kw.get("net_arch", default_arch)) != default_arch or not kw.get("fused", True):
+            raise ValueError("TRPOTrainer needs the env's default net_arch %s and the fused rollout: its kernels are instantiated for that architecture" % (default_arch,))
+        if kw.pop("learner", "fused") != "fused":
+            raise ValueError("TRPOTrainer has no torch learner")
+        super().__init__(env_id, num_envs, n_steps, device, seed, batch_size, learner="torch", **kw)
+        self.hp = dict(TRPO_DEFAULTS, **self.hp)
+        self._learner = FusedTRPO(ENV_IDS[env_id], self.policy, self.opt, self.hp, self.device)

@@ -38,19 +38,29 @@ def main():
     ap.add_argument("--total-timesteps", type=float, default=None, help="default: 2e6 Swing / 1e6 Tennisbot, as the reference")
     ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save")
     ap.add_argument("--load-reference", action="store_true", help="warm start from the reference's shipped ppo_swing policy (tests/golden/ppo_swing_policy.npz)")
-    ap.add_argument("--save", type=str, default="./model/ppo_%s.pt")
+    ap.add_argument("--save", type=str, default=None, help="default: ./model/ppo_%%s.pt, or ./model/trpo_%%s.pt under -s trpo (%%s: the env id)")
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
     ap.add_argument("--gui", action="store_true", help="accepted for CLI compatibility; there is no GUI")
-    ap.add_argument("-s", "--select", default="ppo", help="only ppo is provided (sac / tqc / trpo are third-party learners)")
+    ap.add_argument("-s", "--select", default="ppo", help="ppo or trpo (train_swing.py:102; tennisbot_rl_amd/trpo.py); sac / tqc are third-party learners")
+    ap.add_argument("--kl-delta", type=float, default=0.01, help="trpo: the trust region's KL bound (agent.py:17)")
+    ap.add_argument("--cg-iterations", type=int, default=10, help="trpo: conjugate-gradient iterations")
+    ap.add_argument("--cg-damping", type=float, default=0.001, help="trpo: damping added to the Fisher-vector product")
+    ap.add_argument("--cg-state-percent", type=float, default=0.1, help="trpo: share of the rollout's rows the Fisher-vector products run over")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (court.urdf:19-24; TB_F_RACKET_GROUND, opt-in: DESIGN.md section 3)")
     ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact (rollingFriction=.001 in racket.py:43-45, objects.py:29-31,48-50)")
     ap.add_argument("--no-fused", action="store_true", help="run the policy as torch modules between env steps instead of inside the step kernel")
-    ap.add_argument("--learner", default="torch", choices=["torch", "fused"], help="fused: GAE, minibatch gradient and Adam as HIP kernels (tennisbot_rl_amd/learner.py)")
+    ap.add_argument("--learner", default=None, choices=["torch", "fused"], help="ppo (default torch): fused = GAE, minibatch gradient and Adam as HIP kernels (tennisbot_rl_amd/learner.py); trpo has the fused learner only")
     ap.add_argument("--log-json", type=str, default=None)
     args = ap.parse_args()
-    if args.select != "ppo":
-        sys.exit("only -s ppo is implemented on the batched envs")
+    if args.select not in ("ppo", "trpo"):
+        sys.exit("only -s ppo and -s trpo are implemented on the batched envs")
+    if args.select == "trpo" and args.learner == "torch":
+        sys.exit("-s trpo has no torch learner: its update runs as HIP kernels (leave --learner out, or --learner fused)")
+    if args.select == "trpo" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("-s trpo runs on one rank: multi-rank TRPO is not provided")
+    if args.save is None:
+        args.save = "./model/%s_%%s.pt" % args.select
 
     import torch
     from tennisbot_rl_amd.ppo import PPOTrainer
@@ -66,8 +76,13 @@ def main():
     if args.racket_ground or args.rolling_friction:
         from tennisbot_rl_amd.params import F_DEFAULT, F_RACKET_GROUND, default_params, reference_rolling_friction
         params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
-    tr = PPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed,
-                    fused=not args.no_fused, params=params, learner=args.learner)
+    if args.select == "trpo":
+        from tennisbot_rl_amd.trpo import TRPOTrainer
+        tr = TRPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed, fused=not args.no_fused,
+                         params=params, kl_delta=args.kl_delta, cg_iterations=args.cg_iterations, cg_damping=args.cg_damping, cg_state_percent=args.cg_state_percent)
+    else:
+        tr = PPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed,
+                        fused=not args.no_fused, params=params, learner=args.learner or "torch")
     if args.load_reference:
         import numpy as np
         tr.policy.load_sb3_arrays(dict(np.load(os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz"))))

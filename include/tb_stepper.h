@@ -336,6 +336,30 @@ int tb_policy_rollout(TbHandle *h, int n_steps, const float *weights_dev, const 
                       uint64_t noise_seed, int deterministic, void *stream);
 
 /*
+ * The network of the fused policy. TB_NET_DEFAULT: the env kind's own (above). TB_NET_TUNED, Tennisbot-v0 only: the
+ * reference's `train.py -s tuned_ppo` (train.py:54-67,112-127) -- a ReLU features extractor 12 -> 64 -> A shared by actor and
+ * critic (A = 2, the action dimension), then ReLU towers pi = vf = A -> 32 -> 64 -> 32 with the usual heads and a state-independent log_std; ReLU is exact
+ * (0 for z <= 0, a NaN kept). The net is an argument of the call, not a state of the handle: calls with either net may follow
+ * each other on one handle, and a captured launch keeps the net it was captured with. Any other (kind, net) pair is refused
+ * with TB_E_PARAMS before anything is launched.
+ * Blob (tb_policy_blob_floats(kind, net) floats; for TB_NET_DEFAULT the layout and the length of tb_policy_floats): the
+ * extractor's two layers, the pi tower with its head, the vf tower with its head, log_std padded to 4 -- every layer in the
+ * bias-tile / weight-fragment format above. The extractor's second layer and the heads are padded to 16 outputs with zeros;
+ * the towers' first layer takes the A-wide feature as a 16-wide input (k(4u + r, g) = 16u + 4g + r, zero for k >= A).
+ * tb_policy_step_net / tb_policy_rollout_net: tb_policy_step / tb_policy_rollout with that network; sampling, noise keys,
+ * clipping, episode ends and every output are theirs. The un-suffixed names are the TB_NET_DEFAULT calls.
+ */
+enum { TB_NET_DEFAULT = 0, TB_NET_TUNED = 1 };
+int tb_policy_blob_floats(int env_kind, int net);
+int tb_policy_step_net(TbHandle *h, int net, const float *weights_dev, const float *obs_in_dev, float *actions_dev,
+                       float *raw_actions_dev, float *logp_dev, float *value_dev, float *obs_dev,
+                       float *reward_dev, uint8_t *done_dev, uint64_t noise_seed, int deterministic, void *stream);
+int tb_policy_rollout_net(TbHandle *h, int net, int n_steps, const float *weights_dev, const float *obs_in_dev,
+                          float *actions_dev, float *raw_actions_dev, float *logp_dev, float *value_dev,
+                          float *obs_dev, float *reward_dev, uint8_t *done_dev, const size_t *step_strides_bytes,
+                          uint64_t noise_seed, int deterministic, void *stream);
+
+/*
  * Evolution-strategies population evaluation: the reference's fitness_static (tennisbot/ES/fitness_functions.py:17-159,
  * evolution_strategy_static.py:25-44) for every env at once, one launch for every env's whole episode. Each env runs one episode
  * with a fresh float64 observation normaliser and its member's GatedCNN (tennisbot/ES/policies.py:59-130) on the last 8
@@ -418,6 +442,26 @@ int tb_ppo_grad(int env_kind, int device, void *stream, const float *obs_dev, co
 int tb_ppo_apply(int env_kind, int device, void *stream, int phases, const void *workspace_dev, size_t workspace_bytes, int batch,
                  float *params_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev, int n_params, float *stats_dev,
                  float ent_coef, float max_grad_norm, int world, float lr, float beta1, float beta2, float eps, long long step);
+/*
+ * The same learner for a network given by name (TB_NET_*; the names above are the TB_NET_DEFAULT calls). TB_NET_TUNED
+ * (Tennisbot-v0): tb_ppo_param_floats_net = 9639 floats in the order log_std [2] | features extractor W0 [64][12] b0 W1 [2][64]
+ * b1 | policy_net W0 [32][2] b0 W1 [64][32] b1 W2 [32][64] b2 | value_net_body, the same | action_net W [2][32] b | value_net
+ * W [1][32] b -- named_parameters() of ppo.build_tuned_actor_critic. ReLU' = 0 at z <= 0. Each tower wave differentiates the shared
+ * extractor too: a partial vector holds the pi wave's extractor share in the extractor's slots and the vf wave's in a second
+ * region, and TB_PPO_REDUCE adds the two float64 sums (pi's first), so the result is as reproducible as the default nets'.
+ * TB_PPO_VALUE_ONLY is refused for it (TB_E_UNSUPPORTED): the extractor is shared, there is no critic-only slot range.
+ * tb_ppo_gae does not depend on the network. Other (kind, net) pairs: TB_E_PARAMS.
+ */
+int tb_ppo_param_floats_net(int env_kind, int net);
+long long tb_ppo_workspace_bytes_net(int env_kind, int net, int batch);
+int tb_ppo_grad_net(int env_kind, int net, int device, void *stream, const float *obs_dev, const float *raw_actions_dev,
+                    const float *old_logp_dev, const float *adv_dev, const float *returns_dev, long long n_rows,
+                    const int64_t *idx_dev, int batch, const float *params_dev, int n_params, float clip_range, float vf_coef,
+                    void *workspace_dev, size_t workspace_bytes);
+int tb_ppo_apply_net(int env_kind, int net, int device, void *stream, int phases, const void *workspace_dev, size_t workspace_bytes,
+                     int batch, float *params_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev, int n_params,
+                     float *stats_dev, float ent_coef, float max_grad_norm, int world, float lr, float beta1, float beta2, float eps,
+                     long long step);
 
 /*
  * The TRPO learner's policy step (csrc/tb_trpo.hpp; tennisbot_rl_amd/trpo.py is the caller), in the conventions of the tb_ppo_*

@@ -755,7 +755,7 @@ namespace {
 // MULTI: A.T agent steps in one launch (tb_rollout); otherwise exactly one (tb_step). A compile-time
 // trip count of 1 is worth ~50-100 VGPRs (no loop-carried copies of the per-step bookkeeping), i.e.
 // one to two more waves per SIMD for the kernel every RL step launches.
-// POLICY: the actions are not read from memory but inferred in-kernel (tb_policy_step).
+// POLICY: the actions are not read from memory but inferred in-kernel (tb_policy_step); NET: by which network (tb_policy.hpp).
 // SCHEDULING HINTS. Three places below (and one in tb_device.hpp) steer where the compiler puts scalar argument loads, with empty
 // `asm volatile` statements that only NAME values. They change no result; each was chosen by a same-box A/B on AMD clang 22 / ROCm 7.2
 // (profiles/EXPERIMENTS.md) and is worth 1-4 % to a launch-bound kernel -- on THIS compiler. They are the only compile-time switches
@@ -780,7 +780,7 @@ constexpr bool step_has_two_waves(int kind, bool lean, bool multi, bool rg, bool
 constexpr int step_lds_words(int kind, bool lean, bool multi, bool rg, bool policy) { return lds_words(!step_rows_in_registers(kind, lean, multi, rg, policy), rg); }
 // TWO_WAVE: two waves per 64 envs, the racket's update on one and the ball's on the other (two_wave_step; the pipelined SwingRacket
 // one-step kernel at small batch sizes). A launch whose 64 envs are not all on the common path runs them on wave 0 below.
-template <int KIND, bool LEAN, bool MULTI, bool RG, bool POLICY = false, bool TWO_WAVE = false>
+template <int KIND, bool LEAN, bool MULTI, bool RG, bool POLICY = false, bool TWO_WAVE = false, int NET = TB_NET_DEFAULT>
 __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict__ k_words, const uint8_t* __restrict__ k_done, const float* __restrict__ k_actions,
                                                       const float4* __restrict__ k_hull, int k_n, int k_nhull, KArgs A) {
   // The leading arguments repeat A.words / done_state / actions / hull / n / P.n_hull as separate,
@@ -863,11 +863,11 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
     const bool has_row = (int)threadIdx.x < 2 * w_nhull || ((int)threadIdx.x >= TB_HULL_PLANES && (int)threadIdx.x < TB_HULL_LDS);
     float4 row = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (has_row) row = w_hull[threadIdx.x];
-    policy_towers<KIND>(A, s_mean);
+    policy_towers<KIND, NET>(A, s_mean);
     if (has_row) s_lds_hull[threadIdx.x] = row;
     __syncthreads();
     if (threadIdx.x >= 64) return;  // no barrier below this point
-    if (live) policy_sample<KIND>(A, s_mean, i, e, a);
+    if (live) policy_sample<KIND, NET>(A, s_mean, i, e, a);
   } else if (!TABLE_IN_MEMORY && !LAZYTAB) {
     stage_hull(s_lds_hull, w_hull, w_nhull);
     __syncthreads();
@@ -962,7 +962,7 @@ TB_DEV void idle_env(EnvRegs& e) {
   e.step_count = -(1 << 30); e.episode = 0u; e.done = TB_DONE_NO;
 }
 constexpr int policy_rollout_lds_words(int kind, bool rg) { return lds_words(!policy_rollout_rows_in_registers(kind), rg); }
-template <int KIND, int S, bool RG>
+template <int KIND, int S, bool RG, int NET = TB_NET_DEFAULT>
 __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KArgs A) {
   constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE * S;
   __shared__ float4 s_hull[TB_HULL_LDS];
@@ -974,8 +974,8 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
     const int tower = wave / S, slice = wave % S, grp = lane >> 4;
     const int slot = slice * TB_POLICY_SLICE + (lane & 15), env = blockIdx.x * E + slot;
     const int env_c = env < A.n ? env : A.n - 1;
-    TowerRegs<KIND> regs;
-    regs.load(A.pol_weights + tower * tower_floats<KIND>(), lane);
+    PolicyRegs<KIND, NET> regs;
+    regs.load(A.pol_weights, tower, lane);
     __syncthreads();
     for (int t = 0; t < A.T; ++t) {
       float x0[TowerRegs<KIND>::NC0], out[4];
@@ -1010,7 +1010,7 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   __syncthreads();
   float stdv[NA], lstd[NA];
 #pragma unroll
-  for (int k = 0; k < NA; ++k) { lstd[k] = A.pol_weights[2 * tower_floats<KIND>() + k]; stdv[k] = expf(lstd[k]); }
+  for (int k = 0; k < NA; ++k) { lstd[k] = A.pol_weights[PolicyBlob<KIND, NET>::LOG_STD + k]; stdv[k] = expf(lstd[k]); }
   // The free-flight constants of the substep as VECTOR registers for the whole launch. As kernel arguments they are scalar loads
   // that the compiler, at its SGPR limit in this kernel, re-issues inside the per-step loop (two dozen of them, each behind a wait
   // the lone env wave cannot hide); the env wave has ~300 vector registers to spare, and a value that went through an empty asm

@@ -58,12 +58,17 @@ TB_DEV f32x4 ppo_transpose(const f32x4 c, float* buf, int lane) {
 }
 
 // one nn.Linear of a tower for this lane: forward fragments, transposed fragments, bias, and the gradient accumulators
-template <int IN, int OUT, bool FIRST>
+// WB_REGS = false (the tuned net's extractor output layer and third tower layer: six layers' operands do not fit in 512 registers): the transposed fragments
+// live in the wave's own LDS instead (stage_wb / backward_input_lds)
+template <int IN, int OUT, bool FIRST, bool WB_REGS = true>
 struct PpoLayer {
-  static constexpr int NT = (OUT + 15) / 16, NTI = (IN + 15) / 16, NC = FIRST ? (IN + 3) / 4 : IN / 4;
-  static_assert(FIRST || IN % 16 == 0, "hidden widths are multiples of 16");
+  // (a later layer's input is whole accumulator tiles: IN is a multiple of 16, or -- the tuned net's feature -- narrower than one tile,
+  //  the tile's other rows being exact zeros that meet zero weights)
+  static constexpr int NT = (OUT + 15) / 16, NTI = (IN + 15) / 16, NC = FIRST ? (IN + 3) / 4 : NTI * 4;
+  static_assert(FIRST || IN % 16 == 0 || IN < 16, "hidden widths are multiples of 16");
   float wf[NT * NC];                   // (t, c): W[16 t + j][k(c, g)], k as in tb_policy.hpp
-  float wb[FIRST ? 1 : NTI * NT * 4];  // (ti, t, r): W[16 t + 4 g + r][16 ti + j]
+  static constexpr int NWB = NTI * NT * 4;
+  float wb[FIRST || !WB_REGS ? 1 : NWB];  // (ti, t, r): W[16 t + 4 g + r][16 ti + j]
   f32x4 bias[NT];
   f32x4 dw[NT * NTI];                  // (t, ti), C/D layout: dW[16 t + 4 g + r][16 ti + j]
   float db[NT];                        // feature 16 t + j, summed over the rows = g (mod 4) so far
@@ -86,7 +91,7 @@ struct PpoLayer {
 #pragma unroll
       for (int ti = 0; ti < NTI; ++ti) dw[t * NTI + ti] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
-    if (!FIRST) {
+    if (!FIRST && WB_REGS) {
 #pragma unroll
       for (int ti = 0; ti < NTI; ++ti) {
 #pragma unroll
@@ -97,6 +102,33 @@ struct PpoLayer {
             wb[(ti * NT + t) * 4 + r] = (o < OUT && i < IN) ? W[o * IN + i] : 0.0f;
           }
         }
+      }
+    }
+  }
+  // the transposed fragments into lds[NWB][64] of this wave's own (written and read by the same lane: no barrier)
+  TB_DEV void stage_wb(const float* W, float* lds, int lane) const {
+    const int g = lane >> 4, j = lane & 15;
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int o = 16 * t + 4 * g + r, i = 16 * ti + j;
+          lds[((ti * NT + t) * 4 + r) * 64 + lane] = (o < OUT && i < IN) ? W[o * IN + i] : 0.0f;
+        }
+      }
+    }
+  }
+  TB_DEV void backward_input_lds(const float* lds, int lane, const f32x4 (&dz)[NT], f32x4 (&dh)[NTI]) const {
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti) dh[ti] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int ti = 0; ti < NTI; ++ti) dh[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[((ti * NT + t) * 4 + r) * 64 + lane], dz[t][r], dh[ti], 0, 0, 0);
       }
     }
   }
@@ -466,6 +498,257 @@ __global__ __launch_bounds__(64) void tb_ppo_gae_kernel(int T, int n, const floa
     adv[(size_t)k * n + i] = g;
     ret[(size_t)k * n + i] = g + V;
     next = V;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the tuned net
+// TB_NET_TUNED (Tennisbot; TunedNet in tb_policy.hpp): flat order log_std | extractor W0 b0 W1 b1 | policy_net | value_net_body |
+// action_net | value_net. The two tower waves of a half share both run the shared extractor forward and send their tower's
+// gradient back through it, so BOTH hold an extractor gradient: the pi wave writes its share to the extractor's own slots of the
+// partial vector, the vf wave to a second extractor region behind the two statistics (EXT2), and tb_ppo_reduce_tuned_kernel adds
+// the two regions' float64 sums, pi's first. No atomics, no workgroup barrier, one fixed order.
+struct TunedLayout {
+  using N = TunedNet;
+  static constexpr int O = N::O, A = N::F;
+  static constexpr int EXT_SIZE = N::FH * (O + 1) + A * (N::FH + 1);
+  static constexpr int BODY = N::H0 * (A + 1) + N::H1 * (N::H0 + 1) + N::H2 * (N::H1 + 1);
+  static constexpr int LOG_STD = 0, EXT = A, PI = EXT + EXT_SIZE, VF = PI + BODY, PI_HEAD = VF + BODY, VF_HEAD = PI_HEAD + A * (N::H2 + 1);
+  static constexpr int P = VF_HEAD + N::H2 + 1;
+  static constexpr int EXT2 = P + 2, STRIDE = EXT2 + EXT_SIZE;  // gradient, the two statistics, the vf wave's extractor share
+  // within the extractor: W0, b0, W1, b1; within a body: W0, b0, W1, b1, W2, b2
+  static constexpr int EW0 = 0, EB0 = EW0 + N::FH * O, EW1 = EB0 + N::FH, EB1 = EW1 + A * N::FH;
+  static constexpr int W0 = 0, B0 = W0 + N::H0 * A, W1 = B0 + N::H0, B1 = W1 + N::H1 * N::H0, W2 = B1 + N::H1, B2 = W2 + N::H2 * N::H1;
+};
+
+template <int NTILES>
+TB_DEV void ppo_relu(const f32x4 (&z)[NTILES], f32x4 (&h)[NTILES]) {
+#pragma unroll
+  for (int t = 0; t < NTILES; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h[t][r] = relu(z[t][r]);
+  }
+}
+// dz = dh where the unit is on (h > 0 exactly where z > 0), 0 where z <= 0
+template <int NTILES>
+TB_DEV void ppo_drelu(const f32x4 (&dh)[NTILES], const f32x4 (&h)[NTILES], f32x4 (&dz)[NTILES]) {
+#pragma unroll
+  for (int t = 0; t < NTILES; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dz[t][r] = h[t][r] > 0.0f ? dh[t][r] : 0.0f;
+  }
+}
+
+// one tower of one half share, extractor included: forward through extractor and tower, backward through both.
+// TB_TUNED_STAGE: a scheduling fence between the stages of a tile. Left alone the max-ILP scheduler interleaves a layer's backward
+// products with the next layer's transposes and keeps both layers' temporaries alive: 2-7 VGPRs spilled at the 512-register limit.
+#define TB_TUNED_STAGE() __builtin_amdgcn_sched_barrier(0)
+template <bool PI>
+TB_DEV void ppo_tuned_tower(const PpoGradArgs& a, float* buf, float* wb_lds, int lane, int first, float* part) {
+  using L = TunedLayout;
+  using N = TunedNet;
+  constexpr int O = L::O, NA = L::A, HOUT = PI ? NA : 1;
+  const int g = lane >> 4, e = lane & 15, B = a.batch;
+  const float* ext = a.params + L::EXT;
+  const float* body = a.params + (PI ? L::PI : L::VF);
+  const float* head = a.params + (PI ? L::PI_HEAD : L::VF_HEAD);
+  using E0 = PpoLayer<O, N::FH, true>;
+  using E1 = PpoLayer<N::FH, N::F, false, false>;
+  using L0 = PpoLayer<N::F, N::H0, false>;
+  using L1 = PpoLayer<N::H0, N::H1, false>;
+  using L2 = PpoLayer<N::H1, N::H2, false, false>;
+  using LH = PpoLayer<N::H2, HOUT, false>;
+  float* const wb2_lds = wb_lds + E1::NWB * 64;
+  E0 e0;
+  E1 e1;
+  L0 l0;
+  L1 l1;
+  L2 l2;
+  LH lh;
+  e0.load(ext + L::EW0, ext + L::EB0, lane);
+  e1.load(ext + L::EW1, ext + L::EB1, lane);
+  e1.stage_wb(ext + L::EW1, wb_lds, lane);
+  l0.load(body + L::W0, body + L::B0, lane);
+  l1.load(body + L::W1, body + L::B1, lane);
+  l2.load(body + L::W2, body + L::B2, lane);
+  l2.stage_wb(body + L::W2, wb2_lds, lane);
+  lh.load(head, head + HOUT * N::H2, lane);
+
+  float adv_mean = 0.0f, adv_den = 1.0f;
+  float ls[4], inv_std[4], dls[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (PI) {
+    double sx = 0.0, sq = 0.0;
+    for (int k = 0; k < TB_PPO_STAT_BLOCKS; ++k) { sx += a.adv_sums[2 * k]; sq += a.adv_sums[2 * k + 1]; }
+    const double mean = sx / (double)B, var = (sq - sx * mean) / (double)(B - 1);
+    adv_mean = (float)mean;
+    adv_den = (float)sqrt(var > 0.0 ? var : 0.0) + 1e-8f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      ls[r] = 4 * g + r < NA ? a.params[L::LOG_STD + 4 * g + r] : 0.0f;
+      inv_std[r] = expf(-ls[r]);
+    }
+  }
+  const float fb = (float)B;
+  float stat = 0.0f;
+
+  for (int i0 = first; i0 < first + TB_PPO_HALF && i0 < B; i0 += 16) {
+    const bool valid = i0 + e < B;
+    long long row = a.idx[valid ? i0 + e : B - 1];
+    row = row < 0 ? 0 : row >= a.n_rows ? a.n_rows - 1 : row;
+    float x0[E0::NC];
+    const float* orow = a.obs + (size_t)row * O;
+#pragma unroll
+    for (int c = 0; c < E0::NC; ++c) x0[c] = 4 * c + g < O ? orow[4 * c + g] : 0.0f;
+    f32x4 obsT[1];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int s = i0 + 4 * c + g;
+      long long rc = a.idx[s < B ? s : B - 1];
+      rc = rc < 0 ? 0 : rc >= a.n_rows ? a.n_rows - 1 : rc;
+      obsT[0][c] = e < O ? a.obs[(size_t)rc * O + e] : 0.0f;
+    }
+    // forward
+    f32x4 ze[E0::NT], he[E0::NT], zf[1], f[1], z0[L0::NT], h0[L0::NT], z1[L1::NT], h1[L1::NT], z2[L2::NT], h2[L2::NT], zh[1];
+    e0.forward_first(x0, ze); ppo_relu(ze, he);
+    e1.forward(he, zf); ppo_relu(zf, f);
+    l0.forward(f, z0); ppo_relu(z0, h0);
+    l1.forward(h0, z1); ppo_relu(z1, h1);
+    l2.forward(h1, z2); ppo_relu(z2, h2);
+    lh.forward(h2, zh);
+    TB_TUNED_STAGE();
+    // the loss's derivative with respect to the head's output: ppo_tower's, term for term
+    f32x4 dout[1] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+    if constexpr (PI) {
+      float zeta[4], lp = 0.0f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool on = 4 * g + r < NA;
+        const float raw = on ? a.act[(size_t)row * NA + 4 * g + r] : 0.0f;
+        zeta[r] = on ? (raw - zh[0][r]) * inv_std[r] : 0.0f;
+        if (on) lp += (-0.5f * zeta[r] * zeta[r] - ls[r]) - TB_LN_SQRT_2PI;
+      }
+      lp += __shfl_xor(lp, 16);
+      lp += __shfl_xor(lp, 32);
+      const float ratio = expf(lp - a.old_logp[row]);
+      const float an = (a.adv[row] - adv_mean) / adv_den;
+      const float s1 = an * ratio, s2 = an * fminf(fmaxf(ratio, 1.0f - a.clip_range), 1.0f + a.clip_range);
+      const bool active = s1 <= s2;
+      if (valid && g == 0) stat += -fminf(s1, s2);
+      const float d_logp = (valid && active) ? (-an * ratio) / fb : 0.0f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        dout[0][r] = (d_logp * zeta[r]) * inv_std[r];
+        dls[r] += d_logp * (zeta[r] * zeta[r] - 1.0f);
+      }
+    } else {
+      const float verr = valid ? a.ret[row] - zh[0][0] : 0.0f;
+      if (g == 0) {
+        stat += verr * verr;
+        dout[0][0] = (-2.0f * a.vf_coef / fb) * verr;
+      }
+    }
+    // backward: the tower, then the extractor
+    f32x4 doutT[1], dh2[L2::NT], dz2[L2::NT], dz2T[L2::NT], h2T[L2::NT], dh1[L1::NT], dz1[L1::NT], dz1T[L1::NT], h1T[L1::NT];
+    f32x4 dh0[L0::NT], dz0[L0::NT], dz0T[L0::NT], h0T[L0::NT], df[1], dzf[1], dzfT[1], fT[1], dhe[E0::NT], dze[E0::NT], dzeT[E0::NT], heT[E0::NT];
+    ppo_transpose_all(dout, doutT, buf, lane);
+    lh.backward_input(dout, dh2);
+    ppo_transpose_all(h2, h2T, buf, lane);
+    lh.accumulate(doutT, h2T);
+    TB_TUNED_STAGE();
+    ppo_drelu(dh2, h2, dz2);
+    l2.backward_input_lds(wb2_lds, lane, dz2, dh1);
+    ppo_transpose_all(dz2, dz2T, buf, lane); ppo_transpose_all(h1, h1T, buf, lane);
+    l2.accumulate(dz2T, h1T);
+    TB_TUNED_STAGE();
+    ppo_drelu(dh1, h1, dz1);
+    l1.backward_input(dz1, dh0);
+    ppo_transpose_all(dz1, dz1T, buf, lane); ppo_transpose_all(h0, h0T, buf, lane);
+    l1.accumulate(dz1T, h0T);
+    TB_TUNED_STAGE();
+    ppo_drelu(dh0, h0, dz0);
+    l0.backward_input(dz0, df);
+    ppo_transpose_all(dz0, dz0T, buf, lane); ppo_transpose_all(f, fT, buf, lane);
+    l0.accumulate(dz0T, fT);
+    TB_TUNED_STAGE();
+    ppo_drelu(df, f, dzf);
+    e1.backward_input_lds(wb_lds, lane, dzf, dhe);
+    ppo_transpose_all(dzf, dzfT, buf, lane); ppo_transpose_all(he, heT, buf, lane);
+    e1.accumulate(dzfT, heT);
+    TB_TUNED_STAGE();
+    ppo_drelu(dhe, he, dze);
+    ppo_transpose_all(dze, dzeT, buf, lane);
+    e0.accumulate(dzeT, obsT);
+  }
+
+  float* gext = part + (PI ? L::EXT : L::EXT2);  // this wave's extractor share
+  float* gbody = part + (PI ? L::PI : L::VF);
+  float* ghead = part + (PI ? L::PI_HEAD : L::VF_HEAD);
+  e0.store(gext + L::EW0, gext + L::EB0, lane);
+  e1.store(gext + L::EW1, gext + L::EB1, lane);
+  l0.store(gbody + L::W0, gbody + L::B0, lane);
+  l1.store(gbody + L::W1, gbody + L::B1, lane);
+  l2.store(gbody + L::W2, gbody + L::B2, lane);
+  lh.store(ghead, ghead + HOUT * N::H2, lane);
+#pragma unroll
+  for (int w = 1; w < 16; w <<= 1) {
+    stat += __shfl_xor(stat, w);
+    if (PI) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dls[r] += __shfl_xor(dls[r], w);
+    }
+  }
+  if (PI && e == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (4 * g + r < NA) part[L::LOG_STD + 4 * g + r] = dls[r];
+    }
+  }
+  if (lane == 0) part[L::P + (PI ? 0 : 1)] = stat;
+}
+
+#undef TB_TUNED_STAGE
+
+__global__ __launch_bounds__(256) void tb_ppo_grad_tuned_kernel(const PpoGradArgs a) {
+  constexpr int NWB = PpoLayer<TunedNet::FH, TunedNet::F, false, false>::NWB + PpoLayer<TunedNet::H1, TunedNet::H2, false, false>::NWB;
+  __shared__ __attribute__((aligned(16))) float s_buf[4 * 512];
+  __shared__ float s_wb[4 * NWB * 64];  // per wave: the transposed fragments of the extractor's output layer and of the tower's third layer
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = wave & 1;
+  const int first = blockIdx.x * TB_PPO_SHARE + half * TB_PPO_HALF;
+  float* part = a.partials + (size_t)(2 * blockIdx.x + half) * TunedLayout::STRIDE;
+  if (wave < 2) ppo_tuned_tower<true>(a, s_buf + wave * 512, s_wb + wave * NWB * 64, lane, first, part);
+  else ppo_tuned_tower<false>(a, s_buf + wave * 512, s_wb + wave * NWB * 64, lane, first, part);
+}
+
+// tb_ppo_reduce_kernel for the tuned net: the same fixed-order float64 sums per slot; an extractor slot is (the sum of the pi
+// waves' shares) + (the sum of the vf waves' shares, from the partials' second extractor region)
+__global__ __launch_bounds__(256) void tb_ppo_reduce_tuned_kernel(const float* partials, int n_part, int batch, const float* params, float ent_coef, float* grad,
+                                                                  float* stats) {
+  using L = TunedLayout;
+  __shared__ double s_sum[4][64], s_sum2[4][64];
+  const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;
+  const bool shared_slot = p >= L::EXT && p < L::EXT + L::EXT_SIZE;
+  double s = 0.0, s2 = 0.0;
+  if (p < L::P + 2) {
+    const int per = (n_part + 3) / 4, lo = q * per, hi = lo + per < n_part ? lo + per : n_part;
+    for (int k = lo; k < hi; ++k) s += (double)partials[(size_t)k * L::STRIDE + p];
+    if (shared_slot) {
+      for (int k = lo; k < hi; ++k) s2 += (double)partials[(size_t)k * L::STRIDE + L::EXT2 + (p - L::EXT)];
+    }
+  }
+  s_sum[q][j] = s; s_sum2[q][j] = s2;
+  __syncthreads();
+  if (q == 0 && p < L::P + 2) {
+    double total = (s_sum[0][j] + s_sum[1][j]) + (s_sum[2][j] + s_sum[3][j]);
+    if (shared_slot) total += (s_sum2[0][j] + s_sum2[1][j]) + (s_sum2[2][j] + s_sum2[3][j]);
+    if (p < L::P) {
+      grad[p] = p < L::A ? (float)total - ent_coef : (float)total;
+    } else {
+      stats[p - L::P] = (float)(total / (double)batch);
+      if (p == L::P) {
+        float ent = 0.0f;
+        for (int k = 0; k < L::A; ++k) ent += (0.5f + TB_LN_SQRT_2PI) + params[L::LOG_STD + k];
+        stats[2] = ent;
+      }
+    }
   }
 }
 

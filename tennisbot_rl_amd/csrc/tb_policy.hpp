@@ -47,6 +47,10 @@ TB_DEV float fast_tanh(float x) {
   return FMA(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
 
+// torch's ReLU: 0 for z <= 0 (z = -0 included), a NaN kept -- fmaxf alone would turn a NaN pre-activation into 0
+TB_DEV float relu(float z) { return z <= 0.0f ? 0.0f : z; }
+enum { ACT_TANH = 0, ACT_RELU = 1, ACT_NONE = 2 };  // LayerRegs::apply's activation
+
 // one layer's operands for this lane: NT bias tiles (4 floats each) and NT * NC weight fragments
 template <int NT, int NC>
 struct LayerRegs {
@@ -65,7 +69,7 @@ struct LayerRegs {
   }
   // y[4 t + r] = act(bias + sum over chunks): the next layer's B operands, in place. Chunk-outer, tile-inner: the NT
   // accumulator chains are independent and written side by side, so the matrix pipe always has a ready MFMA
-  template <bool TANH>
+  template <int ACT>
   TB_DEV void apply(const float (&x)[NC], float (&y)[NT * 4]) const {
     f32x4 c[NT];
 #pragma unroll
@@ -78,7 +82,7 @@ struct LayerRegs {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) y[t * 4 + r] = TANH ? fast_tanh(c[t][r]) : c[t][r];
+      for (int r = 0; r < 4; ++r) y[t * 4 + r] = ACT == ACT_TANH ? fast_tanh(c[t][r]) : ACT == ACT_RELU ? relu(c[t][r]) : c[t][r];
     }
   }
 };
@@ -102,10 +106,10 @@ template <> struct TowerRegs<TB_ENV_SWING> {  // 6 -> 32 -> 64 -> 32 -> head
   }
   TB_DEV void apply(const float (&x0)[NC0], float (&out)[4]) const {
     float h0[8], h1[16], h2[8];
-    l0.template apply<true>(x0, h0);
-    l1.template apply<true>(h0, h1);
-    l2.template apply<true>(h1, h2);
-    lh.template apply<false>(h2, out);
+    l0.template apply<ACT_TANH>(x0, h0);
+    l1.template apply<ACT_TANH>(h0, h1);
+    l2.template apply<ACT_TANH>(h1, h2);
+    lh.template apply<ACT_NONE>(h2, out);
   }
 };
 template <> struct TowerRegs<TB_ENV_TENNIS> {  // 12 -> 64 -> 64 -> head
@@ -121,9 +125,87 @@ template <> struct TowerRegs<TB_ENV_TENNIS> {  // 12 -> 64 -> 64 -> head
   }
   TB_DEV void apply(const float (&x0)[NC0], float (&out)[4]) const {
     float h0[16], h1[16];
-    l0.template apply<true>(x0, h0);
-    l1.template apply<true>(h0, h1);
-    lh.template apply<false>(h1, out);
+    l0.template apply<ACT_TANH>(x0, h0);
+    l1.template apply<ACT_TANH>(h0, h1);
+    lh.template apply<ACT_NONE>(h1, out);
+  }
+};
+
+// The tuned network (TB_NET_TUNED, Tennisbot only: the reference's `train.py -s tuned_ppo`, train.py:54-67,112-127): a ReLU trunk
+// 12 -> 64 -> F that SB3 shares between actor and critic, then two ReLU towers F -> 32 -> 64 -> 32 with their heads; F is the
+// action dimension (features_extractor_kwargs output_shape = action_space.shape[0], train.py:116-118): 2 on Tennisbot-v0. The
+// F-wide feature travels as ONE zero-padded 16-row tile: the trunk's second layer is a 16-output layer whose rows F..15 have
+// zero weights and zero bias (exactly 0 after the ReLU), and each tower's first layer is an ordinary 16-in hidden layer (four
+// chunks, the weights of k >= F zero). So the feature is a C/D tile like any other and nothing leaves the registers.
+// Blob: trunk layers, pi tower, vf tower (each with its head), log_std -- layers in the format above.
+struct TunedNet { static constexpr int O = Dims<TB_ENV_TENNIS>::O, FH = 64, F = Dims<TB_ENV_TENNIS>::A, FP = 16, H0 = 32, H1 = 64, H2 = 32; };
+constexpr int tuned_trunk_floats() { return layer_floats(TunedNet::O, TunedNet::FH) + layer_floats(TunedNet::FH, TunedNet::F); }
+constexpr int tuned_tower_floats() {
+  using N = TunedNet;
+  return layer_floats(N::FP, N::H0) + layer_floats(N::H0, N::H1) + layer_floats(N::H1, N::H2) + layer_floats(N::H2, 16);
+}
+struct TunedTrunk {  // 12 -> 64 -> F (in a 16-row tile), ReLU
+  using N = TunedNet;
+  LayerRegs<4, 3> e0;
+  LayerRegs<1, 16> e1;
+  TB_DEV void load(const float* g, int lane) {
+    e0.load(g, lane); g += layer_floats(N::O, N::FH);
+    e1.load(g, lane);
+  }
+  TB_DEV void apply(const float (&x0)[3], float (&f)[4]) const {
+    float h[16];
+    e0.template apply<ACT_RELU>(x0, h);
+    e1.template apply<ACT_RELU>(h, f);
+  }
+};
+struct TunedTower {  // feature tile -> 32 -> 64 -> 32 -> head, ReLU
+  using N = TunedNet;
+  LayerRegs<2, 4> l0;
+  LayerRegs<4, 8> l1;
+  LayerRegs<2, 16> l2;
+  LayerRegs<1, 8> lh;
+  TB_DEV void load(const float* g, int lane) {
+    l0.load(g, lane); g += layer_floats(N::FP, N::H0);
+    l1.load(g, lane); g += layer_floats(N::H0, N::H1);
+    l2.load(g, lane); g += layer_floats(N::H1, N::H2);
+    lh.load(g, lane);
+  }
+  TB_DEV void apply(const float (&f)[4], float (&out)[4]) const {
+    float h0[8], h1[16], h2[8];
+    l0.template apply<ACT_RELU>(f, h0);
+    l1.template apply<ACT_RELU>(h0, h1);
+    l2.template apply<ACT_RELU>(h1, h2);
+    lh.template apply<ACT_NONE>(h2, out);
+  }
+};
+
+// where the pieces of a network's blob lie, and what ONE tower wave of the rollout kernels keeps resident (PolicyRegs: the
+// tower; for the tuned network the trunk in front of it -- both tower waves of a slice evaluate the trunk, the same
+// instructions on the same operands, so the two see the same feature bits)
+template <int KIND, int NET> struct PolicyBlob {
+  static_assert(NET == TB_NET_DEFAULT, "the tuned network is Tennisbot's");
+  static constexpr int PI = 0, TOWER = tower_floats<KIND>(), LOG_STD = 2 * TOWER, TOTAL = policy_floats<KIND>();
+};
+template <> struct PolicyBlob<TB_ENV_TENNIS, TB_NET_TUNED> {
+  static constexpr int PI = tuned_trunk_floats(), TOWER = tuned_tower_floats(), LOG_STD = PI + 2 * TOWER, TOTAL = LOG_STD + 4;
+};
+template <int KIND, int NET> struct PolicyRegs {
+  TowerRegs<KIND> t;
+  TB_DEV void load(const float* blob, int tower, int lane) { t.load(blob + tower * tower_floats<KIND>(), lane); }
+  TB_DEV void apply(const float (&x0)[TowerRegs<KIND>::NC0], float (&out)[4]) const { t.apply(x0, out); }
+};
+template <> struct PolicyRegs<TB_ENV_TENNIS, TB_NET_TUNED> {
+  using B = PolicyBlob<TB_ENV_TENNIS, TB_NET_TUNED>;
+  TunedTrunk f;
+  TunedTower t;
+  TB_DEV void load(const float* blob, int tower, int lane) {
+    f.load(blob, lane);
+    t.load(blob + B::PI + tower * B::TOWER, lane);
+  }
+  TB_DEV void apply(const float (&x0)[3], float (&out)[4]) const {
+    float feat[4];
+    f.apply(x0, feat);
+    t.apply(feat, out);
   }
 };
 
@@ -161,7 +243,7 @@ TB_DEV void policy_noise(unsigned long long seed, unsigned long long env_id, uin
 // the tower part of the one-step kernel (tb_policy_step: 256-thread workgroups, 64 envs): wave w runs BOTH towers of the
 // 16-env slice w -- two independent chains the scheduler interleaves -- leaves the action means in s_mean[64][8] and
 // writes the values
-template <int KIND>
+template <int KIND, int NET = TB_NET_DEFAULT>
 TB_DEV void policy_towers(const KArgs& A, float* s_mean) {
   constexpr int NO = Dims<KIND>::O;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 4;
@@ -169,12 +251,29 @@ TB_DEV void policy_towers(const KArgs& A, float* s_mean) {
   const int env_c = env < A.n ? env : A.n - 1;
   float x0[TowerRegs<KIND>::NC0], mean[4], val[4];
   policy_inputs<KIND>(A.pol_obs + (size_t)env_c * NO, lane, x0);
-  TowerRegs<KIND> pi, vf;
-  pi.load(A.pol_weights, lane);
-  vf.load(A.pol_weights + tower_floats<KIND>(), lane);
-  __builtin_amdgcn_sched_barrier(0);  // keeps the scheduler from sinking each load down to its MFMA
-  pi.apply(x0, mean);
-  vf.apply(x0, val);
+  if constexpr (NET == TB_NET_TUNED) {  // the trunk once, its feature tile into both towers
+    using B = PolicyBlob<KIND, NET>;
+    TunedTrunk f;
+    TunedTower pi, vf;
+    f.load(A.pol_weights, lane);
+    pi.load(A.pol_weights + B::PI, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    float feat[4];
+    f.apply(x0, feat);
+    // (the vf tower's operands are requested once the trunk's registers are free: all three pieces up front is 2 spilled VGPRs
+    //  with the extended contact set compiled in; the loads land while the pi tower computes)
+    vf.load(A.pol_weights + B::PI + B::TOWER, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    pi.apply(feat, mean);
+    vf.apply(feat, val);
+  } else {
+    TowerRegs<KIND> pi, vf;
+    pi.load(A.pol_weights, lane);
+    vf.load(A.pol_weights + tower_floats<KIND>(), lane);
+    __builtin_amdgcn_sched_barrier(0);  // keeps the scheduler from sinking each load down to its MFMA
+    pi.apply(x0, mean);
+    vf.apply(x0, val);
+  }
   if (grp < 2) *reinterpret_cast<float4*>(s_mean + slot * 8 + grp * 4) = make_float4(mean[0], mean[1], mean[2], mean[3]);
   if (lane < 16 && env < A.n) A.pol_value[env] = val[0];
 }
@@ -196,13 +295,13 @@ TB_DEV void policy_draw(const KArgs& A, int i, const EnvRegs& e, float* eps) {
 // np.clip / torch.clamp to [-1, 1], NaN kept: fminf / fmaxf alone (v_med3_f32, minnum / maxnum semantics) would turn a NaN
 // action into -1 and step a diverged policy's env as if it were finite, past the nonfinite_states counter
 TB_DEV float clip_action(float raw) { return raw != raw ? raw : fminf(fmaxf(raw, -1.0f), 1.0f); }
-template <int KIND>
+template <int KIND, int NET = TB_NET_DEFAULT>
 TB_DEV void policy_sample(const KArgs& A, const float* s_mean, int i, const EnvRegs& e, float* a, size_t t = 0, const float* drawn = nullptr,
                           const float* stdv = nullptr /* exp(log_std), when the caller keeps it across steps */) {
   constexpr int NA = Dims<KIND>::A;
   float* out_act = A.pol_actions + t * A.st_act;
   float* out_raw = A.pol_raw + t * A.st_raw;
-  const float* log_std = A.pol_weights + 2 * tower_floats<KIND>();
+  const float* log_std = A.pol_weights + PolicyBlob<KIND, NET>::LOG_STD;
   const float* mean = s_mean + (threadIdx.x & 63) * 8;
   float eps[NA], logp = 0.0f;
   if (drawn) {

@@ -360,18 +360,23 @@ using StepKernel = void (*)(const uint32_t*, const uint8_t*, const float*, const
 using ArgsKernel = void (*)(KArgs);
 using ArgsKernel2 = void (*)(KArgs, EsArgs);
 
-// tb_step_kernel<KIND, LEAN, MULTI, RG, POLICY>; the fused policy step runs one step per launch
+// tb_step_kernel<KIND, LEAN, MULTI, RG, POLICY>; the fused policy step runs one step per launch (Tennisbot: with either network)
 template <int KIND, bool LEAN>
-StepKernel step_kernel_of(bool multi, bool rg, bool pol) {
+StepKernel step_kernel_of(bool multi, bool rg, bool pol, int net) {
+  if constexpr (KIND == TB_ENV_TENNIS) {
+    if (pol && net == TB_NET_TUNED)
+      return multi ? nullptr : rg ? tb_step_kernel<KIND, LEAN, false, true, true, false, TB_NET_TUNED> : tb_step_kernel<KIND, LEAN, false, false, true, false, TB_NET_TUNED>;
+  }
+  if (net != TB_NET_DEFAULT) return nullptr;
   if (pol) return multi ? nullptr : rg ? tb_step_kernel<KIND, LEAN, false, true, true> : tb_step_kernel<KIND, LEAN, false, false, true>;
   if (multi) return rg ? tb_step_kernel<KIND, LEAN, true, true> : tb_step_kernel<KIND, LEAN, true, false>;
   return rg ? tb_step_kernel<KIND, LEAN, false, true> : tb_step_kernel<KIND, LEAN, false, false>;
 }
 // ... and <.., TWO_WAVE> where the variant has that form (step_has_two_waves); LEAN is SwingRacket's only
-StepKernel step_kernel(int kind, bool lean, bool multi, bool rg, bool pol, bool two_wave) {
+StepKernel step_kernel(int kind, bool lean, bool multi, bool rg, bool pol, bool two_wave, int net) {
   if (two_wave) return step_has_two_waves(kind, lean, multi, rg, pol) ? tb_step_kernel<TB_ENV_SWING, true, false, false, false, true> : nullptr;
-  if (kind == TB_ENV_TENNIS) return lean ? nullptr : step_kernel_of<TB_ENV_TENNIS, false>(multi, rg, pol);
-  return lean ? step_kernel_of<TB_ENV_SWING, true>(multi, rg, pol) : step_kernel_of<TB_ENV_SWING, false>(multi, rg, pol);
+  if (kind == TB_ENV_TENNIS) return lean ? nullptr : step_kernel_of<TB_ENV_TENNIS, false>(multi, rg, pol, net);
+  return lean ? step_kernel_of<TB_ENV_SWING, true>(multi, rg, pol, net) : step_kernel_of<TB_ENV_SWING, false>(multi, rg, pol, net);
 }
 
 // tb_ff_kernel<RG, BIG, ESC, POOL>: ESC only as the first of a BIG fast-forward's phases; a BIG POOL only without RG
@@ -382,11 +387,11 @@ ArgsKernel ff_kernel(bool rg, bool big, bool esc, bool pool) {
   return big ? tb_ff_kernel<false, true> : tb_ff_kernel<false, false>;
 }
 
-// tb_policy_rollout_kernel<KIND, S, RG>: every combination (S = 1 or 3 env slices per workgroup)
-template <int KIND>
+// tb_policy_rollout_kernel<KIND, S, RG, NET>: every combination (S = 1 or 3 env slices per workgroup)
+template <int KIND, int NET = TB_NET_DEFAULT>
 ArgsKernel policy_rollout_kernel(int slices, bool rg) {
-  if (slices == 1) return rg ? tb_policy_rollout_kernel<KIND, 1, true> : tb_policy_rollout_kernel<KIND, 1, false>;
-  return slices == 3 ? (rg ? tb_policy_rollout_kernel<KIND, 3, true> : tb_policy_rollout_kernel<KIND, 3, false>) : nullptr;
+  if (slices == 1) return rg ? tb_policy_rollout_kernel<KIND, 1, true, NET> : tb_policy_rollout_kernel<KIND, 1, false, NET>;
+  return slices == 3 ? (rg ? tb_policy_rollout_kernel<KIND, 3, true, NET> : tb_policy_rollout_kernel<KIND, 3, false, NET>) : nullptr;
 }
 
 // the fast-forward family's one launch: one-wave workgroups on stream q
@@ -591,6 +596,7 @@ int count_first_substeps(TbHandle* h, int T, hipStream_t s) {
 struct PolicyIO {  // non-null weights = fused policy step
   const float* weights; const float* obs_in; float* actions; float* raw; float* logp; float* value;
   unsigned long long seed; int deterministic;
+  int net;  // TB_NET_*: checked against the env kind by policy_net_ok
   void apply(KArgs& a) const {
     a.pol_weights = weights; a.pol_obs = obs_in; a.pol_actions = actions; a.pol_raw = raw; a.pol_logp = logp;
     a.pol_value = value; a.pol_seed = seed; a.pol_deterministic = deterministic;
@@ -624,7 +630,7 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
   const bool rg = extended_contacts(h->kp);  // selects the instantiation that contains the rolling-friction rows
   const bool multi = T > 1, policy = pol != nullptr;
   const bool two_wave = h->two_wave && step_has_two_waves(h->kind, piped, multi, rg, policy);
-  const StepKernel kern = step_kernel(h->kind, piped, multi, rg, policy, two_wave);
+  const StepKernel kern = step_kernel(h->kind, piped, multi, rg, policy, two_wave, pol ? pol->net : TB_NET_DEFAULT);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_step_kernel instantiation for this variant");
   if (two_wave) { grid = dim3((unsigned)((h->n + 63) / 64)); block = dim3(128); }  // two waves per 64 envs
   const size_t lds = dyn_lds(step_lds_words(h->kind, piped, multi, rg, policy), policy ? 64u : block.x);
@@ -652,7 +658,9 @@ int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, f
   const int E = narrow ? TB_POLICY_SLICE : 3 * TB_POLICY_SLICE;
   dim3 grid((unsigned)((h->n + E - 1) / E)), block(narrow ? 192 : 448);
   const bool rg = extended_contacts(h->kp);
-  const ArgsKernel kern = swing ? policy_rollout_kernel<TB_ENV_SWING>(narrow ? 1 : 3, rg) : policy_rollout_kernel<TB_ENV_TENNIS>(narrow ? 1 : 3, rg);
+  const ArgsKernel kern = swing                     ? policy_rollout_kernel<TB_ENV_SWING>(narrow ? 1 : 3, rg)
+                          : pol.net == TB_NET_TUNED ? policy_rollout_kernel<TB_ENV_TENNIS, TB_NET_TUNED>(narrow ? 1 : 3, rg)
+                                                    : policy_rollout_kernel<TB_ENV_TENNIS>(narrow ? 1 : 3, rg);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_rollout_kernel instantiation for this variant");
   (void)hipGetLastError();
   if (int rc = launch(kern, grid, block, dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a)) return rc;  // (the env wave's columns)
@@ -1023,21 +1031,50 @@ int tb_policy_floats(int env_kind) {
   return env_kind == TB_ENV_SWING ? policy_floats<TB_ENV_SWING>() : env_kind == TB_ENV_TENNIS ? policy_floats<TB_ENV_TENNIS>() : TB_E_INVAL;
 }
 
-int tb_policy_step(TbHandle* h, const float* weights_dev, const float* obs_in_dev, float* actions_dev, float* raw_actions_dev, float* logp_dev,
-                   float* value_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, uint64_t noise_seed, int deterministic, void* stream) {
+namespace {
+// the (kind, net) pairs the policy kernels are built for: every kind's own network, and Tennisbot's tuned one
+int policy_net_ok(int env_kind, int net, const char* who) {
+  if (net == TB_NET_DEFAULT || (net == TB_NET_TUNED && env_kind == TB_ENV_TENNIS)) return TB_OK;
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: net %d is not built for env kind %d (TB_NET_TUNED is Tennisbot-v0's; every kind has TB_NET_DEFAULT)", who, net, env_kind);
+  return fail(TB_E_PARAMS, msg);
+}
+}  // namespace
+
+int tb_policy_blob_floats(int env_kind, int net) {
+  if (env_kind != TB_ENV_SWING && env_kind != TB_ENV_TENNIS) return TB_E_INVAL;
+  if (int rc = policy_net_ok(env_kind, net, "tb_policy_blob_floats")) return rc;
+  return net == TB_NET_TUNED ? PolicyBlob<TB_ENV_TENNIS, TB_NET_TUNED>::TOTAL : tb_policy_floats(env_kind);
+}
+
+int tb_policy_step_net(TbHandle* h, int net, const float* weights_dev, const float* obs_in_dev, float* actions_dev, float* raw_actions_dev, float* logp_dev,
+                       float* value_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, uint64_t noise_seed, int deterministic, void* stream) {
   if (!h || !weights_dev || !obs_in_dev || !actions_dev || !raw_actions_dev || !logp_dev || !value_dev || !obs_dev || !reward_dev || !done_dev)
     return fail(TB_E_INVAL, "tb_policy_step: null argument");
+  if (int rc = policy_net_ok(h->kind, net, "tb_policy_step")) return rc;
   DeviceGuard g(h->device);
-  PolicyIO pol = {weights_dev, obs_in_dev, actions_dev, raw_actions_dev, logp_dev, value_dev, noise_seed, deterministic};
+  PolicyIO pol = {weights_dev, obs_in_dev, actions_dev, raw_actions_dev, logp_dev, value_dev, noise_seed, deterministic, net};
   return launch_step(h, 1, nullptr, obs_dev, reward_dev, done_dev, nullptr, nullptr, (hipStream_t)stream, &pol);
+}
+int tb_policy_step(TbHandle* h, const float* weights_dev, const float* obs_in_dev, float* actions_dev, float* raw_actions_dev, float* logp_dev,
+                   float* value_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, uint64_t noise_seed, int deterministic, void* stream) {
+  return tb_policy_step_net(h, TB_NET_DEFAULT, weights_dev, obs_in_dev, actions_dev, raw_actions_dev, logp_dev, value_dev, obs_dev, reward_dev, done_dev, noise_seed,
+                            deterministic, stream);
 }
 
 int tb_policy_rollout(TbHandle* h, int n_steps, const float* weights_dev, const float* obs_in_dev, float* actions_dev, float* raw_actions_dev,
                       float* logp_dev, float* value_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, const size_t* step_strides_bytes,
                       uint64_t noise_seed, int deterministic, void* stream) {
+  return tb_policy_rollout_net(h, TB_NET_DEFAULT, n_steps, weights_dev, obs_in_dev, actions_dev, raw_actions_dev, logp_dev, value_dev, obs_dev, reward_dev, done_dev,
+                               step_strides_bytes, noise_seed, deterministic, stream);
+}
+int tb_policy_rollout_net(TbHandle* h, int net, int n_steps, const float* weights_dev, const float* obs_in_dev, float* actions_dev, float* raw_actions_dev,
+                          float* logp_dev, float* value_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, const size_t* step_strides_bytes,
+                          uint64_t noise_seed, int deterministic, void* stream) {
   if (!h || !weights_dev || !obs_in_dev || !actions_dev || !raw_actions_dev || !logp_dev || !value_dev || !obs_dev || !reward_dev || !done_dev)
     return fail(TB_E_INVAL, "tb_policy_rollout: null argument");
   if (n_steps < 1) return fail(TB_E_INVAL, "tb_policy_rollout: n_steps must be >= 1");
+  if (int rc = policy_net_ok(h->kind, net, "tb_policy_rollout")) return rc;
   if (!(h->kp.flags & TB_F_AUTO_RESET)) return fail(TB_E_UNSUPPORTED, "tb_policy_rollout needs TB_F_AUTO_RESET (episodes must restart inside the launch)");
   const bool swing = h->kind == TB_ENV_SWING;
   if (swing && !(h->pipeline && h->phase.valid))
@@ -1061,7 +1098,7 @@ int tb_policy_rollout(TbHandle* h, int n_steps, const float* weights_dev, const 
   for (int t = 0; t < n_steps;) {
     const int chunk = swing ? h->phase.chunk(n_steps - t) : n_steps - t;
     PolicyIO pol = {weights_dev, obs_in, actions_dev + (size_t)t * st[0], raw_actions_dev + (size_t)t * st[1], logp_dev + (size_t)t * st[2],
-                    value_dev + (size_t)t * st[3], noise_seed, deterministic};
+                    value_dev + (size_t)t * st[3], noise_seed, deterministic, net};
     if (int rc = launch_policy_rollout(h, chunk, pol, obs_dev + (size_t)t * st[4], reward_dev + (size_t)t * st[5], done_dev + (size_t)t * st[6], st, s)) return rc;
     t += chunk;
     obs_in = obs_dev + (size_t)(t - 1) * st[4];  // the next launch acts on what this one observed last
@@ -1119,15 +1156,24 @@ int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t 
 int tb_ppo_param_floats(int env_kind) {
   return env_kind == TB_ENV_SWING ? PpoLayout<TB_ENV_SWING>::P : env_kind == TB_ENV_TENNIS ? PpoLayout<TB_ENV_TENNIS>::P : TB_E_INVAL;
 }
+int tb_ppo_param_floats_net(int env_kind, int net) {
+  if (!kind_ok(env_kind)) return TB_E_INVAL;
+  if (int rc = policy_net_ok(env_kind, net, "tb_ppo_param_floats_net")) return rc;
+  return net == TB_NET_TUNED ? TunedLayout::P : tb_ppo_param_floats(env_kind);
+}
 int tb_ppo_rows_per_workgroup(void) { return TB_PPO_SHARE; }
 
 static size_t ppo_partials(int batch) { return 2 * (((size_t)batch + TB_PPO_SHARE - 1) / TB_PPO_SHARE); }
 static constexpr size_t kPpoStatBytes = sizeof(double) * 2 * TB_PPO_STAT_BLOCKS;
+// floats of one partial vector: the gradient and the two statistics; the tuned net's also hold the vf waves' extractor share
+static size_t ppo_partial_stride(int env_kind, int net) { return net == TB_NET_TUNED ? (size_t)TunedLayout::STRIDE : (size_t)tb_ppo_param_floats(env_kind) + 2; }
 
-long long tb_ppo_workspace_bytes(int env_kind, int batch) {
+long long tb_ppo_workspace_bytes_net(int env_kind, int net, int batch) {
   if (!kind_ok(env_kind) || batch < 2) return fail(TB_E_INVAL, "tb_ppo_workspace_bytes: unknown env kind, or batch < 2");
-  return (long long)(kPpoStatBytes + sizeof(float) * ppo_partials(batch) * ((size_t)tb_ppo_param_floats(env_kind) + 2));
+  if (int rc = policy_net_ok(env_kind, net, "tb_ppo_workspace_bytes_net")) return rc;
+  return (long long)(kPpoStatBytes + sizeof(float) * ppo_partials(batch) * ppo_partial_stride(env_kind, net));
 }
+long long tb_ppo_workspace_bytes(int env_kind, int batch) { return tb_ppo_workspace_bytes_net(env_kind, TB_NET_DEFAULT, batch); }
 
 static int ppo_device(int device, const char* what) {
   int ndev = 0;
@@ -1165,16 +1211,23 @@ int tb_ppo_gae(int env_kind, int device, void* stream, int n_steps, int n_envs, 
 int tb_ppo_grad(int env_kind, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev, const float* adv_dev,
                 const float* returns_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* params_dev, int n_params, float clip_range,
                 float vf_coef, void* workspace_dev, size_t workspace_bytes) {
+  return tb_ppo_grad_net(env_kind, TB_NET_DEFAULT, device, stream, obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, n_rows, idx_dev, batch, params_dev,
+                         n_params, clip_range, vf_coef, workspace_dev, workspace_bytes);
+}
+int tb_ppo_grad_net(int env_kind, int net, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev,
+                    const float* adv_dev, const float* returns_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* params_dev, int n_params,
+                    float clip_range, float vf_coef, void* workspace_dev, size_t workspace_bytes) {
   if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_ppo_grad: unknown env kind");
+  if (int rc = policy_net_ok(env_kind, net, "tb_ppo_grad")) return rc;
   if (!obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !returns_dev || !idx_dev || !params_dev || !workspace_dev)
     return fail(TB_E_INVAL, "tb_ppo_grad: null argument");
-  if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_ppo_grad: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_ppo_grad: n_params is not tb_ppo_param_floats(env_kind)");
   if (n_rows < 1 || batch < 2) return fail(TB_E_INVAL, "tb_ppo_grad: n_rows must be >= 1 and batch >= 2 (the unbiased std of one row is undefined)");
   if (misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) || misaligned(returns_dev, 4) ||
       misaligned(params_dev, 4))
     return fail(TB_E_INVAL, "tb_ppo_grad: a float array is not 4-byte aligned");
   if (misaligned(idx_dev, 8) || misaligned(workspace_dev, 8)) return fail(TB_E_INVAL, "tb_ppo_grad: idx and the workspace must be 8-byte aligned");
-  if ((long long)workspace_bytes < tb_ppo_workspace_bytes(env_kind, batch)) return fail(TB_E_INVAL, "tb_ppo_grad: the workspace is smaller than tb_ppo_workspace_bytes");
+  if ((long long)workspace_bytes < tb_ppo_workspace_bytes_net(env_kind, net, batch)) return fail(TB_E_INVAL, "tb_ppo_grad: the workspace is smaller than tb_ppo_workspace_bytes");
   if (int rc = ppo_device(device, "tb_ppo_grad: device index out of range")) return rc;
   DeviceGuard g(device);
   if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
@@ -1184,23 +1237,33 @@ int tb_ppo_grad(int env_kind, int device, void* stream, const float* obs_dev, co
                    (float*)((char*)workspace_dev + kPpoStatBytes), n_rows, batch, clip_range, vf_coef};
   if (int rc = launch(tb_ppo_adv_stats_kernel, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
   const dim3 grid((unsigned)(ppo_partials(batch) / 2));
+  if (net == TB_NET_TUNED) return launch(tb_ppo_grad_tuned_kernel, grid, dim3(256), 0, s, a);
   return env_kind == TB_ENV_SWING ? launch(tb_ppo_grad_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a) : launch(tb_ppo_grad_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a);
 }
 
 int tb_ppo_apply(int env_kind, int device, void* stream, int phases, const void* workspace_dev, size_t workspace_bytes, int batch, float* params_dev,
                  float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int n_params, float* stats_dev, float ent_coef, float max_grad_norm, int world,
                  float lr, float beta1, float beta2, float eps, long long step) {
+  return tb_ppo_apply_net(env_kind, TB_NET_DEFAULT, device, stream, phases, workspace_dev, workspace_bytes, batch, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev,
+                          n_params, stats_dev, ent_coef, max_grad_norm, world, lr, beta1, beta2, eps, step);
+}
+int tb_ppo_apply_net(int env_kind, int net, int device, void* stream, int phases, const void* workspace_dev, size_t workspace_bytes, int batch, float* params_dev,
+                     float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int n_params, float* stats_dev, float ent_coef, float max_grad_norm, int world,
+                     float lr, float beta1, float beta2, float eps, long long step) {
   if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_ppo_apply: unknown env kind");
+  if (int rc = policy_net_ok(env_kind, net, "tb_ppo_apply")) return rc;
+  if (net == TB_NET_TUNED && (phases & TB_PPO_VALUE_ONLY))
+    return fail(TB_E_UNSUPPORTED, "tb_ppo_apply: TB_PPO_VALUE_ONLY is not offered for TB_NET_TUNED (the extractor is shared: there is no critic-only slot range)");
   if (!(phases & (TB_PPO_REDUCE | TB_PPO_STEP)) || (phases & ~(TB_PPO_REDUCE | TB_PPO_STEP | TB_PPO_VALUE_ONLY)))
     return fail(TB_E_INVAL, "tb_ppo_apply: phases must be TB_PPO_REDUCE, TB_PPO_STEP or both, with or without TB_PPO_VALUE_ONLY");
   const int value_only = (phases & TB_PPO_VALUE_ONLY) != 0;
   if (!params_dev || !grad_dev) return fail(TB_E_INVAL, "tb_ppo_apply: null argument");
-  if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_ppo_apply: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_ppo_apply: n_params is not tb_ppo_param_floats(env_kind)");
   if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(stats_dev, 4))
     return fail(TB_E_INVAL, "tb_ppo_apply: a float array is not 4-byte aligned");
   if (phases & TB_PPO_REDUCE) {
     if (!workspace_dev || !stats_dev) return fail(TB_E_INVAL, "tb_ppo_apply: TB_PPO_REDUCE needs the workspace and stats_dev");
-    if (batch < 2 || misaligned(workspace_dev, 8) || (long long)workspace_bytes < tb_ppo_workspace_bytes(env_kind, batch))
+    if (batch < 2 || misaligned(workspace_dev, 8) || (long long)workspace_bytes < tb_ppo_workspace_bytes_net(env_kind, net, batch))
       return fail(TB_E_INVAL, "tb_ppo_apply: batch < 2, or the workspace is misaligned or smaller than tb_ppo_workspace_bytes");
   }
   if (phases & TB_PPO_STEP) {
@@ -1215,7 +1278,9 @@ int tb_ppo_apply(int env_kind, int device, void* stream, int phases, const void*
     const float* partials = (const float*)((const char*)workspace_dev + kPpoStatBytes);
     const int n_part = (int)ppo_partials(batch);
     const dim3 grid((unsigned)((n_params + 2 + 63) / 64));
-    if (int rc = env_kind == TB_ENV_SWING ? launch(tb_ppo_reduce_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only)
+    if (net == TB_NET_TUNED) {
+      if (int rc = launch(tb_ppo_reduce_tuned_kernel, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev)) return rc;
+    } else if (int rc = env_kind == TB_ENV_SWING ? launch(tb_ppo_reduce_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only)
                                           : launch(tb_ppo_reduce_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only))
       return rc;
   }

@@ -1,6 +1,7 @@
 """The PPO learner as HIP kernels (csrc/tb_learner.hpp; C ABI tb_ppo_gae / tb_ppo_grad / tb_ppo_apply in include/tb_stepper.h).
 
-`PPOTrainer(..., learner="fused")` hands `advantages` and `update` to a `FusedLearner`. The kernels work on ONE flat fp32 parameter
+`PPOTrainer(..., learner="fused")` hands `advantages` and `update` to a `FusedLearner` -- for the env's default network or, with
+policy="tuned", Tennisbot's tuned one (the `_net` entry points; the module tells which). The kernels work on ONE flat fp32 parameter
 vector, so `flatten_parameters` first re-points every parameter of the torch module at a view of one buffer, in
 `named_parameters()` order: the module, its state_dict, `pack_policy` and a torch optimiser see the same tensors as before.
 The gradient and both Adam moments live in flat buffers of the same order; `p.grad` and `opt.state[p]` hold views of them,
@@ -57,12 +58,16 @@ class FusedLearner:
 
     def __init__(self, kind, policy, opt, hp, device):
         import torch
+        from .ppo import policy_net_of
         self.torch, self.kind, self.policy, self.opt, self.hp = torch, int(kind), policy, opt, hp
+        self.net = policy_net_of(policy)  # NET_TUNED for build_tuned_actor_critic's module: its own gradient kernel, shared-trunk partials
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise StepperError("FusedLearner needs a GPU (there is no CPU fallback)")
         self.lib = load_library()
-        self.n_params = self.lib.tb_ppo_param_floats(self.kind)
+        self.n_params = self.lib.tb_ppo_param_floats_net(self.kind, self.net)
+        if self.n_params < 0:
+            _check(self.lib, self.n_params, "tb_ppo_param_floats_net")
         self.params = [p for _, p in policy.named_parameters()]
         if self.n_params != sum(p.numel() for p in self.params):
             raise StepperError("the policy has %d parameters, the learner kernels of this env kind take %d (another net_arch?)"
@@ -143,9 +148,9 @@ class FusedLearner:
         return step
 
     def workspace(self, batch):
-        need = self.lib.tb_ppo_workspace_bytes(self.kind, int(batch))
+        need = self.lib.tb_ppo_workspace_bytes_net(self.kind, self.net, int(batch))
         if need < 0:
-            _check(self.lib, int(need), "tb_ppo_workspace_bytes")
+            _check(self.lib, int(need), "tb_ppo_workspace_bytes_net")
         if self._ws is None or self._ws.numel() * 8 < need:
             self._ws = self.torch.zeros((need + 7) // 8, dtype=self.torch.float64, device=self.device)
         return self._ws
@@ -156,17 +161,17 @@ class FusedLearner:
         obs, act, old_logp, adv, returns = arrays
         ws = self.workspace(batch)
         wb = ws.numel() * 8
-        _check(L, L.tb_ppo_grad(self.kind, dev, s, obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), returns.data_ptr(), n_rows,
+        _check(L, L.tb_ppo_grad_net(self.kind, self.net, dev, s, obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), returns.data_ptr(), n_rows,
                                 idx_ptr, batch, self.flat.data_ptr(), self.n_params, float(hp["clip_range"]), float(hp["vf_coef"]), ws.data_ptr(), wb), "tb_ppo_grad")
         g = self.opt.param_groups[0]
         tail = (self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.n_params, self.stats.data_ptr(),
                 float(hp["ent_coef"]), float(hp["max_grad_norm"]), int(world), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), int(step))
         if world > 1:  # the average first, the clip second: ONE collective on the flat gradient
-            _check(L, L.tb_ppo_apply(self.kind, dev, s, TB_PPO_REDUCE, ws.data_ptr(), wb, batch, *tail), "tb_ppo_apply")
+            _check(L, L.tb_ppo_apply_net(self.kind, self.net, dev, s, TB_PPO_REDUCE, ws.data_ptr(), wb, batch, *tail), "tb_ppo_apply")
             self.torch.distributed.all_reduce(self.grad)
-            _check(L, L.tb_ppo_apply(self.kind, dev, s, TB_PPO_STEP, ws.data_ptr(), wb, batch, *tail), "tb_ppo_apply")
+            _check(L, L.tb_ppo_apply_net(self.kind, self.net, dev, s, TB_PPO_STEP, ws.data_ptr(), wb, batch, *tail), "tb_ppo_apply")
         else:
-            _check(L, L.tb_ppo_apply(self.kind, dev, s, TB_PPO_REDUCE | TB_PPO_STEP, ws.data_ptr(), wb, batch, *tail), "tb_ppo_apply")
+            _check(L, L.tb_ppo_apply_net(self.kind, self.net, dev, s, TB_PPO_REDUCE | TB_PPO_STEP, ws.data_ptr(), wb, batch, *tail), "tb_ppo_apply")
 
     def update(self, obs, act, old_logp, adv, returns, n_epochs, batch_size, world=1):
         """n_epochs over the flat rollout [n, ...] in minibatches of batch_size rows (a ragged tail included). Draws exactly one

@@ -17,6 +17,8 @@ TB_HULL_REC = 8
 
 ENV_SWING = 0   # SwingRacket-v0, tennisbot/__init__.py:8-11
 ENV_TENNIS = 1  # Tennisbot-v0,   tennisbot/__init__.py:3-6
+NET_DEFAULT = 0  # include/tb_stepper.h TB_NET_*: the env kind's own policy network ...
+NET_TUNED = 1    # ... and Tennisbot's `train.py -s tuned_ppo` network (ppo.build_tuned_actor_critic)
 
 F_AUTO_RESET = 0x1
 F_NET = 0x2

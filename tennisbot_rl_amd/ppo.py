@@ -15,13 +15,18 @@ import time
 
 import numpy as np
 
-from .params import ACT_DIM, ENV_SWING, OBS_DIM
+from .params import ACT_DIM, ENV_SWING, ENV_TENNIS, NET_DEFAULT, NET_TUNED, OBS_DIM
 from .rollout import RolloutBuffer
 from .stepper import ENV_IDS, BatchedEnv, StepperError
 
 # hyper-parameters of the reference scripts (and SB3 1.8.0 defaults where they are silent)
 SWING_DEFAULTS = dict(net_arch=(32, 64, 32), ent_coef=0.002, learning_rate=3e-4)   # train_swing.py:80-91
 TENNIS_DEFAULTS = dict(net_arch=(64, 64), ent_coef=0.01, learning_rate=3e-4)        # train.py:4-33,104-110
+# `train.py -s tuned_ppo` (train.py:112-127): ReLU, a shared features extractor obs -> 64 -> act_dim (train.py:54-67,116-118), pi = vf =
+# [32, 64, 32]; ent_coef is SB3's default 0. The reference also passes n_epochs = int(1e6 / 500) = 2000 (train.py:76-78,126), recorded
+# here as `reference_n_epochs`: PPOTrainer keeps COMMON's 10 unless n_epochs is given -- 2000 epochs over a 4096-env rollout is not a
+# usable default.
+TUNED_TENNIS_DEFAULTS = dict(net_arch=(32, 64, 32), extractor_hidden=64, ent_coef=0.0, learning_rate=3e-4, reference_n_epochs=2000)
 COMMON = dict(gamma=0.99, gae_lambda=0.95, clip_range=0.2, vf_coef=0.5, max_grad_norm=0.5, n_epochs=10)
 
 
@@ -81,19 +86,113 @@ def build_actor_critic(obs_dim, act_dim, net_arch=(32, 64, 32)):
     return ActorCritic()
 
 
+def build_tuned_actor_critic(obs_dim, act_dim, net_arch=(32, 64, 32), extractor_hidden=64):
+    """The policy of the reference's `train.py -s tuned_ppo` (train.py:54-67,112-127): SB3 `MlpPolicy` with activation_fn=ReLU,
+    CustomFeaturesExtractor(output_shape=act_dim) = ReLU(Linear(64, act_dim)(ReLU(Linear(obs_dim, 64)(obs)))) shared by actor and
+    critic (SB3's share_features_extractor default), then separate ReLU towers pi = vf = net_arch, linear heads, state-independent
+    log_std. named_parameters(): log_std | features_extractor.layers.{0,2} | policy_net | value_net_body | action_net | value_net
+    (Tennisbot-v0: 2 + 962 + 2 x 4288 + 66 + 33 = 9639 floats). Same act / evaluate as build_actor_critic's module."""
+    import torch
+    from torch import nn
+
+    class FeaturesExtractor(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.layers = nn.Sequential(nn.Linear(obs_dim, extractor_hidden), nn.ReLU(), nn.Linear(extractor_hidden, act_dim), nn.ReLU())
+
+        def forward(self, x):
+            return self.layers(x)
+
+    class TunedActorCritic(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.log_std = nn.Parameter(torch.zeros(act_dim))
+            self.features_extractor = FeaturesExtractor()
+
+            def tower():
+                layers, d = [], act_dim
+                for h in net_arch:
+                    layers += [nn.Linear(d, h), nn.ReLU()]
+                    d = h
+                return nn.Sequential(*layers)
+            self.policy_net, self.value_net_body = tower(), tower()
+            self.action_net = nn.Linear(net_arch[-1], act_dim)
+            self.value_net = nn.Linear(net_arch[-1], 1)
+            for m in list(self.features_extractor.layers) + list(self.policy_net) + list(self.value_net_body):  # SB3 ortho_init gains
+                if isinstance(m, nn.Linear):
+                    nn.init.orthogonal_(m.weight, gain=math.sqrt(2)); nn.init.zeros_(m.bias)
+            nn.init.orthogonal_(self.action_net.weight, gain=0.01); nn.init.zeros_(self.action_net.bias)
+            nn.init.orthogonal_(self.value_net.weight, gain=1.0); nn.init.zeros_(self.value_net.bias)
+
+        def forward(self, obs):
+            f = self.features_extractor(obs)
+            return self.action_net(self.policy_net(f)), self.value_net(self.value_net_body(f)).squeeze(-1)
+
+        def act(self, obs, deterministic=False):
+            mean, value = self(obs)
+            std = self.log_std.exp()
+            a = mean if deterministic else mean + std * torch.randn_like(mean)
+            logp = (-0.5 * ((a - mean) / std) ** 2 - self.log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+            return a, value, logp
+
+        def evaluate(self, obs, actions):
+            mean, value = self(obs)
+            std = self.log_std.exp()
+            logp = (-0.5 * ((actions - mean) / std) ** 2 - self.log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+            entropy = (0.5 + 0.5 * math.log(2 * math.pi) + self.log_std).sum()
+            return value, logp, entropy
+
+        def load_sb3_arrays(self, arrays):
+            """weights in SB3's `policy.pth` naming. SB3 lists the shared extractor three times (features_extractor,
+            pi_features_extractor, vf_features_extractor: one module); the first name is taken, the aliases dropped."""
+            sd = {}
+            for k, v in arrays.items():
+                k = k.replace("__", ".")
+                if k.startswith(("pi_features_extractor.", "vf_features_extractor.")):
+                    continue
+                k = k.replace("mlp_extractor.policy_net.", "policy_net.").replace("mlp_extractor.value_net.", "value_net_body.")
+                sd[k] = torch.as_tensor(np.asarray(v))
+            self.load_state_dict(sd)
+            return self
+
+    return TunedActorCritic()
+
+
+def policy_net_of(policy):
+    """NET_TUNED for build_tuned_actor_critic's module, NET_DEFAULT for build_actor_critic's"""
+    return NET_TUNED if hasattr(policy, "features_extractor") else NET_DEFAULT
+
+
+def _blob_layers(policy):
+    """[(nn.Linear, first)] in blob order. `first`: the layer reads the observation (k in natural order); every other layer reads
+    a previous layer's accumulator tiles. The tuned net: extractor layers, pi tower + head, vf tower + head -- the towers' first
+    layers read the extractor's (padded) output tile."""
+    import torch
+    lin = lambda body: [m for m in body if isinstance(m, torch.nn.Linear)]
+    out = []
+    if policy_net_of(policy) == NET_TUNED:
+        out += [(m, j == 0) for j, m in enumerate(lin(policy.features_extractor.layers))]
+        for body, head in ((policy.policy_net, policy.action_net), (policy.value_net_body, policy.value_net)):
+            out += [(m, False) for m in lin(body)] + [(head, False)]
+    else:
+        for body, head in ((policy.policy_net, policy.action_net), (policy.value_net_body, policy.value_net)):
+            out += [(m, j == 0) for j, m in enumerate(lin(body))] + [(head, False)]
+    return out
+
+
 def _fragment_indices(n_in, n_out, first_layer):
     """Gather indices into [bias (n_out), W^T (n_in x n_out) row-major, one trailing 0.0] that produce
     one layer of the blob `tb_policy_step` reads (include/tb_stepper.h; csrc/tb_policy.hpp, LayerRegs): bias tiles
     [out/16][4 lane groups][4 regs], then weight fragments [out/16][chunks][64 lanes] of v_mfma_f32_16x16x4_f32 -- lane l of
     a fragment holds W[out 16 t + l % 16][k(chunk, l // 16)]. The first layer takes k in natural order, k = 4 c + g (zero
     beyond the observation); every later layer takes it in the order the previous layer's accumulator registers hold it:
-    chunk 4 u + r = register r of output tile u, whose lane group g holds row 16 u + 4 g + r."""
+    chunk 4 u + r = register r of output tile u, whose lane group g holds row 16 u + 4 g + r (an input narrower than its last
+    tile -- the tuned net's feature -- is zero beyond n_in like the tile's padded rows)."""
     zero = n_out + n_in * n_out
     if first_layer:
         chunks = [[4 * c + g for g in range(4)] for c in range((n_in + 3) // 4)]
     else:
-        assert n_in % 16 == 0
-        chunks = [[16 * u + 4 * g + r for g in range(4)] for u in range(n_in // 16) for r in range(4)]
+        chunks = [[16 * u + 4 * g + r for g in range(4)] for u in range((n_in + 15) // 16) for r in range(4)]
     n_tiles = (n_out + 15) // 16
     idx = []
     for t in range(n_tiles):
@@ -112,24 +211,23 @@ def _fragment_indices(n_in, n_out, first_layer):
 
 def pack_policy(policy, out=None):
     """The blob `tb_policy_step` reads: pi tower layers, action head, vf tower layers, value head (each
-    in MFMA fragment order, see _fragment_indices), then log_std padded to a multiple of 4 floats.
+    in MFMA fragment order, see _fragment_indices), then log_std padded to a multiple of 4 floats; for the tuned net
+    (build_tuned_actor_critic) the extractor's layers come first (_blob_layers).
     `out`: a preallocated device tensor to refresh in place (its address is baked into captured graphs).
     ONE gather: the parameters are concatenated as they lie in memory ([bias, weight (out x in) row-major] per layer, log_std,
     one 0.0) and a cached index vector -- _fragment_indices composed with the weight's transpose -- picks the blob out of that
     (two kernels per call; the per-layer cat / transpose / index form was ~40 launches, 0.2 ms of a 4.5 ms collect)."""
     import torch
     dev = policy.log_std.device
-    layers = []
-    for body, head in ((policy.policy_net, policy.action_net), (policy.value_net_body, policy.value_net)):
-        layers += [m for m in body if isinstance(m, torch.nn.Linear)] + [head]
+    spec = _blob_layers(policy)
+    layers = [m for m, _ in spec]
     cache = getattr(policy, "_pack_index", None)
     if cache is None or cache.device != dev:
-        n_body = (len(layers) - 2) // 2
         total = sum(m.out_features * (m.in_features + 1) for m in layers) + policy.log_std.numel()  # ... and the 0.0 lies at `total`
         gidx, off = [], 0
-        for li, m in enumerate(layers):
+        for m, first in spec:
             n_in, n_out = m.in_features, m.out_features
-            for k in _fragment_indices(n_in, n_out, li % (n_body + 1) == 0):
+            for k in _fragment_indices(n_in, n_out, first):
                 if k < n_out:                      # bias
                     gidx.append(off + k)
                 elif k < n_out + n_in * n_out:     # W^T[i][o] = weight[o][i]
@@ -153,13 +251,21 @@ class PPOTrainer:
     """clipped-surrogate PPO over a BatchedEnv; one process per GPU when distributed"""
 
     def __init__(self, env_id="SwingRacket-v0", num_envs=4096, n_steps=104, device=None, seed=0, batch_size=None,
-                 pipeline=True, graph=True, fused=True, rollout_launch=True, params=None, ff_defer="all", options=None, learner="torch", **hp):
+                 pipeline=True, graph=True, fused=True, rollout_launch=True, params=None, ff_defer="all", options=None, learner="torch", policy="default", **hp):
         import torch
         self.torch = torch
         if learner not in ("torch", "fused"):
             raise ValueError("learner must be 'torch' or 'fused', not %r" % (learner,))
+        if policy not in ("default", "tuned"):
+            raise ValueError("policy must be 'default' or 'tuned', not %r" % (policy,))
         kind = ENV_IDS[env_id]
-        d = dict(SWING_DEFAULTS if kind == ENV_SWING else TENNIS_DEFAULTS)
+        # policy="tuned": the reference's `train.py -s tuned_ppo` network and hyper-parameters (TUNED_TENNIS_DEFAULTS), Tennisbot-v0 only
+        tuned = policy == "tuned"
+        if tuned and kind != ENV_TENNIS:
+            raise ValueError("policy='tuned' is Tennisbot-v0's network (the reference's train.py -s tuned_ppo), not %s's" % env_id)
+        self.net = NET_TUNED if tuned else NET_DEFAULT
+        arch_defaults = TUNED_TENNIS_DEFAULTS if tuned else SWING_DEFAULTS if kind == ENV_SWING else TENNIS_DEFAULTS
+        d = dict(arch_defaults)
         d.update(COMMON)
         d.update(hp)
         self.hp = d
@@ -179,7 +285,10 @@ class PPOTrainer:
         self.n_steps, self.num_envs = int(n_steps), int(num_envs)
         self.buf = RolloutBuffer(kind, self.n_steps, num_envs, self.device).bind(self.env)
         torch.manual_seed(seed)  # identical initial weights on every rank
-        self.policy = build_actor_critic(OBS_DIM[kind], ACT_DIM[kind], tuple(d["net_arch"])).to(self.device)
+        if tuned:
+            self.policy = build_tuned_actor_critic(OBS_DIM[kind], ACT_DIM[kind], tuple(d["net_arch"]), int(d["extractor_hidden"])).to(self.device)
+        else:
+            self.policy = build_actor_critic(OBS_DIM[kind], ACT_DIM[kind], tuple(d["net_arch"])).to(self.device)
         torch.manual_seed(seed + 1000 * (self.rank + 1))  # ... but rank-local exploration noise
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=d["learning_rate"], eps=1e-5)
         # minibatches of <= 65536 rows. (The reference's batch_size = n_steps = 1100 is its whole 1-env rollout, ONE minibatch per
@@ -205,19 +314,19 @@ class PPOTrainer:
         self._aux_stream = None  # the collect's bookkeeping, beside the join (see _collect_fused)
         # fused=True: the policy runs inside the step kernel (tb_policy_step); the torch module is
         # then only the learner's view of the same weights, repacked once per rollout
-        self.fused = bool(fused) and tuple(d["net_arch"]) == tuple((SWING_DEFAULTS if kind == ENV_SWING else TENNIS_DEFAULTS)["net_arch"])
+        self.fused = bool(fused) and tuple(d["net_arch"]) == tuple(arch_defaults["net_arch"]) and (not tuned or d["extractor_hidden"] == arch_defaults["extractor_hidden"])
         self.noise_seed = (seed * 1000003 + 7919 * (self.rank + 1)) & 0xFFFFFFFF
         # whole episodes per launch need the pipelined fast-forward on SwingRacket (always on for Tennisbot)
         self.rollout_launch = bool(rollout_launch) and self.fused and (kind != ENV_SWING or self.env.pipeline)
         self._rollouts = 0
         if self.fused:
             self.packed = pack_policy(self.policy)
-            assert self.packed.numel() == self.env.policy_floats()
+            assert self.packed.numel() == self.env.policy_floats(self.net)
         # learner="fused": advantages / update run as HIP kernels on the flat parameter vector (learner.py); "torch": the bodies below
         self._learner = None
         if learner == "fused":
             if not self.fused:
-                raise ValueError("learner='fused' needs the architecture the kernels are instantiated for (fused=True and the env's default net_arch)")
+                raise ValueError("learner='fused' needs the architecture the kernels are instantiated for (fused=True and the env's default net_arch, or policy='tuned' as it is)")
             from .learner import FusedLearner
             self._learner = FusedLearner(kind, self.policy, self.opt, self.hp, self.device)
 
@@ -237,13 +346,13 @@ class PPOTrainer:
             rec = buf.record
             env.policy_rollout_ptrs(self.n_steps, wp, cur, buf.actions[0].data_ptr(), self._raw_actions.data_ptr(), self.logps.data_ptr(),
                                     self.values.data_ptr(), buf.obs[0].data_ptr(), buf.rewards[0].data_ptr(), buf.dones[0].data_ptr(),
-                                    (rec, 0, 0, 0, rec, rec, rec), self.noise_seed)
+                                    (rec, 0, 0, 0, rec, rec, rec), self.noise_seed, net=self.net)
         for k in range(0 if by_launch else self.n_steps):
             obs_k = buf.obs[k]
             # exploration noise is keyed by (seed, env, episode, step) inside the kernel: replaying
             # the captured graph draws fresh noise because episodes / steps advance
             env.policy_step_ptrs(wp, cur, buf.actions[k].data_ptr(), self._raw_actions[k].data_ptr(), self.logps[k].data_ptr(),
-                                 self.values[k].data_ptr(), obs_k.data_ptr(), buf.rewards[k].data_ptr(), buf.dones[k].data_ptr(), self.noise_seed)
+                                 self.values[k].data_ptr(), obs_k.data_ptr(), buf.rewards[k].data_ptr(), buf.dones[k].data_ptr(), self.noise_seed, net=self.net)
             cur = obs_k.data_ptr()
         # observations are final when the step kernels are; only terminal rewards are still missing. The join (in the pool form: ONE
         # launch over every episode end of the rollout, ~0.5-0.8 ms of the main stream) and the bookkeeping -- a dozen small torch

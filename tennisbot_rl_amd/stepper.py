@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from .params import (ACT_DIM, COUNTER_NAMES, ENV_SWING, ENV_TENNIS, F_AUTO_RESET, N_COUNTERS, OBS_DIM,
+from .params import (ACT_DIM, COUNTER_NAMES, ENV_SWING, ENV_TENNIS, F_AUTO_RESET, N_COUNTERS, NET_DEFAULT, NET_TUNED, OBS_DIM,  # noqa: F401
                      STATE_ROWS, STATE_WORDS, TbOptions, TbParams, default_params, make_options)
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtb_stepper.so")
@@ -87,6 +87,12 @@ def load_library():
     L.tb_policy_floats.restype = i32
     L.tb_policy_step.argtypes = [vp] * 10 + [u64, i32, vp]
     L.tb_policy_step.restype = i32
+    L.tb_policy_blob_floats.argtypes = [i32, i32]
+    L.tb_policy_blob_floats.restype = i32
+    L.tb_policy_step_net.argtypes = [vp, i32] + [vp] * 9 + [u64, i32, vp]
+    L.tb_policy_step_net.restype = i32
+    L.tb_policy_rollout_net.argtypes = [vp, i32, i32] + [vp] * 9 + [ctypes.POINTER(ctypes.c_size_t), u64, i32, vp]
+    L.tb_policy_rollout_net.restype = i32
     L.tb_es_floats.argtypes = [i32]
     L.tb_es_floats.restype = i32
     L.tb_es_evaluate.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, vp, vp, ctypes.POINTER(TbEsTrace), vp]
@@ -104,6 +110,14 @@ def load_library():
     L.tb_ppo_grad.restype = i32
     L.tb_ppo_apply.argtypes = [i32, i32, vp, i32, vp, ctypes.c_size_t, i32] + [vp] * 4 + [i32, vp, f32, f32, i32, f32, f32, f32, f32, i64]
     L.tb_ppo_apply.restype = i32
+    L.tb_ppo_param_floats_net.argtypes = [i32, i32]
+    L.tb_ppo_param_floats_net.restype = i32
+    L.tb_ppo_workspace_bytes_net.argtypes = [i32, i32, i32]
+    L.tb_ppo_workspace_bytes_net.restype = i64
+    L.tb_ppo_grad_net.argtypes = [i32, i32, i32, vp] + [vp] * 5 + [i64, vp, i32, vp, i32, f32, f32, vp, ctypes.c_size_t]
+    L.tb_ppo_grad_net.restype = i32
+    L.tb_ppo_apply_net.argtypes = [i32, i32, i32, vp, i32, vp, ctypes.c_size_t, i32] + [vp] * 4 + [i32, vp, f32, f32, i32, f32, f32, f32, f32, i64]
+    L.tb_ppo_apply_net.restype = i32
     L.tb_trpo_rows_per_workgroup.argtypes = []
     L.tb_trpo_rows_per_workgroup.restype = i32
     L.tb_trpo_search_rows_per_workgroup.argtypes = []
@@ -363,16 +377,20 @@ class BatchedEnv:
             _check(self.L, rc, "tb_step_sequence")
         self._steps_issued += int(n_steps)
 
-    def policy_floats(self):
-        """length of the packed MlpPolicy blob tb_policy_step expects for this env kind"""
-        return int(self.L.tb_policy_floats(self.kind))
+    def policy_floats(self, net=NET_DEFAULT):
+        """length of the packed policy blob tb_policy_step expects for this env kind and network (NET_DEFAULT, or Tennisbot's NET_TUNED)"""
+        nf = int(self.L.tb_policy_blob_floats(self.kind, int(net)))
+        if nf < 0:
+            _check(self.L, nf, "tb_policy_blob_floats")
+        return nf
 
-    def policy_step(self, weights, obs_in, seed=0, deterministic=False, out=None, policy_out=None):
+    def policy_step(self, weights, obs_in, seed=0, deterministic=False, out=None, policy_out=None, net=NET_DEFAULT):
         """step() with SB3's MlpPolicy evaluated inside the step kernel (tb_policy_step): each env
         acts on its row of `obs_in`. weights: the packed blob of `ppo.pack_policy`. Returns ((obs, reward, done), (actions, raw_actions, logp, value));
-        `out` / `policy_out` are optional tuples of preallocated tensors of those shapes."""
+        `out` / `policy_out` are optional tuples of preallocated tensors of those shapes. net: the network the blob holds
+        (NET_TUNED: `ppo.build_tuned_actor_critic`, Tennisbot only)."""
         t, n = self.torch, self.num_envs
-        nf = self.policy_floats()
+        nf = self.policy_floats(net)
         w = self._check_tensor(weights, (nf,), t.float32, "weights")
         if w.data_ptr() % 16:
             raise ValueError("weights must be 16-byte aligned")
@@ -390,14 +408,14 @@ class BatchedEnv:
         self._check_tensor(logp, (n,), t.float32, "policy_out[2]")
         self._check_tensor(value, (n,), t.float32, "policy_out[3]")
         self.policy_step_ptrs(w.data_ptr(), oi.data_ptr(), act.data_ptr(), raw.data_ptr(), logp.data_ptr(), value.data_ptr(),
-                              obs.data_ptr(), rew.data_ptr(), done.data_ptr(), seed, deterministic)
+                              obs.data_ptr(), rew.data_ptr(), done.data_ptr(), seed, deterministic, net)
         if self.pipeline and out is None:
             self._inflight.append(rew)
         return (obs, rew, done), (act, raw, logp, value)
 
-    def policy_step_ptrs(self, weights_ptr, obs_in_ptr, act_ptr, raw_ptr, logp_ptr, value_ptr, obs_ptr, reward_ptr, done_ptr, seed, deterministic=False):
+    def policy_step_ptrs(self, weights_ptr, obs_in_ptr, act_ptr, raw_ptr, logp_ptr, value_ptr, obs_ptr, reward_ptr, done_ptr, seed, deterministic=False, net=NET_DEFAULT):
         """unchecked fast path of policy_step (raw device addresses, validated once by the caller)"""
-        rc = self.L.tb_policy_step(self._h, weights_ptr, obs_in_ptr, act_ptr, raw_ptr, logp_ptr, value_ptr, obs_ptr, reward_ptr, done_ptr,
+        rc = self.L.tb_policy_step_net(self._h, int(net), weights_ptr, obs_in_ptr, act_ptr, raw_ptr, logp_ptr, value_ptr, obs_ptr, reward_ptr, done_ptr,
                                    int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if deterministic else 0, self.torch.cuda.current_stream(self.device).cuda_stream)
         if rc:
             _check(self.L, rc, "tb_policy_step")
@@ -434,29 +452,29 @@ class BatchedEnv:
         _check(self.L, self.L.tb_mark_host_wait(self._h, int(k), int(timeout_ms)), "tb_mark_host_wait")
 
     def policy_rollout_ptrs(self, n_steps, weights_ptr, obs_in_ptr, act_ptr, raw_ptr, logp_ptr, value_ptr, obs_ptr, reward_ptr, done_ptr,
-                            strides_bytes, seed, deterministic=False):
+                            strides_bytes, seed, deterministic=False, net=NET_DEFAULT):
         """n_steps of policy_step_ptrs in as few launches as the episodes allow (tb_policy_rollout): the
         towers' weights and the envs' state stay in registers from step to step. strides_bytes: distance
         between consecutive steps of (actions, raw, logp, value, obs, reward, done), 0 = contiguous.
         Unchecked fast path; terminal SwingRacket rewards are complete after flush()."""
         st = (ctypes.c_size_t * 7)(*[int(x) for x in strides_bytes])
-        rc = self.L.tb_policy_rollout(self._h, int(n_steps), weights_ptr, obs_in_ptr, act_ptr, raw_ptr, logp_ptr, value_ptr, obs_ptr, reward_ptr, done_ptr,
+        rc = self.L.tb_policy_rollout_net(self._h, int(net), int(n_steps), weights_ptr, obs_in_ptr, act_ptr, raw_ptr, logp_ptr, value_ptr, obs_ptr, reward_ptr, done_ptr,
                                       st, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if deterministic else 0, self.torch.cuda.current_stream(self.device).cuda_stream)
         if rc:
             _check(self.L, rc, "tb_policy_rollout")
         self._steps_issued += int(n_steps)
 
-    def policy_rollout(self, weights, obs_in, n_steps, seed=0, deterministic=False):
+    def policy_rollout(self, weights, obs_in, n_steps, seed=0, deterministic=False, net=NET_DEFAULT):
         """T = n_steps agent steps with the MlpPolicy inside the kernel, whole episodes per launch.
         Returns ((obs [T,N,O], reward [T,N], done [T,N]), (actions [T,N,A], raw [T,N,A], logp [T,N], value [T,N]))."""
         t, n, T = self.torch, self.num_envs, int(n_steps)
-        w = self._check_tensor(weights, (self.policy_floats(),), t.float32, "weights")
+        w = self._check_tensor(weights, (self.policy_floats(net),), t.float32, "weights")
         oi = self._check_tensor(obs_in, (n, self.obs_dim), t.float32, "obs_in")
         f = dict(dtype=t.float32, device=self.device)
         obs, rew, done = t.empty((T, n, self.obs_dim), **f), t.empty((T, n), **f), t.empty((T, n), dtype=t.uint8, device=self.device)
         act, raw, logp, value = t.empty((T, n, self.act_dim), **f), t.empty((T, n, self.act_dim), **f), t.empty((T, n), **f), t.empty((T, n), **f)
         self.policy_rollout_ptrs(T, w.data_ptr(), oi.data_ptr(), act.data_ptr(), raw.data_ptr(), logp.data_ptr(), value.data_ptr(),
-                                 obs.data_ptr(), rew.data_ptr(), done.data_ptr(), (0,) * 7, seed, deterministic)
+                                 obs.data_ptr(), rew.data_ptr(), done.data_ptr(), (0,) * 7, seed, deterministic, net)
         if self.pipeline:
             self._inflight.append(rew)
         return (obs, rew, done), (act, raw, logp, value)

@@ -54,6 +54,8 @@ class FusedTRPO(FusedLearner):
     """GAE (inherited), the trust-region policy step and the critic's epochs on the device for one policy / optimiser pair"""
 
     def __init__(self, kind, policy, opt, hp, device):
+        if hasattr(policy, "features_extractor"):
+            raise ValueError("FusedTRPO needs the env's default net_arch: its kernels are not instantiated for the tuned network")
         for k, v in TRPO_DEFAULTS.items():        # filled in place: hp stays the caller's dict, as with FusedLearner, so a later
             hp.setdefault(k, v)                   # change of trainer.hp reaches the learner
         super().__init__(kind, policy, opt, hp, device)
@@ -220,7 +222,7 @@ class TRPOTrainer(PPOTrainer):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise ValueError("TRPOTrainer runs on one rank (world size %d): multi-rank TRPO is not provided" % dist.get_world_size())
         default_arch = tuple((SWING_DEFAULTS if ENV_IDS[env_id] == ENV_SWING else TENNIS_DEFAULTS)["net_arch"])
-        if tuple(kw.get("net_arch", default_arch)) != default_arch or not kw.get("fused", True):
+        if tuple(kw.get("net_arch", default_arch)) != default_arch or not kw.get("fused", True) or kw.get("policy", "default") != "default":
             raise ValueError("TRPOTrainer needs the env's default net_arch %s and the fused rollout: its kernels are instantiated for that architecture" % (default_arch,))
         if kw.pop("learner", "fused") != "fused":
             raise ValueError("TRPOTrainer has no torch learner")

@@ -495,6 +495,56 @@ int tb_trpo_search(int env_kind, int device, void *stream, const float *obs_dev,
                    double *out_dev, void *workspace_dev, size_t workspace_bytes);
 
 /*
+ * The SAC learner (csrc/tb_sac.hpp; tennisbot_rl_amd/sac.py is the caller): SB3 1.8.0's SAC with MlpPolicy, [256, 256] ReLU nets,
+ * in the conventions of the tb_ppo_* / tb_trpo_* blocks: (env_kind, device, stream), caller-owned device buffers, a host-only
+ * workspace query, refusals before any device is looked for. fp32 on the f32-input MFMA; losses and statistics are float64 sums
+ * in a fixed order; no float atomics: the same inputs give the same bits.
+ *
+ * Flat parameter vectors, named_parameters() order. TB_SAC_ACTOR (70668 floats SwingRacket-v0, 70148 Tennisbot-v0): latent_pi.0
+ * W [256][O] b | latent_pi.2 W [256][256] b | mu W [A][256] b | log_std W [A][256] b. TB_SAC_CRITIC (138754 / 139778; the target
+ * has the same shape): qf0 then qf1, each W [256][O + A] b | W [256][256] b | W [1][256] b on cat(obs, action).
+ *
+ * The replay arrays are obs / next_obs [n_rows][O], action [n_rows][A], reward [n_rows], done [n_rows] (float32, 0 or 1); the
+ * batch is the rows idx[0 .. batch) (int64; values outside [0, n_rows) are clamped), gathered by the kernels. eps is the
+ * standard-normal noise [batch][A], an input. The workspace (tb_sac_workspace_bytes(kind, batch), 8-byte aligned) carries the
+ * activations from one stage to the next: the stages of one gradient step use ONE workspace and ONE batch, in this order:
+ *
+ * tb_sac_actor_forward: a~ = tanh(mu + exp(clamp(log_std, -20, 2)) eps), logp = sum(-eps^2 / 2 - log_std - ln sqrt(2 pi)) -
+ *   sum log(1 - a~^2 + 1e-6) on obs; act_out [batch][A], logp_out [batch]. Keeps the actor's activations for tb_sac_actor_grad.
+ * tb_sac_targets: y = r + (1 - d) gamma (min(Q1t, Q2t)(s', a') - alpha logp'), (a', logp') the actor on next_obs with eps_next,
+ *   alpha = exp(*log_ent_coef_dev). The envs carry no time limit: done is a true terminal, and y == r bit for bit there.
+ * tb_sac_critic_grad: grad_dev = the gradient of 0.5 (mean (Q1(s, a) - y)^2 + mean (Q2(s, a) - y)^2); stats_dev[0] = that loss.
+ * tb_sac_actor_grad: the gradient of mean(alpha logp - min(Q1, Q2)(s, a~)) with respect to the actor alone, with critic_dev as it
+ *   is NOW (the caller has stepped it), through both critics' input gradients, the min, tanh and the log(1 - a~^2 + 1e-6) term;
+ *   *ent_grad_dev = -mean(logp - A), the gradient of log_ent_coef; stats_dev[1] = the loss, [2] = mean logp, [3] = the entropy
+ *   coefficient's gradient. Needs tb_sac_actor_forward's workspace content of the same batch. Writes no critic gradient.
+ * tb_sac_adam: plain Adam (torch's: eps added to sqrt(v_hat)) on params[0 .. n); step is the 1-based count of this step. With
+ *   target_dev the Polyak update target = (1 - tau) target + tau params (SB3's two roundings) follows on the NEW parameters in the
+ *   same launch; with params-only pointers null (grad, moments) and target_dev set it is the Polyak update alone.
+ * stats_dev: 4 doubles. tb_sac_rows_per_workgroup(): the rows one workgroup of the tile kernels takes.
+ */
+#define TB_SAC_ACTOR 0
+#define TB_SAC_CRITIC 1
+int tb_sac_param_floats(int env_kind, int which);
+int tb_sac_rows_per_workgroup(void);
+long long tb_sac_workspace_bytes(int env_kind, int batch);
+int tb_sac_actor_forward(int env_kind, int device, void *stream, const float *obs_dev, long long n_rows, const int64_t *idx_dev,
+                         int batch, const float *actor_dev, const float *eps_dev, float *act_out_dev, float *logp_out_dev,
+                         void *workspace_dev, size_t workspace_bytes);
+int tb_sac_targets(int env_kind, int device, void *stream, const float *next_obs_dev, const float *reward_dev, const float *done_dev,
+                   long long n_rows, const int64_t *idx_dev, int batch, const float *actor_dev, const float *target_dev,
+                   const float *log_ent_coef_dev, const float *eps_next_dev, float gamma, float *y_dev, void *workspace_dev,
+                   size_t workspace_bytes);
+int tb_sac_critic_grad(int env_kind, int device, void *stream, const float *obs_dev, const float *action_dev, long long n_rows,
+                       const int64_t *idx_dev, int batch, const float *critic_dev, const float *y_dev, float *grad_dev,
+                       double *stats_dev, void *workspace_dev, size_t workspace_bytes);
+int tb_sac_actor_grad(int env_kind, int device, void *stream, int batch, const float *actor_dev, const float *critic_dev,
+                      const float *log_ent_coef_dev, const float *eps_dev, float *actor_grad_dev, float *ent_grad_dev,
+                      double *stats_dev, void *workspace_dev, size_t workspace_bytes);
+int tb_sac_adam(int device, void *stream, float *params_dev, const float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
+                long long n, float lr, float beta1, float beta2, float eps, long long step, float *target_dev, float tau);
+
+/*
  * Pipelined fast-forward (SwingRacket-v0 with TB_F_AUTO_RESET; HIP streams, no reference
  * counterpart). The <= 775-substep fast-forward of swingracket_env.py:105-141 takes no
  * agent input, and the next episode does not depend on its outcome. With the pipeline

@@ -28,6 +28,7 @@
 #include "tb_es.hpp"
 #include "tb_learner.hpp"
 #include "tb_trpo.hpp"
+#include "tb_sac.hpp"
 
 using namespace tb;
 
@@ -1369,6 +1370,209 @@ int tb_trpo_search(int env_kind, int device, void* stream, const float* obs_dev,
   if (int rc = env_kind == TB_ENV_SWING ? launch(tb_trpo_search_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a) : launch(tb_trpo_search_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a))
     return rc;
   return launch(tb_trpo_search_reduce_kernel, dim3((unsigned)n_candidates), dim3(256), 0, s, (const double*)partials, shares, batch, out_dev);
+}
+
+// --------------------------------------------------------------------------------------------- the SAC learner (tb_sac.hpp)
+extern "C++" {
+namespace {
+struct SacDims {  // SacLayout<KIND> at run time
+  int O, A, C, pi_w0, pi_b0, pi_w1, pi_b1, pi_head, pi_block, pi_p, q_w0, q_b0, q_w1, q_b1, q_w2, q_b2, q_one, q_p;
+};
+template <int KIND> SacDims sac_dims_of() {
+  using L = SacLayout<KIND>;
+  return {L::O, L::A, L::C, L::PI_W0, L::PI_B0, L::PI_W1, L::PI_B1, L::PI_HEAD, L::PI_HEAD_BLOCK, L::PI_P, L::Q_W0, L::Q_B0, L::Q_W1, L::Q_B1, L::Q_W2, L::Q_B2, L::Q_ONE, L::Q_P};
+}
+SacDims sac_dims(int env_kind) { return env_kind == TB_ENV_SWING ? sac_dims_of<TB_ENV_SWING>() : sac_dims_of<TB_ENV_TENNIS>(); }
+
+unsigned sac_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
+
+struct SacRun {  // one stage's launches: the dims, the stream, the batch and the workspace's regions
+  SacDims d;
+  hipStream_t s;
+  int B;
+  float* ws;
+  float* at(int region) const { return ws + (size_t)region * (size_t)B; }
+
+  int forward(bool relu, const float* x, int xs, long long xz, const float* w, int wrs, long long wz, const float* bias, float* y, int ys, long long yz, int K, int M, int nets) const {
+    SacFwdArgs a = {x, xs, xz, w, wrs, wz, bias, y, ys, yz, B, K, M};
+    const dim3 grid(sac_blocks(B, SAC_ROWS_PER_WG), sac_blocks(M, 16), (unsigned)nets);
+    return relu ? launch(sac_forward_kernel<true>, grid, dim3(256), 0, s, a) : launch(sac_forward_kernel<false>, grid, dim3(256), 0, s, a);
+  }
+  int backward(const float* dz, int dzs, long long dzz, const float* w, int wrs, long long wz, int split, int extra, const float* h, int hs, long long hz, float* dx, int dxs,
+               long long dxz, int K, int M, int nets) const {
+    SacBwdArgs a = {dz, dzs, dzz, w, wrs, wz, split, extra, h, hs, hz, dx, dxs, dxz, B, K, M};
+    const dim3 grid(sac_blocks(B, SAC_ROWS_PER_WG), sac_blocks(K, 16), (unsigned)nets);
+    return h ? launch(sac_backward_kernel<true>, grid, dim3(256), 0, s, a) : launch(sac_backward_kernel<false>, grid, dim3(256), 0, s, a);
+  }
+  int wgrad(const float* dz, int dzs, long long dzz, const float* h, int hs, long long hz, float* gw, int wrs, long long wz, float* gb, int K, int M, int nets) const {
+    SacWgradArgs a = {dz, dzs, dzz, h, hs, hz, gw, wrs, wz, gb, B, K, M};
+    return launch(sac_wgrad_kernel, dim3(sac_blocks(K, 64), sac_blocks(M, 16), (unsigned)nets), dim3(256), 0, s, a);
+  }
+  // the actor on the gathered rows x0: h1, h2, the head's outputs zh; then the sample: act / logp out, xc = obs | sample, lp
+  int actor(const float* actor, const float* eps, int x0, int h1, int h2, int zh, int xc, int lp, float* act_out, float* logp_out) const {
+    if (int rc = forward(true, at(x0), SAC_XW, 0, actor + d.pi_w0, d.O, 0, actor + d.pi_b0, at(h1), SAC_H, 0, d.O, SAC_H, 1)) return rc;
+    if (int rc = forward(true, at(h1), SAC_H, 0, actor + d.pi_w1, SAC_H, 0, actor + d.pi_b1, at(h2), SAC_H, 0, SAC_H, SAC_H, 1)) return rc;
+    if (int rc = forward(false, at(h2), SAC_H, 0, actor + d.pi_head, SAC_H, d.pi_block, actor + d.pi_head + d.A * SAC_H, at(zh), SAC_XW, d.A, SAC_H, d.A, 2)) return rc;
+    return launch(sac_sample_kernel, dim3(sac_blocks(B, 256)), dim3(256), 0, s, (const float*)at(x0), (const float*)at(zh), eps, d.O, d.A, B, act_out, logp_out, at(xc), at(lp));
+  }
+  // both nets of a critic vector on the rows xc: h1, h2 [2][B][256], q [2][B][16] (column 0)
+  int critics(const float* critic, int xc, int h1, int h2, int q) const {
+    const long long BH = (long long)B * SAC_H;
+    if (int rc = forward(true, at(xc), SAC_XW, 0, critic + d.q_w0, d.C, d.q_one, critic + d.q_b0, at(h1), SAC_H, BH, d.C, SAC_H, 2)) return rc;
+    if (int rc = forward(true, at(h1), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, critic + d.q_b1, at(h2), SAC_H, BH, SAC_H, SAC_H, 2)) return rc;
+    return forward(false, at(h2), SAC_H, BH, critic + d.q_w2, SAC_H, d.q_one, critic + d.q_b2, at(q), SAC_XW, (long long)B * SAC_XW, SAC_H, 1, 2);
+  }
+  // dq [2][B][16] back to dz2 and dz1 [2][B][256] through both nets
+  int critics_backward(const float* critic) const {
+    const long long BH = (long long)B * SAC_H;
+    if (int rc = backward(at(SacWs::DQ), SAC_XW, (long long)B * SAC_XW, critic + d.q_w2, SAC_H, d.q_one, 1 << 30, 0, at(SacWs::C2), SAC_H, BH, at(SacWs::DZ2), SAC_H, BH, SAC_H, 1, 2)) return rc;
+    return backward(at(SacWs::DZ2), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, 1 << 30, 0, at(SacWs::C1), SAC_H, BH, at(SacWs::DZ1), SAC_H, BH, SAC_H, SAC_H, 2);
+  }
+};
+
+int sac_check(const char* what, int env_kind, int batch, const void* workspace_dev, size_t workspace_bytes) {
+  static thread_local char msg[160];
+  if (!kind_ok(env_kind)) { snprintf(msg, sizeof msg, "%s: unknown env kind", what); return fail(TB_E_INVAL, msg); }
+  if (batch < 1) { snprintf(msg, sizeof msg, "%s: batch must be >= 1", what); return fail(TB_E_INVAL, msg); }
+  if (!workspace_dev) { snprintf(msg, sizeof msg, "%s: null argument (the workspace)", what); return fail(TB_E_INVAL, msg); }
+  if (reinterpret_cast<uintptr_t>(workspace_dev) % 8 != 0) { snprintf(msg, sizeof msg, "%s: the workspace must be 8-byte aligned", what); return fail(TB_E_INVAL, msg); }
+  if ((long long)workspace_bytes < tb_sac_workspace_bytes(env_kind, batch)) { snprintf(msg, sizeof msg, "%s: the workspace is smaller than tb_sac_workspace_bytes", what); return fail(TB_E_PARAMS, msg); }
+  return TB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int tb_sac_param_floats(int env_kind, int which) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_sac_param_floats: unknown env kind");
+  if (which != TB_SAC_ACTOR && which != TB_SAC_CRITIC) return fail(TB_E_INVAL, "tb_sac_param_floats: which must be TB_SAC_ACTOR or TB_SAC_CRITIC");
+  const SacDims d = sac_dims(env_kind);
+  return which == TB_SAC_ACTOR ? d.pi_p : d.q_p;
+}
+int tb_sac_rows_per_workgroup(void) { return SAC_ROWS_PER_WG; }
+long long tb_sac_workspace_bytes(int env_kind, int batch) {
+  if (!kind_ok(env_kind) || batch < 1) return fail(TB_E_INVAL, "tb_sac_workspace_bytes: unknown env kind, or batch < 1");
+  return (long long)sizeof(float) * SacWs::PER_ROW * (long long)batch;
+}
+
+int tb_sac_actor_forward(int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* actor_dev,
+                         const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (int rc = sac_check("tb_sac_actor_forward", env_kind, batch, workspace_dev, workspace_bytes)) return rc;
+  if (!obs_dev || !idx_dev || !actor_dev || !eps_dev || !act_out_dev || !logp_out_dev) return fail(TB_E_INVAL, "tb_sac_actor_forward: null argument");
+  if (n_rows < 1) return fail(TB_E_INVAL, "tb_sac_actor_forward: n_rows must be >= 1");
+  if (misaligned(obs_dev, 4) || misaligned(actor_dev, 4) || misaligned(eps_dev, 4) || misaligned(act_out_dev, 4) || misaligned(logp_out_dev, 4) || misaligned(idx_dev, 8))
+    return fail(TB_E_INVAL, "tb_sac_actor_forward: a float array is not 4-byte aligned, or idx not 8-byte aligned");
+  if (int rc = ppo_device(device, "tb_sac_actor_forward: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = {sac_dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev};
+  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, obs_dev, r.d.O, (const float*)nullptr, 0, (const long long*)idx_dev, n_rows,
+                      batch, r.at(SacWs::X0)))
+    return rc;
+  return r.actor(actor_dev, eps_dev, SacWs::X0, SacWs::H1, SacWs::H2, SacWs::ZH, SacWs::XC, SacWs::LP, act_out_dev, logp_out_dev);
+}
+
+int tb_sac_targets(int env_kind, int device, void* stream, const float* next_obs_dev, const float* reward_dev, const float* done_dev, long long n_rows,
+                   const int64_t* idx_dev, int batch, const float* actor_dev, const float* target_dev, const float* log_ent_coef_dev, const float* eps_next_dev,
+                   float gamma, float* y_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (int rc = sac_check("tb_sac_targets", env_kind, batch, workspace_dev, workspace_bytes)) return rc;
+  if (!next_obs_dev || !reward_dev || !done_dev || !idx_dev || !actor_dev || !target_dev || !log_ent_coef_dev || !eps_next_dev || !y_dev)
+    return fail(TB_E_INVAL, "tb_sac_targets: null argument");
+  if (n_rows < 1) return fail(TB_E_INVAL, "tb_sac_targets: n_rows must be >= 1");
+  if (misaligned(next_obs_dev, 4) || misaligned(reward_dev, 4) || misaligned(done_dev, 4) || misaligned(actor_dev, 4) || misaligned(target_dev, 4) ||
+      misaligned(log_ent_coef_dev, 4) || misaligned(eps_next_dev, 4) || misaligned(y_dev, 4) || misaligned(idx_dev, 8))
+    return fail(TB_E_INVAL, "tb_sac_targets: a float array is not 4-byte aligned, or idx not 8-byte aligned");
+  if (int rc = ppo_device(device, "tb_sac_targets: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = {sac_dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev};
+  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, next_obs_dev, r.d.O, (const float*)nullptr, 0, (const long long*)idx_dev,
+                      n_rows, batch, r.at(SacWs::NX0)))
+    return rc;
+  if (int rc = r.actor(actor_dev, eps_next_dev, SacWs::NX0, SacWs::NH1, SacWs::NH2, SacWs::NZH, SacWs::NXC, SacWs::NAL, nullptr, nullptr)) return rc;  // logp' in NAL
+  if (int rc = r.critics(target_dev, SacWs::NXC, SacWs::T1, SacWs::T2, SacWs::QT)) return rc;
+  return launch(sac_target_kernel, dim3(sac_blocks(batch, 256)), dim3(256), 0, r.s, reward_dev, done_dev, (const long long*)idx_dev, n_rows, batch, (const float*)r.at(SacWs::QT),
+                (const float*)r.at(SacWs::NAL), log_ent_coef_dev, gamma, y_dev);
+}
+
+int tb_sac_critic_grad(int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev, int batch,
+                       const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (int rc = sac_check("tb_sac_critic_grad", env_kind, batch, workspace_dev, workspace_bytes)) return rc;
+  if (!obs_dev || !action_dev || !idx_dev || !critic_dev || !y_dev || !grad_dev || !stats_dev) return fail(TB_E_INVAL, "tb_sac_critic_grad: null argument");
+  if (n_rows < 1) return fail(TB_E_INVAL, "tb_sac_critic_grad: n_rows must be >= 1");
+  if (misaligned(obs_dev, 4) || misaligned(action_dev, 4) || misaligned(critic_dev, 4) || misaligned(y_dev, 4) || misaligned(grad_dev, 4) || misaligned(idx_dev, 8) ||
+      misaligned(stats_dev, 8))
+    return fail(TB_E_INVAL, "tb_sac_critic_grad: a float array is not 4-byte aligned, or idx / stats not 8-byte aligned");
+  if (grad_dev == critic_dev) return fail(TB_E_INVAL, "tb_sac_critic_grad: grad_dev must not be critic_dev");
+  if (int rc = ppo_device(device, "tb_sac_critic_grad: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = {sac_dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev};
+  const SacDims& d = r.d;
+  const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
+  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, obs_dev, d.O, action_dev, d.A, (const long long*)idx_dev, n_rows, batch,
+                      r.at(SacWs::XSA)))
+    return rc;
+  if (int rc = r.critics(critic_dev, SacWs::XSA, SacWs::C1, SacWs::C2, SacWs::Q)) return rc;
+  if (int rc = launch(sac_critic_loss_kernel, dim3(1), dim3(256), 0, r.s, (const float*)r.at(SacWs::Q), y_dev, batch, r.at(SacWs::DQ), stats_dev)) return rc;
+  if (int rc = r.critics_backward(critic_dev)) return rc;
+  if (int rc = r.wgrad(r.at(SacWs::DQ), SAC_XW, BX, r.at(SacWs::C2), SAC_H, BH, grad_dev + d.q_w2, SAC_H, d.q_one, grad_dev + d.q_b2, SAC_H, 1, 2)) return rc;
+  if (int rc = r.wgrad(r.at(SacWs::DZ2), SAC_H, BH, r.at(SacWs::C1), SAC_H, BH, grad_dev + d.q_w1, SAC_H, d.q_one, grad_dev + d.q_b1, SAC_H, SAC_H, 2)) return rc;
+  return r.wgrad(r.at(SacWs::DZ1), SAC_H, BH, r.at(SacWs::XSA), SAC_XW, 0, grad_dev + d.q_w0, d.C, d.q_one, grad_dev + d.q_b0, d.C, SAC_H, 2);
+}
+
+int tb_sac_actor_grad(int env_kind, int device, void* stream, int batch, const float* actor_dev, const float* critic_dev, const float* log_ent_coef_dev, const float* eps_dev,
+                      float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (int rc = sac_check("tb_sac_actor_grad", env_kind, batch, workspace_dev, workspace_bytes)) return rc;
+  if (!actor_dev || !critic_dev || !log_ent_coef_dev || !eps_dev || !actor_grad_dev || !ent_grad_dev || !stats_dev) return fail(TB_E_INVAL, "tb_sac_actor_grad: null argument");
+  if (misaligned(actor_dev, 4) || misaligned(critic_dev, 4) || misaligned(log_ent_coef_dev, 4) || misaligned(eps_dev, 4) || misaligned(actor_grad_dev, 4) ||
+      misaligned(ent_grad_dev, 4) || misaligned(stats_dev, 8))
+    return fail(TB_E_INVAL, "tb_sac_actor_grad: a float array is not 4-byte aligned, or stats not 8-byte aligned");
+  if (actor_grad_dev == actor_dev) return fail(TB_E_INVAL, "tb_sac_actor_grad: actor_grad_dev must not be actor_dev");
+  if (int rc = ppo_device(device, "tb_sac_actor_grad: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = {sac_dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev};
+  const SacDims& d = r.d;
+  const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
+  // the critics as they are now on (s, a~), the min, and back to their input
+  if (int rc = r.critics(critic_dev, SacWs::XC, SacWs::C1, SacWs::C2, SacWs::Q)) return rc;
+  if (int rc = launch(sac_actor_loss_kernel, dim3(1), dim3(256), 0, r.s, (const float*)r.at(SacWs::Q), (const float*)r.at(SacWs::LP), log_ent_coef_dev, -(float)d.A, batch,
+                      r.at(SacWs::DQ), ent_grad_dev, stats_dev))
+    return rc;
+  if (int rc = r.critics_backward(critic_dev)) return rc;
+  if (int rc = r.backward(r.at(SacWs::DZ1), SAC_H, BH, critic_dev + d.q_w0, d.C, d.q_one, 1 << 30, 0, nullptr, 0, 0, r.at(SacWs::DX), SAC_XW, BX, d.C, SAC_H, 2)) return rc;
+  // through tanh and logp to the head's outputs, then the actor's own backward pass
+  if (int rc = launch(sac_head_backward_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, (const float*)r.at(SacWs::ZH), (const float*)r.at(SacWs::XC),
+                      (const float*)r.at(SacWs::DX), eps_dev, log_ent_coef_dev, d.O, d.A, batch, r.at(SacWs::DHD)))
+    return rc;
+  float* gh = actor_grad_dev + d.pi_head;
+  if (int rc = r.wgrad(r.at(SacWs::DHD), SAC_XW, d.A, r.at(SacWs::H2), SAC_H, 0, gh, SAC_H, d.pi_block, gh + d.A * SAC_H, SAC_H, d.A, 2)) return rc;
+  if (int rc = r.backward(r.at(SacWs::DHD), SAC_XW, 0, actor_dev + d.pi_head, SAC_H, 0, d.A, d.A, r.at(SacWs::H2), SAC_H, 0, r.at(SacWs::DA2), SAC_H, 0, SAC_H, 2 * d.A, 1)) return rc;
+  if (int rc = r.wgrad(r.at(SacWs::DA2), SAC_H, 0, r.at(SacWs::H1), SAC_H, 0, actor_grad_dev + d.pi_w1, SAC_H, 0, actor_grad_dev + d.pi_b1, SAC_H, SAC_H, 1)) return rc;
+  if (int rc = r.backward(r.at(SacWs::DA2), SAC_H, 0, actor_dev + d.pi_w1, SAC_H, 0, 1 << 30, 0, r.at(SacWs::H1), SAC_H, 0, r.at(SacWs::DA1), SAC_H, 0, SAC_H, SAC_H, 1)) return rc;
+  return r.wgrad(r.at(SacWs::DA1), SAC_H, 0, r.at(SacWs::X0), SAC_XW, 0, actor_grad_dev + d.pi_w0, d.O, 0, actor_grad_dev + d.pi_b0, d.O, SAC_H, 1);
+}
+
+int tb_sac_adam(int device, void* stream, float* params_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, long long n, float lr, float beta1, float beta2,
+                float eps, long long step, float* target_dev, float tau) {
+  if (!params_dev) return fail(TB_E_INVAL, "tb_sac_adam: null argument (params)");
+  if (n < 1) return fail(TB_E_INVAL, "tb_sac_adam: n must be >= 1");
+  const bool polyak_only = !grad_dev && !exp_avg_dev && !exp_avg_sq_dev;
+  if (polyak_only && !target_dev) return fail(TB_E_INVAL, "tb_sac_adam: null argument (neither a gradient with both moments nor a target)");
+  if (!polyak_only && (!grad_dev || !exp_avg_dev || !exp_avg_sq_dev)) return fail(TB_E_INVAL, "tb_sac_adam: null argument (the gradient and both moments go together)");
+  if (!polyak_only && step < 1) return fail(TB_E_INVAL, "tb_sac_adam: step must be >= 1");
+  if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(target_dev, 4))
+    return fail(TB_E_INVAL, "tb_sac_adam: a float array is not 4-byte aligned");
+  if (target_dev == params_dev) return fail(TB_E_INVAL, "tb_sac_adam: target_dev must not be params_dev");
+  if (int rc = ppo_device(device, "tb_sac_adam: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  hipStream_t s = (hipStream_t)stream;
+  const float omt = (float)(1.0 - (double)tau);
+  const dim3 grid(sac_blocks(n, 256));
+  if (polyak_only) return launch(sac_polyak_kernel, grid, dim3(256), 0, s, (const float*)params_dev, target_dev, n, omt, tau);
+  const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
+  return launch(sac_adam_kernel, grid, dim3(256), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, c1, c2, target_dev, omt, tau);
 }
 
 int tb_rollout(TbHandle* h, int n_steps, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,

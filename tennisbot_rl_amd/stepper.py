@@ -130,6 +130,22 @@ def load_library():
     L.tb_trpo_fvp.restype = i32
     L.tb_trpo_search.argtypes = [i32, i32, vp] + [vp] * 4 + [i64, vp, i32, vp, vp, i32, vp, i32, vp, vp, ctypes.c_size_t]
     L.tb_trpo_search.restype = i32
+    L.tb_sac_param_floats.argtypes = [i32, i32]
+    L.tb_sac_param_floats.restype = i32
+    L.tb_sac_rows_per_workgroup.argtypes = []
+    L.tb_sac_rows_per_workgroup.restype = i32
+    L.tb_sac_workspace_bytes.argtypes = [i32, i32]
+    L.tb_sac_workspace_bytes.restype = i64
+    L.tb_sac_actor_forward.argtypes = [i32, i32, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, ctypes.c_size_t]
+    L.tb_sac_actor_forward.restype = i32
+    L.tb_sac_targets.argtypes = [i32, i32, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, f32, vp, vp, ctypes.c_size_t]
+    L.tb_sac_targets.restype = i32
+    L.tb_sac_critic_grad.argtypes = [i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, ctypes.c_size_t]
+    L.tb_sac_critic_grad.restype = i32
+    L.tb_sac_actor_grad.argtypes = [i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
+    L.tb_sac_actor_grad.restype = i32
+    L.tb_sac_adam.argtypes = [i32, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp, f32]
+    L.tb_sac_adam.restype = i32
     L.tb_phase.argtypes = [vp]
     L.tb_phase.restype = i32
     L.tb_phase_advance.argtypes = [vp, i32]

@@ -10,7 +10,7 @@ TB_NET_TUNED) and, with --learner fused, its update in the learner kernels (tb_p
 env x num_envs instead of 1100 x 1. One deviation: the reference passes n_epochs = int(1e6 / 500) = 2000 to the tuned model
 (train.py:76-78,126; recorded as TUNED_TENNIS_DEFAULTS["reference_n_epochs"]); this script keeps PPOTrainer's 10 for both
 selections unless --n-epochs is given, because 2000 epochs over a 4096-env rollout is not a usable default. `--curri` is the
-racket-size curriculum of train.py:155-176. `-s sac` is a third-party learner the batched envs do not provide. `--gui` is
+racket-size curriculum of train.py:155-176. `-s sac` has its own script, train_sac.py (tennisbot_rl_amd/sac.py). `--gui` is
 accepted and does nothing. train_swing.py stays the script for SwingRacket-v0 and for TRPO.
 """
 import argparse
@@ -44,7 +44,7 @@ def main(argv=None):
     ap.add_argument("--log-json", type=str, default=None)
     args = ap.parse_args(argv)
     if args.select not in SELECT:
-        sys.exit("-s %s: only ppo and tuned_ppo are implemented on the batched envs (sac is a third-party learner; trpo: train_swing.py)" % args.select)
+        sys.exit("-s %s: only ppo and tuned_ppo are implemented on the batched envs (trpo: train_swing.py). SAC: train_sac.py" % args.select)
 
     import torch
     from tennisbot_rl_amd.ppo import PPOTrainer

@@ -545,6 +545,47 @@ int tb_sac_adam(int device, void *stream, float *params_dev, const float *grad_d
                 long long n, float lr, float beta1, float beta2, float eps, long long step, float *target_dev, float tau);
 
 /*
+ * The TQC learner (csrc/tb_tqc.hpp; tennisbot_rl_amd/tqc.py is the caller): sb3_contrib 1.8.0's TQC with MlpPolicy at its
+ * defaults, in the conventions of the tb_sac_* block above, whose actor, replay arrays, index vector, noise, stats_dev and
+ * tb_sac_adam (Adam and Polyak, unchanged) it shares. Each of the two critics ends in TB_TQC_QUANTILES outputs; the top
+ * TB_TQC_DROP_PER_NET per net of the sorted target quantiles are dropped, TB_TQC_TARGETS are kept.
+ *
+ * Flat parameter vectors, named_parameters() order. TB_SAC_ACTOR: SAC's (70668 / 70148). TB_SAC_CRITIC (151090 floats
+ * SwingRacket-v0, 152114 Tennisbot-v0; the target has the same shape): qf0 then qf1, each W [256][O + A] b | W [256][256] b |
+ * W [25][256] b on cat(obs, action). The workspace is tb_tqc_workspace_bytes(kind, batch), 8-byte aligned: ONE workspace and
+ * ONE batch for the stages of a gradient step, in this order:
+ *
+ * tb_tqc_actor_forward: as tb_sac_actor_forward. Keeps the actor's activations for tb_tqc_actor_grad.
+ * tb_tqc_targets: z = the 50 quantiles of both targets on (s', a'), sorted ascending (equal values keep one slot each; a NaN
+ *   orders last, as torch.sort has it); y_dev [batch][46], y[b][j] = r + (1 - d) gamma (z[j] - alpha logp'), j < 46,
+ *   alpha = exp(*log_ent_coef_dev). A terminal row's 46 entries are r bit for bit.
+ * tb_tqc_critic_grad: grad_dev = the gradient of the quantile Huber loss, the mean over rows b, critics n, quantiles i and
+ *   targets j of |tau_i - [delta < 0]| H(delta), delta = y[b][j] - Q_n(s, a)[i], tau_i = (i + 0.5) / 25, H(delta) = |delta| - 0.5
+ *   where |delta| > 1 and delta^2 / 2 elsewhere; stats_dev[0] = that loss.
+ * tb_tqc_actor_grad: the gradient of mean(alpha logp - Qbar(s, a~)), Qbar the mean over the 25 quantiles and the 2 critics, with
+ *   respect to the actor alone, with critic_dev as it is NOW; *ent_grad_dev and stats_dev[1 .. 3] as tb_sac_actor_grad. Needs
+ *   tb_tqc_actor_forward's workspace content of the same batch. Writes no critic gradient.
+ */
+#define TB_TQC_QUANTILES 25
+#define TB_TQC_DROP_PER_NET 2
+#define TB_TQC_TARGETS 46
+int tb_tqc_param_floats(int env_kind, int which);
+long long tb_tqc_workspace_bytes(int env_kind, int batch);
+int tb_tqc_actor_forward(int env_kind, int device, void *stream, const float *obs_dev, long long n_rows, const int64_t *idx_dev,
+                         int batch, const float *actor_dev, const float *eps_dev, float *act_out_dev, float *logp_out_dev,
+                         void *workspace_dev, size_t workspace_bytes);
+int tb_tqc_targets(int env_kind, int device, void *stream, const float *next_obs_dev, const float *reward_dev, const float *done_dev,
+                   long long n_rows, const int64_t *idx_dev, int batch, const float *actor_dev, const float *target_dev,
+                   const float *log_ent_coef_dev, const float *eps_next_dev, float gamma, float *y_dev, void *workspace_dev,
+                   size_t workspace_bytes);
+int tb_tqc_critic_grad(int env_kind, int device, void *stream, const float *obs_dev, const float *action_dev, long long n_rows,
+                       const int64_t *idx_dev, int batch, const float *critic_dev, const float *y_dev, float *grad_dev,
+                       double *stats_dev, void *workspace_dev, size_t workspace_bytes);
+int tb_tqc_actor_grad(int env_kind, int device, void *stream, int batch, const float *actor_dev, const float *critic_dev,
+                      const float *log_ent_coef_dev, const float *eps_dev, float *actor_grad_dev, float *ent_grad_dev,
+                      double *stats_dev, void *workspace_dev, size_t workspace_bytes);
+
+/*
  * Pipelined fast-forward (SwingRacket-v0 with TB_F_AUTO_RESET; HIP streams, no reference
  * counterpart). The <= 775-substep fast-forward of swingracket_env.py:105-141 takes no
  * agent input, and the next episode does not depend on its outcome. With the pipeline

@@ -29,6 +29,7 @@
 #include "tb_learner.hpp"
 #include "tb_trpo.hpp"
 #include "tb_sac.hpp"
+#include "tb_tqc.hpp"
 
 using namespace tb;
 
@@ -1391,6 +1392,7 @@ struct SacRun {  // one stage's launches: the dims, the stream, the batch and th
   hipStream_t s;
   int B;
   float* ws;
+  int heads = 1, hw = SAC_XW;  // a critic's outputs and the padded width of its head rows: 1 / 16 for SAC, 25 / 32 for TQC
   float* at(int region) const { return ws + (size_t)region * (size_t)B; }
 
   int forward(bool relu, const float* x, int xs, long long xz, const float* w, int wrs, long long wz, const float* bias, float* y, int ys, long long yz, int K, int M, int nets) const {
@@ -1415,29 +1417,43 @@ struct SacRun {  // one stage's launches: the dims, the stream, the batch and th
     if (int rc = forward(false, at(h2), SAC_H, 0, actor + d.pi_head, SAC_H, d.pi_block, actor + d.pi_head + d.A * SAC_H, at(zh), SAC_XW, d.A, SAC_H, d.A, 2)) return rc;
     return launch(sac_sample_kernel, dim3(sac_blocks(B, 256)), dim3(256), 0, s, (const float*)at(x0), (const float*)at(zh), eps, d.O, d.A, B, act_out, logp_out, at(xc), at(lp));
   }
-  // both nets of a critic vector on the rows xc: h1, h2 [2][B][256], q [2][B][16] (column 0)
+  // both nets of a critic vector on the rows xc: h1, h2 [2][B][256], q [2][B][hw] (columns 0 .. heads)
   int critics(const float* critic, int xc, int h1, int h2, int q) const {
     const long long BH = (long long)B * SAC_H;
     if (int rc = forward(true, at(xc), SAC_XW, 0, critic + d.q_w0, d.C, d.q_one, critic + d.q_b0, at(h1), SAC_H, BH, d.C, SAC_H, 2)) return rc;
     if (int rc = forward(true, at(h1), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, critic + d.q_b1, at(h2), SAC_H, BH, SAC_H, SAC_H, 2)) return rc;
-    return forward(false, at(h2), SAC_H, BH, critic + d.q_w2, SAC_H, d.q_one, critic + d.q_b2, at(q), SAC_XW, (long long)B * SAC_XW, SAC_H, 1, 2);
+    return forward(false, at(h2), SAC_H, BH, critic + d.q_w2, SAC_H, d.q_one, critic + d.q_b2, at(q), hw, (long long)B * hw, SAC_H, heads, 2);
   }
-  // dq [2][B][16] back to dz2 and dz1 [2][B][256] through both nets
-  int critics_backward(const float* critic) const {
+  // dq [2][B][hw] back to dz2 and dz1 [2][B][256] through both nets, in the regions of the workspace layout Ws
+  template <class Ws = SacWs> int critics_backward(const float* critic) const {
     const long long BH = (long long)B * SAC_H;
-    if (int rc = backward(at(SacWs::DQ), SAC_XW, (long long)B * SAC_XW, critic + d.q_w2, SAC_H, d.q_one, 1 << 30, 0, at(SacWs::C2), SAC_H, BH, at(SacWs::DZ2), SAC_H, BH, SAC_H, 1, 2)) return rc;
-    return backward(at(SacWs::DZ2), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, 1 << 30, 0, at(SacWs::C1), SAC_H, BH, at(SacWs::DZ1), SAC_H, BH, SAC_H, SAC_H, 2);
+    if (int rc = backward(at(Ws::DQ), hw, (long long)B * hw, critic + d.q_w2, SAC_H, d.q_one, 1 << 30, 0, at(Ws::C2), SAC_H, BH, at(Ws::DZ2), SAC_H, BH, SAC_H, heads, 2)) return rc;
+    return backward(at(Ws::DZ2), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, 1 << 30, 0, at(Ws::C1), SAC_H, BH, at(Ws::DZ1), SAC_H, BH, SAC_H, SAC_H, 2);
   }
 };
 
-int sac_check(const char* what, int env_kind, int batch, const void* workspace_dev, size_t workspace_bytes) {
+int sac_check(const char* what, int env_kind, int batch, const void* workspace_dev, size_t workspace_bytes, bool tqc = false) {
   static thread_local char msg[160];
   if (!kind_ok(env_kind)) { snprintf(msg, sizeof msg, "%s: unknown env kind", what); return fail(TB_E_INVAL, msg); }
   if (batch < 1) { snprintf(msg, sizeof msg, "%s: batch must be >= 1", what); return fail(TB_E_INVAL, msg); }
   if (!workspace_dev) { snprintf(msg, sizeof msg, "%s: null argument (the workspace)", what); return fail(TB_E_INVAL, msg); }
   if (reinterpret_cast<uintptr_t>(workspace_dev) % 8 != 0) { snprintf(msg, sizeof msg, "%s: the workspace must be 8-byte aligned", what); return fail(TB_E_INVAL, msg); }
-  if ((long long)workspace_bytes < tb_sac_workspace_bytes(env_kind, batch)) { snprintf(msg, sizeof msg, "%s: the workspace is smaller than tb_sac_workspace_bytes", what); return fail(TB_E_PARAMS, msg); }
+  if ((long long)workspace_bytes < (tqc ? tb_tqc_workspace_bytes(env_kind, batch) : tb_sac_workspace_bytes(env_kind, batch))) {
+    snprintf(msg, sizeof msg, "%s: the workspace is smaller than %s", what, tqc ? "tb_tqc_workspace_bytes" : "tb_sac_workspace_bytes");
+    return fail(TB_E_PARAMS, msg);
+  }
   return TB_OK;
+}
+
+// TQC: SAC's dims with the critic's 25-wide last layer
+template <int KIND> SacDims tqc_dims_of() {
+  using L = TqcLayout<KIND>;
+  SacDims d = sac_dims_of<KIND>();
+  d.q_w2 = L::Q_W2; d.q_b2 = L::Q_B2; d.q_one = L::Q_ONE; d.q_p = L::Q_P;
+  return d;
+}
+SacRun tqc_run(int env_kind, void* stream, int batch, void* workspace_dev) {
+  return {env_kind == TB_ENV_SWING ? tqc_dims_of<TB_ENV_SWING>() : tqc_dims_of<TB_ENV_TENNIS>(), (hipStream_t)stream, batch, (float*)workspace_dev, TQC_Q, TQC_HW};
 }
 }  // namespace
 }  // extern "C++"
@@ -1573,6 +1589,119 @@ int tb_sac_adam(int device, void* stream, float* params_dev, const float* grad_d
   if (polyak_only) return launch(sac_polyak_kernel, grid, dim3(256), 0, s, (const float*)params_dev, target_dev, n, omt, tau);
   const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
   return launch(sac_adam_kernel, grid, dim3(256), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, c1, c2, target_dev, omt, tau);
+}
+
+// --------------------------------------------------------------------------------------------- the TQC learner (tb_tqc.hpp)
+int tb_tqc_param_floats(int env_kind, int which) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_tqc_param_floats: unknown env kind");
+  if (which != TB_SAC_ACTOR && which != TB_SAC_CRITIC) return fail(TB_E_INVAL, "tb_tqc_param_floats: which must be TB_SAC_ACTOR or TB_SAC_CRITIC");
+  const SacDims d = tqc_run(env_kind, nullptr, 1, nullptr).d;
+  return which == TB_SAC_ACTOR ? d.pi_p : d.q_p;
+}
+long long tb_tqc_workspace_bytes(int env_kind, int batch) {
+  if (!kind_ok(env_kind) || batch < 1) return fail(TB_E_INVAL, "tb_tqc_workspace_bytes: unknown env kind, or batch < 1");
+  return (long long)sizeof(float) * TqcWs::PER_ROW * (long long)batch;
+}
+
+int tb_tqc_actor_forward(int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* actor_dev,
+                         const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (int rc = sac_check("tb_tqc_actor_forward", env_kind, batch, workspace_dev, workspace_bytes, true)) return rc;
+  if (!obs_dev || !idx_dev || !actor_dev || !eps_dev || !act_out_dev || !logp_out_dev) return fail(TB_E_INVAL, "tb_tqc_actor_forward: null argument");
+  if (n_rows < 1) return fail(TB_E_INVAL, "tb_tqc_actor_forward: n_rows must be >= 1");
+  if (misaligned(obs_dev, 4) || misaligned(actor_dev, 4) || misaligned(eps_dev, 4) || misaligned(act_out_dev, 4) || misaligned(logp_out_dev, 4) || misaligned(idx_dev, 8))
+    return fail(TB_E_INVAL, "tb_tqc_actor_forward: a float array is not 4-byte aligned, or idx not 8-byte aligned");
+  if (int rc = ppo_device(device, "tb_tqc_actor_forward: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = tqc_run(env_kind, stream, batch, workspace_dev);
+  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, obs_dev, r.d.O, (const float*)nullptr, 0, (const long long*)idx_dev, n_rows,
+                      batch, r.at(TqcWs::X0)))
+    return rc;
+  return r.actor(actor_dev, eps_dev, TqcWs::X0, TqcWs::H1, TqcWs::H2, TqcWs::ZH, TqcWs::XC, TqcWs::LP, act_out_dev, logp_out_dev);
+}
+
+int tb_tqc_targets(int env_kind, int device, void* stream, const float* next_obs_dev, const float* reward_dev, const float* done_dev, long long n_rows,
+                   const int64_t* idx_dev, int batch, const float* actor_dev, const float* target_dev, const float* log_ent_coef_dev, const float* eps_next_dev,
+                   float gamma, float* y_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (int rc = sac_check("tb_tqc_targets", env_kind, batch, workspace_dev, workspace_bytes, true)) return rc;
+  if (!next_obs_dev || !reward_dev || !done_dev || !idx_dev || !actor_dev || !target_dev || !log_ent_coef_dev || !eps_next_dev || !y_dev)
+    return fail(TB_E_INVAL, "tb_tqc_targets: null argument");
+  if (n_rows < 1) return fail(TB_E_INVAL, "tb_tqc_targets: n_rows must be >= 1");
+  if (misaligned(next_obs_dev, 4) || misaligned(reward_dev, 4) || misaligned(done_dev, 4) || misaligned(actor_dev, 4) || misaligned(target_dev, 4) ||
+      misaligned(log_ent_coef_dev, 4) || misaligned(eps_next_dev, 4) || misaligned(y_dev, 4) || misaligned(idx_dev, 8))
+    return fail(TB_E_INVAL, "tb_tqc_targets: a float array is not 4-byte aligned, or idx not 8-byte aligned");
+  if (int rc = ppo_device(device, "tb_tqc_targets: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = tqc_run(env_kind, stream, batch, workspace_dev);
+  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, next_obs_dev, r.d.O, (const float*)nullptr, 0, (const long long*)idx_dev,
+                      n_rows, batch, r.at(TqcWs::NX0)))
+    return rc;
+  if (int rc = r.actor(actor_dev, eps_next_dev, TqcWs::NX0, TqcWs::NH1, TqcWs::NH2, TqcWs::NZH, TqcWs::NXC, TqcWs::NAL, nullptr, nullptr)) return rc;  // logp' in NAL
+  if (int rc = r.critics(target_dev, TqcWs::NXC, TqcWs::T1, TqcWs::T2, TqcWs::QT)) return rc;
+  return launch(tqc_target_kernel, dim3(sac_blocks(batch, 4)), dim3(256), 0, r.s, reward_dev, done_dev, (const long long*)idx_dev, n_rows, batch, (const float*)r.at(TqcWs::QT),
+                (const float*)r.at(TqcWs::NAL), log_ent_coef_dev, gamma, y_dev);
+}
+
+int tb_tqc_critic_grad(int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev, int batch,
+                       const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (int rc = sac_check("tb_tqc_critic_grad", env_kind, batch, workspace_dev, workspace_bytes, true)) return rc;
+  if (!obs_dev || !action_dev || !idx_dev || !critic_dev || !y_dev || !grad_dev || !stats_dev) return fail(TB_E_INVAL, "tb_tqc_critic_grad: null argument");
+  if (n_rows < 1) return fail(TB_E_INVAL, "tb_tqc_critic_grad: n_rows must be >= 1");
+  if (misaligned(obs_dev, 4) || misaligned(action_dev, 4) || misaligned(critic_dev, 4) || misaligned(y_dev, 4) || misaligned(grad_dev, 4) || misaligned(idx_dev, 8) ||
+      misaligned(stats_dev, 8))
+    return fail(TB_E_INVAL, "tb_tqc_critic_grad: a float array is not 4-byte aligned, or idx / stats not 8-byte aligned");
+  if (grad_dev == critic_dev) return fail(TB_E_INVAL, "tb_tqc_critic_grad: grad_dev must not be critic_dev");
+  if (int rc = ppo_device(device, "tb_tqc_critic_grad: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = tqc_run(env_kind, stream, batch, workspace_dev);
+  const SacDims& d = r.d;
+  const long long BH = (long long)batch * SAC_H, BQ = (long long)batch * TQC_HW;
+  double* row_loss = reinterpret_cast<double*>(r.at(TqcWs::RL));
+  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, obs_dev, d.O, action_dev, d.A, (const long long*)idx_dev, n_rows, batch,
+                      r.at(TqcWs::XSA)))
+    return rc;
+  if (int rc = r.critics(critic_dev, TqcWs::XSA, TqcWs::C1, TqcWs::C2, TqcWs::Q)) return rc;
+  if (int rc = launch(tqc_critic_loss_kernel, dim3(sac_blocks(batch, 4)), dim3(256), 0, r.s, (const float*)r.at(TqcWs::Q), y_dev, batch, r.at(TqcWs::DQ), row_loss)) return rc;
+  if (int rc = launch(tqc_loss_sum_kernel, dim3(1), dim3(256), 0, r.s, (const double*)row_loss, batch, stats_dev)) return rc;
+  if (int rc = r.critics_backward<TqcWs>(critic_dev)) return rc;
+  if (int rc = r.wgrad(r.at(TqcWs::DQ), TQC_HW, BQ, r.at(TqcWs::C2), SAC_H, BH, grad_dev + d.q_w2, SAC_H, d.q_one, grad_dev + d.q_b2, SAC_H, TQC_Q, 2)) return rc;
+  if (int rc = r.wgrad(r.at(TqcWs::DZ2), SAC_H, BH, r.at(TqcWs::C1), SAC_H, BH, grad_dev + d.q_w1, SAC_H, d.q_one, grad_dev + d.q_b1, SAC_H, SAC_H, 2)) return rc;
+  return r.wgrad(r.at(TqcWs::DZ1), SAC_H, BH, r.at(TqcWs::XSA), SAC_XW, 0, grad_dev + d.q_w0, d.C, d.q_one, grad_dev + d.q_b0, d.C, SAC_H, 2);
+}
+
+int tb_tqc_actor_grad(int env_kind, int device, void* stream, int batch, const float* actor_dev, const float* critic_dev, const float* log_ent_coef_dev, const float* eps_dev,
+                      float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+  if (int rc = sac_check("tb_tqc_actor_grad", env_kind, batch, workspace_dev, workspace_bytes, true)) return rc;
+  if (!actor_dev || !critic_dev || !log_ent_coef_dev || !eps_dev || !actor_grad_dev || !ent_grad_dev || !stats_dev) return fail(TB_E_INVAL, "tb_tqc_actor_grad: null argument");
+  if (misaligned(actor_dev, 4) || misaligned(critic_dev, 4) || misaligned(log_ent_coef_dev, 4) || misaligned(eps_dev, 4) || misaligned(actor_grad_dev, 4) ||
+      misaligned(ent_grad_dev, 4) || misaligned(stats_dev, 8))
+    return fail(TB_E_INVAL, "tb_tqc_actor_grad: a float array is not 4-byte aligned, or stats not 8-byte aligned");
+  if (actor_grad_dev == actor_dev) return fail(TB_E_INVAL, "tb_tqc_actor_grad: actor_grad_dev must not be actor_dev");
+  if (int rc = ppo_device(device, "tb_tqc_actor_grad: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = tqc_run(env_kind, stream, batch, workspace_dev);
+  const SacDims& d = r.d;
+  const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
+  // the critics as they are now on (s, a~), the mean over their 50 quantiles, and back to their input
+  if (int rc = r.critics(critic_dev, TqcWs::XC, TqcWs::C1, TqcWs::C2, TqcWs::Q)) return rc;
+  if (int rc = launch(tqc_actor_loss_kernel, dim3(1), dim3(256), 0, r.s, (const float*)r.at(TqcWs::Q), (const float*)r.at(TqcWs::LP), log_ent_coef_dev, -(float)d.A, batch,
+                      r.at(TqcWs::DQ), ent_grad_dev, stats_dev))
+    return rc;
+  if (int rc = r.critics_backward<TqcWs>(critic_dev)) return rc;
+  if (int rc = r.backward(r.at(TqcWs::DZ1), SAC_H, BH, critic_dev + d.q_w0, d.C, d.q_one, 1 << 30, 0, nullptr, 0, 0, r.at(TqcWs::DX), SAC_XW, BX, d.C, SAC_H, 2)) return rc;
+  // through tanh and logp to the head's outputs, then the actor's own backward pass: SAC's
+  if (int rc = launch(sac_head_backward_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, (const float*)r.at(TqcWs::ZH), (const float*)r.at(TqcWs::XC),
+                      (const float*)r.at(TqcWs::DX), eps_dev, log_ent_coef_dev, d.O, d.A, batch, r.at(TqcWs::DHD)))
+    return rc;
+  float* gh = actor_grad_dev + d.pi_head;
+  if (int rc = r.wgrad(r.at(TqcWs::DHD), SAC_XW, d.A, r.at(TqcWs::H2), SAC_H, 0, gh, SAC_H, d.pi_block, gh + d.A * SAC_H, SAC_H, d.A, 2)) return rc;
+  if (int rc = r.backward(r.at(TqcWs::DHD), SAC_XW, 0, actor_dev + d.pi_head, SAC_H, 0, d.A, d.A, r.at(TqcWs::H2), SAC_H, 0, r.at(TqcWs::DA2), SAC_H, 0, SAC_H, 2 * d.A, 1)) return rc;
+  if (int rc = r.wgrad(r.at(TqcWs::DA2), SAC_H, 0, r.at(TqcWs::H1), SAC_H, 0, actor_grad_dev + d.pi_w1, SAC_H, 0, actor_grad_dev + d.pi_b1, SAC_H, SAC_H, 1)) return rc;
+  if (int rc = r.backward(r.at(TqcWs::DA2), SAC_H, 0, actor_dev + d.pi_w1, SAC_H, 0, 1 << 30, 0, r.at(TqcWs::H1), SAC_H, 0, r.at(TqcWs::DA1), SAC_H, 0, SAC_H, SAC_H, 1)) return rc;
+  return r.wgrad(r.at(TqcWs::DA1), SAC_H, 0, r.at(TqcWs::X0), SAC_XW, 0, actor_grad_dev + d.pi_w0, d.O, 0, actor_grad_dev + d.pi_b0, d.O, SAC_H, 1);
 }
 
 int tb_rollout(TbHandle* h, int n_steps, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,

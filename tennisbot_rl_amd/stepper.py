@@ -146,6 +146,13 @@ def load_library():
     L.tb_sac_actor_grad.restype = i32
     L.tb_sac_adam.argtypes = [i32, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp, f32]
     L.tb_sac_adam.restype = i32
+    L.tb_tqc_param_floats.argtypes = [i32, i32]
+    L.tb_tqc_param_floats.restype = i32
+    L.tb_tqc_workspace_bytes.argtypes = [i32, i32]
+    L.tb_tqc_workspace_bytes.restype = i64
+    for sac, tqc in ((L.tb_sac_actor_forward, L.tb_tqc_actor_forward), (L.tb_sac_targets, L.tb_tqc_targets), (L.tb_sac_critic_grad, L.tb_tqc_critic_grad),
+                     (L.tb_sac_actor_grad, L.tb_tqc_actor_grad)):   # the same signatures
+        tqc.argtypes, tqc.restype = sac.argtypes, i32
     L.tb_phase.argtypes = [vp]
     L.tb_phase.restype = i32
     L.tb_phase_advance.argtypes = [vp, i32]

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Registers, spills, scratch, LDS and occupancy of every kernel of libtb_stepper.so, as the compiler reports them
 (-Rpass-analysis=kernel-resource-usage; no GPU needed):   python tools/kernel_resources.py [--only PREFIX] [extra hipcc flags]
---only sac_ lists the SAC learner's kernels alone (csrc/tb_sac.hpp), --only tb_trpo_ the TRPO learner's, and so on."""
+--only sac_ lists the SAC learner's kernels alone (csrc/tb_sac.hpp), --only tqc_ TQC's own (csrc/tb_tqc.hpp), --only tb_trpo_ the
+TRPO learner's, and so on."""
 import os
 import re
 import subprocess

@@ -41,7 +41,7 @@ def main():
     ap.add_argument("--save", type=str, default=None, help="default: ./model/ppo_%%s.pt, or ./model/trpo_%%s.pt under -s trpo (%%s: the env id)")
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
     ap.add_argument("--gui", action="store_true", help="accepted for CLI compatibility; there is no GUI")
-    ap.add_argument("-s", "--select", default="ppo", help="ppo or trpo (train_swing.py:102; tennisbot_rl_amd/trpo.py); sac has its own script, train_sac.py; tqc is not provided")
+    ap.add_argument("-s", "--select", default="ppo", help="ppo or trpo (train_swing.py:102; tennisbot_rl_amd/trpo.py); sac and tqc have their own scripts, train_sac.py and train_tqc.py")
     ap.add_argument("--kl-delta", type=float, default=0.01, help="trpo: the trust region's KL bound (agent.py:17)")
     ap.add_argument("--cg-iterations", type=int, default=10, help="trpo: conjugate-gradient iterations")
     ap.add_argument("--cg-damping", type=float, default=0.001, help="trpo: damping added to the Fisher-vector product")
@@ -54,7 +54,7 @@ def main():
     ap.add_argument("--log-json", type=str, default=None)
     args = ap.parse_args()
     if args.select not in ("ppo", "trpo"):
-        sys.exit("only -s ppo and -s trpo are implemented on the batched envs by this script. SAC: train_sac.py")
+        sys.exit("only -s ppo and -s trpo are implemented on the batched envs by this script. SAC: train_sac.py; TQC: train_tqc.py")
     if args.select == "trpo" and args.learner == "torch":
         sys.exit("-s trpo has no torch learner: its update runs as HIP kernels (leave --learner out, or --learner fused)")
     if args.select == "trpo" and int(os.environ.get("WORLD_SIZE", "1")) > 1:

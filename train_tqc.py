@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""`-s sac` of the reference's train.py / train_swing.py on the batched MI355X envs: SB3's SAC with MlpPolicy, its gradient step
-as HIP kernels (tennisbot_rl_amd/sac.py, csrc/tb_sac.hpp).
+"""`-s tqc` of the reference's train_swing.py on the batched MI355X envs: sb3_contrib's TQC with MlpPolicy, its gradient step as
+HIP kernels (tennisbot_rl_amd/tqc.py, csrc/tb_tqc.hpp on csrc/tb_sac.hpp).
 
-  python train_sac.py                                  # SwingRacket-v0, 256 envs, batch 1100 (train_swing.py:93-96)
-  python train_sac.py --env Tennisbot-v0 --curri       # batch 256 (train.py:129-130), the racket-size curriculum
+  python train_tqc.py                                  # SwingRacket-v0, 256 envs, batch 256 (train_swing.py:98-99)
+  python train_tqc.py --env Tennisbot-v0 --curri       # the racket-size curriculum
 
-Hyper-parameters are SB3 1.8.0's SAC defaults as the reference leaves them (lr 3e-4, gamma 0.99, tau 0.005, ent_coef "auto",
-buffer_size 1e6, learning_starts 100). One vector step collects --num-envs transitions and runs --gradient-steps gradient steps
-(default: one per transition, the reference's update-to-data ratio). Checkpoints hold the learner, the replay ring AND the env
-batch state. One rank only. TQC (train_swing.py only) is train_tqc.py.
+Hyper-parameters are sb3_contrib 1.8.0's TQC defaults as the reference leaves them (25 quantiles, 2 critics, 2 dropped per net,
+lr 3e-4, gamma 0.99, tau 0.005, ent_coef "auto", batch_size 256, buffer_size 1e6, learning_starts 100). One vector step collects
+--num-envs transitions and runs --gradient-steps gradient steps (default: one per transition, the reference's update-to-data
+ratio). Checkpoints hold the learner, the replay ring AND the env batch state. One rank only.
 """
 import argparse
 import json
@@ -23,34 +23,34 @@ from train_swing import racket_scale_for  # noqa: E402  (train.py:164-176, one t
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="SAC on SwingRacket-v0 or Tennisbot-v0 (the reference's -s sac)")
+    ap = argparse.ArgumentParser(description="TQC on SwingRacket-v0 or Tennisbot-v0 (the reference's train_swing.py -s tqc)")
     ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
     ap.add_argument("--num-envs", type=int, default=256)
-    ap.add_argument("--batch-size", type=int, default=None, help="default: 1100 on SwingRacket-v0, 256 on Tennisbot-v0, as the reference scripts")
+    ap.add_argument("--batch-size", type=int, default=None, help="default: 256, sb3_contrib's, as the reference script leaves it")
     ap.add_argument("--gradient-steps", type=int, default=None, help="gradient steps per vector step (default: --num-envs, one per transition)")
     ap.add_argument("--buffer-size", type=int, default=1_000_000)
     ap.add_argument("--learning-starts", type=int, default=100, help="timesteps of uniform actions before the first gradient step")
-    ap.add_argument("--total-timesteps", type=float, default=None, help="default: 2e6 SwingRacket-v0 / 1e6 Tennisbot-v0, as the reference")
+    ap.add_argument("--total-timesteps", type=float, default=2e6, help="default: 2e6, as the reference")
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
     ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save")
-    ap.add_argument("--save", type=str, default=None, help="default: ./model/sac_<env id>.pt")
+    ap.add_argument("--save", type=str, default=None, help="default: ./model/tqc_<env id>.pt")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-json", type=str, default=None)
     ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (TB_F_RACKET_GROUND)")
     ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact")
     args = ap.parse_args(argv)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        sys.exit("train_sac.py runs on one rank: multi-rank SAC is not provided")
+        sys.exit("train_tqc.py runs on one rank: multi-rank TQC is not provided")
 
     import torch
-    from tennisbot_rl_amd.sac import SACTrainer
+    from tennisbot_rl_amd.tqc import TQCTrainer
 
-    total = args.total_timesteps or (2e6 if args.env == "SwingRacket-v0" else 1e6)
+    total = args.total_timesteps
     params = None
     if args.racket_ground or args.rolling_friction:
         from tennisbot_rl_amd.params import F_DEFAULT, F_RACKET_GROUND, default_params, reference_rolling_friction
         params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
-    tr = SACTrainer(args.env, num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
+    tr = TQCTrainer(args.env, num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
                     learning_starts=args.learning_starts, seed=args.seed, params=params, device=torch.device("cuda", 0))
     if args.load:
         tr.load(args.load)
@@ -60,7 +60,7 @@ def main(argv=None):
         if args.curri and args.env == "Tennisbot-v0":
             tr.env.set_racket_scale(racket_scale_for(100.0 * tr.num_timesteps / total))
         history += tr.learn(min(total, tr.num_timesteps + chunk))
-    path = args.save or "./model/sac_%s.pt" % args.env
+    path = args.save or "./model/tqc_%s.pt" % args.env
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tr.save(path)
     print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate())

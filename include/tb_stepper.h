@@ -392,6 +392,25 @@ int tb_es_evaluate(TbHandle *h, const float *weights_dev, int n_members, size_t 
                    double *return_dev, int32_t *length_dev, const TbEsTrace *trace_or_null, void *stream);
 
 /*
+ * Whole-episode evaluation of the fused policy: one launch runs every env's whole episode with the network of
+ * tb_policy_step_net inside (csrc/tb_kernels.hpp, tb_policy_evaluate_kernel: 16 envs per two-wave workgroup, only the pi tower).
+ *   weights_dev: the tb_policy_blob_floats(kind, net) blob of pack_policy, 16-byte aligned.
+ *   Sampling, noise keys (noise_seed, global env id, episode, step) and clipping are tb_policy_step_net's; deterministic != 0
+ *     acts on the mean. Per env, the actions are bit for bit those tb_policy_step_net would have produced, step after step.
+ *   return_dev [n_envs] doubles: the float64 sum of the float32 step rewards in step order through the first done;
+ *   length_dev [n_envs]: the episode length in agent steps (SwingRacket: always 26; Tennisbot: <= 1001).
+ * Every call first resets every env exactly as tb_reset(h, NULL, ...) does: env i evaluates the episode whose index is one past
+ * the one it was in (on a fresh handle the k-th call, counted from 0 and with no other reset in between, evaluates episode k),
+ * and on return every env holds that episode's freshly reset state again (the episode phase is 0): no state word is written.
+ * SwingRacket-v0 requires tb_set_pipeline(h, 1) (TB_E_UNSUPPORTED otherwise): the 26th step's fast-forward runs on the
+ * pipeline's kernels. Both results are complete in stream order on `stream` when the call returns -- no tb_flush is needed.
+ * Null arguments: TB_E_INVAL; a (kind, net) pair that is not built: TB_E_PARAMS; nothing is launched on a refusal.
+ * Counters: episodes finished and substeps are counted by the kernel (no host share).
+ */
+int tb_policy_evaluate(TbHandle *h, int net, const float *weights_dev, double *return_dev, int32_t *length_dev,
+                       uint64_t noise_seed, int deterministic, void *stream);
+
+/*
  * The PPO learner (csrc/tb_learner.hpp; tennisbot_rl_amd/learner.py is the caller): GAE, one minibatch's gradient, and the
  * optimiser step, fp32, for the two policy architectures the fused policy kernels are instantiated for. These functions need
  * no env: they take (env_kind, device, stream) instead of a TbHandle, every buffer is caller-owned device memory, and every

@@ -1,6 +1,6 @@
 // tb_kernels.hpp -- the HIP kernels of libtb_stepper.so (gfx950 / MI355X): kernel arguments, state rows, reset, the env logic of both
-// gym envs around tb_device.hpp's substep, and the __global__ entry points (step / rollout, fused policy rollout, fast-forward, reset,
-// init, marks, diagnostics). Included once, by tb_stepper.hip, which holds the host side (handle, launches, C ABI).
+// gym envs around tb_device.hpp's substep, and the __global__ entry points (step / rollout, fused policy rollout, whole-episode policy
+// evaluation, fast-forward, reset, init, marks, diagnostics). Included once, by tb_stepper.hip, which holds the host side (handle, launches, C ABI).
 // Everything here lives in an anonymous namespace of that one translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1076,6 +1076,121 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   flush_counters(A.counters, cnt);
   TB_DIAG_STAMPS_END(st);
   TB_DIAG_ADD_LANE0(9, 1);
+}
+
+// Whole episodes with the policy inside, ONE launch (tb_policy_evaluate): tb_policy_rollout_kernel at S = 1 with the loop of
+// tb_es_rollout_kernel. A workgroup owns 16 envs and is TWO waves: wave 0 is the pi tower (the value head is not needed; the tuned
+// network's shared extractor runs in front of it), its weights resident in registers; wave 1 holds the 16 envs' state in registers
+// (lanes >= 16 step the dummy). Every env starts from the state tb_reset just wrote and runs through its first `done`; a lane whose
+// episode is over steps the dummy from then on (idle_env), and the workgroup leaves once its last env has finished. Returns are
+// summed in float64 in step order, no per-step row is written, and the state words are not written either: on return every env is
+// where tb_reset left it. Sampling, noise keys and clipping are policy_draw / policy_sample_regs: per env the actions are those of
+// tb_policy_step, step after step. SwingRacket's 26th step parks its fast-forward as in tb_es_rollout_kernel (the host folds the
+// terminal reward in afterwards). Static contact rows: where tb_policy_rollout_kernel keeps them.
+// THE LOOP EXIT. Both waves must leave the loop at the same t, or one of them waits at a barrier the other never reaches. The
+// decision is therefore ONE value: after step t the env wave computes go = (__ballot(active) != 0) and its lane 0 writes it to the
+// LDS word s_go BEFORE the barrier "the observations after step t are in LDS". Both waves read s_go only AFTER that barrier, and both
+// evaluate the same expression, t + 1 < T_MAX && s_go: the same t, the same word, hence the same verdict. The word is next written
+// in iteration t + 1, which the env wave does only after the barrier "the action means of step t + 1 are in LDS" -- and the tower
+// wave arrives at that barrier after its read of s_go in iteration t. So no reader can see the next value early or lose the
+// current one. s_mean and s_obs are handed over as in tb_policy_rollout_kernel. Barriers per wave: one behind the set-up, then two
+// per iteration on every path (the exit, by s_go or by T_MAX, is behind an iteration's second barrier in both roles).
+template <int KIND, bool RG, int NET = TB_NET_DEFAULT>
+__global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double* ret_out, int32_t* len_out) {
+  constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE;
+  constexpr int T_MAX = KIND == TB_ENV_SWING ? 26 : 1001;  // tb_es_rollout_kernel's: every episode is over by then
+  __shared__ float4 s_hull[TB_HULL_LDS];
+  __shared__ __attribute__((aligned(16))) float s_mean[E * 8];
+  __shared__ __attribute__((aligned(16))) float s_obs[E * NO];
+  __shared__ int s_go;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  stage_hull(s_hull, A.hull, A.P.n_hull);  // (behind the first barrier of each role below)
+  if (wave == 0) {
+    const int grp = lane >> 4, slot = lane & 15;
+    PolicyRegs<KIND, NET> regs;
+    regs.load(A.pol_weights, 0, lane);
+    __syncthreads();  // the outline table and the episodes' first observations are in LDS
+    for (int t = 0;; ++t) {
+      float x0[TowerRegs<KIND>::NC0], out[4];
+      policy_inputs<KIND>(s_obs + slot * NO, lane, x0);
+      regs.apply(x0, out);
+      if (grp < 2) *reinterpret_cast<float4*>(s_mean + slot * 8 + grp * 4) = make_float4(out[0], out[1], out[2], out[3]);
+      __syncthreads();  // the action means of step t are in LDS
+      __syncthreads();  // the observations after step t, and s_go, are in LDS
+      if (!(t + 1 < T_MAX && __builtin_amdgcn_readfirstlane(s_go) != 0)) break;
+    }
+    return;
+  }
+  const int i = blockIdx.x * E + lane;
+  const bool live = lane < E && i < A.n;
+  EnvRegs e;
+  idle_env(e);
+  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);  // the state tb_reset just wrote: the episode's start, no contacts cached
+  Manifold M;
+  init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
+  uint32_t cnt[TB_N_COUNTERS] = {};
+  {
+    float o[NO];
+    make_obs<KIND>(e, o);
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+    }
+  }
+  __syncthreads();  // the outline table and the episodes' first observations are in LDS
+  float stdv[NA], lstd[NA];
+#pragma unroll
+  for (int k = 0; k < NA; ++k) { lstd[k] = A.pol_weights[PolicyBlob<KIND, NET>::LOG_STD + k]; stdv[k] = expf(lstd[k]); }
+  KParams Pl = A.P;  // (the substep's constants in vector registers: see tb_policy_rollout_kernel)
+#if TB_HINT_POLICY_VGPR_PARAMS
+#define TB_PIN(f) asm volatile("" : "+v"(Pl.f))
+  TB_PIN(dt); TB_PIN(gravity); TB_PIN(lin_damp); TB_PIN(ang_damp); TB_PIN(lin_damp_quad); TB_PIN(ang_damp_quad); TB_PIN(max_ang_step); TB_PIN(contact_threshold);
+  TB_PIN(racket_inv_mass); TB_PIN(racket_inertia[0]); TB_PIN(racket_inertia[1]); TB_PIN(racket_inertia[2]);
+  TB_PIN(racket_inv_inertia[0]); TB_PIN(racket_inv_inertia[1]); TB_PIN(racket_inv_inertia[2]);
+  TB_PIN(racket_half_thick); TB_PIN(hull_margin); TB_PIN(hull_bound_radius); TB_PIN(ball_inv_mass); TB_PIN(ball_radius); TB_PIN(magnus_k); TB_PIN(static_top);
+#undef TB_PIN
+#endif
+  bool active = live;
+  double ret = 0.0;
+  int len = 0;
+  constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);  // tb_policy_rollout_kernel<KIND, 1>'s
+  for (int t = 0;; ++t) {
+    float eps[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) eps[k] = 0.0f;
+    if (active) policy_draw<KIND>(A, i, e, eps);  // while the tower runs
+    __syncthreads();  // the action means of step t are in LDS
+    float a[NA], raw[NA], o[NO];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) { a[k] = 0.0f; raw[k] = 0.0f; }
+    if (active) (void)policy_sample_regs<NA>(s_mean + lane * 8, eps, stdv, lstd, raw, a);
+    int ns = 1;
+    bool d = false, parked = false;
+    float rew;
+    // (every lane of the wave, dummies included: the substep's outline sweep is shared among all 64, SF_WIDE)
+    if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
+    else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
+    if (active) {
+      end_agent_step<KIND, RG, false>(A, i, e, M, parked, ns, (size_t)i, o, d, cnt);  // (tb_policy_evaluate claims a slot for every env)
+      if (!parked) ret += (double)rew;  // the 26th step's reward is the fast-forward's, folded in after the flush
+      len = t + 1;
+      if (d) {
+        cnt[5]++;
+        active = false;
+        idle_env(e);  // from here on this lane steps the dummy
+        M.n = 0; M.deep = 0;
+      } else {
+#pragma unroll
+        for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+      }
+    }
+    const bool go = __ballot(active) != 0ull;
+    if (lane == 0) s_go = go ? 1 : 0;
+    __syncthreads();  // the observations after step t, and s_go, are in LDS
+    if (!(t + 1 < T_MAX && __builtin_amdgcn_readfirstlane(s_go) != 0)) break;
+  }
+  if (live) { ret_out[i] = ret; len_out[i] = len; }
+  flush_counters(A.counters, cnt);
 }
 
 // progress mark (tb_mark_record): one thread bumps a counter in pinned host memory. Relaxed on purpose: the kernels this

@@ -1154,6 +1154,46 @@ int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t 
   return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
 }
 
+namespace {
+// tb_policy_evaluate_kernel<KIND, RG, NET>: the (kind, RG, net) combinations of tb_policy_rollout_kernel
+using EvalKernel = void (*)(KArgs, double*, int32_t*);
+EvalKernel policy_evaluate_kernel(int kind, bool rg, int net) {
+  if (kind == TB_ENV_SWING) return rg ? tb_policy_evaluate_kernel<TB_ENV_SWING, true> : tb_policy_evaluate_kernel<TB_ENV_SWING, false>;
+  if (net == TB_NET_TUNED) return rg ? tb_policy_evaluate_kernel<TB_ENV_TENNIS, true, TB_NET_TUNED> : tb_policy_evaluate_kernel<TB_ENV_TENNIS, false, TB_NET_TUNED>;
+  return rg ? tb_policy_evaluate_kernel<TB_ENV_TENNIS, true> : tb_policy_evaluate_kernel<TB_ENV_TENNIS, false>;
+}
+}  // namespace
+
+int tb_policy_evaluate(TbHandle* h, int net, const float* weights_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
+                       void* stream) {
+  if (!h || !weights_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_policy_evaluate: null argument");
+  if (int rc = policy_net_ok(h->kind, net, "tb_policy_evaluate")) return rc;
+  const bool swing = h->kind == TB_ENV_SWING;
+  if (swing && !h->pipeline)
+    return fail(TB_E_UNSUPPORTED, "tb_policy_evaluate on SwingRacket-v0 needs tb_set_pipeline(h, 1): the 26th step's fast-forward runs on the pipeline's kernels");
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (swing && !h->d_es_rew) HIP_TRY(hipMalloc((void**)&h->d_es_rew, sizeof(float) * (size_t)h->n));
+  if (int rc = tb_reset(h, nullptr, nullptr, stream)) return rc;  // (flushes the pipeline; every env in lockstep at phase 0)
+  KArgs a = base_args(h);
+  a.pol_weights = weights_dev; a.pol_seed = noise_seed; a.pol_deterministic = deterministic;
+  a.reward = h->d_es_rew;  // (SwingRacket: the fast-forward's destination for the 26th step's reward)
+  Park park;
+  if (int rc = claim_park(h, swing, a, s, &park)) return rc;
+  const bool rg = extended_contacts(h->kp);
+  const unsigned groups = (unsigned)((h->n + TB_POLICY_SLICE - 1) / TB_POLICY_SLICE);
+  (void)hipGetLastError();
+  if (int rc = launch(policy_evaluate_kernel(h->kind, rg, net), dim3(groups), dim3(128), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, return_dev,
+                      length_dev))
+    return rc;  // (dynamic LDS: the env wave's columns)
+  if (swing) {
+    if (int rc = finish_park(h, park, a, 0, s)) return rc;
+    if (int rc = flush_all(h, s)) return rc;  // every fast-forward's reward is in d_es_rew once `s` gets past here
+    if (int rc = launch(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n, (float*)nullptr)) return rc;
+  }
+  return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
+}
+
 // ------------------------------------------------------------------------------------------ the PPO learner (tb_learner.hpp)
 int tb_ppo_param_floats(int env_kind) {
   return env_kind == TB_ENV_SWING ? PpoLayout<TB_ENV_SWING>::P : env_kind == TB_ENV_TENNIS ? PpoLayout<TB_ENV_TENNIS>::P : TB_E_INVAL;

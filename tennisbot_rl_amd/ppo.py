@@ -465,7 +465,8 @@ class PPOTrainer:
             stats = {"policy_loss": float(pg.detach()), "value_loss": float(vl.detach()), "entropy": float(entropy.detach())}
         return stats
 
-    def learn(self, total_timesteps, log=print, gather_rollouts=True):
+    def learn(self, total_timesteps, log=print, gather_rollouts=True, schedule=None):
+        """schedule: an evaluation.EvalSchedule, asked after every update whether an evaluation or a checkpoint is due"""
         history = []
         while self.num_timesteps < total_timesteps:
             t0 = time.perf_counter()
@@ -499,6 +500,8 @@ class PPOTrainer:
             if log and self.rank == 0:
                 log("timesteps %10d  episodes %7d  mean episode reward %8.3f  collect %.1f M steps/s  update %.2f s"
                     % (stats["timesteps"], ep, stats["mean_episode_reward"], stats["collect_steps_per_s"] / 1e6, stats["update_s"]))
+            if schedule is not None:
+                schedule.after_rollout(self)
         return history
 
     def evaluate(self, n_episodes_steps=26, deterministic=False):
@@ -515,6 +518,22 @@ class PPOTrainer:
                 self.obs_in.copy_(obs)
                 total += r.sum(); eps += d.float().sum()
         return float(total) / max(float(eps), 1.0)
+
+    def evaluate_episodes(self, n_episodes=64, deterministic=False, n_envs=64):
+        """Mean return over n_episodes WHOLE episodes of the current policy on a separate env batch (evaluation.PolicyEvaluator:
+        one tb_policy_evaluate launch per n_envs episodes): {episodes, mean, std, min, max, mean_length}. The training envs, their
+        episode phase, the captured rollout graph and torch's RNG are not touched, so a run that evaluates is the run that does
+        not. The evaluation envs get the trainer's engine parameters and its CURRENT racket scale (the reference evaluates on the
+        env its curriculum has scaled). Needs fused=True: the policy runs inside the kernel."""
+        if not self.fused:
+            raise StepperError("evaluate_episodes needs fused=True (the architecture the policy kernels are instantiated for)")
+        from .evaluation import PolicyEvaluator
+        ev = getattr(self, "_evaluator", None)
+        if ev is None or ev.n_envs != int(n_envs):
+            ev = self._evaluator = PolicyEvaluator(self.env.kind, n_envs=n_envs, seed=self.env.seed + 1000003, params=self.env.params, device=self.device, net=self.net)
+        if ev.env.params.racket_scale != self.env.params.racket_scale:
+            ev.set_racket_scale(self.env.params.racket_scale)
+        return ev.evaluate(pack_policy(self.policy), n_episodes, deterministic=deterministic)
 
     def save(self, path):
         """policy + optimizer + the env batch itself (the reference checkpoints only the learner,

@@ -418,9 +418,10 @@ class SACTrainer:
             self.train()
         return out
 
-    def learn(self, total_timesteps, log=print, log_every=10):
+    def learn(self, total_timesteps, log=print, log_every=10, schedule=None):
         """vector steps until num_timesteps >= total_timesteps. One read of the device per vector step (losses, entropy
-        coefficient, episode statistics); a progress line every `log_every` vector steps."""
+        coefficient, episode statistics); a progress line every `log_every` vector steps. schedule: an evaluation.EvalSchedule,
+        asked after every vector step whether an evaluation or a checkpoint is due."""
         history, k = [], 0
         t0, steps0 = time.perf_counter(), self._learner.step
         while self.num_timesteps < total_timesteps:
@@ -444,6 +445,8 @@ class SACTrainer:
                     log("timesteps %10d  episodes %7d  mean episode reward %8.3f  ent_coef %.4f  critic loss %.4g  actor loss %.4g  %.0f gradient steps/s"
                         % (self.num_timesteps, ep, rew, stats["ent_coef"], stats["critic_loss"], stats["actor_loss"], stats["gradient_steps_per_s"]))
                 t0, steps0 = now, self._learner.step
+            if schedule is not None:
+                schedule.after_rollout(self)
         return history
 
     def evaluate(self, n_steps=None, deterministic=False):
@@ -461,6 +464,27 @@ class SACTrainer:
                 total += r.sum(); eps += d.float().sum()
         self._ep_return.zero_()
         return float(total) / max(float(eps), 1.0)
+
+    def evaluate_episodes(self, n_episodes=64, deterministic=False, n_envs=64):
+        """Mean return over n_episodes WHOLE episodes of the current actor: {episodes, mean, std, min, max, mean_length}
+        (evaluation.evaluate_actor_episodes). A separate, unpipelined env batch with the trainer's engine parameters is stepped by
+        the torch actor until every env has finished its first episode (the 256-wide actor does not fit the fused policy kernels);
+        the noise comes from a torch.Generator of its own. The training envs, self.obs and torch's global RNG are not touched."""
+        from .evaluation import EVAL_ENV_ID_BASE, evaluate_actor_episodes
+        t = self.torch
+        ev = getattr(self, "_eval_env", None)
+        if ev is None or ev.num_envs != int(n_envs):
+            ev = self._eval_env = BatchedEnv(self.kind, int(n_envs), device=self.device, seed=self.env.seed + 1000003, env_id_base=EVAL_ENV_ID_BASE,
+                                             params=self.env.params, track_terminal_obs=False, pipeline=False)
+            self._eval_gen = t.Generator(device=self.device)
+            self._eval_gen.manual_seed(self.env.seed + 1000003)
+        if ev.params.racket_scale != self.env.params.racket_scale:
+            ev.set_racket_scale(self.env.params.racket_scale)
+        if deterministic:
+            act = self.actor.mean_action
+        else:
+            act = lambda obs: self.actor.sample(obs, t.randn((ev.num_envs, ev.act_dim), device=self.device, generator=self._eval_gen))[0]  # noqa: E731
+        return evaluate_actor_episodes(ev, act, n_episodes)
 
     def save(self, path):
         """the nets, the three optimisers, log_ent_coef, num_timesteps, the env batch's state words and the replay ring with its cursor"""

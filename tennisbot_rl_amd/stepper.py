@@ -97,6 +97,8 @@ def load_library():
     L.tb_es_floats.restype = i32
     L.tb_es_evaluate.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, vp, vp, ctypes.POINTER(TbEsTrace), vp]
     L.tb_es_evaluate.restype = i32
+    L.tb_policy_evaluate.argtypes = [vp, i32, vp, vp, vp, u64, i32, vp]
+    L.tb_policy_evaluate.restype = i32
     f32, f64, i64 = ctypes.c_float, ctypes.c_double, ctypes.c_longlong
     L.tb_ppo_param_floats.argtypes = [i32]
     L.tb_ppo_param_floats.restype = i32
@@ -540,6 +542,22 @@ class BatchedEnv:
                                              None if tr is None else ctypes.byref(tr), self._stream()), "tb_es_evaluate")
         out = (ret.view(M, R), length.view(M, R))
         return out + (rec,) if trace else out
+
+    def policy_evaluate(self, weights, seed=0, deterministic=False, net=NET_DEFAULT):
+        """One whole episode per env with the fused policy inside, in one launch (tb_policy_evaluate). weights: the packed blob of
+        `ppo.pack_policy`; sampling, noise keys and clipping are policy_step's, so every env sees the actions a policy_step loop with
+        the same seed would have given it. Every call resets every env first (the episode after the one it was in) and leaves every
+        env at that episode's freshly reset state. SwingRacket-v0 needs pipeline=True. Returns (returns float64 [N], lengths int32 [N]),
+        complete in stream order."""
+        t, n = self.torch, self.num_envs
+        w = self._check_tensor(weights, (self.policy_floats(net),), t.float32, "weights")
+        if w.data_ptr() % 16:
+            raise ValueError("weights must be 16-byte aligned")
+        ret = t.empty(n, dtype=t.float64, device=self.device)
+        length = t.empty(n, dtype=t.int32, device=self.device)
+        _check(self.L, self.L.tb_policy_evaluate(self._h, int(net), w.data_ptr(), ret.data_ptr(), length.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                 1 if deterministic else 0, self._stream()), "tb_policy_evaluate")
+        return ret, length
 
     def capture(self, fn):
         """Capture `fn()` -- a fixed sequence of step()/step_ptrs()/RolloutBuffer.step_into calls on

@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tennisbot_rl_amd.evaluation import add_schedule_arguments, resolve_load, schedule_from_args  # noqa: E402
 from train_swing import racket_scale_for  # noqa: E402  (train.py:164-176, one table for both scripts)
 
 ENV_ID = "Tennisbot-v0"
@@ -32,7 +33,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="PPO on Tennisbot-v0 (the reference's train.py)")
     ap.add_argument("-s", "--select", default="ppo", help="ppo or tuned_ppo")
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket")
-    ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save")
+    ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save; `best`: best_model.pt beside --save (written under --eval-freq)")
     ap.add_argument("--save", type=str, default=None, help="default: ./model/<select>_Tennisbot-v0.pt")
     ap.add_argument("--gui", action="store_true", help="accepted for CLI compatibility; there is no GUI")
     ap.add_argument("--learner", default="torch", choices=["torch", "fused"], help="fused: GAE, minibatch gradient and Adam as HIP kernels (tennisbot_rl_amd/learner.py)")
@@ -42,6 +43,7 @@ def main(argv=None):
     ap.add_argument("--total-timesteps", type=float, default=1e6)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-json", type=str, default=None)
+    add_schedule_arguments(ap)
     args = ap.parse_args(argv)
     if args.select not in SELECT:
         sys.exit("-s %s: only ppo and tuned_ppo are implemented on the batched envs (trpo: train_swing.py). SAC: train_sac.py" % args.select)
@@ -58,19 +60,26 @@ def main(argv=None):
     hp = {} if args.n_epochs is None else {"n_epochs": args.n_epochs}
     tr = PPOTrainer(ENV_ID, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed,
                     learner=args.learner, policy=SELECT[args.select], **hp)
+    path = args.save or "./model/%s_%s.pt" % (args.select, ENV_ID)
     if args.load:
-        tr.load(args.load)
+        tr.load(resolve_load(args.load, path))
+    schedule = schedule_from_args(args, path)
+    if schedule is not None:
+        schedule.reset(tr.num_timesteps)
     total = args.total_timesteps
     history = []
     while tr.num_timesteps < total:
         if args.curri:
             tr.env.set_racket_scale(racket_scale_for(100.0 * tr.num_timesteps / total))
-        history += tr.learn(min(total, tr.num_timesteps + tr.n_steps * tr.num_envs * world))
+        history += tr.learn(min(total, tr.num_timesteps + tr.n_steps * tr.num_envs * world), schedule=schedule)
     if tr.rank == 0:
-        path = args.save or "./model/%s_%s.pt" % (args.select, ENV_ID)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         tr.save(path)
-        print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate(n_episodes_steps=200))
+        if args.eval_freq:
+            print("saved", path, "eval (%d whole episodes, %s policy):" % (args.n_eval_episodes, "deterministic" if args.eval_deterministic else "stochastic"),
+                  tr.evaluate_episodes(args.n_eval_episodes, deterministic=args.eval_deterministic))
+        else:
+            print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate(n_episodes_steps=200))
         if args.log_json:
             json.dump(history, open(args.log_json, "w"))
     if world > 1:

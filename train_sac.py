@@ -19,6 +19,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tennisbot_rl_amd.evaluation import add_schedule_arguments, resolve_load, schedule_from_args  # noqa: E402
 from train_swing import racket_scale_for  # noqa: E402  (train.py:164-176, one table for every script)
 
 
@@ -32,12 +33,13 @@ def main(argv=None):
     ap.add_argument("--learning-starts", type=int, default=100, help="timesteps of uniform actions before the first gradient step")
     ap.add_argument("--total-timesteps", type=float, default=None, help="default: 2e6 SwingRacket-v0 / 1e6 Tennisbot-v0, as the reference")
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
-    ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save")
+    ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save; `best`: best_model.pt beside --save (written under --eval-freq)")
     ap.add_argument("--save", type=str, default=None, help="default: ./model/sac_<env id>.pt")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-json", type=str, default=None)
     ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (TB_F_RACKET_GROUND)")
     ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact")
+    add_schedule_arguments(ap)
     args = ap.parse_args(argv)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("train_sac.py runs on one rank: multi-rank SAC is not provided")
@@ -52,18 +54,25 @@ def main(argv=None):
         params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
     tr = SACTrainer(args.env, num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
                     learning_starts=args.learning_starts, seed=args.seed, params=params, device=torch.device("cuda", 0))
+    path = args.save or "./model/sac_%s.pt" % args.env
     if args.load:
-        tr.load(args.load)
+        tr.load(resolve_load(args.load, path))
+    schedule = schedule_from_args(args, path)
+    if schedule is not None:
+        schedule.reset(tr.num_timesteps)
     history = []
     chunk = 10 * tr.num_envs
     while tr.num_timesteps < total:
         if args.curri and args.env == "Tennisbot-v0":
             tr.env.set_racket_scale(racket_scale_for(100.0 * tr.num_timesteps / total))
-        history += tr.learn(min(total, tr.num_timesteps + chunk))
-    path = args.save or "./model/sac_%s.pt" % args.env
+        history += tr.learn(min(total, tr.num_timesteps + chunk), schedule=schedule)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tr.save(path)
-    print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate())
+    if args.eval_freq:
+        print("saved", path, "eval (%d whole episodes, %s policy):" % (args.n_eval_episodes, "deterministic" if args.eval_deterministic else "stochastic"),
+              tr.evaluate_episodes(args.n_eval_episodes, deterministic=args.eval_deterministic))
+    else:
+        print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate())
     if args.log_json:
         json.dump(history, open(args.log_json, "w"))
 

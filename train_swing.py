@@ -36,7 +36,7 @@ def main():
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--n-steps", type=int, default=104, help="agent steps per env per rollout (4 SwingRacket episodes)")
     ap.add_argument("--total-timesteps", type=float, default=None, help="default: 2e6 Swing / 1e6 Tennisbot, as the reference")
-    ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save")
+    ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save; `best`: best_model.pt beside --save (written under --eval-freq)")
     ap.add_argument("--load-reference", action="store_true", help="warm start from the reference's shipped ppo_swing policy (tests/golden/ppo_swing_policy.npz)")
     ap.add_argument("--save", type=str, default=None, help="default: ./model/ppo_%%s.pt, or ./model/trpo_%%s.pt under -s trpo (%%s: the env id)")
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
@@ -52,6 +52,8 @@ def main():
     ap.add_argument("--no-fused", action="store_true", help="run the policy as torch modules between env steps instead of inside the step kernel")
     ap.add_argument("--learner", default=None, choices=["torch", "fused"], help="ppo (default torch): fused = GAE, minibatch gradient and Adam as HIP kernels (tennisbot_rl_amd/learner.py); trpo has the fused learner only")
     ap.add_argument("--log-json", type=str, default=None)
+    from tennisbot_rl_amd.evaluation import add_schedule_arguments, resolve_load, schedule_from_args
+    add_schedule_arguments(ap)
     args = ap.parse_args()
     if args.select not in ("ppo", "trpo"):
         sys.exit("only -s ppo and -s trpo are implemented on the batched envs by this script. SAC: train_sac.py; TQC: train_tqc.py")
@@ -86,18 +88,25 @@ def main():
     if args.load_reference:
         import numpy as np
         tr.policy.load_sb3_arrays(dict(np.load(os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz"))))
+    path = args.save % args.env if "%s" in args.save else args.save
     if args.load:
-        tr.load(args.load)
+        tr.load(resolve_load(args.load, path))
+    schedule = schedule_from_args(args, path)
+    if schedule is not None:
+        schedule.reset(tr.num_timesteps)
     history = []
     while tr.num_timesteps < total:
         if args.curri and args.env == "Tennisbot-v0":
             tr.env.set_racket_scale(racket_scale_for(100.0 * tr.num_timesteps / total))
-        history += tr.learn(min(total, tr.num_timesteps + tr.n_steps * tr.num_envs * world))
+        history += tr.learn(min(total, tr.num_timesteps + tr.n_steps * tr.num_envs * world), schedule=schedule)
     if tr.rank == 0:
-        path = args.save % args.env if "%s" in args.save else args.save
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         tr.save(path)
-        print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate())
+        if args.eval_freq:
+            print("saved", path, "eval (%d whole episodes, %s policy):" % (args.n_eval_episodes, "deterministic" if args.eval_deterministic else "stochastic"),
+                  tr.evaluate_episodes(args.n_eval_episodes, deterministic=args.eval_deterministic))
+        else:
+            print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate())
         if args.log_json:
             json.dump(history, open(args.log_json, "w"))
     if world > 1:

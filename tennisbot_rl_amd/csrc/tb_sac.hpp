@@ -41,17 +41,20 @@ template <int KIND> struct SacLayout {
 static_assert(SacLayout<TB_ENV_SWING>::PI_P == 70668 && SacLayout<TB_ENV_TENNIS>::PI_P == 70148, "actor parameter count");
 static_assert(SacLayout<TB_ENV_SWING>::Q_P == 138754 && SacLayout<TB_ENV_TENNIS>::Q_P == 139778, "critic parameter count");
 
-// The workspace: per batch row these many floats, region by region (each region is [B][width], or [2][B][width] for two nets)
-struct SacWs {
+// The workspace: per batch row these many floats, region by region (each region is [B][width], or [2][B][width] for two nets).
+// HW is the padded width of a critic's head rows (QT, Q, DQ); ROW_SUM the floats per row of the critic loss's row sums (RL).
+template <int HW, int ROW_SUM> struct SacWsT {
   // stage (a), kept until stage (d): actor on s
   static constexpr int X0 = 0, H1 = X0 + 16, H2 = H1 + 256, ZH = H2 + 256, XC = ZH + 16, LP = XC + 16;
   // stage (b): actor on s', targets on (s', a')
   static constexpr int NX0 = LP + 16, NH1 = NX0 + 16, NH2 = NH1 + 256, NZH = NH2 + 256, NXC = NZH + 16, NAL = NXC + 16, T1 = NAL + 16, T2 = T1 + 512, QT = T2 + 512;
   // stages (c) and (d): the critics on (s, a), then on (s, a~)
-  static constexpr int XSA = QT + 32, C1 = XSA + 16, C2 = C1 + 512, Q = C2 + 512, DQ = Q + 32, DZ2 = DQ + 32, DZ1 = DZ2 + 512;
+  static constexpr int XSA = QT + 2 * HW, C1 = XSA + 16, C2 = C1 + 512, Q = C2 + 512, DQ = Q + 2 * HW, DZ2 = DQ + 2 * HW, DZ1 = DZ2 + 512;
   // stage (d): the critics' input gradient, the actor's backward pass
-  static constexpr int DX = DZ1 + 512, DHD = DX + 32, DA2 = DHD + 16, DA1 = DA2 + 256, PER_ROW = DA1 + 256;
+  static constexpr int DX = DZ1 + 512, DHD = DX + 32, DA2 = DHD + 16, DA1 = DA2 + 256, RL = DA1 + 256, PER_ROW = RL + ROW_SUM;
 };
+using SacWs = SacWsT<SAC_XW, 0>;
+static_assert(SacWs::QT == 2176 && SacWs::Q == 3248 && SacWs::DQ == 3280 && SacWs::DX == 4336 && SacWs::PER_ROW == 4896, "SAC's workspace layout");
 
 TB_DEV long long sac_row(const long long* idx, int b, long long n_rows) {
   long long r = idx[b];

@@ -1413,7 +1413,8 @@ int tb_trpo_search(int env_kind, int device, void* stream, const float* obs_dev,
   return launch(tb_trpo_search_reduce_kernel, dim3((unsigned)n_candidates), dim3(256), 0, s, (const double*)partials, shares, batch, out_dev);
 }
 
-// --------------------------------------------------------------------------------------------- the SAC learner (tb_sac.hpp)
+// --------------------------------------------------------------------------------------------- the SAC and TQC learners (tb_sac.hpp, tb_tqc.hpp)
+// Every stage is written once, as a template over an algorithm descriptor (SacAlgo, TqcAlgo); the C entry points forward to it.
 extern "C++" {
 namespace {
 struct SacDims {  // SacLayout<KIND> at run time
@@ -1423,7 +1424,13 @@ template <int KIND> SacDims sac_dims_of() {
   using L = SacLayout<KIND>;
   return {L::O, L::A, L::C, L::PI_W0, L::PI_B0, L::PI_W1, L::PI_B1, L::PI_HEAD, L::PI_HEAD_BLOCK, L::PI_P, L::Q_W0, L::Q_B0, L::Q_W1, L::Q_B1, L::Q_W2, L::Q_B2, L::Q_ONE, L::Q_P};
 }
-SacDims sac_dims(int env_kind) { return env_kind == TB_ENV_SWING ? sac_dims_of<TB_ENV_SWING>() : sac_dims_of<TB_ENV_TENNIS>(); }
+// TQC: SAC's dims with the critic's 25-wide last layer
+template <int KIND> SacDims tqc_dims_of() {
+  using L = TqcLayout<KIND>;
+  SacDims d = sac_dims_of<KIND>();
+  d.q_w2 = L::Q_W2; d.q_b2 = L::Q_B2; d.q_one = L::Q_ONE; d.q_p = L::Q_P;
+  return d;
+}
 
 unsigned sac_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
@@ -1432,7 +1439,7 @@ struct SacRun {  // one stage's launches: the dims, the stream, the batch and th
   hipStream_t s;
   int B;
   float* ws;
-  int heads = 1, hw = SAC_XW;  // a critic's outputs and the padded width of its head rows: 1 / 16 for SAC, 25 / 32 for TQC
+  int heads, hw;  // a critic's outputs and the padded width of its head rows: 1 / 16 for SAC, 25 / 32 for TQC
   float* at(int region) const { return ws + (size_t)region * (size_t)B; }
 
   int forward(bool relu, const float* x, int xs, long long xz, const float* w, int wrs, long long wz, const float* bias, float* y, int ys, long long yz, int K, int M, int nets) const {
@@ -1450,6 +1457,10 @@ struct SacRun {  // one stage's launches: the dims, the stream, the batch and th
     SacWgradArgs a = {dz, dzs, dzz, h, hs, hz, gw, wrs, wz, gb, B, K, M};
     return launch(sac_wgrad_kernel, dim3(sac_blocks(K, 64), sac_blocks(M, 16), (unsigned)nets), dim3(256), 0, s, a);
   }
+  // rows idx of obs, and of action beside them where there is one, into the 16-wide rows of region x
+  int gather(const float* obs, const float* action, const int64_t* idx, long long n_rows, int x) const {
+    return launch(sac_gather_kernel, dim3(sac_blocks((long long)B * 16, 256)), dim3(256), 0, s, obs, d.O, action, action ? d.A : 0, (const long long*)idx, n_rows, B, at(x));
+  }
   // the actor on the gathered rows x0: h1, h2, the head's outputs zh; then the sample: act / logp out, xc = obs | sample, lp
   int actor(const float* actor, const float* eps, int x0, int h1, int h2, int zh, int xc, int lp, float* act_out, float* logp_out) const {
     if (int rc = forward(true, at(x0), SAC_XW, 0, actor + d.pi_w0, d.O, 0, actor + d.pi_b0, at(h1), SAC_H, 0, d.O, SAC_H, 1)) return rc;
@@ -1465,148 +1476,219 @@ struct SacRun {  // one stage's launches: the dims, the stream, the batch and th
     return forward(false, at(h2), SAC_H, BH, critic + d.q_w2, SAC_H, d.q_one, critic + d.q_b2, at(q), hw, (long long)B * hw, SAC_H, heads, 2);
   }
   // dq [2][B][hw] back to dz2 and dz1 [2][B][256] through both nets, in the regions of the workspace layout Ws
-  template <class Ws = SacWs> int critics_backward(const float* critic) const {
+  template <class Ws> int critics_backward(const float* critic) const {
     const long long BH = (long long)B * SAC_H;
     if (int rc = backward(at(Ws::DQ), hw, (long long)B * hw, critic + d.q_w2, SAC_H, d.q_one, 1 << 30, 0, at(Ws::C2), SAC_H, BH, at(Ws::DZ2), SAC_H, BH, SAC_H, heads, 2)) return rc;
     return backward(at(Ws::DZ2), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, 1 << 30, 0, at(Ws::C1), SAC_H, BH, at(Ws::DZ1), SAC_H, BH, SAC_H, SAC_H, 2);
   }
 };
 
-int sac_check(const char* what, int env_kind, int batch, const void* workspace_dev, size_t workspace_bytes, bool tqc = false) {
-  static thread_local char msg[160];
-  if (!kind_ok(env_kind)) { snprintf(msg, sizeof msg, "%s: unknown env kind", what); return fail(TB_E_INVAL, msg); }
-  if (batch < 1) { snprintf(msg, sizeof msg, "%s: batch must be >= 1", what); return fail(TB_E_INVAL, msg); }
-  if (!workspace_dev) { snprintf(msg, sizeof msg, "%s: null argument (the workspace)", what); return fail(TB_E_INVAL, msg); }
-  if (reinterpret_cast<uintptr_t>(workspace_dev) % 8 != 0) { snprintf(msg, sizeof msg, "%s: the workspace must be 8-byte aligned", what); return fail(TB_E_INVAL, msg); }
-  if ((long long)workspace_bytes < (tqc ? tb_tqc_workspace_bytes(env_kind, batch) : tb_sac_workspace_bytes(env_kind, batch))) {
-    snprintf(msg, sizeof msg, "%s: the workspace is smaller than %s", what, tqc ? "tb_tqc_workspace_bytes" : "tb_sac_workspace_bytes");
-    return fail(TB_E_PARAMS, msg);
+// What is an algorithm's own in a stage: its layouts, a critic's head count and padded head width, the name of its workspace
+// query, and the launches of its targets and its two losses. The target and actor-loss kernels of both take the same arguments,
+// which the stage lists; the critic loss is one launch in SAC and two in TQC (the rows' sums into RL, then their sum).
+struct SacAlgo {
+  using Ws = SacWs;
+  static constexpr int HEADS = 1, HW = SAC_XW;
+  static constexpr const char* WS_QUERY = "tb_sac_workspace_bytes";
+  static SacDims dims(int env_kind) { return env_kind == TB_ENV_SWING ? sac_dims_of<TB_ENV_SWING>() : sac_dims_of<TB_ENV_TENNIS>(); }
+  template <class... A> static int targets(const SacRun& r, const A&... a) { return launch(sac_target_kernel, dim3(sac_blocks(r.B, 256)), dim3(256), 0, r.s, a...); }
+  static int critic_loss(const SacRun& r, const float* y, double* stats) {
+    return launch(sac_critic_loss_kernel, dim3(1), dim3(256), 0, r.s, (const float*)r.at(Ws::Q), y, r.B, r.at(Ws::DQ), stats);
   }
-  return TB_OK;
+  template <class... A> static int actor_loss(const SacRun& r, const A&... a) { return launch(sac_actor_loss_kernel, dim3(1), dim3(256), 0, r.s, a...); }  // the critics' min
+};
+struct TqcAlgo {
+  using Ws = TqcWs;
+  static constexpr int HEADS = TQC_Q, HW = TQC_HW;
+  static constexpr const char* WS_QUERY = "tb_tqc_workspace_bytes";
+  static SacDims dims(int env_kind) { return env_kind == TB_ENV_SWING ? tqc_dims_of<TB_ENV_SWING>() : tqc_dims_of<TB_ENV_TENNIS>(); }
+  template <class... A> static int targets(const SacRun& r, const A&... a) { return launch(tqc_target_kernel, dim3(sac_blocks(r.B, 4)), dim3(256), 0, r.s, a...); }
+  static int critic_loss(const SacRun& r, const float* y, double* stats) {
+    double* row_loss = reinterpret_cast<double*>(r.at(Ws::RL));
+    if (int rc = launch(tqc_critic_loss_kernel, dim3(sac_blocks(r.B, 4)), dim3(256), 0, r.s, (const float*)r.at(Ws::Q), y, r.B, r.at(Ws::DQ), row_loss)) return rc;
+    return launch(tqc_loss_sum_kernel, dim3(1), dim3(256), 0, r.s, (const double*)row_loss, r.B, stats);
+  }
+  template <class... A> static int actor_loss(const SacRun& r, const A&... a) { return launch(tqc_actor_loss_kernel, dim3(1), dim3(256), 0, r.s, a...); }  // their 50 quantiles' mean
+};
+
+int sac_fail(int code, const char* what, const char* words, const char* more = "") {
+  char msg[192];
+  snprintf(msg, sizeof msg, "%s: %s%s", what, words, more);
+  return fail(code, msg);
 }
 
-// TQC: SAC's dims with the critic's 25-wide last layer
-template <int KIND> SacDims tqc_dims_of() {
-  using L = TqcLayout<KIND>;
-  SacDims d = sac_dims_of<KIND>();
-  d.q_w2 = L::Q_W2; d.q_b2 = L::Q_B2; d.q_one = L::Q_ONE; d.q_p = L::Q_P;
-  return d;
+// What a stage refuses before its first launch, in this order: the env kind, the batch and the workspace; null pointers;
+// n_rows; alignment (wide8 names what must be 8-byte aligned); aliasing (aliased: the words of the refusal, or null); the device.
+template <class Algo>
+int sac_check(const char* what, int env_kind, int batch, const void* workspace_dev, size_t workspace_bytes, bool any_null, long long n_rows, bool any_misaligned,
+              const char* wide8, const char* aliased, int device) {
+  if (!kind_ok(env_kind)) return sac_fail(TB_E_INVAL, what, "unknown env kind");
+  if (batch < 1) return sac_fail(TB_E_INVAL, what, "batch must be >= 1");
+  if (!workspace_dev) return sac_fail(TB_E_INVAL, what, "null argument (the workspace)");
+  if (misaligned(workspace_dev, 8)) return sac_fail(TB_E_INVAL, what, "the workspace must be 8-byte aligned");
+  if ((long long)workspace_bytes < (long long)sizeof(float) * Algo::Ws::PER_ROW * (long long)batch) return sac_fail(TB_E_PARAMS, what, "the workspace is smaller than ", Algo::WS_QUERY);
+  if (any_null) return sac_fail(TB_E_INVAL, what, "null argument");
+  if (n_rows < 1) return sac_fail(TB_E_INVAL, what, "n_rows must be >= 1");
+  if (any_misaligned) return sac_fail(TB_E_INVAL, what, "a float array is not 4-byte aligned, or ", wide8);
+  if (aliased) return sac_fail(TB_E_INVAL, what, aliased);
+  char msg[96];
+  snprintf(msg, sizeof msg, "%s: device index out of range", what);
+  return ppo_device(device, msg);
 }
-SacRun tqc_run(int env_kind, void* stream, int batch, void* workspace_dev) {
-  return {env_kind == TB_ENV_SWING ? tqc_dims_of<TB_ENV_SWING>() : tqc_dims_of<TB_ENV_TENNIS>(), (hipStream_t)stream, batch, (float*)workspace_dev, TQC_Q, TQC_HW};
+template <class Algo> SacRun sac_run(int env_kind, void* stream, int batch, void* workspace_dev) {
+  return {Algo::dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev, Algo::HEADS, Algo::HW};
+}
+
+template <class Algo> int sac_param_floats(const char* what, int env_kind, int which) {
+  if (!kind_ok(env_kind)) return sac_fail(TB_E_INVAL, what, "unknown env kind");
+  if (which != TB_SAC_ACTOR && which != TB_SAC_CRITIC) return sac_fail(TB_E_INVAL, what, "which must be TB_SAC_ACTOR or TB_SAC_CRITIC");
+  const SacDims d = Algo::dims(env_kind);
+  return which == TB_SAC_ACTOR ? d.pi_p : d.q_p;
+}
+template <class Algo> long long sac_workspace_bytes(const char* what, int env_kind, int batch) {
+  if (!kind_ok(env_kind) || batch < 1) return sac_fail(TB_E_INVAL, what, "unknown env kind, or batch < 1");
+  return (long long)sizeof(float) * Algo::Ws::PER_ROW * (long long)batch;
+}
+
+template <class Algo>
+int sac_actor_forward(const char* what, int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* actor_dev,
+                      const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes) {
+  using Ws = typename Algo::Ws;
+  if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes, !obs_dev || !idx_dev || !actor_dev || !eps_dev || !act_out_dev || !logp_out_dev, n_rows,
+                               misaligned(obs_dev, 4) || misaligned(actor_dev, 4) || misaligned(eps_dev, 4) || misaligned(act_out_dev, 4) || misaligned(logp_out_dev, 4) ||
+                                   misaligned(idx_dev, 8),
+                               "idx not 8-byte aligned", nullptr, device))
+    return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
+  if (int rc = r.gather(obs_dev, nullptr, idx_dev, n_rows, Ws::X0)) return rc;
+  return r.actor(actor_dev, eps_dev, Ws::X0, Ws::H1, Ws::H2, Ws::ZH, Ws::XC, Ws::LP, act_out_dev, logp_out_dev);
+}
+
+template <class Algo>
+int sac_targets(const char* what, int env_kind, int device, void* stream, const float* next_obs_dev, const float* reward_dev, const float* done_dev, long long n_rows,
+                const int64_t* idx_dev, int batch, const float* actor_dev, const float* target_dev, const float* log_ent_coef_dev, const float* eps_next_dev, float gamma,
+                float* y_dev, void* workspace_dev, size_t workspace_bytes) {
+  using Ws = typename Algo::Ws;
+  if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes,
+                               !next_obs_dev || !reward_dev || !done_dev || !idx_dev || !actor_dev || !target_dev || !log_ent_coef_dev || !eps_next_dev || !y_dev, n_rows,
+                               misaligned(next_obs_dev, 4) || misaligned(reward_dev, 4) || misaligned(done_dev, 4) || misaligned(actor_dev, 4) || misaligned(target_dev, 4) ||
+                                   misaligned(log_ent_coef_dev, 4) || misaligned(eps_next_dev, 4) || misaligned(y_dev, 4) || misaligned(idx_dev, 8),
+                               "idx not 8-byte aligned", nullptr, device))
+    return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
+  if (int rc = r.gather(next_obs_dev, nullptr, idx_dev, n_rows, Ws::NX0)) return rc;
+  if (int rc = r.actor(actor_dev, eps_next_dev, Ws::NX0, Ws::NH1, Ws::NH2, Ws::NZH, Ws::NXC, Ws::NAL, nullptr, nullptr)) return rc;  // logp' in NAL
+  if (int rc = r.critics(target_dev, Ws::NXC, Ws::T1, Ws::T2, Ws::QT)) return rc;
+  return Algo::targets(r, reward_dev, done_dev, (const long long*)idx_dev, n_rows, batch, (const float*)r.at(Ws::QT), (const float*)r.at(Ws::NAL), log_ent_coef_dev, gamma, y_dev);
+}
+
+template <class Algo>
+int sac_critic_grad(const char* what, int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev, int batch,
+                    const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+  using Ws = typename Algo::Ws;
+  if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes, !obs_dev || !action_dev || !idx_dev || !critic_dev || !y_dev || !grad_dev || !stats_dev, n_rows,
+                               misaligned(obs_dev, 4) || misaligned(action_dev, 4) || misaligned(critic_dev, 4) || misaligned(y_dev, 4) || misaligned(grad_dev, 4) ||
+                                   misaligned(idx_dev, 8) || misaligned(stats_dev, 8),
+                               "idx / stats not 8-byte aligned", grad_dev == critic_dev ? "grad_dev must not be critic_dev" : nullptr, device))
+    return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
+  const SacDims& d = r.d;
+  const long long BH = (long long)batch * SAC_H;
+  if (int rc = r.gather(obs_dev, action_dev, idx_dev, n_rows, Ws::XSA)) return rc;
+  if (int rc = r.critics(critic_dev, Ws::XSA, Ws::C1, Ws::C2, Ws::Q)) return rc;
+  if (int rc = Algo::critic_loss(r, y_dev, stats_dev)) return rc;
+  if (int rc = r.template critics_backward<Ws>(critic_dev)) return rc;
+  if (int rc = r.wgrad(r.at(Ws::DQ), r.hw, (long long)batch * r.hw, r.at(Ws::C2), SAC_H, BH, grad_dev + d.q_w2, SAC_H, d.q_one, grad_dev + d.q_b2, SAC_H, r.heads, 2)) return rc;
+  if (int rc = r.wgrad(r.at(Ws::DZ2), SAC_H, BH, r.at(Ws::C1), SAC_H, BH, grad_dev + d.q_w1, SAC_H, d.q_one, grad_dev + d.q_b1, SAC_H, SAC_H, 2)) return rc;
+  return r.wgrad(r.at(Ws::DZ1), SAC_H, BH, r.at(Ws::XSA), SAC_XW, 0, grad_dev + d.q_w0, d.C, d.q_one, grad_dev + d.q_b0, d.C, SAC_H, 2);
+}
+
+template <class Algo>
+int sac_actor_grad(const char* what, int env_kind, int device, void* stream, int batch, const float* actor_dev, const float* critic_dev, const float* log_ent_coef_dev,
+                   const float* eps_dev, float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+  using Ws = typename Algo::Ws;
+  if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes,
+                               !actor_dev || !critic_dev || !log_ent_coef_dev || !eps_dev || !actor_grad_dev || !ent_grad_dev || !stats_dev, 1,
+                               misaligned(actor_dev, 4) || misaligned(critic_dev, 4) || misaligned(log_ent_coef_dev, 4) || misaligned(eps_dev, 4) || misaligned(actor_grad_dev, 4) ||
+                                   misaligned(ent_grad_dev, 4) || misaligned(stats_dev, 8),
+                               "stats not 8-byte aligned", actor_grad_dev == actor_dev ? "actor_grad_dev must not be actor_dev" : nullptr, device))
+    return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
+  const SacDims& d = r.d;
+  const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
+  // the critics as they are now on (s, a~), the algorithm's statistic of them, and back to their input
+  if (int rc = r.critics(critic_dev, Ws::XC, Ws::C1, Ws::C2, Ws::Q)) return rc;
+  if (int rc = Algo::actor_loss(r, (const float*)r.at(Ws::Q), (const float*)r.at(Ws::LP), log_ent_coef_dev, -(float)d.A, batch, r.at(Ws::DQ), ent_grad_dev, stats_dev)) return rc;
+  if (int rc = r.template critics_backward<Ws>(critic_dev)) return rc;
+  if (int rc = r.backward(r.at(Ws::DZ1), SAC_H, BH, critic_dev + d.q_w0, d.C, d.q_one, 1 << 30, 0, nullptr, 0, 0, r.at(Ws::DX), SAC_XW, BX, d.C, SAC_H, 2)) return rc;
+  // through tanh and logp to the head's outputs, then the actor's own backward pass
+  if (int rc = launch(sac_head_backward_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, (const float*)r.at(Ws::ZH), (const float*)r.at(Ws::XC),
+                      (const float*)r.at(Ws::DX), eps_dev, log_ent_coef_dev, d.O, d.A, batch, r.at(Ws::DHD)))
+    return rc;
+  float* gh = actor_grad_dev + d.pi_head;
+  if (int rc = r.wgrad(r.at(Ws::DHD), SAC_XW, d.A, r.at(Ws::H2), SAC_H, 0, gh, SAC_H, d.pi_block, gh + d.A * SAC_H, SAC_H, d.A, 2)) return rc;
+  if (int rc = r.backward(r.at(Ws::DHD), SAC_XW, 0, actor_dev + d.pi_head, SAC_H, 0, d.A, d.A, r.at(Ws::H2), SAC_H, 0, r.at(Ws::DA2), SAC_H, 0, SAC_H, 2 * d.A, 1)) return rc;
+  if (int rc = r.wgrad(r.at(Ws::DA2), SAC_H, 0, r.at(Ws::H1), SAC_H, 0, actor_grad_dev + d.pi_w1, SAC_H, 0, actor_grad_dev + d.pi_b1, SAC_H, SAC_H, 1)) return rc;
+  if (int rc = r.backward(r.at(Ws::DA2), SAC_H, 0, actor_dev + d.pi_w1, SAC_H, 0, 1 << 30, 0, r.at(Ws::H1), SAC_H, 0, r.at(Ws::DA1), SAC_H, 0, SAC_H, SAC_H, 1)) return rc;
+  return r.wgrad(r.at(Ws::DA1), SAC_H, 0, r.at(Ws::X0), SAC_XW, 0, actor_grad_dev + d.pi_w0, d.O, 0, actor_grad_dev + d.pi_b0, d.O, SAC_H, 1);
 }
 }  // namespace
 }  // extern "C++"
 
-int tb_sac_param_floats(int env_kind, int which) {
-  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_sac_param_floats: unknown env kind");
-  if (which != TB_SAC_ACTOR && which != TB_SAC_CRITIC) return fail(TB_E_INVAL, "tb_sac_param_floats: which must be TB_SAC_ACTOR or TB_SAC_CRITIC");
-  const SacDims d = sac_dims(env_kind);
-  return which == TB_SAC_ACTOR ? d.pi_p : d.q_p;
-}
+int tb_sac_param_floats(int env_kind, int which) { return sac_param_floats<SacAlgo>(__func__, env_kind, which); }
+int tb_tqc_param_floats(int env_kind, int which) { return sac_param_floats<TqcAlgo>(__func__, env_kind, which); }
 int tb_sac_rows_per_workgroup(void) { return SAC_ROWS_PER_WG; }
-long long tb_sac_workspace_bytes(int env_kind, int batch) {
-  if (!kind_ok(env_kind) || batch < 1) return fail(TB_E_INVAL, "tb_sac_workspace_bytes: unknown env kind, or batch < 1");
-  return (long long)sizeof(float) * SacWs::PER_ROW * (long long)batch;
-}
+long long tb_sac_workspace_bytes(int env_kind, int batch) { return sac_workspace_bytes<SacAlgo>(__func__, env_kind, batch); }
+long long tb_tqc_workspace_bytes(int env_kind, int batch) { return sac_workspace_bytes<TqcAlgo>(__func__, env_kind, batch); }
 
 int tb_sac_actor_forward(int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* actor_dev,
                          const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes) {
-  if (int rc = sac_check("tb_sac_actor_forward", env_kind, batch, workspace_dev, workspace_bytes)) return rc;
-  if (!obs_dev || !idx_dev || !actor_dev || !eps_dev || !act_out_dev || !logp_out_dev) return fail(TB_E_INVAL, "tb_sac_actor_forward: null argument");
-  if (n_rows < 1) return fail(TB_E_INVAL, "tb_sac_actor_forward: n_rows must be >= 1");
-  if (misaligned(obs_dev, 4) || misaligned(actor_dev, 4) || misaligned(eps_dev, 4) || misaligned(act_out_dev, 4) || misaligned(logp_out_dev, 4) || misaligned(idx_dev, 8))
-    return fail(TB_E_INVAL, "tb_sac_actor_forward: a float array is not 4-byte aligned, or idx not 8-byte aligned");
-  if (int rc = ppo_device(device, "tb_sac_actor_forward: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  const SacRun r = {sac_dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev};
-  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, obs_dev, r.d.O, (const float*)nullptr, 0, (const long long*)idx_dev, n_rows,
-                      batch, r.at(SacWs::X0)))
-    return rc;
-  return r.actor(actor_dev, eps_dev, SacWs::X0, SacWs::H1, SacWs::H2, SacWs::ZH, SacWs::XC, SacWs::LP, act_out_dev, logp_out_dev);
+  return sac_actor_forward<SacAlgo>(__func__, env_kind, device, stream, obs_dev, n_rows, idx_dev, batch, actor_dev, eps_dev, act_out_dev, logp_out_dev, workspace_dev, workspace_bytes);
+}
+int tb_tqc_actor_forward(int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* actor_dev,
+                         const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes) {
+  return sac_actor_forward<TqcAlgo>(__func__, env_kind, device, stream, obs_dev, n_rows, idx_dev, batch, actor_dev, eps_dev, act_out_dev, logp_out_dev, workspace_dev, workspace_bytes);
 }
 
 int tb_sac_targets(int env_kind, int device, void* stream, const float* next_obs_dev, const float* reward_dev, const float* done_dev, long long n_rows,
                    const int64_t* idx_dev, int batch, const float* actor_dev, const float* target_dev, const float* log_ent_coef_dev, const float* eps_next_dev,
                    float gamma, float* y_dev, void* workspace_dev, size_t workspace_bytes) {
-  if (int rc = sac_check("tb_sac_targets", env_kind, batch, workspace_dev, workspace_bytes)) return rc;
-  if (!next_obs_dev || !reward_dev || !done_dev || !idx_dev || !actor_dev || !target_dev || !log_ent_coef_dev || !eps_next_dev || !y_dev)
-    return fail(TB_E_INVAL, "tb_sac_targets: null argument");
-  if (n_rows < 1) return fail(TB_E_INVAL, "tb_sac_targets: n_rows must be >= 1");
-  if (misaligned(next_obs_dev, 4) || misaligned(reward_dev, 4) || misaligned(done_dev, 4) || misaligned(actor_dev, 4) || misaligned(target_dev, 4) ||
-      misaligned(log_ent_coef_dev, 4) || misaligned(eps_next_dev, 4) || misaligned(y_dev, 4) || misaligned(idx_dev, 8))
-    return fail(TB_E_INVAL, "tb_sac_targets: a float array is not 4-byte aligned, or idx not 8-byte aligned");
-  if (int rc = ppo_device(device, "tb_sac_targets: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  const SacRun r = {sac_dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev};
-  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, next_obs_dev, r.d.O, (const float*)nullptr, 0, (const long long*)idx_dev,
-                      n_rows, batch, r.at(SacWs::NX0)))
-    return rc;
-  if (int rc = r.actor(actor_dev, eps_next_dev, SacWs::NX0, SacWs::NH1, SacWs::NH2, SacWs::NZH, SacWs::NXC, SacWs::NAL, nullptr, nullptr)) return rc;  // logp' in NAL
-  if (int rc = r.critics(target_dev, SacWs::NXC, SacWs::T1, SacWs::T2, SacWs::QT)) return rc;
-  return launch(sac_target_kernel, dim3(sac_blocks(batch, 256)), dim3(256), 0, r.s, reward_dev, done_dev, (const long long*)idx_dev, n_rows, batch, (const float*)r.at(SacWs::QT),
-                (const float*)r.at(SacWs::NAL), log_ent_coef_dev, gamma, y_dev);
+  return sac_targets<SacAlgo>(__func__, env_kind, device, stream, next_obs_dev, reward_dev, done_dev, n_rows, idx_dev, batch, actor_dev, target_dev, log_ent_coef_dev, eps_next_dev,
+                              gamma, y_dev, workspace_dev, workspace_bytes);
+}
+int tb_tqc_targets(int env_kind, int device, void* stream, const float* next_obs_dev, const float* reward_dev, const float* done_dev, long long n_rows,
+                   const int64_t* idx_dev, int batch, const float* actor_dev, const float* target_dev, const float* log_ent_coef_dev, const float* eps_next_dev,
+                   float gamma, float* y_dev, void* workspace_dev, size_t workspace_bytes) {
+  return sac_targets<TqcAlgo>(__func__, env_kind, device, stream, next_obs_dev, reward_dev, done_dev, n_rows, idx_dev, batch, actor_dev, target_dev, log_ent_coef_dev, eps_next_dev,
+                              gamma, y_dev, workspace_dev, workspace_bytes);
 }
 
 int tb_sac_critic_grad(int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev, int batch,
                        const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
-  if (int rc = sac_check("tb_sac_critic_grad", env_kind, batch, workspace_dev, workspace_bytes)) return rc;
-  if (!obs_dev || !action_dev || !idx_dev || !critic_dev || !y_dev || !grad_dev || !stats_dev) return fail(TB_E_INVAL, "tb_sac_critic_grad: null argument");
-  if (n_rows < 1) return fail(TB_E_INVAL, "tb_sac_critic_grad: n_rows must be >= 1");
-  if (misaligned(obs_dev, 4) || misaligned(action_dev, 4) || misaligned(critic_dev, 4) || misaligned(y_dev, 4) || misaligned(grad_dev, 4) || misaligned(idx_dev, 8) ||
-      misaligned(stats_dev, 8))
-    return fail(TB_E_INVAL, "tb_sac_critic_grad: a float array is not 4-byte aligned, or idx / stats not 8-byte aligned");
-  if (grad_dev == critic_dev) return fail(TB_E_INVAL, "tb_sac_critic_grad: grad_dev must not be critic_dev");
-  if (int rc = ppo_device(device, "tb_sac_critic_grad: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  const SacRun r = {sac_dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev};
-  const SacDims& d = r.d;
-  const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
-  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, obs_dev, d.O, action_dev, d.A, (const long long*)idx_dev, n_rows, batch,
-                      r.at(SacWs::XSA)))
-    return rc;
-  if (int rc = r.critics(critic_dev, SacWs::XSA, SacWs::C1, SacWs::C2, SacWs::Q)) return rc;
-  if (int rc = launch(sac_critic_loss_kernel, dim3(1), dim3(256), 0, r.s, (const float*)r.at(SacWs::Q), y_dev, batch, r.at(SacWs::DQ), stats_dev)) return rc;
-  if (int rc = r.critics_backward(critic_dev)) return rc;
-  if (int rc = r.wgrad(r.at(SacWs::DQ), SAC_XW, BX, r.at(SacWs::C2), SAC_H, BH, grad_dev + d.q_w2, SAC_H, d.q_one, grad_dev + d.q_b2, SAC_H, 1, 2)) return rc;
-  if (int rc = r.wgrad(r.at(SacWs::DZ2), SAC_H, BH, r.at(SacWs::C1), SAC_H, BH, grad_dev + d.q_w1, SAC_H, d.q_one, grad_dev + d.q_b1, SAC_H, SAC_H, 2)) return rc;
-  return r.wgrad(r.at(SacWs::DZ1), SAC_H, BH, r.at(SacWs::XSA), SAC_XW, 0, grad_dev + d.q_w0, d.C, d.q_one, grad_dev + d.q_b0, d.C, SAC_H, 2);
+  return sac_critic_grad<SacAlgo>(__func__, env_kind, device, stream, obs_dev, action_dev, n_rows, idx_dev, batch, critic_dev, y_dev, grad_dev, stats_dev, workspace_dev, workspace_bytes);
+}
+int tb_tqc_critic_grad(int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev, int batch,
+                       const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+  return sac_critic_grad<TqcAlgo>(__func__, env_kind, device, stream, obs_dev, action_dev, n_rows, idx_dev, batch, critic_dev, y_dev, grad_dev, stats_dev, workspace_dev, workspace_bytes);
 }
 
 int tb_sac_actor_grad(int env_kind, int device, void* stream, int batch, const float* actor_dev, const float* critic_dev, const float* log_ent_coef_dev, const float* eps_dev,
                       float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
-  if (int rc = sac_check("tb_sac_actor_grad", env_kind, batch, workspace_dev, workspace_bytes)) return rc;
-  if (!actor_dev || !critic_dev || !log_ent_coef_dev || !eps_dev || !actor_grad_dev || !ent_grad_dev || !stats_dev) return fail(TB_E_INVAL, "tb_sac_actor_grad: null argument");
-  if (misaligned(actor_dev, 4) || misaligned(critic_dev, 4) || misaligned(log_ent_coef_dev, 4) || misaligned(eps_dev, 4) || misaligned(actor_grad_dev, 4) ||
-      misaligned(ent_grad_dev, 4) || misaligned(stats_dev, 8))
-    return fail(TB_E_INVAL, "tb_sac_actor_grad: a float array is not 4-byte aligned, or stats not 8-byte aligned");
-  if (actor_grad_dev == actor_dev) return fail(TB_E_INVAL, "tb_sac_actor_grad: actor_grad_dev must not be actor_dev");
-  if (int rc = ppo_device(device, "tb_sac_actor_grad: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  const SacRun r = {sac_dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev};
-  const SacDims& d = r.d;
-  const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
-  // the critics as they are now on (s, a~), the min, and back to their input
-  if (int rc = r.critics(critic_dev, SacWs::XC, SacWs::C1, SacWs::C2, SacWs::Q)) return rc;
-  if (int rc = launch(sac_actor_loss_kernel, dim3(1), dim3(256), 0, r.s, (const float*)r.at(SacWs::Q), (const float*)r.at(SacWs::LP), log_ent_coef_dev, -(float)d.A, batch,
-                      r.at(SacWs::DQ), ent_grad_dev, stats_dev))
-    return rc;
-  if (int rc = r.critics_backward(critic_dev)) return rc;
-  if (int rc = r.backward(r.at(SacWs::DZ1), SAC_H, BH, critic_dev + d.q_w0, d.C, d.q_one, 1 << 30, 0, nullptr, 0, 0, r.at(SacWs::DX), SAC_XW, BX, d.C, SAC_H, 2)) return rc;
-  // through tanh and logp to the head's outputs, then the actor's own backward pass
-  if (int rc = launch(sac_head_backward_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, (const float*)r.at(SacWs::ZH), (const float*)r.at(SacWs::XC),
-                      (const float*)r.at(SacWs::DX), eps_dev, log_ent_coef_dev, d.O, d.A, batch, r.at(SacWs::DHD)))
-    return rc;
-  float* gh = actor_grad_dev + d.pi_head;
-  if (int rc = r.wgrad(r.at(SacWs::DHD), SAC_XW, d.A, r.at(SacWs::H2), SAC_H, 0, gh, SAC_H, d.pi_block, gh + d.A * SAC_H, SAC_H, d.A, 2)) return rc;
-  if (int rc = r.backward(r.at(SacWs::DHD), SAC_XW, 0, actor_dev + d.pi_head, SAC_H, 0, d.A, d.A, r.at(SacWs::H2), SAC_H, 0, r.at(SacWs::DA2), SAC_H, 0, SAC_H, 2 * d.A, 1)) return rc;
-  if (int rc = r.wgrad(r.at(SacWs::DA2), SAC_H, 0, r.at(SacWs::H1), SAC_H, 0, actor_grad_dev + d.pi_w1, SAC_H, 0, actor_grad_dev + d.pi_b1, SAC_H, SAC_H, 1)) return rc;
-  if (int rc = r.backward(r.at(SacWs::DA2), SAC_H, 0, actor_dev + d.pi_w1, SAC_H, 0, 1 << 30, 0, r.at(SacWs::H1), SAC_H, 0, r.at(SacWs::DA1), SAC_H, 0, SAC_H, SAC_H, 1)) return rc;
-  return r.wgrad(r.at(SacWs::DA1), SAC_H, 0, r.at(SacWs::X0), SAC_XW, 0, actor_grad_dev + d.pi_w0, d.O, 0, actor_grad_dev + d.pi_b0, d.O, SAC_H, 1);
+  return sac_actor_grad<SacAlgo>(__func__, env_kind, device, stream, batch, actor_dev, critic_dev, log_ent_coef_dev, eps_dev, actor_grad_dev, ent_grad_dev, stats_dev, workspace_dev,
+                                 workspace_bytes);
+}
+int tb_tqc_actor_grad(int env_kind, int device, void* stream, int batch, const float* actor_dev, const float* critic_dev, const float* log_ent_coef_dev, const float* eps_dev,
+                      float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+  return sac_actor_grad<TqcAlgo>(__func__, env_kind, device, stream, batch, actor_dev, critic_dev, log_ent_coef_dev, eps_dev, actor_grad_dev, ent_grad_dev, stats_dev, workspace_dev,
+                                 workspace_bytes);
 }
 
 int tb_sac_adam(int device, void* stream, float* params_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, long long n, float lr, float beta1, float beta2,
@@ -1629,119 +1711,6 @@ int tb_sac_adam(int device, void* stream, float* params_dev, const float* grad_d
   if (polyak_only) return launch(sac_polyak_kernel, grid, dim3(256), 0, s, (const float*)params_dev, target_dev, n, omt, tau);
   const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
   return launch(sac_adam_kernel, grid, dim3(256), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, c1, c2, target_dev, omt, tau);
-}
-
-// --------------------------------------------------------------------------------------------- the TQC learner (tb_tqc.hpp)
-int tb_tqc_param_floats(int env_kind, int which) {
-  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_tqc_param_floats: unknown env kind");
-  if (which != TB_SAC_ACTOR && which != TB_SAC_CRITIC) return fail(TB_E_INVAL, "tb_tqc_param_floats: which must be TB_SAC_ACTOR or TB_SAC_CRITIC");
-  const SacDims d = tqc_run(env_kind, nullptr, 1, nullptr).d;
-  return which == TB_SAC_ACTOR ? d.pi_p : d.q_p;
-}
-long long tb_tqc_workspace_bytes(int env_kind, int batch) {
-  if (!kind_ok(env_kind) || batch < 1) return fail(TB_E_INVAL, "tb_tqc_workspace_bytes: unknown env kind, or batch < 1");
-  return (long long)sizeof(float) * TqcWs::PER_ROW * (long long)batch;
-}
-
-int tb_tqc_actor_forward(int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* actor_dev,
-                         const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes) {
-  if (int rc = sac_check("tb_tqc_actor_forward", env_kind, batch, workspace_dev, workspace_bytes, true)) return rc;
-  if (!obs_dev || !idx_dev || !actor_dev || !eps_dev || !act_out_dev || !logp_out_dev) return fail(TB_E_INVAL, "tb_tqc_actor_forward: null argument");
-  if (n_rows < 1) return fail(TB_E_INVAL, "tb_tqc_actor_forward: n_rows must be >= 1");
-  if (misaligned(obs_dev, 4) || misaligned(actor_dev, 4) || misaligned(eps_dev, 4) || misaligned(act_out_dev, 4) || misaligned(logp_out_dev, 4) || misaligned(idx_dev, 8))
-    return fail(TB_E_INVAL, "tb_tqc_actor_forward: a float array is not 4-byte aligned, or idx not 8-byte aligned");
-  if (int rc = ppo_device(device, "tb_tqc_actor_forward: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  const SacRun r = tqc_run(env_kind, stream, batch, workspace_dev);
-  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, obs_dev, r.d.O, (const float*)nullptr, 0, (const long long*)idx_dev, n_rows,
-                      batch, r.at(TqcWs::X0)))
-    return rc;
-  return r.actor(actor_dev, eps_dev, TqcWs::X0, TqcWs::H1, TqcWs::H2, TqcWs::ZH, TqcWs::XC, TqcWs::LP, act_out_dev, logp_out_dev);
-}
-
-int tb_tqc_targets(int env_kind, int device, void* stream, const float* next_obs_dev, const float* reward_dev, const float* done_dev, long long n_rows,
-                   const int64_t* idx_dev, int batch, const float* actor_dev, const float* target_dev, const float* log_ent_coef_dev, const float* eps_next_dev,
-                   float gamma, float* y_dev, void* workspace_dev, size_t workspace_bytes) {
-  if (int rc = sac_check("tb_tqc_targets", env_kind, batch, workspace_dev, workspace_bytes, true)) return rc;
-  if (!next_obs_dev || !reward_dev || !done_dev || !idx_dev || !actor_dev || !target_dev || !log_ent_coef_dev || !eps_next_dev || !y_dev)
-    return fail(TB_E_INVAL, "tb_tqc_targets: null argument");
-  if (n_rows < 1) return fail(TB_E_INVAL, "tb_tqc_targets: n_rows must be >= 1");
-  if (misaligned(next_obs_dev, 4) || misaligned(reward_dev, 4) || misaligned(done_dev, 4) || misaligned(actor_dev, 4) || misaligned(target_dev, 4) ||
-      misaligned(log_ent_coef_dev, 4) || misaligned(eps_next_dev, 4) || misaligned(y_dev, 4) || misaligned(idx_dev, 8))
-    return fail(TB_E_INVAL, "tb_tqc_targets: a float array is not 4-byte aligned, or idx not 8-byte aligned");
-  if (int rc = ppo_device(device, "tb_tqc_targets: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  const SacRun r = tqc_run(env_kind, stream, batch, workspace_dev);
-  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, next_obs_dev, r.d.O, (const float*)nullptr, 0, (const long long*)idx_dev,
-                      n_rows, batch, r.at(TqcWs::NX0)))
-    return rc;
-  if (int rc = r.actor(actor_dev, eps_next_dev, TqcWs::NX0, TqcWs::NH1, TqcWs::NH2, TqcWs::NZH, TqcWs::NXC, TqcWs::NAL, nullptr, nullptr)) return rc;  // logp' in NAL
-  if (int rc = r.critics(target_dev, TqcWs::NXC, TqcWs::T1, TqcWs::T2, TqcWs::QT)) return rc;
-  return launch(tqc_target_kernel, dim3(sac_blocks(batch, 4)), dim3(256), 0, r.s, reward_dev, done_dev, (const long long*)idx_dev, n_rows, batch, (const float*)r.at(TqcWs::QT),
-                (const float*)r.at(TqcWs::NAL), log_ent_coef_dev, gamma, y_dev);
-}
-
-int tb_tqc_critic_grad(int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev, int batch,
-                       const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
-  if (int rc = sac_check("tb_tqc_critic_grad", env_kind, batch, workspace_dev, workspace_bytes, true)) return rc;
-  if (!obs_dev || !action_dev || !idx_dev || !critic_dev || !y_dev || !grad_dev || !stats_dev) return fail(TB_E_INVAL, "tb_tqc_critic_grad: null argument");
-  if (n_rows < 1) return fail(TB_E_INVAL, "tb_tqc_critic_grad: n_rows must be >= 1");
-  if (misaligned(obs_dev, 4) || misaligned(action_dev, 4) || misaligned(critic_dev, 4) || misaligned(y_dev, 4) || misaligned(grad_dev, 4) || misaligned(idx_dev, 8) ||
-      misaligned(stats_dev, 8))
-    return fail(TB_E_INVAL, "tb_tqc_critic_grad: a float array is not 4-byte aligned, or idx / stats not 8-byte aligned");
-  if (grad_dev == critic_dev) return fail(TB_E_INVAL, "tb_tqc_critic_grad: grad_dev must not be critic_dev");
-  if (int rc = ppo_device(device, "tb_tqc_critic_grad: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  const SacRun r = tqc_run(env_kind, stream, batch, workspace_dev);
-  const SacDims& d = r.d;
-  const long long BH = (long long)batch * SAC_H, BQ = (long long)batch * TQC_HW;
-  double* row_loss = reinterpret_cast<double*>(r.at(TqcWs::RL));
-  if (int rc = launch(sac_gather_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, obs_dev, d.O, action_dev, d.A, (const long long*)idx_dev, n_rows, batch,
-                      r.at(TqcWs::XSA)))
-    return rc;
-  if (int rc = r.critics(critic_dev, TqcWs::XSA, TqcWs::C1, TqcWs::C2, TqcWs::Q)) return rc;
-  if (int rc = launch(tqc_critic_loss_kernel, dim3(sac_blocks(batch, 4)), dim3(256), 0, r.s, (const float*)r.at(TqcWs::Q), y_dev, batch, r.at(TqcWs::DQ), row_loss)) return rc;
-  if (int rc = launch(tqc_loss_sum_kernel, dim3(1), dim3(256), 0, r.s, (const double*)row_loss, batch, stats_dev)) return rc;
-  if (int rc = r.critics_backward<TqcWs>(critic_dev)) return rc;
-  if (int rc = r.wgrad(r.at(TqcWs::DQ), TQC_HW, BQ, r.at(TqcWs::C2), SAC_H, BH, grad_dev + d.q_w2, SAC_H, d.q_one, grad_dev + d.q_b2, SAC_H, TQC_Q, 2)) return rc;
-  if (int rc = r.wgrad(r.at(TqcWs::DZ2), SAC_H, BH, r.at(TqcWs::C1), SAC_H, BH, grad_dev + d.q_w1, SAC_H, d.q_one, grad_dev + d.q_b1, SAC_H, SAC_H, 2)) return rc;
-  return r.wgrad(r.at(TqcWs::DZ1), SAC_H, BH, r.at(TqcWs::XSA), SAC_XW, 0, grad_dev + d.q_w0, d.C, d.q_one, grad_dev + d.q_b0, d.C, SAC_H, 2);
-}
-
-int tb_tqc_actor_grad(int env_kind, int device, void* stream, int batch, const float* actor_dev, const float* critic_dev, const float* log_ent_coef_dev, const float* eps_dev,
-                      float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
-  if (int rc = sac_check("tb_tqc_actor_grad", env_kind, batch, workspace_dev, workspace_bytes, true)) return rc;
-  if (!actor_dev || !critic_dev || !log_ent_coef_dev || !eps_dev || !actor_grad_dev || !ent_grad_dev || !stats_dev) return fail(TB_E_INVAL, "tb_tqc_actor_grad: null argument");
-  if (misaligned(actor_dev, 4) || misaligned(critic_dev, 4) || misaligned(log_ent_coef_dev, 4) || misaligned(eps_dev, 4) || misaligned(actor_grad_dev, 4) ||
-      misaligned(ent_grad_dev, 4) || misaligned(stats_dev, 8))
-    return fail(TB_E_INVAL, "tb_tqc_actor_grad: a float array is not 4-byte aligned, or stats not 8-byte aligned");
-  if (actor_grad_dev == actor_dev) return fail(TB_E_INVAL, "tb_tqc_actor_grad: actor_grad_dev must not be actor_dev");
-  if (int rc = ppo_device(device, "tb_tqc_actor_grad: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  const SacRun r = tqc_run(env_kind, stream, batch, workspace_dev);
-  const SacDims& d = r.d;
-  const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
-  // the critics as they are now on (s, a~), the mean over their 50 quantiles, and back to their input
-  if (int rc = r.critics(critic_dev, TqcWs::XC, TqcWs::C1, TqcWs::C2, TqcWs::Q)) return rc;
-  if (int rc = launch(tqc_actor_loss_kernel, dim3(1), dim3(256), 0, r.s, (const float*)r.at(TqcWs::Q), (const float*)r.at(TqcWs::LP), log_ent_coef_dev, -(float)d.A, batch,
-                      r.at(TqcWs::DQ), ent_grad_dev, stats_dev))
-    return rc;
-  if (int rc = r.critics_backward<TqcWs>(critic_dev)) return rc;
-  if (int rc = r.backward(r.at(TqcWs::DZ1), SAC_H, BH, critic_dev + d.q_w0, d.C, d.q_one, 1 << 30, 0, nullptr, 0, 0, r.at(TqcWs::DX), SAC_XW, BX, d.C, SAC_H, 2)) return rc;
-  // through tanh and logp to the head's outputs, then the actor's own backward pass: SAC's
-  if (int rc = launch(sac_head_backward_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, (const float*)r.at(TqcWs::ZH), (const float*)r.at(TqcWs::XC),
-                      (const float*)r.at(TqcWs::DX), eps_dev, log_ent_coef_dev, d.O, d.A, batch, r.at(TqcWs::DHD)))
-    return rc;
-  float* gh = actor_grad_dev + d.pi_head;
-  if (int rc = r.wgrad(r.at(TqcWs::DHD), SAC_XW, d.A, r.at(TqcWs::H2), SAC_H, 0, gh, SAC_H, d.pi_block, gh + d.A * SAC_H, SAC_H, d.A, 2)) return rc;
-  if (int rc = r.backward(r.at(TqcWs::DHD), SAC_XW, 0, actor_dev + d.pi_head, SAC_H, 0, d.A, d.A, r.at(TqcWs::H2), SAC_H, 0, r.at(TqcWs::DA2), SAC_H, 0, SAC_H, 2 * d.A, 1)) return rc;
-  if (int rc = r.wgrad(r.at(TqcWs::DA2), SAC_H, 0, r.at(TqcWs::H1), SAC_H, 0, actor_grad_dev + d.pi_w1, SAC_H, 0, actor_grad_dev + d.pi_b1, SAC_H, SAC_H, 1)) return rc;
-  if (int rc = r.backward(r.at(TqcWs::DA2), SAC_H, 0, actor_dev + d.pi_w1, SAC_H, 0, 1 << 30, 0, r.at(TqcWs::H1), SAC_H, 0, r.at(TqcWs::DA1), SAC_H, 0, SAC_H, SAC_H, 1)) return rc;
-  return r.wgrad(r.at(TqcWs::DA1), SAC_H, 0, r.at(TqcWs::X0), SAC_XW, 0, actor_grad_dev + d.pi_w0, d.O, 0, actor_grad_dev + d.pi_b0, d.O, SAC_H, 1);
 }
 
 int tb_rollout(TbHandle* h, int n_steps, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,

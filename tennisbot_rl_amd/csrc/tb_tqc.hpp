@@ -2,7 +2,9 @@
 // included by tb_stepper.hip after tb_sac.hpp, whose tile kernels, gather, sample, head backward, Adam and Polyak kernels it uses
 // as they are: TQC's actor is SAC's, and its critics differ from SAC's in the last layer alone, which has 25 outputs (the
 // quantiles) instead of one. A head is one launch of a tile kernel with K = 256, M = 25: two column tiles, the second of 9 live
-// columns, and in the backward kernel a reduction of 6 whole k-steps and one of a single live row.
+// columns, and in the backward kernel a reduction of 6 whole k-steps and one of a single live row. The host path is SAC's as
+// well: tb_stepper.hip writes each stage once, and its descriptor TqcAlgo supplies this file's layouts (TqcLayout, TqcWs), the
+// head's 25 outputs in rows of 32, and the launches of the three loss kernels below.
 //
 // What is TQC's own is row-wise, one wave per batch row, no LDS and no barrier in the per-row work:
 //   tqc_target_kernel       the 50 target quantiles of a row, sorted by rank counting, the 46 smallest into y[b][0 .. 46)
@@ -28,14 +30,10 @@ template <int KIND> struct TqcLayout {
 };
 static_assert(TqcLayout<TB_ENV_SWING>::Q_P == 151090 && TqcLayout<TB_ENV_TENNIS>::Q_P == 152114, "critic parameter count");
 
-// The workspace: SacWs with head regions (QT, Q, DQ) of [2][B][32], and one double per row for the critic loss (RL)
-struct TqcWs {
-  static constexpr int X0 = 0, H1 = X0 + 16, H2 = H1 + 256, ZH = H2 + 256, XC = ZH + 16, LP = XC + 16;
-  static constexpr int NX0 = LP + 16, NH1 = NX0 + 16, NH2 = NH1 + 256, NZH = NH2 + 256, NXC = NZH + 16, NAL = NXC + 16, T1 = NAL + 16, T2 = T1 + 512, QT = T2 + 512;
-  static constexpr int XSA = QT + 2 * TQC_HW, C1 = XSA + 16, C2 = C1 + 512, Q = C2 + 512, DQ = Q + 2 * TQC_HW, DZ2 = DQ + 2 * TQC_HW, DZ1 = DZ2 + 512;
-  static constexpr int DX = DZ1 + 512, DHD = DX + 32, DA2 = DHD + 16, DA1 = DA2 + 256, RL = DA1 + 256, PER_ROW = RL + 2;
-};
-static_assert(TqcWs::X0 == SacWs::X0 && TqcWs::LP == SacWs::LP && TqcWs::RL % 2 == 0, "the actor's regions are SAC's; the row sums are 8-byte aligned");
+// The workspace: SAC's layout with head regions (QT, Q, DQ) of [2][B][32], and one double per row for the critic loss (RL)
+using TqcWs = SacWsT<TQC_HW, 2>;
+static_assert(TqcWs::QT == 2176 && TqcWs::Q == 3280 && TqcWs::DQ == 3344 && TqcWs::DX == 4432 && TqcWs::PER_ROW == 4994, "TQC's workspace layout");
+static_assert(TqcWs::RL % 2 == 0, "the row sums are 8-byte aligned");
 
 // one wave per row, four rows per workgroup: grid ceil(B / 4), 256 threads. Lane l < 50 holds quantile l % 25 of target net
 // l / 25; its rank is the number of lanes that precede it in the total order (is-NaN, value, lane), so equal values take

@@ -136,34 +136,39 @@ class _Flat:
 class FusedSAC:
     """SAC's gradient step on the device for (actor, critic, critic_target, log_ent_coef) and their three Adam optimisers
     `optimisers = (actor_opt, critic_opt, ent_opt)`. hp: gamma, tau (SAC_DEFAULTS); lr, betas and eps are the optimisers' own.
-    hp stays the CALLER'S dict (missing keys are filled in place, as FusedLearner does): a later change of trainer.hp reaches the learner."""
+    hp stays the CALLER'S dict (missing keys are filled in place, as FusedLearner does): a later change of trainer.hp reaches the learner.
+    What another algorithm on the same actor and stages changes is in the class attributes (tqc.FusedTQC)."""
+
+    ABI = "tb_sac_"   # the C entry points of the stages and the two queries are ABI + their names
+    DEFAULTS = SAC_DEFAULTS
+    Y_SHAPE = ()      # the trailing shape of y [B, ...]: one target per row
+    NET, NET_SHAPE = "SB3's SAC MlpPolicy", "[256, 256] ReLU"   # the words of the architecture message
 
     def __init__(self, kind, actor, critic, critic_target, log_ent_coef, optimisers, hp, device):
         import torch
+        name = type(self).__name__
         self.torch, self.kind, self.hp = torch, int(kind), hp
         self.actor, self.critic, self.critic_target, self.log_ent_coef = actor, critic, critic_target, log_ent_coef
-        for k, v in SAC_DEFAULTS.items():
+        for k, v in self.DEFAULTS.items():
             hp.setdefault(k, v)
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise StepperError("FusedSAC needs a GPU (there is no CPU fallback)")
+            raise StepperError("%s needs a GPU (there is no CPU fallback)" % name)
         self.lib = load_library()
         self.O, self.A = OBS_DIM[self.kind], ACT_DIM[self.kind]
         want = {"actor": ACTOR_NAMES, "critic": CRITIC_NAMES, "critic_target": CRITIC_NAMES}
         sets = {}
         for what, module, which in (("actor", actor, TB_SAC_ACTOR), ("critic", critic, TB_SAC_CRITIC), ("critic_target", critic_target, TB_SAC_CRITIC)):
             named = list(module.named_parameters())
-            n = self.lib.tb_sac_param_floats(self.kind, which)
-            if n < 0:
-                _check(self.lib, n, "tb_sac_param_floats")
+            n = self._query("param_floats", self.kind, which)
             if tuple(k for k, _ in named) != want[what] or sum(p.numel() for _, p in named) != n:
-                raise StepperError("FusedSAC: the %s is not SB3's SAC MlpPolicy net for this env kind (%d parameters in %d tensors; the kernels take %d: [256, 256] ReLU)"
-                                   % (what, sum(p.numel() for _, p in named), len(named), n))
+                raise StepperError("%s: the %s is not %s net for this env kind (%d parameters in %d tensors; the kernels take %d: %s)"
+                                   % (name, what, self.NET, sum(p.numel() for _, p in named), len(named), n, self.NET_SHAPE))
             if any(p.device != self.device and p.device.type != "cuda" for _, p in named):
-                raise StepperError("FusedSAC: the %s is not on a GPU" % what)
+                raise StepperError("%s: the %s is not on a GPU" % (name, what))
             sets[what] = [p for _, p in named]
         if tuple(log_ent_coef.shape) != (1,) or log_ent_coef.dtype != torch.float32 or log_ent_coef.device.type != "cuda":
-            raise StepperError("FusedSAC: log_ent_coef must be a float32 tensor of shape [1] on the GPU")
+            raise StepperError("%s: log_ent_coef must be a float32 tensor of shape [1] on the GPU" % name)
         actor_opt, critic_opt, ent_opt = optimisers
         self.pi = _Flat(torch, sets["actor"], flatten_parameters(actor), actor_opt, "actor")
         self.q = _Flat(torch, sets["critic"], flatten_parameters(critic), critic_opt, "critic")
@@ -173,6 +178,17 @@ class FusedSAC:
         self.step = 0
         self._ws = self._batch = self._pi_batch = None   # _pi_batch: the batch whose actor activations the workspace holds
         self.adopt()
+
+    def _query(self, what, *args):
+        """a count from this algorithm's C query `what`; a refusal raises"""
+        n = getattr(self.lib, self.ABI + what)(*args)
+        if n < 0:
+            _check(self.lib, int(n), self.ABI + what)
+        return n
+
+    def _call(self, stage, *args):
+        """this algorithm's C entry point of a stage; a refusal raises"""
+        _check(self.lib, getattr(self.lib, self.ABI + stage)(*args), self.ABI + stage)
 
     def _stream(self):
         return self.torch.cuda.current_stream(self.device).cuda_stream
@@ -192,16 +208,14 @@ class FusedSAC:
         return idx
 
     def workspace(self, batch):
-        need = self.lib.tb_sac_workspace_bytes(self.kind, int(batch))
-        if need < 0:
-            _check(self.lib, int(need), "tb_sac_workspace_bytes")
+        need = self._query("workspace_bytes", self.kind, int(batch))
         if self._ws is None or self._ws.numel() * 8 < need:
             self._ws = self.torch.zeros((need + 7) // 8, dtype=self.torch.float64, device=self.device)
         if self._batch != int(batch):   # the regions' offsets scale with the batch: what an earlier stage kept is gone
             B = self._batch = int(batch)
             self._pi_batch = None
             e = lambda *s: self.torch.empty(s, dtype=self.torch.float32, device=self.device)  # noqa: E731
-            self.act_pi, self.logp_pi, self.y = e(B, self.A), e(B), e(B)
+            self.act_pi, self.logp_pi, self.y = e(B, self.A), e(B), e(B, *self.Y_SHAPE)
         return self._ws
 
     def adopt(self):
@@ -227,21 +241,20 @@ class FusedSAC:
         ws = self.workspace(B)
         act_out, logp_out = self.act_pi if act_out is None else act_out, self.logp_pi if logp_out is None else logp_out
         obs, eps = self._float(obs, "obs"), self._float(eps, "eps", (B, self.A))
-        _check(self.lib, self.lib.tb_sac_actor_forward(self.kind, self._dev(), self._stream(), obs.data_ptr(), int(obs.shape[0]), idx.data_ptr(), B, self.pi.flat.data_ptr(),
-                                                       eps.data_ptr(), self._float(act_out, "act_out", (B, self.A)).data_ptr(), self._float(logp_out, "logp_out", (B,)).data_ptr(),
-                                                       ws.data_ptr(), ws.numel() * 8), "tb_sac_actor_forward")
+        self._call("actor_forward", self.kind, self._dev(), self._stream(), obs.data_ptr(), int(obs.shape[0]), idx.data_ptr(), B, self.pi.flat.data_ptr(), eps.data_ptr(),
+                   self._float(act_out, "act_out", (B, self.A)).data_ptr(), self._float(logp_out, "logp_out", (B,)).data_ptr(), ws.data_ptr(), ws.numel() * 8)
         self._pi_batch = B
         return act_out, logp_out
 
     def targets(self, next_obs, reward, done, idx, eps_next, y=None):
+        """y [B, *Y_SHAPE]: SAC's target of every row, or TQC's truncated target distribution [B, 46]"""
         B = int(self._index(idx).numel())
         ws = self.workspace(B)
         y = self.y if y is None else y
         next_obs, n = self._float(next_obs, "next_obs"), int(next_obs.shape[0])
-        _check(self.lib, self.lib.tb_sac_targets(self.kind, self._dev(), self._stream(), next_obs.data_ptr(), self._float(reward, "reward", (n,)).data_ptr(),
-                                                 self._float(done, "done", (n,)).data_ptr(), n, idx.data_ptr(), B, self.pi.flat.data_ptr(), self.qt.flat.data_ptr(),
-                                                 self.log_ent_coef.data_ptr(), self._float(eps_next, "eps_next", (B, self.A)).data_ptr(), float(self.hp["gamma"]),
-                                                 self._float(y, "y", (B,)).data_ptr(), ws.data_ptr(), ws.numel() * 8), "tb_sac_targets")
+        self._call("targets", self.kind, self._dev(), self._stream(), next_obs.data_ptr(), self._float(reward, "reward", (n,)).data_ptr(), self._float(done, "done", (n,)).data_ptr(),
+                   n, idx.data_ptr(), B, self.pi.flat.data_ptr(), self.qt.flat.data_ptr(), self.log_ent_coef.data_ptr(), self._float(eps_next, "eps_next", (B, self.A)).data_ptr(),
+                   float(self.hp["gamma"]), self._float(y, "y", (B,) + self.Y_SHAPE).data_ptr(), ws.data_ptr(), ws.numel() * 8)
         return y
 
     def critic_gradient(self, obs, action, idx, y):
@@ -249,9 +262,8 @@ class FusedSAC:
         B = int(self._index(idx).numel())
         ws = self.workspace(B)
         obs, n = self._float(obs, "obs"), int(obs.shape[0])
-        _check(self.lib, self.lib.tb_sac_critic_grad(self.kind, self._dev(), self._stream(), obs.data_ptr(), self._float(action, "action", (n, self.A)).data_ptr(), n, idx.data_ptr(),
-                                                     B, self.q.flat.data_ptr(), self._float(y, "y", (B,)).data_ptr(), self.q.grad.data_ptr(), self.stats.data_ptr(), ws.data_ptr(),
-                                                     ws.numel() * 8), "tb_sac_critic_grad")
+        self._call("critic_grad", self.kind, self._dev(), self._stream(), obs.data_ptr(), self._float(action, "action", (n, self.A)).data_ptr(), n, idx.data_ptr(), B,
+                   self.q.flat.data_ptr(), self._float(y, "y", (B,) + self.Y_SHAPE).data_ptr(), self.q.grad.data_ptr(), self.stats.data_ptr(), ws.data_ptr(), ws.numel() * 8)
         return self.q.grad
 
     def actor_gradient(self, batch, eps):
@@ -261,9 +273,8 @@ class FusedSAC:
             raise ValueError("actor_gradient: the workspace holds %s, not an actor_forward of %d rows (a stage at another batch size in between overwrites it)"
                              % ("no actor_forward" if self._pi_batch is None else "an actor_forward of %d rows" % self._pi_batch, B))
         ws = self.workspace(B)
-        _check(self.lib, self.lib.tb_sac_actor_grad(self.kind, self._dev(), self._stream(), B, self.pi.flat.data_ptr(), self.q.flat.data_ptr(), self.log_ent_coef.data_ptr(),
-                                                    self._float(eps, "eps", (B, self.A)).data_ptr(), self.pi.grad.data_ptr(), self.ent.grad.data_ptr(), self.stats.data_ptr(),
-                                                    ws.data_ptr(), ws.numel() * 8), "tb_sac_actor_grad")
+        self._call("actor_grad", self.kind, self._dev(), self._stream(), B, self.pi.flat.data_ptr(), self.q.flat.data_ptr(), self.log_ent_coef.data_ptr(),
+                   self._float(eps, "eps", (B, self.A)).data_ptr(), self.pi.grad.data_ptr(), self.ent.grad.data_ptr(), self.stats.data_ptr(), ws.data_ptr(), ws.numel() * 8)
         return self.pi.grad, self.ent.grad
 
     def adam(self, f, step, target=None):
@@ -341,7 +352,13 @@ class SACTrainer:
     """SAC over a BatchedEnv. Collect: one BatchedEnv.step of every env with the torch actor (uniform actions in [-1, 1] while
     num_timesteps < learning_starts), the transitions into the replay ring; then `gradient_steps` fused gradient steps (default
     num_envs: one per collected transition, the update-to-data ratio of the reference's single env). The env is not pipelined, so
-    SwingRacket's terminal reward is complete when its transition is stored. hp: learning_rate, gamma, tau (SAC_DEFAULTS)."""
+    SwingRacket's terminal reward is complete when its transition is stored. hp: learning_rate, gamma, tau (SAC_DEFAULTS).
+    What another algorithm with the same loop changes is in the class attributes (tqc.TQCTrainer)."""
+
+    LEARNER, DEFAULTS = FusedSAC, SAC_DEFAULTS
+    build_modules = staticmethod(build_sac_modules)
+    default_batch = staticmethod(BATCH_SIZE.__getitem__)   # of an env id
+    ALGO, NETS = "SAC", "SB3's MlpPolicy [256, 256]"          # the words of the two messages
 
     def __init__(self, env_id="SwingRacket-v0", num_envs=256, batch_size=None, gradient_steps=None, buffer_size=1_000_000, learning_starts=100, seed=0, params=None,
                  device=None, **hp):
@@ -349,26 +366,26 @@ class SACTrainer:
         self.torch = torch
         dist = torch.distributed
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise ValueError("SACTrainer runs on one rank (world size %d): multi-rank SAC is not provided" % dist.get_world_size())
-        unknown = set(hp) - set(SAC_DEFAULTS)
+            raise ValueError("%s runs on one rank (world size %d): multi-rank %s is not provided" % (type(self).__name__, dist.get_world_size(), self.ALGO))
+        unknown = set(hp) - set(self.DEFAULTS)
         if unknown:
-            raise ValueError("SACTrainer: unknown hyper-parameters %s (the nets are SB3's MlpPolicy [256, 256]: the kernels are instantiated for that architecture)" % sorted(unknown))
+            raise ValueError("%s: unknown hyper-parameters %s (the nets are %s: the kernels are instantiated for that architecture)" % (type(self).__name__, sorted(unknown), self.NETS))
         kind = ENV_IDS[env_id]
         self.env_id, self.kind, self.num_envs = env_id, kind, int(num_envs)
-        self.hp = dict(SAC_DEFAULTS, **hp)
-        self.batch_size = int(batch_size or BATCH_SIZE[env_id])
+        self.hp = dict(self.DEFAULTS, **hp)
+        self.batch_size = int(batch_size or self.default_batch(env_id))
         self.gradient_steps = self.num_envs if gradient_steps is None else int(gradient_steps)
         self.learning_starts = int(learning_starts)
         self.env = BatchedEnv(kind, self.num_envs, device=device, seed=seed, params=params, track_terminal_obs=False, pipeline=False)
         self.device = self.env.device
         O, A = self.env.obs_dim, self.env.act_dim
         torch.manual_seed(seed)
-        self.actor, self.critic, self.critic_target = (m.to(self.device) for m in build_sac_modules(O, A))
+        self.actor, self.critic, self.critic_target = (m.to(self.device) for m in self.build_modules(O, A))
         self.log_ent_coef = torch.zeros(1, dtype=torch.float32, device=self.device, requires_grad=True)  # ent_coef "auto": starts at 0
         lr, eps = self.hp["learning_rate"], self.hp["adam_eps"]
         self.opts = (torch.optim.Adam(self.actor.parameters(), lr=lr, eps=eps), torch.optim.Adam(self.critic.parameters(), lr=lr, eps=eps),
                      torch.optim.Adam([self.log_ent_coef], lr=lr, eps=eps))
-        self._learner = FusedSAC(kind, self.actor, self.critic, self.critic_target, self.log_ent_coef, self.opts, self.hp, self.device)
+        self._learner = self.LEARNER(kind, self.actor, self.critic, self.critic_target, self.log_ent_coef, self.opts, self.hp, self.device)
         self.replay = ReplayBuffer(O, A, buffer_size, self.device)
         self.obs = self.env.reset()
         self.num_timesteps = 0

@@ -23,18 +23,21 @@ from tennisbot_rl_amd.evaluation import add_schedule_arguments, resolve_load, sc
 from train_swing import racket_scale_for  # noqa: E402  (train.py:164-176, one table for every script)
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description="SAC on SwingRacket-v0 or Tennisbot-v0 (the reference's -s sac)")
+def off_policy_main(argv, script, algo, trainer, description, batch_help, total_default, total_help, total_by_env):
+    """the body of train_sac.py and train_tqc.py. trainer() returns the trainer class (called after the arguments are parsed, so
+    that --help needs no torch); algo names it in messages and in the default --save path; total_by_env: the timesteps per env id
+    where --total-timesteps is not given (its own default is total_default)."""
+    ap = argparse.ArgumentParser(description=description)
     ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
     ap.add_argument("--num-envs", type=int, default=256)
-    ap.add_argument("--batch-size", type=int, default=None, help="default: 1100 on SwingRacket-v0, 256 on Tennisbot-v0, as the reference scripts")
+    ap.add_argument("--batch-size", type=int, default=None, help=batch_help)
     ap.add_argument("--gradient-steps", type=int, default=None, help="gradient steps per vector step (default: --num-envs, one per transition)")
     ap.add_argument("--buffer-size", type=int, default=1_000_000)
     ap.add_argument("--learning-starts", type=int, default=100, help="timesteps of uniform actions before the first gradient step")
-    ap.add_argument("--total-timesteps", type=float, default=None, help="default: 2e6 SwingRacket-v0 / 1e6 Tennisbot-v0, as the reference")
+    ap.add_argument("--total-timesteps", type=float, default=total_default, help=total_help)
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
     ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save; `best`: best_model.pt beside --save (written under --eval-freq)")
-    ap.add_argument("--save", type=str, default=None, help="default: ./model/sac_<env id>.pt")
+    ap.add_argument("--save", type=str, default=None, help="default: ./model/%s_<env id>.pt" % algo.lower())
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-json", type=str, default=None)
     ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (TB_F_RACKET_GROUND)")
@@ -42,19 +45,18 @@ def main(argv=None):
     add_schedule_arguments(ap)
     args = ap.parse_args(argv)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        sys.exit("train_sac.py runs on one rank: multi-rank SAC is not provided")
+        sys.exit("%s runs on one rank: multi-rank %s is not provided" % (script, algo))
 
     import torch
-    from tennisbot_rl_amd.sac import SACTrainer
 
-    total = args.total_timesteps or (2e6 if args.env == "SwingRacket-v0" else 1e6)
+    total = args.total_timesteps or total_by_env.get(args.env, 0)
     params = None
     if args.racket_ground or args.rolling_friction:
         from tennisbot_rl_amd.params import F_DEFAULT, F_RACKET_GROUND, default_params, reference_rolling_friction
         params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
-    tr = SACTrainer(args.env, num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
-                    learning_starts=args.learning_starts, seed=args.seed, params=params, device=torch.device("cuda", 0))
-    path = args.save or "./model/sac_%s.pt" % args.env
+    tr = trainer()(args.env, num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
+                   learning_starts=args.learning_starts, seed=args.seed, params=params, device=torch.device("cuda", 0))
+    path = args.save or "./model/%s_%s.pt" % (algo.lower(), args.env)
     if args.load:
         tr.load(resolve_load(args.load, path))
     schedule = schedule_from_args(args, path)
@@ -75,6 +77,18 @@ def main(argv=None):
         print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate())
     if args.log_json:
         json.dump(history, open(args.log_json, "w"))
+
+
+
+def _trainer():
+    from tennisbot_rl_amd.sac import SACTrainer
+    return SACTrainer
+
+
+def main(argv=None):
+    off_policy_main(argv, "train_sac.py", "SAC", _trainer, "SAC on SwingRacket-v0 or Tennisbot-v0 (the reference's -s sac)",
+                    "default: 1100 on SwingRacket-v0, 256 on Tennisbot-v0, as the reference scripts", None, "default: 2e6 SwingRacket-v0 / 1e6 Tennisbot-v0, as the reference",
+                    {"SwingRacket-v0": 2e6, "Tennisbot-v0": 1e6})
 
 
 if __name__ == "__main__":

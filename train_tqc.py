@@ -10,8 +10,6 @@ lr 3e-4, gamma 0.99, tau 0.005, ent_coef "auto", batch_size 256, buffer_size 1e6
 --num-envs transitions and runs --gradient-steps gradient steps (default: one per transition, the reference's update-to-data
 ratio). Checkpoints hold the learner, the replay ring AND the env batch state. One rank only.
 """
-import argparse
-import json
 import os
 import sys
 
@@ -19,62 +17,17 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from tennisbot_rl_amd.evaluation import add_schedule_arguments, resolve_load, schedule_from_args  # noqa: E402
-from train_swing import racket_scale_for  # noqa: E402  (train.py:164-176, one table for every script)
+from train_sac import off_policy_main  # noqa: E402  (one body for both off-policy scripts)
+
+
+def _trainer():
+    from tennisbot_rl_amd.tqc import TQCTrainer
+    return TQCTrainer
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="TQC on SwingRacket-v0 or Tennisbot-v0 (the reference's train_swing.py -s tqc)")
-    ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
-    ap.add_argument("--num-envs", type=int, default=256)
-    ap.add_argument("--batch-size", type=int, default=None, help="default: 256, sb3_contrib's, as the reference script leaves it")
-    ap.add_argument("--gradient-steps", type=int, default=None, help="gradient steps per vector step (default: --num-envs, one per transition)")
-    ap.add_argument("--buffer-size", type=int, default=1_000_000)
-    ap.add_argument("--learning-starts", type=int, default=100, help="timesteps of uniform actions before the first gradient step")
-    ap.add_argument("--total-timesteps", type=float, default=2e6, help="default: 2e6, as the reference")
-    ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
-    ap.add_argument("--load", type=str, default=None, help="checkpoint written by --save; `best`: best_model.pt beside --save (written under --eval-freq)")
-    ap.add_argument("--save", type=str, default=None, help="default: ./model/tqc_<env id>.pt")
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--log-json", type=str, default=None)
-    ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (TB_F_RACKET_GROUND)")
-    ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact")
-    add_schedule_arguments(ap)
-    args = ap.parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        sys.exit("train_tqc.py runs on one rank: multi-rank TQC is not provided")
-
-    import torch
-    from tennisbot_rl_amd.tqc import TQCTrainer
-
-    total = args.total_timesteps
-    params = None
-    if args.racket_ground or args.rolling_friction:
-        from tennisbot_rl_amd.params import F_DEFAULT, F_RACKET_GROUND, default_params, reference_rolling_friction
-        params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
-    tr = TQCTrainer(args.env, num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
-                    learning_starts=args.learning_starts, seed=args.seed, params=params, device=torch.device("cuda", 0))
-    path = args.save or "./model/tqc_%s.pt" % args.env
-    if args.load:
-        tr.load(resolve_load(args.load, path))
-    schedule = schedule_from_args(args, path)
-    if schedule is not None:
-        schedule.reset(tr.num_timesteps)
-    history = []
-    chunk = 10 * tr.num_envs
-    while tr.num_timesteps < total:
-        if args.curri and args.env == "Tennisbot-v0":
-            tr.env.set_racket_scale(racket_scale_for(100.0 * tr.num_timesteps / total))
-        history += tr.learn(min(total, tr.num_timesteps + chunk), schedule=schedule)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tr.save(path)
-    if args.eval_freq:
-        print("saved", path, "eval (%d whole episodes, %s policy):" % (args.n_eval_episodes, "deterministic" if args.eval_deterministic else "stochastic"),
-              tr.evaluate_episodes(args.n_eval_episodes, deterministic=args.eval_deterministic))
-    else:
-        print("saved", path, "eval (stochastic policy, as EvalCallback in the reference):", tr.evaluate())
-    if args.log_json:
-        json.dump(history, open(args.log_json, "w"))
+    off_policy_main(argv, "train_tqc.py", "TQC", _trainer, "TQC on SwingRacket-v0 or Tennisbot-v0 (the reference's train_swing.py -s tqc)",
+                    "default: 256, sb3_contrib's, as the reference script leaves it", 2e6, "default: 2e6, as the reference", {})
 
 
 if __name__ == "__main__":

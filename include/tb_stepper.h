@@ -679,6 +679,11 @@ int tb_phase_advance(TbHandle *h, int n_steps);
 int tb_pipeline_form(TbHandle *h);
 /* waves per 64 envs of the pipelined SwingRacket-v0 one-step kernel (TbOptions.step_waves): 2 or 1; 0 for a handle without that kernel */
 int tb_step_waves(TbHandle *h);
+/* which form of that kernel the next tb_step would launch: 0 = one-wave (also the episodes' last step while the library knows the episode
+ * phase: every env parks there), 1 = two-wave with the early gate and full loads (phase unknown: after a masked reset or an injected
+ * state out of lockstep), 2 = two-wave short (phase known, not the last step: each wave loads its own side only); -1 for a handle
+ * without that kernel. A captured launch keeps the form of the phase it was captured at. */
+int tb_step_form(TbHandle *h);
 /* After a capture that contained tb_step calls was ABANDONED (it failed, e.g. because something else
  * in it was not capturable): the handle's side streams were forked into that capture and stay
  * invalidated, and the host's episode-phase hint ran ahead of the device. Replaces the side streams

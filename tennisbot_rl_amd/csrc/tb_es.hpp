@@ -195,6 +195,7 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
   double ret = 0.0;
   int len = 0;
   constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (es_rows_in_registers(KIND, RG) ? SF_REGROWS : 0u);
+  TB_DIAG_STAMPS_BEGIN(st);  // (the substep's stamps: the diagnostic build compiles every kernel that steps envs)
   for (int t = 0; t < T_MAX && __ballot(active) != 0ull; ++t) {
     float a[NA];
 #pragma unroll
@@ -239,6 +240,7 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
   }
   if (live) { E.ret[i] = ret; E.len[i] = len; }
   flush_counters(A.counters, cnt);
+  TB_DIAG_STAMPS_END(st);
 }
 
 // SwingRacket: the 26th step's reward, written by the fast-forward into rew_last, completes the return (and the trace's row 25)

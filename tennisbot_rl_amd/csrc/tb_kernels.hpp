@@ -104,6 +104,17 @@ TB_DEV void row_store(uint32_t* w, int row, int n, int i, uint32_t v) {
 template <int KIND> constexpr bool off32() { return KIND == TB_ENV_SWING; }
 template <int KIND> TB_DEV float ld(const uint32_t* w, int row, int n, int i) { return __uint_as_float(row_word<off32<KIND>()>(w, row, n, i)); }
 template <int KIND> TB_DEV void st(uint32_t* w, int row, int n, int i, float v) { row_store<off32<KIND>()>(w, row, n, i, __float_as_uint(v)); }
+// A row's 32-bit byte offset as a value of its own, for a row that is loaded and later stored by the same lane (the two-wave short
+// step): computed once and then opaque to the compiler, which otherwise sinks the arithmetic next to each use and pays for it twice.
+TB_DEV uint32_t row_byte(int row, int n, int i) {
+  uint32_t byte = ((uint32_t)row * (uint32_t)n + (uint32_t)i) * 4u;
+  asm("" : "+v"(byte));
+  return byte;
+}
+TB_DEV uint32_t word_at(const uint32_t* w, uint32_t byte) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(w) + byte); }
+TB_DEV void word_to(uint32_t* w, uint32_t byte, uint32_t v) { *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(w) + byte) = v; }
+TB_DEV float ld_at(const uint32_t* w, uint32_t byte) { return __uint_as_float(word_at(w, byte)); }
+TB_DEV void st_at(uint32_t* w, uint32_t byte, float v) { word_to(w, byte, __float_as_uint(v)); }
 
 template <int KIND>
 TB_DEV void load_env(const uint32_t* w, const uint8_t* done_state, int n, int i, EnvRegs& e) {
@@ -653,9 +664,21 @@ TB_DEV bool two_wave_rare(const KParams& P, const EnvRegs& e) {
   rare |= !(ball_low_point(P, e.b) >= P.static_top + 1.0e-3f);
   return rare;
 }
-// true: this launch's step of the wave's envs is done (both waves return it alike). e is not modified: on false it is the loaded state.
-TB_DEV bool two_wave_step(const KArgs& A, const EnvRegs& e, const float* a, int i, bool live TB_DIAG_T0_ARG) {
+// THE SHORT FORM (two_wave_step<true>, tb_step_kernel<.., TWO_WAVE, .., SHORT>): the host launches it where it knows the episode phase
+// and the launch does not end the episodes (launch_step) -- every env has done = 0 and step_count = phase < 25, so only the geometric
+// tests can send a launch down the rare path. Each wave then loads what its common path reads and nothing else: the racket wave the
+// racket's 13 rows and the actions, the ball wave what load_ball_side names. No early gate: the racket wave waits for nothing but its
+// own operands, each at its first use, and the verdict reaches it through s_rare alone (two_wave_rare's first line still holds the
+// done byte and the step count, so a broken lockstep is a rare verdict like any other). A row's byte offset is computed once, for its
+// load and its store (row_byte). On a rare verdict nothing has been stored: the ball wave returns and wave 0 loads the whole env then,
+// a second round trip that only rare launches pay, and steps the 64 envs with the one-wave code.
+// true: this launch's step of the wave's envs is done (both waves return it alike). SHORT: `e` and `a` come in unloaded, and on false the
+// caller loads the env (the actions are in `a` for wave 0); otherwise e is not modified: on false it is the loaded state.
+template <bool SHORT>
+TB_DEV bool two_wave_step(const KArgs& A, EnvRegs& e, float* a, int i, bool live TB_DIAG_T0_ARG) {
   constexpr int K = TB_ENV_SWING;
+  static_assert(TB_W_RQ == TB_W_RP + 3 && TB_W_RV == TB_W_RP + 7 && TB_W_RW == TB_W_RP + 10 && TB_W_BV == TB_W_BP + 3 && TB_W_BW == TB_W_BP + 6,
+                "the racket's 13 rows and the ball's 9 are consecutive");
   const KParams& P = A.P;
   const bool racket_wave = threadIdx.x < 64;
   const int lane = (int)(threadIdx.x & 63);
@@ -663,14 +686,33 @@ TB_DEV bool two_wave_step(const KArgs& A, const EnvRegs& e, const float* a, int 
   __shared__ float s_ball_fin[64];  // the ball's new state is finite: 1 (wave 1 -> wave 0)
   __shared__ int s_rare;            // some env of the 64 fails the geometric tests (wave 1 -> wave 0)
   [[maybe_unused]] const int mk0 = racket_wave ? 0 : 8;  // (diagnostic marks, tools/diag/r06_two_wave_stamps.py)
-  TB_DIAG_WAIT_LOADS(live);
-  TB_DIAG_MARK(mk0);
-  if (__any(live && (e.done != TB_DONE_NO || e.step_count >= 25))) return false;  // two_wave_rare's first line: both waves hold these
+  if constexpr (!SHORT) {
+    TB_DIAG_WAIT_LOADS(live);
+    TB_DIAG_MARK(mk0);
+    if (__any(live && (e.done != TB_DONE_NO || e.step_count >= 25))) return false;  // two_wave_rare's first line: both waves hold these
+  }
   if (racket_wave) {
-    TB_DIAG_MARK(mk0 + 1);
     // swing_step and substep without a contact: the forces of :76-78, the velocity update, the pose update. Into a copy, and in
     // every lane (a lane past n computes on what its registers hold and stores nothing): no merge with the loaded state, no moves.
-    Racket r = e.r;
+    Racket r;
+    [[maybe_unused]] uint32_t at[13];  // SHORT: where the racket's rows are
+    if constexpr (SHORT) {
+      // (the offsets in front of the branch, all lanes: computed next to their loads inside it, 4096 envs ran 1.5 % slower)
+#pragma unroll
+      for (int k = 0; k < 13; ++k) at[k] = row_byte(TB_W_RP + k, A.n, i);
+      if (live) {
+        load_actions<K>(A.actions, (size_t)i, a);  // in the order of first use: the torque, the angular update, the linear one, the pose
+        r.w = mk(ld_at(A.words, at[10]), ld_at(A.words, at[11]), ld_at(A.words, at[12]));
+        r.q.x = ld_at(A.words, at[3]); r.q.y = ld_at(A.words, at[4]); r.q.z = ld_at(A.words, at[5]); r.q.w = ld_at(A.words, at[6]);
+        r.v = mk(ld_at(A.words, at[7]), ld_at(A.words, at[8]), ld_at(A.words, at[9]));
+        r.p = mk(ld_at(A.words, at[0]), ld_at(A.words, at[1]), ld_at(A.words, at[2]));
+      }
+      TB_DIAG_WAIT_LOADS(live);
+      TB_DIAG_MARK(mk0);
+    } else {
+      r = e.r;
+    }
+    TB_DIAG_MARK(mk0 + 1);
     const vec3 F = mk(a[0] * 400.0f, a[1] * 400.0f, FMA(a[2], 400.0f, 4.0f * 9.81f));
     const vec3 T = mk(a[3] * 5.0f, a[4] * 5.0f, a[5] * 5.0f);
     const float speed_r = sqrtf(dot(r.v, r.v));
@@ -684,11 +726,12 @@ TB_DEV bool two_wave_step(const KArgs& A, const EnvRegs& e, const float* a, int 
     if (__builtin_amdgcn_readfirstlane(s_rare)) return false;
     uint32_t cnt[TB_N_COUNTERS] = {};
     if (live) {
-      st<K>(A.words, TB_W_RP, A.n, i, r.p.x); st<K>(A.words, TB_W_RP + 1, A.n, i, r.p.y); st<K>(A.words, TB_W_RP + 2, A.n, i, r.p.z);
-      st<K>(A.words, TB_W_RQ, A.n, i, r.q.x); st<K>(A.words, TB_W_RQ + 1, A.n, i, r.q.y); st<K>(A.words, TB_W_RQ + 2, A.n, i, r.q.z);
-      st<K>(A.words, TB_W_RQ + 3, A.n, i, r.q.w);
-      st<K>(A.words, TB_W_RV, A.n, i, r.v.x); st<K>(A.words, TB_W_RV + 1, A.n, i, r.v.y); st<K>(A.words, TB_W_RV + 2, A.n, i, r.v.z);
-      st<K>(A.words, TB_W_RW, A.n, i, r.w.x); st<K>(A.words, TB_W_RW + 1, A.n, i, r.w.y); st<K>(A.words, TB_W_RW + 2, A.n, i, r.w.z);
+      const float out[13] = {r.p.x, r.p.y, r.p.z, r.q.x, r.q.y, r.q.z, r.q.w, r.v.x, r.v.y, r.v.z, r.w.x, r.w.y, r.w.z};
+#pragma unroll
+      for (int k = 0; k < 13; ++k) {
+        if constexpr (SHORT) st_at(A.words, at[k], out[k]);
+        else st<K>(A.words, TB_W_RP + k, A.n, i, out[k]);
+      }
       // state_is_finite's verdict on all 22 values: the racket's 13 here, the ball's 9 from wave 1
       float a0 = r.p.x * 0.0f, a1 = r.p.y * 0.0f, a2 = r.p.z * 0.0f, a3 = r.q.x * 0.0f;
       a0 = FMA(r.q.y, 0.0f, a0); a1 = FMA(r.q.z, 0.0f, a1); a2 = FMA(r.q.w, 0.0f, a2); a3 = FMA(r.v.x, 0.0f, a3);
@@ -700,6 +743,25 @@ TB_DEV bool two_wave_step(const KArgs& A, const EnvRegs& e, const float* a, int 
     flush_counters(A.counters, cnt);
     TB_DIAG_MARK(mk0 + 4);
   } else {
+    [[maybe_unused]] uint32_t at[10];  // SHORT: where the ball's rows and the step counter are
+    if constexpr (SHORT) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) at[k] = row_byte(TB_W_BP + k, A.n, i);
+      at[9] = row_byte(Dims<K>::W - 2, A.n, i);
+      if (live) {  // load_ball_side, the rows this wave stores through their kept offsets
+        const uint32_t* w = A.words;
+        e.r.p = mk(ld<K>(w, TB_W_RP, A.n, i), ld<K>(w, TB_W_RP + 1, A.n, i), ld<K>(w, TB_W_RP + 2, A.n, i));
+        e.r.q.x = ld<K>(w, TB_W_RQ, A.n, i); e.r.q.y = ld<K>(w, TB_W_RQ + 1, A.n, i); e.r.q.z = ld<K>(w, TB_W_RQ + 2, A.n, i); e.r.q.w = ld<K>(w, TB_W_RQ + 3, A.n, i);
+        e.b.p = mk(ld_at(w, at[0]), ld_at(w, at[1]), ld_at(w, at[2]));
+        e.b.v = mk(ld_at(w, at[3]), ld_at(w, at[4]), ld_at(w, at[5]));
+        e.b.w = mk(ld_at(w, at[6]), ld_at(w, at[7]), ld_at(w, at[8]));
+        e.aux[0] = ld<K>(w, 22, A.n, i); e.aux[1] = ld<K>(w, 23, A.n, i);
+        e.step_count = (int)word_at(w, at[9]);
+        e.done = A.done_state[i];
+      }
+      TB_DIAG_WAIT_LOADS(live);
+      TB_DIAG_MARK(mk0);
+    }
     Ball b = e.b;  // (as the racket: a copy, every lane)
     const float speed_b = sqrtf(dot(b.v, b.v)), spin_b = sqrtf(dot(b.w, b.w));
     ball_velocity(P, b, mk(0.0f, 0.0f, 0.0f), speed_b, spin_b);
@@ -717,10 +779,15 @@ TB_DEV bool two_wave_step(const KArgs& A, const EnvRegs& e, const float* a, int 
     TB_DIAG_MARK(mk0 + 3);
     if (rare) return false;
     if (live) {
-      st<K>(A.words, TB_W_BP, A.n, i, b.p.x); st<K>(A.words, TB_W_BP + 1, A.n, i, b.p.y); st<K>(A.words, TB_W_BP + 2, A.n, i, b.p.z);
-      st<K>(A.words, TB_W_BV, A.n, i, b.v.x); st<K>(A.words, TB_W_BV + 1, A.n, i, b.v.y); st<K>(A.words, TB_W_BV + 2, A.n, i, b.v.z);
-      st<K>(A.words, TB_W_BW, A.n, i, b.w.x); st<K>(A.words, TB_W_BW + 1, A.n, i, b.w.y); st<K>(A.words, TB_W_BW + 2, A.n, i, b.w.z);
-      row_store<true>(A.words, Dims<K>::W - 2, A.n, i, (uint32_t)(e.step_count + 1));  // :83; no contact: reward 0, not done (:98-106)
+      const float out[9] = {b.p.x, b.p.y, b.p.z, b.v.x, b.v.y, b.v.z, b.w.x, b.w.y, b.w.z};
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        if constexpr (SHORT) st_at(A.words, at[k], out[k]);
+        else st<K>(A.words, TB_W_BP + k, A.n, i, out[k]);
+      }
+      // :83; no contact: reward 0, not done (:98-106)
+      if constexpr (SHORT) word_to(A.words, at[9], (uint32_t)(e.step_count + 1));
+      else row_store<true>(A.words, Dims<K>::W - 2, A.n, i, (uint32_t)(e.step_count + 1));
       float2* o = reinterpret_cast<float2*>(A.obs + (size_t)i * 6);  // write_obs's rows
       o[0] = s_rp[lane]; o[1] = make_float2(b.p.x, b.p.y); o[2] = make_float2(e.aux[0], e.aux[1]);
       A.reward[i] = 0.0f;
@@ -778,11 +845,20 @@ constexpr bool step_rows_in_registers(int kind, bool lean, bool multi, bool rg, 
 // the variant that has a two-wave form (TWO_WAVE below), and the step kernel's dynamic LDS in words per lane (init_manifold below)
 constexpr bool step_has_two_waves(int kind, bool lean, bool multi, bool rg, bool policy) { return kind == TB_ENV_SWING && lean && !multi && !rg && !policy; }
 constexpr int step_lds_words(int kind, bool lean, bool multi, bool rg, bool policy) { return lds_words(!step_rows_in_registers(kind, lean, multi, rg, policy), rg); }
+// tb_step_kernel's arguments as they lie in the kernel-argument segment, and its KArgs fetched from there anew (see the kernel's SHORT form)
+struct StepKernelArgs { const uint32_t* words; const uint8_t* done; const float* actions; const float4* hull; int n, n_hull; KArgs A; };
+TB_DEV const KArgs* refetched_args() {
+  auto seg = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(seg));
+  return (const KArgs*)(seg + offsetof(StepKernelArgs, A));
+}
 // TWO_WAVE: two waves per 64 envs, the racket's update on one and the ball's on the other (two_wave_step; the pipelined SwingRacket
 // one-step kernel at small batch sizes). A launch whose 64 envs are not all on the common path runs them on wave 0 below.
-template <int KIND, bool LEAN, bool MULTI, bool RG, bool POLICY = false, bool TWO_WAVE = false, int NET = TB_NET_DEFAULT>
+// SHORT: the two-wave form for launches inside the lockstep episodes' short steps (two_wave_step<true>): loads are the waves' own.
+template <int KIND, bool LEAN, bool MULTI, bool RG, bool POLICY = false, bool TWO_WAVE = false, int NET = TB_NET_DEFAULT, bool SHORT = false>
 __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict__ k_words, const uint8_t* __restrict__ k_done, const float* __restrict__ k_actions,
-                                                      const float4* __restrict__ k_hull, int k_n, int k_nhull, KArgs A) {
+                                                      const float4* __restrict__ k_hull, int k_n, int k_nhull, KArgs k_args) {
+  const KArgs& A = k_args;
   // The leading arguments repeat A.words / done_state / actions / hull / n / P.n_hull as separate,
   // restrict-qualified kernel arguments: the compiler then knows that the state loads every launch starts
   // with cannot alias the stores it ends with. (Preloading them into SGPRs at wave launch,
@@ -796,6 +872,7 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
   // like every kernel that loops (fast-forward, tb_rollout, the fused policy).
   constexpr bool TABLE_IN_MEMORY = !POLICY && !MULTI && KIND == TB_ENV_TENNIS;
   static_assert(!TWO_WAVE || step_has_two_waves(KIND, LEAN, MULTI, RG, POLICY), "the two-wave form is the pipelined SwingRacket one-step kernel's");
+  static_assert(!SHORT || TWO_WAVE, "the short form is a two-wave form");
   constexpr bool REGROWS = step_rows_in_registers(KIND, LEAN, MULTI, RG, POLICY);
   // LAZYTAB (tb_step on pipelined SwingRacket without the extended contact set): the LDS copy is made by the first wave that reads it (substep's SF_LAZYTAB form)
   constexpr bool LAZYTAB = !POLICY && !MULTI && KIND == TB_ENV_SWING && LEAN && !RG;
@@ -823,7 +900,7 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
   // issue every load this launch depends on back to back -- state rows, the first step's actions,
   // the outline table -- so that their latencies overlap instead of queueing behind the barrier
   float a[NA];
-  if (live && !(POLICY && threadIdx.x >= 64)) {
+  if (!SHORT && live && !(POLICY && threadIdx.x >= 64)) {
     if (TWO_WAVE && threadIdx.x >= 64) {
       load_ball_side(w_words, w_done, w_n, i, e);
     } else {
@@ -832,12 +909,24 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
     }
   }
   if constexpr (TWO_WAVE) {
-    if (two_wave_step(A, e, a, i, live TB_DIAG_T0_PASS)) {
+    if (two_wave_step<SHORT>(A, e, a, i, live TB_DIAG_T0_PASS)) {
       TB_DIAG_TRACE_EXIT(trace_slot);
       TB_DIAG_CADENCE_EXIT(cad_t0, cad_n);
       return;
     }
     if (threadIdx.x >= 64) return;  // a rare-path launch: wave 0 steps the 64 envs below from the loaded state (no barrier there)
+  }
+  // SHORT, a rare-path launch: from here on wave 0 reads its arguments through a pointer the compiler cannot look behind. Left alone it
+  // fetches what only the code below needs (most of the parameter block) at the kernel's entry, past the scalar register file's end, and
+  // the spills -- scalar round trips one behind the other -- stand in front of the common path's first state load.
+  const KArgs* late_args = &k_args;
+  if constexpr (SHORT) late_args = refetched_args();
+  {
+  const KArgs& A = *late_args;
+  const float4* __restrict__ w_hull = SEP ? k_hull : A.hull;
+  const int w_nhull = SEP ? k_nhull : A.P.n_hull;
+  if constexpr (SHORT) {
+    if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);  // the whole env only now (the actions are in `a`)
   }
 #if TB_HINT_TENNIS_CONSTANTS
   if constexpr (KIND == TB_ENV_TENNIS && !POLICY && !MULTI) {
@@ -933,6 +1022,7 @@ __global__ void __launch_bounds__(256) tb_step_kernel(const uint32_t* __restrict
   TB_DIAG_ADD_LANE0(14, __builtin_amdgcn_s_memrealtime() - rt_kernel0);
   TB_DIAG_TRACE_EXIT(trace_slot);
   TB_DIAG_CADENCE_EXIT(cad_t0, cad_n);
+  }
 }
 
 // T agent steps with the policy inside, ONE launch: no launch boundary, no state round trip between the
@@ -1154,6 +1244,7 @@ __global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double
   double ret = 0.0;
   int len = 0;
   constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);  // tb_policy_rollout_kernel<KIND, 1>'s
+  TB_DIAG_STAMPS_BEGIN(st);
   for (int t = 0;; ++t) {
     float eps[NA];
 #pragma unroll
@@ -1191,6 +1282,7 @@ __global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double
   }
   if (live) { ret_out[i] = ret; len_out[i] = len; }
   flush_counters(A.counters, cnt);
+  TB_DIAG_STAMPS_END(st);
 }
 
 // progress mark (tb_mark_record): one thread bumps a counter in pinned host memory. Relaxed on purpose: the kernels this

@@ -605,6 +605,19 @@ struct PolicyIO {  // non-null weights = fused policy step
   }
 };
 
+// Which form of the pipelined SwingRacket one-step kernel a launch gets (tb_step_form's values). A handle with the two-wave kernel
+// (TbOptions.step_waves) runs it where the variant has that form -- and the host, which knows the episode phase while the envs are in
+// lockstep, picks per launch: steps 1-25 (every env has done = 0 and step_count = phase < 25) the SHORT form, whose waves load only
+// their own side and test nothing before they compute; the 26th step, where every env parks, the one-wave kernel at once, without a
+// ball wave started only to be thrown away; with the phase unknown (a masked reset, an injected state) the form with the early gate
+// and the full loads. A captured launch keeps the form of the phase it was captured at, like its fast-forward slot.
+enum { TB_STEP_ONE_WAVE = 0, TB_STEP_TWO_WAVE_GATE = 1, TB_STEP_TWO_WAVE_SHORT = 2 };
+int step_form(const TbHandle* h, bool lean, bool multi, bool rg, bool policy) {
+  if (!h->two_wave || !step_has_two_waves(h->kind, lean, multi, rg, policy)) return TB_STEP_ONE_WAVE;
+  if (!h->phase.valid) return TB_STEP_TWO_WAVE_GATE;
+  return h->phase.launch_ends_episode(1) ? TB_STEP_ONE_WAVE : TB_STEP_TWO_WAVE_SHORT;
+}
+
 // lean_multi (T > 1): the caller guarantees lockstep episodes (phase_valid) and that an episode can only
 // end at the LAST of the T steps (phase + T <= 26), so the launch parks at most once per env and the
 // pipelined kernel (no in-kernel fast-forward) can run several steps per launch too.
@@ -631,8 +644,12 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
   if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
   const bool rg = extended_contacts(h->kp);  // selects the instantiation that contains the rolling-friction rows
   const bool multi = T > 1, policy = pol != nullptr;
-  const bool two_wave = h->two_wave && step_has_two_waves(h->kind, piped, multi, rg, policy);
-  const StepKernel kern = step_kernel(h->kind, piped, multi, rg, policy, two_wave, pol ? pol->net : TB_NET_DEFAULT);
+  // the handle's two-wave kernel in the form the episode phase allows (step_form): the parking step of lockstep episodes goes to the
+  // one-wave kernel directly, with the grid and block of a step_waves = 1 handle
+  const int form = step_form(h, piped, multi, rg, policy);
+  const bool two_wave = form != TB_STEP_ONE_WAVE;
+  const StepKernel kern = form == TB_STEP_TWO_WAVE_SHORT ? tb_step_kernel<TB_ENV_SWING, true, false, false, false, true, TB_NET_DEFAULT, true>
+                                                         : step_kernel(h->kind, piped, multi, rg, policy, two_wave, pol ? pol->net : TB_NET_DEFAULT);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_step_kernel instantiation for this variant");
   if (two_wave) { grid = dim3((unsigned)((h->n + 63) / 64)); block = dim3(128); }  // two waves per 64 envs
   const size_t lds = dyn_lds(step_lds_words(h->kind, piped, multi, rg, policy), policy ? 64u : block.x);
@@ -886,6 +903,12 @@ int tb_step_waves(TbHandle* h) {
   if (!h) return fail(TB_E_INVAL, "tb_step_waves: null handle");
   if (h->kind != TB_ENV_SWING || !h->pipeline) return 0;
   return h->two_wave ? 2 : 1;
+}
+
+int tb_step_form(TbHandle* h) {
+  if (!h) return fail(TB_E_INVAL, "tb_step_form: null handle");
+  if (h->kind != TB_ENV_SWING || !h->pipeline || !(h->kp.flags & TB_F_AUTO_RESET)) return -1;
+  return step_form(h, true, false, extended_contacts(h->kp), false);
 }
 
 int tb_phase_advance(TbHandle* h, int n_steps) {

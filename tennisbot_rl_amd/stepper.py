@@ -163,6 +163,8 @@ def load_library():
     L.tb_pipeline_form.restype = i32
     L.tb_step_waves.argtypes = [vp]
     L.tb_step_waves.restype = i32
+    L.tb_step_form.argtypes = [vp]
+    L.tb_step_form.restype = i32
     L.tb_params_generation.argtypes = [vp]
     L.tb_params_generation.restype = i32
     L.tb_set_racket_scale.argtypes = [vp, ctypes.c_float, vp]
@@ -669,6 +671,11 @@ class BatchedEnv:
         """tb_step_waves: waves per 64 envs of the pipelined SwingRacket one-step kernel, 2 (racket and ball on waves of their own) or 1;
         0 without that kernel"""
         return int(self.L.tb_step_waves(self._h))
+
+    def step_form(self):
+        """tb_step_form: which form of that kernel the next step() launches -- 0 one-wave, 1 two-wave with the early gate, 2 two-wave
+        short (lockstep episodes, not their last step); -1 without that kernel"""
+        return int(self.L.tb_step_form(self._h))
 
     # ------------------------------------------------------------------ state save / restore
     def get_state_words(self):

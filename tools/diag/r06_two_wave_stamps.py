@@ -4,7 +4,9 @@ episode, at 4096 envs (diagnostic build, -DTB_DIAG_STAMPS; needs a GPU). For eac
 entry stamp to: its loads landed (an explicit wait for every load: the build is not the product's), the common-path gate done,
 barrier arrival, barrier passed, stores issued. Every mark fences the scheduler and costs ~40 cycles: read the differences, not the
 absolute span. Prints a table (and writes it to --out FILE: profiles/r06_two_wave_stamps_*.txt).
-    python tools/diag/r06_two_wave_stamps.py [--envs N] [--out FILE]"""
+On a handle in lockstep these are launches of the kernel's SHORT form (BatchedEnv.step_form() == 2), whose waves issue their own
+loads: "loads landed" and "gate done" then coincide (that form has no gate).
+    python tools/diag/r06_two_wave_stamps.py [--envs N] [--out FILE] [--lib BUILD.so]"""
 import argparse
 import ctypes
 import os
@@ -24,9 +26,12 @@ from tennisbot_rl_amd.params import ENV_SWING  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--out", default=None)
+ap.add_argument("--lib", default=None, help="a -DTB_DIAG_STAMPS build made beforehand (default: compile one now)")
 args = ap.parse_args()
-out = os.path.join(tempfile.mkdtemp(prefix="tb_r06_"), "libtb_stamps.so")
-subprocess.check_call([hipcc()] + HIPCC_FLAGS + ["-DTB_DIAG_STAMPS", "-o", out] + SOURCES)
+out = args.lib
+if out is None:
+    out = os.path.join(tempfile.mkdtemp(prefix="tb_r06_"), "libtb_stamps.so")
+    subprocess.check_call([hipcc()] + HIPCC_FLAGS + ["-DTB_DIAG_STAMPS", "-o", out] + SOURCES)
 stepper.use_library(out)
 L = stepper.load_library()
 L.tb_diag_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]

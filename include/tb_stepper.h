@@ -411,6 +411,36 @@ int tb_policy_evaluate(TbHandle *h, int net, const float *weights_dev, double *r
                        uint64_t noise_seed, int deterministic, void *stream);
 
 /*
+ * Whole-episode evaluation of a SAC / TQC actor (the two share it): one launch runs every env's whole episode with the
+ * 256-wide actor inside (csrc/tb_sac.hpp, tb_sac_evaluate_kernel: 16 envs per four-wave workgroup, weights streamed from L2).
+ *   actor_dev: the flat TB_SAC_ACTOR vector, tb_sac_param_floats(kind, TB_SAC_ACTOR) floats, as the learner trains it.
+ *   Per step a = tanh(mu + exp(clamp(log_std, -20, 2)) eps) with mu / log_std computed element for element as
+ *     tb_sac_actor_forward computes them; eps is tb_policy_step's noise, keyed by (noise_seed, global env id, episode, step);
+ *     deterministic != 0 gives eps = 0. A NaN action stays NaN.
+ *   return_dev [n_envs] doubles: the float64 sum of the float32 step rewards in step order through the first done;
+ *   length_dev [n_envs]: the episode length in agent steps (SwingRacket: always 26; Tennisbot: <= 1001).
+ * Every call first resets every env exactly as tb_reset(h, NULL, ...) does: env i evaluates the episode whose index is one past
+ * the one it was in (on a fresh handle the k-th call, counted from 0 and with no other reset in between, evaluates episode k),
+ * and on return every env holds that episode's freshly reset state again (the episode phase is 0): no state word is written.
+ * SwingRacket-v0 requires tb_set_pipeline(h, 1) (TB_E_UNSUPPORTED otherwise): the 26th step's fast-forward runs on the
+ * pipeline's kernels. Results are complete in stream order on `stream` when the call returns -- no tb_flush is needed.
+ * Null h / actor_dev / return_dev / length_dev, or a trace whose struct_size is not sizeof(TbSacEvalTrace) or with a null
+ * array: TB_E_INVAL; nothing is launched on a refusal. The trace never changes a result; rows after an env's last step are
+ * not written. Counters: episodes finished and substeps are counted by the kernel (no host share).
+ */
+typedef struct TbSacEvalTrace {
+  size_t struct_size;  /* sizeof(TbSacEvalTrace) */
+  int max_steps;       /* rows [max_steps][n_envs]; later steps are not recorded */
+  float *obs;          /* [T][N][O] the observation step t acted on (t = 0: the reset's) */
+  float *eps;          /* [T][N][A] the noise drawn for step t (0 when deterministic) */
+  float *actions;      /* [T][N][A] the squashed action step t was taken with */
+  float *reward;       /* [T][N]   (SwingRacket's step 25: the fast-forward's terminal reward) */
+  uint8_t *done;       /* [T][N] */
+} TbSacEvalTrace;
+int tb_sac_evaluate(TbHandle *h, const float *actor_dev, double *return_dev, int32_t *length_dev, uint64_t noise_seed,
+                    int deterministic, const TbSacEvalTrace *trace_or_null, void *stream);
+
+/*
  * The PPO learner (csrc/tb_learner.hpp; tennisbot_rl_amd/learner.py is the caller): GAE, one minibatch's gradient, and the
  * optimiser step, fp32, for the two policy architectures the fused policy kernels are instantiated for. These functions need
  * no env: they take (env_kind, device, stream) instead of a TbHandle, every buffer is caller-owned device memory, and every

@@ -225,6 +225,14 @@ __global__ __launch_bounds__(256) void sac_gather_kernel(const float* obs, int O
   out[(size_t)b * SAC_XW + c] = v;
 }
 
+// the squashed sample of one action component from the head's outputs (ls: the clamped log_std): ONE copy for sac_sample_kernel and
+// tb_sac_evaluate_kernel, so the two cannot drift
+TB_DEV float sac_squash_sample(float mu, float log_std, float ep, float& ls) {
+  ls = fminf(fmaxf(log_std, SAC_LOG_STD_MIN), SAC_LOG_STD_MAX);
+  const float gs = mu + expf(ls) * ep;
+  return tanhf(gs);
+}
+
 // one thread per row: the squashed sample and its log-probability from the head's outputs zh[b] = mu [A] | log_std [A];
 // xc[b] = the row's observation | the sample | 0: the critics' input; lp[b][0] = logp. act_out / logp_out may be null
 __global__ __launch_bounds__(256) void sac_sample_kernel(const float* x0, const float* zh, const float* eps, int O, int A, int B, float* act_out, float* logp_out, float* xc,
@@ -236,9 +244,9 @@ __global__ __launch_bounds__(256) void sac_sample_kernel(const float* x0, const 
   float s_gauss = 0.0f, s_squash = 0.0f;
   for (int c = 0; c < SAC_XW; ++c) xr[c] = c < O ? x0[(size_t)b * SAC_XW + c] : 0.0f;
   for (int j = 0; j < A; ++j) {
-    const float ls = fminf(fmaxf(z[A + j], SAC_LOG_STD_MIN), SAC_LOG_STD_MAX), ep = eps[(size_t)b * A + j];
-    const float gs = z[j] + expf(ls) * ep;
-    const float t = tanhf(gs);
+    const float ep = eps[(size_t)b * A + j];
+    float ls;
+    const float t = sac_squash_sample(z[j], z[A + j], ep, ls);
     s_gauss += (-0.5f * ep * ep - ls) - TB_LN_SQRT_2PI;
     s_squash += logf((1.0f - t * t) + SAC_SQUASH_EPS);
     xr[O + j] = t;
@@ -357,6 +365,215 @@ __global__ __launch_bounds__(256) void sac_adam_kernel(float* params, const floa
 __global__ __launch_bounds__(256) void sac_polyak_kernel(const float* params, float* target, long long n, float one_minus_tau, float tau) {
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
   if (p < n) target[p] = one_minus_tau * target[p] + tau * params[p];
+}
+
+// ------------------------------------------------------------------------------- whole episodes in one launch (tb_sac_evaluate)
+// tb_policy_evaluate_kernel's env side with SAC's / TQC's 256-wide actor inside the episode loop. A workgroup owns 16 envs and is
+// FOUR waves, one per SIMD (__launch_bounds__(256): the env wave keeps the register budget it has in tb_policy_evaluate_kernel).
+// Waves 0-3 share the actor; wave 3 is also the env wave: the 16 envs' state in its registers, lanes >= 16 and lanes whose episode
+// is over step the dummy (idle_env). The actor does not fit registers or LDS (283 KB): its weights stream from global memory (L2)
+// every step, straight from the flat TB_SAC_ACTOR vector, and the activations of the 16 rows live in LDS.
+// ARITHMETIC: every output element is sac_forward_kernel's: one f32-input MFMA chain from a zero accumulator over k ascending in
+// steps of four (zeros beyond O in the first layer), then + bias, then fmaxf(., 0) on the hidden layers. An output row depends on
+// its own input row only and a tile on its own chain only, so which wave runs which tile changes no bit. A wave owns 4 of the 16
+// tiles of a hidden layer (four interleaved chains hide the MFMA's dependent latency); mu is one tile on wave 0, log_std on wave 1.
+// LDS: s_obs [16][O]; s_h1, s_h2 [16][SAC_EV_STRIDE]: a row stride of 260 floats puts the 16 rows x 4 k's a lane group reads of
+// one MFMA step into 64 different banks (4 e + g; 256 would be a 16-way conflict) and keeps the float4 stores aligned; s_head
+// [16][16]: mu at [0 .. A), log_std at [8 .. 8 + A); s_go.
+// BARRIERS. Every wave executes one barrier behind the set-up and FOUR per iteration, on every path; no wave returns inside the
+// loop, and the loop ends at T_MAX whatever s_go holds:
+//   set-up  env wave: s_obs = the reset observations (idle rows too); all: the outline table          -> barrier 0
+//   (1)     all: s_h1 = relu(W0 s_obs + b0), tiles 4 w .. 4 w + 3                                      -> barrier 1  "h1 is in LDS"
+//   (2)     all: s_h2 = relu(W1 s_h1 + b1)                                                             -> barrier 2  "h2 is in LDS"
+//   (3)     wave 0: s_head mu, wave 1: s_head log_std (from s_h2); env wave: draws the noise           -> barrier 3  "the head is in LDS"
+//   (4)     env wave: sample (s_head), trace (s_obs), env step, s_obs of the live envs, lane 0: s_go   -> barrier 4  "obs and s_go are in LDS"
+//           all: leave unless t + 1 < T_MAX && s_go -- the same t and the same word in every wave, hence the same verdict.
+// Who may overwrite what: s_h1 is next written in (1) of t + 1, behind barrier 4, its readers ((2) of t) are in front of barrier
+// 2; s_h2 is next written behind barrier 1 of t + 1, its readers ((3) of t) are in front of barrier 3; s_head is next written
+// behind barrier 2 of t + 1, its reader ((4) of t) is in front of barrier 4; s_obs and s_go are written behind barrier 3 only,
+// s_obs is read in front of barrier 1 (and by the env wave itself in (4), before it writes), s_go between barrier 4 and barrier 1.
+constexpr int SAC_EV_STRIDE = SAC_H + 4;
+
+struct SacEvalArgs {
+  const float* actor;  // the flat TB_SAC_ACTOR vector
+  double* ret;         // [n] (SwingRacket: without the terminal reward, which tb_es_fold_kernel adds)
+  int32_t* len;        // [n]
+  // optional trace, rows [t][n] (TbSacEvalTrace); t_max = 0: off
+  int t_max;
+  float *t_obs, *t_eps, *t_act, *t_rew;
+  uint8_t* t_done;
+};
+
+// NT tiles of one layer for the 16 rows x (LDS): tile j's weight row of this lane is w + j * tile_step. acc[j][r]: output
+// 16 j + 4 g + r of row e. The chain of sac_forward_kernel per tile: whole chunks of SAC_UNROLL steps, then single steps.
+template <int NT, int K>
+TB_DEV void sac_ev_chain(const float* w, int tile_step, bool o_in, const float* xrow, int g, f32x4* acc) {
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  constexpr int KW = K / (4 * SAC_UNROLL) * (4 * SAC_UNROLL);
+#pragma unroll 1  // (one chunk's loads in flight, not the layer's: the env wave's state stays in registers beside them)
+  for (int k0 = 0; k0 < KW; k0 += 4 * SAC_UNROLL) {
+    float wl[NT][SAC_UNROLL], xl[SAC_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SAC_UNROLL; ++u) {
+      xl[u] = xrow[k0 + 4 * u + g];
+#pragma unroll
+      for (int j = 0; j < NT; ++j) wl[j][u] = w[j * tile_step + k0 + 4 * u + g];
+    }
+#pragma unroll
+    for (int u = 0; u < SAC_UNROLL; ++u) {
+#pragma unroll
+      for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(o_in ? wl[j][u] : 0.0f, xl[u], acc[j], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int k0 = KW; k0 < K; k0 += 4) {
+    const int k = k0 + g, kc = k < K ? k : K - 1;  // (every address is a valid one; what lies outside is selected away)
+    const bool k_in = k < K;
+    const float xl = xrow[kc];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const float wl = w[j * tile_step + kc];
+      acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32((o_in && k_in) ? wl : 0.0f, k_in ? xl : 0.0f, acc[j], 0, 0, 0);
+    }
+  }
+}
+
+// one hidden layer's share of a wave: h[e][64 wave + 16 j + 4 g + r] = relu(acc + bias)
+template <int K>
+TB_DEV void sac_ev_hidden(const float* W, const float* bias, const float* x, int xs, float* h, int wave, int g, int e) {
+  f32x4 acc[4];
+  const int o0 = 64 * wave;
+  sac_ev_chain<4, K>(W + (size_t)(o0 + e) * K, 16 * K, true, x + e * xs, g, acc);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int oo = o0 + 16 * j + 4 * g;
+    float4 v;
+    v.x = fmaxf(acc[j][0] + bias[oo], 0.0f); v.y = fmaxf(acc[j][1] + bias[oo + 1], 0.0f);
+    v.z = fmaxf(acc[j][2] + bias[oo + 2], 0.0f); v.w = fmaxf(acc[j][3] + bias[oo + 3], 0.0f);
+    *reinterpret_cast<float4*>(h + e * SAC_EV_STRIDE + oo) = v;
+  }
+}
+
+template <int KIND, bool RG>
+__global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalArgs S) {
+  using L = SacLayout<KIND>;
+  constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE, ENV_WAVE = 3;
+  static_assert(NA == L::A && NO == L::O && E == 16 && NA <= 8, "the actor's rows are the envs of one slice");
+  constexpr int T_MAX = KIND == TB_ENV_SWING ? 26 : 1001;  // tb_es_rollout_kernel's: every episode is over by then
+  __shared__ float4 s_hull[TB_HULL_LDS];
+  __shared__ __attribute__((aligned(16))) float s_obs[E * NO];
+  __shared__ __attribute__((aligned(16))) float s_h1[E * SAC_EV_STRIDE];
+  __shared__ __attribute__((aligned(16))) float s_h2[E * SAC_EV_STRIDE];
+  __shared__ __attribute__((aligned(16))) float s_head[E * 16];
+  __shared__ int s_go;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, g = lane >> 4, er = lane & 15;
+  const bool env_wave = wave == ENV_WAVE;
+  stage_hull(s_hull, A.hull, A.P.n_hull);
+  const int i = blockIdx.x * E + lane;
+  const bool live = env_wave && lane < E && i < A.n;
+  EnvRegs e;
+  idle_env(e);
+  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);  // the state tb_reset just wrote: the episode's start, no contacts cached
+  Manifold M;
+  init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
+  uint32_t cnt[TB_N_COUNTERS] = {};
+  if (env_wave && lane < E) {  // (rows without an env hold the dummy's observation: finite, and no row reads another)
+    float o[NO];
+    make_obs<KIND>(e, o);
+#pragma unroll
+    for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+  }
+  __syncthreads();  // barrier 0: the outline table and the episodes' first observations are in LDS
+  KParams Pl = A.P;  // (the substep's constants in vector registers: see tb_policy_rollout_kernel)
+#if TB_HINT_POLICY_VGPR_PARAMS
+#define TB_PIN(f) asm volatile("" : "+v"(Pl.f))
+  TB_PIN(dt); TB_PIN(gravity); TB_PIN(lin_damp); TB_PIN(ang_damp); TB_PIN(lin_damp_quad); TB_PIN(ang_damp_quad); TB_PIN(max_ang_step); TB_PIN(contact_threshold);
+  TB_PIN(racket_inv_mass); TB_PIN(racket_inertia[0]); TB_PIN(racket_inertia[1]); TB_PIN(racket_inertia[2]);
+  TB_PIN(racket_inv_inertia[0]); TB_PIN(racket_inv_inertia[1]); TB_PIN(racket_inv_inertia[2]);
+  TB_PIN(racket_half_thick); TB_PIN(hull_margin); TB_PIN(hull_bound_radius); TB_PIN(ball_inv_mass); TB_PIN(ball_radius); TB_PIN(magnus_k); TB_PIN(static_top);
+#undef TB_PIN
+#endif
+  bool active = live;
+  double ret = 0.0;
+  int len = 0;
+  constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);  // tb_policy_evaluate_kernel's
+  TB_DIAG_STAMPS_BEGIN(st);
+  for (int t = 0;; ++t) {
+    sac_ev_hidden<NO>(S.actor + L::PI_W0, S.actor + L::PI_B0, s_obs, NO, s_h1, wave, g, er);
+    __syncthreads();  // barrier 1: h1 is in LDS
+    sac_ev_hidden<SAC_H>(S.actor + L::PI_W1, S.actor + L::PI_B1, s_h1, SAC_EV_STRIDE, s_h2, wave, g, er);
+    __syncthreads();  // barrier 2: h2 is in LDS
+    float eps[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) eps[k] = 0.0f;
+    if (wave < 2) {  // mu (wave 0) and log_std (wave 1): one tile each, rows er < A of the head's block
+      const float* hw = S.actor + L::PI_HEAD + wave * L::PI_HEAD_BLOCK;
+      const bool o_in = er < NA;
+      f32x4 acc[1];
+      sac_ev_chain<1, SAC_H>(hw + (size_t)(o_in ? er : 0) * SAC_H, 0, o_in, s_h2 + er * SAC_EV_STRIDE, g, acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int oo = 4 * g + r;
+        if (oo < NA) s_head[er * 16 + wave * 8 + oo] = acc[0][r] + hw[NA * SAC_H + oo];
+      }
+    } else if (env_wave) {
+      if (active) policy_draw<KIND>(A, i, e, eps);  // while the head runs
+    }
+    __syncthreads();  // barrier 3: the head is in LDS
+    if (env_wave) {
+      float a[NA], o[NO];
+#pragma unroll
+      for (int k = 0; k < NA; ++k) a[k] = 0.0f;
+      const bool rec = active && t < S.t_max;
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+          float ls;
+          a[k] = sac_squash_sample(s_head[lane * 16 + k], s_head[lane * 16 + 8 + k], eps[k], ls);
+        }
+        if (rec) {
+          const size_t row = (size_t)t * A.n + i;
+#pragma unroll
+          for (int k = 0; k < NO; ++k) S.t_obs[row * NO + k] = s_obs[lane * NO + k];
+#pragma unroll
+          for (int k = 0; k < NA; ++k) { S.t_eps[row * NA + k] = eps[k]; S.t_act[row * NA + k] = a[k]; }
+        }
+      }
+      int ns = 1;
+      bool d = false, parked = false;
+      float rew;
+      // (every lane of the wave, dummies included: the substep's outline sweep is shared among all 64, SF_WIDE)
+      if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
+      else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
+      if (active) {
+        end_agent_step<KIND, RG, false>(A, i, e, M, parked, ns, (size_t)i, o, d, cnt);  // (tb_sac_evaluate claims a slot for every env)
+        if (parked) rew = 0.0f;  // the 26th step: its reward is the fast-forward's, folded in after the flush
+        else ret += (double)rew;
+        len = t + 1;
+        if (rec) {
+          S.t_rew[(size_t)t * A.n + i] = rew;
+          S.t_done[(size_t)t * A.n + i] = d ? 1 : 0;
+        }
+        if (d) {
+          cnt[5]++;
+          active = false;
+          idle_env(e);  // from here on this lane steps the dummy
+          M.n = 0; M.deep = 0;
+        } else {
+#pragma unroll
+          for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+        }
+      }
+      const bool go = __ballot(active) != 0ull;
+      if (lane == 0) s_go = go ? 1 : 0;
+    }
+    __syncthreads();  // barrier 4: the observations after step t, and s_go, are in LDS
+    if (!(t + 1 < T_MAX && __builtin_amdgcn_readfirstlane(s_go) != 0)) break;
+  }
+  if (live) { S.ret[i] = ret; S.len[i] = len; }
+  if (env_wave) flush_counters(A.counters, cnt);
+  TB_DIAG_STAMPS_END(st);
 }
 
 }  // namespace

@@ -1217,6 +1217,47 @@ int tb_policy_evaluate(TbHandle* h, int net, const float* weights_dev, double* r
   return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
 }
 
+// tb_policy_evaluate's body with SAC's / TQC's actor inside the loop (tb_sac.hpp, tb_sac_evaluate_kernel), four waves per 16 envs
+int tb_sac_evaluate(TbHandle* h, const float* actor_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
+                    const TbSacEvalTrace* trace, void* stream) {
+  if (!h || !actor_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_sac_evaluate: null argument");
+  const bool swing = h->kind == TB_ENV_SWING;
+  if (swing && !h->pipeline)
+    return fail(TB_E_UNSUPPORTED, "tb_sac_evaluate on SwingRacket-v0 needs tb_set_pipeline(h, 1): the 26th step's fast-forward runs on the pipeline's kernels");
+  SacEvalArgs S;
+  memset(&S, 0, sizeof S);
+  S.actor = actor_dev; S.ret = return_dev; S.len = length_dev;
+  if (trace) {
+    if (trace->struct_size != sizeof(TbSacEvalTrace)) return fail(TB_E_INVAL, "tb_sac_evaluate: TbSacEvalTrace.struct_size is not sizeof(TbSacEvalTrace)");
+    if (trace->max_steps > 0) {
+      if (!trace->obs || !trace->eps || !trace->actions || !trace->reward || !trace->done) return fail(TB_E_INVAL, "tb_sac_evaluate: a TbSacEvalTrace array is null");
+      S.t_max = trace->max_steps; S.t_obs = trace->obs; S.t_eps = trace->eps; S.t_act = trace->actions; S.t_rew = trace->reward; S.t_done = trace->done;
+    }
+  }
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (swing && !h->d_es_rew) HIP_TRY(hipMalloc((void**)&h->d_es_rew, sizeof(float) * (size_t)h->n));
+  if (int rc = tb_reset(h, nullptr, nullptr, stream)) return rc;  // (flushes the pipeline; every env in lockstep at phase 0)
+  KArgs a = base_args(h);
+  a.pol_seed = noise_seed; a.pol_deterministic = deterministic;
+  a.reward = h->d_es_rew;  // (SwingRacket: the fast-forward's destination for the 26th step's reward)
+  Park park;
+  if (int rc = claim_park(h, swing, a, s, &park)) return rc;
+  const bool rg = extended_contacts(h->kp);
+  void (*kern)(KArgs, SacEvalArgs) = swing ? (rg ? tb_sac_evaluate_kernel<TB_ENV_SWING, true> : tb_sac_evaluate_kernel<TB_ENV_SWING, false>)
+                                           : (rg ? tb_sac_evaluate_kernel<TB_ENV_TENNIS, true> : tb_sac_evaluate_kernel<TB_ENV_TENNIS, false>);
+  const unsigned groups = (unsigned)((h->n + TB_POLICY_SLICE - 1) / TB_POLICY_SLICE);
+  (void)hipGetLastError();
+  if (int rc = launch(kern, dim3(groups), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S)) return rc;  // (dynamic LDS: the env wave's columns)
+  if (swing) {
+    if (int rc = finish_park(h, park, a, 0, s)) return rc;
+    if (int rc = flush_all(h, s)) return rc;  // every fast-forward's reward is in d_es_rew once `s` gets past here
+    float* const last_rew = S.t_max >= kEpisodeSteps ? S.t_rew : nullptr;  // (a trace that reaches the episode's last step)
+    if (int rc = launch(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n, last_rew)) return rc;
+  }
+  return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
+}
+
 // ------------------------------------------------------------------------------------------ the PPO learner (tb_learner.hpp)
 int tb_ppo_param_floats(int env_kind) {
   return env_kind == TB_ENV_SWING ? PpoLayout<TB_ENV_SWING>::P : env_kind == TB_ENV_TENNIS ? PpoLayout<TB_ENV_TENNIS>::P : TB_E_INVAL;

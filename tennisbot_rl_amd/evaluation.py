@@ -7,8 +7,10 @@ Counterpart of the two callbacks the reference's scripts install around `learn()
     tb_policy_evaluate): the mean is a mean over finished episodes, each counted once from its first step to its first `done`;
     the training batch, its episode phase and its captured graph are never touched, and no torch RNG is drawn from (the
     exploration noise is keyed inside the kernel).
-  * `evaluate_actor_episodes` is the same protocol for a torch actor stepped between env steps (SAC / TQC, whose 256-wide
-    actor does not fit the register-resident towers): first-`done` masks and float64 sums stay on the device.
+  * `ActorEvaluator` is its counterpart for SAC / TQC: the flat actor vector the learner trains, inside the episode loop of one
+    launch (BatchedEnv.sac_evaluate, tb_sac_evaluate).
+  * `evaluate_actor_episodes` is the same protocol for a torch actor stepped between env steps (SAC / TQC's default form):
+    first-`done` masks and float64 sums stay on the device.
   * `EvalSchedule` fires evaluations and checkpoints as `num_timesteps` crosses multiples of `eval_freq` / `save_freq`.
 """
 import math
@@ -29,14 +31,14 @@ def summarise(torch, returns, lengths):
     return {"episodes": int(r.numel()), "mean": row[0], "std": row[1], "min": row[2], "max": row[3], "mean_length": row[4]}
 
 
-class PolicyEvaluator:
-    """n_envs evaluation envs of their own for the fused policy networks (PPO / TRPO; NET_DEFAULT or Tennisbot's NET_TUNED)"""
+class _EpisodeEvaluator:
+    """n_envs evaluation envs of their own; a subclass says which launch runs their episodes (_launch)"""
 
-    def __init__(self, kind, n_envs=64, seed=0, params=None, options=None, device=None, net=NET_DEFAULT, env_id_base=EVAL_ENV_ID_BASE):
+    def __init__(self, kind, n_envs, seed, params, options, device, env_id_base):
         if isinstance(kind, str):
             kind = ENV_IDS[kind]
-        self.kind, self.n_envs, self.net, self.seed = kind, int(n_envs), int(net), int(seed)
-        # SwingRacket: the 26th step's fast-forward runs on the pipeline's kernels (tb_policy_evaluate requires it)
+        self.kind, self.n_envs, self.seed = kind, int(n_envs), int(seed)
+        # SwingRacket: the 26th step's fast-forward runs on the pipeline's kernels (tb_policy_evaluate / tb_sac_evaluate require it)
         self.env = BatchedEnv(kind, self.n_envs, device=device, seed=self.seed, env_id_base=int(env_id_base), params=params, track_terminal_obs=False,
                               pipeline=kind == ENV_SWING, options=options)
         self.device = self.env.device
@@ -46,7 +48,7 @@ class PolicyEvaluator:
         """Tennisbot's racket-size curriculum: takes effect at the reset every evaluation call starts with"""
         self.env.set_racket_scale(float(scale))
 
-    def episodes(self, packed_weights, n_episodes, deterministic=False):
+    def episodes(self, weights, n_episodes, deterministic=False):
         """(returns float64 [n_episodes], lengths int32 [n_episodes]) on the device: ceil(n_episodes / n_envs) launches, every one
         the next episode of every env; the surplus of the last launch is dropped"""
         n_episodes = int(n_episodes)
@@ -55,17 +57,40 @@ class PolicyEvaluator:
         torch = self.env.torch
         rets, lens = [], []
         for _ in range(-(-n_episodes // self.n_envs)):
-            r, ln = self.env.policy_evaluate(packed_weights, seed=self.noise_seed, deterministic=deterministic, net=self.net)
+            r, ln = self._launch(weights, deterministic)
             rets.append(r); lens.append(ln)
         return torch.cat(rets)[:n_episodes], torch.cat(lens)[:n_episodes]
 
-    def evaluate(self, packed_weights, n_episodes, deterministic=False):
+    def evaluate(self, weights, n_episodes, deterministic=False):
         """{episodes, mean, std, min, max, mean_length} over n_episodes whole episodes; float64 on the device, one host read"""
-        r, ln = self.episodes(packed_weights, n_episodes, deterministic)
+        r, ln = self.episodes(weights, n_episodes, deterministic)
         return summarise(self.env.torch, r, ln)
 
     def close(self):
         self.env.close()
+
+
+class PolicyEvaluator(_EpisodeEvaluator):
+    """n_envs evaluation envs of their own for the fused policy networks (PPO / TRPO; NET_DEFAULT or Tennisbot's NET_TUNED); weights:
+    the packed blob of ppo.pack_policy"""
+
+    def __init__(self, kind, n_envs=64, seed=0, params=None, options=None, device=None, net=NET_DEFAULT, env_id_base=EVAL_ENV_ID_BASE):
+        super().__init__(kind, n_envs, seed, params, options, device, env_id_base)
+        self.net = int(net)
+
+    def _launch(self, packed_weights, deterministic):
+        return self.env.policy_evaluate(packed_weights, seed=self.noise_seed, deterministic=deterministic, net=self.net)
+
+
+class ActorEvaluator(_EpisodeEvaluator):
+    """the same for the SAC / TQC actor (the two share it); weights: the flat TB_SAC_ACTOR vector -- what the learner's kernels
+    train, so there is nothing to pack"""
+
+    def __init__(self, kind, n_envs=64, seed=0, params=None, options=None, device=None, env_id_base=EVAL_ENV_ID_BASE):
+        super().__init__(kind, n_envs, seed, params, options, device, env_id_base)
+
+    def _launch(self, actor_flat, deterministic):
+        return self.env.sac_evaluate(actor_flat, seed=self.noise_seed, deterministic=deterministic)
 
 
 def evaluate_actor_episodes(env, act, n_episodes, check_every=8):

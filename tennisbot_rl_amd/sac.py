@@ -40,6 +40,7 @@ BATCH_SIZE = {"SwingRacket-v0": 1100, "Tennisbot-v0": 256}   # train_swing.py:93
 # three layers in 3, y), critic gradient 10 (gather, forward 3, loss, backward 2, weight gradients 3), its Adam + Polyak 1, actor
 # gradient 13 (critics forward 3, loss, their backward 3, the head's backward, the actor's backward 2 and weight gradients 3), Adam 2
 LAUNCHES_PER_STEP = 40
+EVAL_FORMS = ("torch", "fused")   # SACTrainer.evaluate_episodes: the torch actor between env steps / one tb_sac_evaluate launch
 ACTOR_NAMES = ("latent_pi.0.weight", "latent_pi.0.bias", "latent_pi.2.weight", "latent_pi.2.bias", "mu.weight", "mu.bias", "log_std.weight", "log_std.bias")
 CRITIC_NAMES = tuple("qf%d.%d.%s" % (q, layer, w) for q in (0, 1) for layer in (0, 2, 4) for w in ("weight", "bias"))
 
@@ -361,9 +362,12 @@ class SACTrainer:
     ALGO, NETS = "SAC", "SB3's MlpPolicy [256, 256]"          # the words of the two messages
 
     def __init__(self, env_id="SwingRacket-v0", num_envs=256, batch_size=None, gradient_steps=None, buffer_size=1_000_000, learning_starts=100, seed=0, params=None,
-                 device=None, **hp):
+                 device=None, eval_form="torch", **hp):
         import torch
         self.torch = torch
+        if eval_form not in EVAL_FORMS:
+            raise ValueError("%s: eval_form must be one of %s, not %r" % (type(self).__name__, EVAL_FORMS, eval_form))
+        self.eval_form = eval_form
         dist = torch.distributed
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise ValueError("%s runs on one rank (world size %d): multi-rank %s is not provided" % (type(self).__name__, dist.get_world_size(), self.ALGO))
@@ -482,13 +486,27 @@ class SACTrainer:
         self._ep_return.zero_()
         return float(total) / max(float(eps), 1.0)
 
-    def evaluate_episodes(self, n_episodes=64, deterministic=False, n_envs=64):
-        """Mean return over n_episodes WHOLE episodes of the current actor: {episodes, mean, std, min, max, mean_length}
-        (evaluation.evaluate_actor_episodes). A separate, unpipelined env batch with the trainer's engine parameters is stepped by
-        the torch actor until every env has finished its first episode (the 256-wide actor does not fit the fused policy kernels);
-        the noise comes from a torch.Generator of its own. The training envs, self.obs and torch's global RNG are not touched."""
-        from .evaluation import EVAL_ENV_ID_BASE, evaluate_actor_episodes
+    def evaluate_episodes(self, n_episodes=64, deterministic=False, n_envs=64, form=None):
+        """Mean return over n_episodes WHOLE episodes of the current actor: {episodes, mean, std, min, max, mean_length}.
+        form (default: the constructor's eval_form) "torch": evaluation.evaluate_actor_episodes. A separate, unpipelined env batch
+        with the trainer's engine parameters is stepped by the torch actor until every env has finished its first episode;
+        the noise comes from a torch.Generator of its own. "fused": evaluation.ActorEvaluator, every episode of a batch in ONE
+        launch with the learner's flat actor vector inside (tb_sac_evaluate), the noise keyed in the kernel. Either way the
+        training envs, self.obs and torch's global RNG are not touched."""
+        from .evaluation import EVAL_ENV_ID_BASE, ActorEvaluator, evaluate_actor_episodes
         t = self.torch
+        form = self.eval_form if form is None else form
+        if form not in EVAL_FORMS:
+            raise ValueError("evaluate_episodes: form must be one of %s, not %r" % (EVAL_FORMS, form))
+        if form == "fused":
+            fe = getattr(self, "_eval_fused", None)
+            if fe is None or fe.n_envs != int(n_envs):
+                if fe is not None:
+                    fe.close()
+                fe = self._eval_fused = ActorEvaluator(self.kind, int(n_envs), seed=self.env.seed + 1000003, params=self.env.params, device=self.device)
+            if fe.env.params.racket_scale != self.env.params.racket_scale:
+                fe.set_racket_scale(self.env.params.racket_scale)
+            return fe.evaluate(self._learner.pi.flat, n_episodes, deterministic=deterministic)   # (the vector the kernels train: nothing to repack)
         ev = getattr(self, "_eval_env", None)
         if ev is None or ev.num_envs != int(n_envs):
             ev = self._eval_env = BatchedEnv(self.kind, int(n_envs), device=self.device, seed=self.env.seed + 1000003, env_id_base=EVAL_ENV_ID_BASE,

@@ -99,6 +99,8 @@ def load_library():
     L.tb_es_evaluate.restype = i32
     L.tb_policy_evaluate.argtypes = [vp, i32, vp, vp, vp, u64, i32, vp]
     L.tb_policy_evaluate.restype = i32
+    L.tb_sac_evaluate.argtypes = [vp, vp, vp, vp, u64, i32, ctypes.POINTER(TbSacEvalTrace), vp]
+    L.tb_sac_evaluate.restype = i32
     f32, f64, i64 = ctypes.c_float, ctypes.c_double, ctypes.c_longlong
     L.tb_ppo_param_floats.argtypes = [i32]
     L.tb_ppo_param_floats.restype = i32
@@ -205,6 +207,12 @@ class TbEsTrace(ctypes.Structure):
     """include/tb_stepper.h TbEsTrace: optional per-step record of tb_es_evaluate"""
     _fields_ = [("struct_size", ctypes.c_size_t), ("max_steps", ctypes.c_int), ("net_in", ctypes.c_void_p), ("obs", ctypes.c_void_p),
                 ("actions", ctypes.c_void_p), ("raw", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p)]
+
+
+class TbSacEvalTrace(ctypes.Structure):
+    """include/tb_stepper.h TbSacEvalTrace: optional per-step record of tb_sac_evaluate"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("max_steps", ctypes.c_int), ("obs", ctypes.c_void_p), ("eps", ctypes.c_void_p),
+                ("actions", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p)]
 
 
 def _check(L, rc, what):
@@ -560,6 +568,34 @@ class BatchedEnv:
         _check(self.L, self.L.tb_policy_evaluate(self._h, int(net), w.data_ptr(), ret.data_ptr(), length.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                  1 if deterministic else 0, self._stream()), "tb_policy_evaluate")
         return ret, length
+
+    def sac_actor_floats(self):
+        """Floats of the flat SAC / TQC actor vector for this env kind (70668 SwingRacket-v0, 70148 Tennisbot-v0)"""
+        return int(self.L.tb_sac_param_floats(self.kind, 0))
+
+    def sac_evaluate(self, actor_flat, seed=0, deterministic=False, trace=False, max_steps=None):
+        """One whole episode per env with the SAC / TQC actor inside, in one launch (tb_sac_evaluate). actor_flat: the flat
+        TB_SAC_ACTOR vector (named_parameters() order, as the learner trains it), float32 on this device. Per step
+        a = tanh(mu + exp(clamp(log_std, -20, 2)) eps) with policy_step's noise keys (seed, env id, episode, step);
+        deterministic=True acts on tanh(mu). Every call resets every env first (the episode after the one it was in) and leaves
+        every env at that episode's freshly reset state. SwingRacket-v0 needs pipeline=True. Returns (returns float64 [N],
+        lengths int32 [N]), complete in stream order; with trace=True also a dict of the per-step record (obs [T, N, O], eps /
+        actions [T, N, A], reward [T, N], done [T, N]; rows after an env's last step stay zero), T = max_steps or the longest
+        episode (26 / 1001). The trace never changes a result."""
+        t, n = self.torch, self.num_envs
+        w = self._check_tensor(actor_flat, (self.sac_actor_floats(),), t.float32, "actor_flat")
+        ret = t.empty(n, dtype=t.float64, device=self.device)
+        length = t.empty(n, dtype=t.int32, device=self.device)
+        tr, rec = None, None
+        if trace:
+            T = int(max_steps) if max_steps is not None else (26 if self.kind == ENV_SWING else 1001)
+            f = dict(dtype=t.float32, device=self.device)
+            rec = dict(obs=t.zeros((T, n, self.obs_dim), **f), eps=t.zeros((T, n, self.act_dim), **f), actions=t.zeros((T, n, self.act_dim), **f),
+                       reward=t.zeros((T, n), **f), done=t.zeros((T, n), dtype=t.uint8, device=self.device))
+            tr = TbSacEvalTrace(ctypes.sizeof(TbSacEvalTrace), T, *(rec[k].data_ptr() for k in ("obs", "eps", "actions", "reward", "done")))
+        _check(self.L, self.L.tb_sac_evaluate(self._h, w.data_ptr(), ret.data_ptr(), length.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              1 if deterministic else 0, None if tr is None else ctypes.byref(tr), self._stream()), "tb_sac_evaluate")
+        return (ret, length, rec) if trace else (ret, length)
 
     def capture(self, fn):
         """Capture `fn()` -- a fixed sequence of step()/step_ptrs()/RolloutBuffer.step_into calls on

@@ -23,10 +23,8 @@ from tennisbot_rl_amd.evaluation import add_schedule_arguments, resolve_load, sc
 from train_swing import racket_scale_for  # noqa: E402  (train.py:164-176, one table for every script)
 
 
-def off_policy_main(argv, script, algo, trainer, description, batch_help, total_default, total_help, total_by_env):
-    """the body of train_sac.py and train_tqc.py. trainer() returns the trainer class (called after the arguments are parsed, so
-    that --help needs no torch); algo names it in messages and in the default --save path; total_by_env: the timesteps per env id
-    where --total-timesteps is not given (its own default is total_default)."""
+def off_policy_parser(description, algo, batch_help, total_default, total_help):
+    """the arguments of train_sac.py and train_tqc.py"""
     ap = argparse.ArgumentParser(description=description)
     ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
     ap.add_argument("--num-envs", type=int, default=256)
@@ -43,7 +41,22 @@ def off_policy_main(argv, script, algo, trainer, description, batch_help, total_
     ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (TB_F_RACKET_GROUND)")
     ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact")
     add_schedule_arguments(ap)
-    args = ap.parse_args(argv)
+    ap.add_argument("--eval-form", choices=["torch", "fused"], default="torch", help="how --eval-freq's whole episodes run: `torch` steps a separate batch with "
+                    "the torch actor; `fused` runs every episode of a batch in one launch with the actor inside (tb_sac_evaluate)")
+    return ap
+
+
+def trainer_arguments(args):
+    """the trainer's keyword arguments that come straight from the parsed command line"""
+    return dict(num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
+                learning_starts=args.learning_starts, seed=args.seed, eval_form=args.eval_form)
+
+
+def off_policy_main(argv, script, algo, trainer, description, batch_help, total_default, total_help, total_by_env):
+    """the body of train_sac.py and train_tqc.py. trainer() returns the trainer class (called after the arguments are parsed, so
+    that --help needs no torch); algo names it in messages and in the default --save path; total_by_env: the timesteps per env id
+    where --total-timesteps is not given (its own default is total_default)."""
+    args = off_policy_parser(description, algo, batch_help, total_default, total_help).parse_args(argv)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("%s runs on one rank: multi-rank %s is not provided" % (script, algo))
 
@@ -54,8 +67,7 @@ def off_policy_main(argv, script, algo, trainer, description, batch_help, total_
     if args.racket_ground or args.rolling_friction:
         from tennisbot_rl_amd.params import F_DEFAULT, F_RACKET_GROUND, default_params, reference_rolling_friction
         params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
-    tr = trainer()(args.env, num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
-                   learning_starts=args.learning_starts, seed=args.seed, params=params, device=torch.device("cuda", 0))
+    tr = trainer()(args.env, params=params, device=torch.device("cuda", 0), **trainer_arguments(args))
     path = args.save or "./model/%s_%s.pt" % (algo.lower(), args.env)
     if args.load:
         tr.load(resolve_load(args.load, path))
@@ -79,16 +91,17 @@ def off_policy_main(argv, script, algo, trainer, description, batch_help, total_
         json.dump(history, open(args.log_json, "w"))
 
 
-
 def _trainer():
     from tennisbot_rl_amd.sac import SACTrainer
     return SACTrainer
 
 
+PARSER = ("SAC on SwingRacket-v0 or Tennisbot-v0 (the reference's -s sac)", "SAC", "default: 1100 on SwingRacket-v0, 256 on Tennisbot-v0, as the reference scripts", None,
+          "default: 2e6 SwingRacket-v0 / 1e6 Tennisbot-v0, as the reference")   # off_policy_parser's arguments
+
+
 def main(argv=None):
-    off_policy_main(argv, "train_sac.py", "SAC", _trainer, "SAC on SwingRacket-v0 or Tennisbot-v0 (the reference's -s sac)",
-                    "default: 1100 on SwingRacket-v0, 256 on Tennisbot-v0, as the reference scripts", None, "default: 2e6 SwingRacket-v0 / 1e6 Tennisbot-v0, as the reference",
-                    {"SwingRacket-v0": 2e6, "Tennisbot-v0": 1e6})
+    off_policy_main(argv, "train_sac.py", "SAC", _trainer, PARSER[0], PARSER[2], PARSER[3], PARSER[4], {"SwingRacket-v0": 2e6, "Tennisbot-v0": 1e6})
 
 
 if __name__ == "__main__":

@@ -25,9 +25,12 @@ def _trainer():
     return TQCTrainer
 
 
+PARSER = ("TQC on SwingRacket-v0 or Tennisbot-v0 (the reference's train_swing.py -s tqc)", "TQC", "default: 256, sb3_contrib's, as the reference script leaves it", 2e6,
+          "default: 2e6, as the reference")   # off_policy_parser's arguments
+
+
 def main(argv=None):
-    off_policy_main(argv, "train_tqc.py", "TQC", _trainer, "TQC on SwingRacket-v0 or Tennisbot-v0 (the reference's train_swing.py -s tqc)",
-                    "default: 256, sb3_contrib's, as the reference script leaves it", 2e6, "default: 2e6, as the reference", {})
+    off_policy_main(argv, "train_tqc.py", "TQC", _trainer, PARSER[0], PARSER[2], PARSER[3], PARSER[4], {})
 
 
 if __name__ == "__main__":

@@ -8,6 +8,7 @@ import pytest
 
 import ppo_reference as ref
 import trpo_reference as tr
+from learner_edge_fixtures import search_fixture
 from policy_reference import state_dict_arrays
 from test_ppo_reference import flat_shard, make_policy, rollout
 
@@ -162,30 +163,6 @@ def test_gradient_and_conjugate_gradient_against_the_reference(torch, kname):
 
 
 # ----------------------------------------------------------------------------------------------------------------- line search
-def search_fixture(ro, P, rows, which):
-    """(old_logp, direction over theta, steps float32) on the rows given. 'kl': along the surrogate's gradient with a first step
-    that leaves the trust region (KL_0 about 3 delta: KL_k = KL_0 1.5^-2k re-enters at k = 2); 'none': against the gradient from a
-    behaviour policy that IS theta (L_0 = 0 at a zero step, so every L_k < 0): nothing is accepted; 'random': a random direction"""
-    obs, act, old_logp, adv, _ = (x[rows] for x in flat_shard(ro, ro.gae.adv, ro.gae.returns))
-    theta = tr.theta_of(P)
-    if which == "none":
-        _, mu = tr.mean_of(P, obs)
-        zeta = (act - mu) * np.exp(-P["log_std"])
-        old_logp = (-0.5 * zeta * zeta - P["log_std"] - tr.LN_SQRT_2PI).sum(-1).astype(np.float32)
-    if which == "random":
-        rng = np.random.default_rng(len(rows))
-        x = {k: rng.normal(size=np.shape(v)) for k, v in theta.items()}
-    else:
-        g = tr.surrogate_gradient(P, obs, act, old_logp, adv)
-        x = {k: (-v if which == "none" else v) for k, v in g.items()}
-    x = {k: v.astype(np.float32).astype(np.float64) for k, v in x.items()}
-    probe = 1e-3 / max(np.abs(v).max() for v in x.values())
-    c = tr.kl(P, tr.moved(P, x, probe), obs) / probe ** 2                      # KL(s) ~ c s^2
-    beta = np.sqrt({"kl": 3.0, "none": 0.5, "random": 1.2}[which] * tr.KL_DELTA / c)
-    steps = (beta * tr.DECAY ** -np.arange(tr.CANDIDATES)).astype(np.float32)
-    return (obs, act, old_logp, adv), x, steps
-
-
 @pytest.mark.parametrize("kname", list(CASE))
 def test_search_against_the_reference(torch, kname):
     ro = rollout(CASE[kname])

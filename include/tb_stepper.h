@@ -441,6 +441,46 @@ int tb_sac_evaluate(TbHandle *h, const float *actor_dev, double *return_dev, int
                     int deterministic, const TbSacEvalTrace *trace_or_null, void *stream);
 
 /*
+ * SAC / TQC collect: n_steps agent steps of every env with the 256-wide actor inside, one launch, every transition written as a
+ * replay ring stores it (csrc/tb_sac.hpp, tb_sac_collect_kernel: tb_sac_evaluate_kernel's four-wave workgroup and actor stage
+ * around tb_policy_rollout's env wave).
+ *   Steps and state: every env is stepped n_steps agent steps from the state the handle holds -- no reset. An env that
+ *     finishes restarts inside the launch exactly as the step kernels do on done (TB_F_AUTO_RESET is required, TB_E_UNSUPPORTED
+ *     otherwise), and the state is written back: on return the handle is where n_steps calls of tb_step with the same actions
+ *     would have left it, episode phase included.
+ *   mode TB_SAC_COLLECT_ACTOR: a = tanh(mu + exp(clamp(log_std, -20, 2)) eps) with mu / log_std computed element for element
+ *     as tb_sac_actor_forward computes them from actor_dev (the flat TB_SAC_ACTOR vector); eps is tb_policy_step's noise, keyed
+ *     by (noise_seed, global env id, episode, step). A NaN action stays NaN.
+ *   mode TB_SAC_COLLECT_UNIFORM: no actor stage runs and actor_dev may be null. Action k is (float)(w >> 8) * 0x1p-23f - 1.0f,
+ *     w being word k % 4 of the Philox block k / 4 that the noise of that (noise_seed, env, episode, step) would have been
+ *     made from: exact in float32, range [-1, 1 - 2^-23]. The mode is a kernel argument, the same for the whole grid.
+ *   out: rows are plain [S][N] arrays, S = n_steps, no stride and no wrap -- the caller hands in pointers into its ring. All
+ *     five arrays are required; eps_or_null is optional and changes no result. obs / next_obs rows must be 16-byte aligned
+ *     (SwingRacket-v0: 8), action / eps rows 8-byte aligned.
+ *   SwingRacket-v0 needs tb_set_pipeline(h, 1) and episodes in lockstep (TB_E_UNSUPPORTED otherwise, as tb_policy_rollout), and
+ *     the launch must stay inside the episode: phase + n_steps <= 26 (TB_E_INVAL otherwise; tb_policy_rollout cuts its launches
+ *     there itself, this call leaves the cut to the caller, whose ring rows it writes). A launch that ends the episodes parks
+ *     them for the fast-forward, which writes the terminal reward into out->reward's last row itself; the call then flushes on
+ *     `stream`: every output, that reward included, is complete in stream order on `stream` when the call returns.
+ *   Tennisbot-v0: any n_steps >= 1.
+ * Null h / out, a null required array, a struct_size that is not sizeof(TbSacCollectOut), n_steps < 1, an unknown mode, a
+ * null actor_dev in actor mode, a misaligned array: TB_E_INVAL. Nothing is launched on a refusal.
+ * Counters: as tb_policy_rollout counts them (each step's first substep by the host, the rest and the episodes by the kernel).
+ */
+enum { TB_SAC_COLLECT_ACTOR = 0, TB_SAC_COLLECT_UNIFORM = 1 };
+typedef struct TbSacCollectOut {
+  size_t struct_size;   /* sizeof(TbSacCollectOut) */
+  float *obs;           /* [S][N][O] the observation step t acted on */
+  float *next_obs;      /* [S][N][O] what tb_step would have returned (a done row: the next episode's first observation) */
+  float *action;        /* [S][N][A] the action the env was stepped with */
+  float *reward;        /* [S][N] */
+  float *done;          /* [S][N]   0.0f / 1.0f: the replay ring's type */
+  float *eps_or_null;   /* [S][N][A] the noise drawn (0 in uniform mode); optional, changes no result */
+} TbSacCollectOut;
+int tb_sac_collect(TbHandle *h, const float *actor_dev, int n_steps, int mode, uint64_t noise_seed,
+                   const TbSacCollectOut *out, void *stream);
+
+/*
  * The PPO learner (csrc/tb_learner.hpp; tennisbot_rl_amd/learner.py is the caller): GAE, one minibatch's gradient, and the
  * optimiser step, fp32, for the two policy architectures the fused policy kernels are instantiated for. These functions need
  * no env: they take (env_kind, device, stream) instead of a TbHandle, every buffer is caller-owned device memory, and every

@@ -240,6 +240,20 @@ TB_DEV void policy_noise(unsigned long long seed, unsigned long long env_id, uin
     }
   }
 }
+// uniform actions in [-1, 1 - 2^-23] from the very Philox words policy_noise would have turned into normals for that key: action k is
+// the top 24 bits of word k % 4 of block k / 4, scaled by 2^-23 and shifted -- every step exact in float32 (tb_sac_collect's uniform mode)
+template <int NA>
+TB_DEV void policy_uniform(unsigned long long seed, unsigned long long env_id, uint32_t episode, int step_count, float* a) {
+  uint32_t u[4];
+#pragma unroll
+  for (int blk = 0; blk < (NA + 3) / 4; ++blk) {
+    philox4x32((uint32_t)env_id, (uint32_t)(env_id >> 32), episode, (uint32_t)step_count * 4u + (uint32_t)blk, (uint32_t)seed,
+               (uint32_t)(seed >> 32) ^ 0x504F4C49u, u);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (4 * blk + r < NA) a[4 * blk + r] = (float)(u[r] >> 8) * 1.1920928955078125e-07f - 1.0f;
+  }
+}
 // the tower part of the one-step kernel (tb_policy_step: 256-thread workgroups, 64 envs): wave w runs BOTH towers of the
 // 16-env slice w -- two independent chains the scheduler interleaves -- leaves the action means in s_mean[64][8] and
 // writes the values

@@ -455,6 +455,30 @@ TB_DEV void sac_ev_hidden(const float* W, const float* bias, const float* x, int
   }
 }
 
+// The actor's stages (1)-(3) of one step, for the 16 observation rows in s_obs: ONE copy for tb_sac_evaluate_kernel and
+// tb_sac_collect_kernel. Every wave of the workgroup calls it; barriers 1 and 2 are inside, and the caller places barrier 3 ("the head
+// is in LDS") behind it -- the env wave draws its noise in between, while waves 0 and 1 run the head.
+template <int KIND>
+TB_DEV void sac_actor_stage(const float* actor, const float* s_obs, float* s_h1, float* s_h2, float* s_head, int wave, int g, int er) {
+  using L = SacLayout<KIND>;
+  constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O;
+  sac_ev_hidden<NO>(actor + L::PI_W0, actor + L::PI_B0, s_obs, NO, s_h1, wave, g, er);
+  __syncthreads();  // barrier 1: h1 is in LDS
+  sac_ev_hidden<SAC_H>(actor + L::PI_W1, actor + L::PI_B1, s_h1, SAC_EV_STRIDE, s_h2, wave, g, er);
+  __syncthreads();  // barrier 2: h2 is in LDS
+  if (wave < 2) {  // mu (wave 0) and log_std (wave 1): one tile each, rows er < A of the head's block
+    const float* hw = actor + L::PI_HEAD + wave * L::PI_HEAD_BLOCK;
+    const bool o_in = er < NA;
+    f32x4 acc[1];
+    sac_ev_chain<1, SAC_H>(hw + (size_t)(o_in ? er : 0) * SAC_H, 0, o_in, s_h2 + er * SAC_EV_STRIDE, g, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int oo = 4 * g + r;
+      if (oo < NA) s_head[er * 16 + wave * 8 + oo] = acc[0][r] + hw[NA * SAC_H + oo];
+    }
+  }
+}
+
 template <int KIND, bool RG>
 __global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalArgs S) {
   using L = SacLayout<KIND>;
@@ -500,26 +524,11 @@ __global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalAr
   constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);  // tb_policy_evaluate_kernel's
   TB_DIAG_STAMPS_BEGIN(st);
   for (int t = 0;; ++t) {
-    sac_ev_hidden<NO>(S.actor + L::PI_W0, S.actor + L::PI_B0, s_obs, NO, s_h1, wave, g, er);
-    __syncthreads();  // barrier 1: h1 is in LDS
-    sac_ev_hidden<SAC_H>(S.actor + L::PI_W1, S.actor + L::PI_B1, s_h1, SAC_EV_STRIDE, s_h2, wave, g, er);
-    __syncthreads();  // barrier 2: h2 is in LDS
+    sac_actor_stage<KIND>(S.actor, s_obs, s_h1, s_h2, s_head, wave, g, er);
     float eps[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) eps[k] = 0.0f;
-    if (wave < 2) {  // mu (wave 0) and log_std (wave 1): one tile each, rows er < A of the head's block
-      const float* hw = S.actor + L::PI_HEAD + wave * L::PI_HEAD_BLOCK;
-      const bool o_in = er < NA;
-      f32x4 acc[1];
-      sac_ev_chain<1, SAC_H>(hw + (size_t)(o_in ? er : 0) * SAC_H, 0, o_in, s_h2 + er * SAC_EV_STRIDE, g, acc);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int oo = 4 * g + r;
-        if (oo < NA) s_head[er * 16 + wave * 8 + oo] = acc[0][r] + hw[NA * SAC_H + oo];
-      }
-    } else if (env_wave) {
-      if (active) policy_draw<KIND>(A, i, e, eps);  // while the head runs
-    }
+    if (env_wave && active) policy_draw<KIND>(A, i, e, eps);  // while the head runs
     __syncthreads();  // barrier 3: the head is in LDS
     if (env_wave) {
       float a[NA], o[NO];
@@ -572,6 +581,131 @@ __global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalAr
     if (!(t + 1 < T_MAX && __builtin_amdgcn_readfirstlane(s_go) != 0)) break;
   }
   if (live) { S.ret[i] = ret; S.len[i] = len; }
+  if (env_wave) flush_counters(A.counters, cnt);
+  TB_DIAG_STAMPS_END(st);
+}
+
+// ------------------------------------------------------------------------------- transitions into the replay ring (tb_sac_collect)
+// n_steps agent steps of every env from the state the handle holds, ONE launch, every transition written as the replay ring stores
+// it: tb_sac_evaluate_kernel's workgroup (16 envs, four waves, sac_actor_stage) around tb_policy_rollout_kernel<KIND, 1>'s env wave
+// (state and contact cache in, in-loop restart_episode on done, SwingRacket parking at a launch's last step, state and cache out).
+// Rows [t][n]: obs = what step t acted on, action, reward, done (0.0f / 1.0f), next_obs = what tb_step would have returned (a done
+// row: the next episode's first observation), eps (optional). The trip count is the argument n_steps for every wave: no s_go, no
+// early exit. UNIFORM (a kernel argument, the same in every wave of the grid): no actor stage runs -- barriers 1 and 2 are skipped by
+// every wave alike -- and the action is policy_uniform's of the key policy_draw would have used.
+// BARRIERS. One behind the set-up, then FOUR per iteration in actor mode and TWO in uniform mode, on every path; no wave returns
+// inside the loop:
+//   set-up  env wave: s_obs = the observations of the loaded state (idle rows too); all: the outline table -> barrier 0
+//   (1)     all: s_h1 = relu(W0 s_obs + b0)            [actor mode]                                       -> barrier 1  "h1 is in LDS"
+//   (2)     all: s_h2 = relu(W1 s_h1 + b1)             [actor mode]                                       -> barrier 2  "h2 is in LDS"
+//   (3)     wave 0: s_head mu, wave 1: s_head log_std  [actor mode]; env wave: draws noise / the action   -> barrier 3  "the head is in LDS"
+//   (4)     env wave: sample (s_head), the obs row (s_obs), env step, restart on done, s_obs = next obs   -> barrier 4  "obs is in LDS"
+//           env wave: the step's other rows go to memory behind barrier 4, while the actor already runs step t + 1
+// Who may overwrite what: s_h1 is next written in (1) of t + 1, behind barrier 4, its readers ((2) of t) are in front of barrier 2;
+// s_h2 is next written behind barrier 1 of t + 1, its readers ((3) of t) are in front of barrier 3; s_head is next written behind
+// barrier 2 of t + 1, its reader ((4) of t) is in front of barrier 4; s_obs is written behind barrier 3 only (by the env wave, after
+// its own read of the row) and read by the others in front of barrier 1. Uniform mode touches s_obs only, in the env wave.
+struct SacCollectArgs {
+  const float* actor;  // the flat TB_SAC_ACTOR vector (null in uniform mode)
+  int n_steps, uniform;
+  float *obs, *next_obs, *action, *reward, *done, *eps;  // TbSacCollectOut's rows [n_steps][n]; eps may be null
+};
+
+template <int KIND, bool RG>
+__global__ void __launch_bounds__(256) tb_sac_collect_kernel(KArgs A, SacCollectArgs S) {
+  using L = SacLayout<KIND>;
+  constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE, ENV_WAVE = 3;
+  static_assert(NA == L::A && NO == L::O && E == 16 && NA <= 8, "the actor's rows are the envs of one slice");
+  __shared__ float4 s_hull[TB_HULL_LDS];
+  __shared__ __attribute__((aligned(16))) float s_obs[E * NO];
+  __shared__ __attribute__((aligned(16))) float s_h1[E * SAC_EV_STRIDE];
+  __shared__ __attribute__((aligned(16))) float s_h2[E * SAC_EV_STRIDE];
+  __shared__ __attribute__((aligned(16))) float s_head[E * 16];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, g = lane >> 4, er = lane & 15;
+  const bool env_wave = wave == ENV_WAVE;
+  const bool uniform = S.uniform != 0;  // (a kernel argument: the same verdict in every wave of the grid)
+  stage_hull(s_hull, A.hull, A.P.n_hull);
+  const int i = blockIdx.x * E + lane;
+  const bool live = env_wave && lane < E && i < A.n;
+  EnvRegs e;
+  idle_env(e);
+  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);
+  Manifold M;
+  init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
+  const bool had_contacts = load_contacts<RG>(A, i, live, M);
+  uint32_t cnt[TB_N_COUNTERS] = {};
+  bool any_reset = false;
+  if (env_wave && lane < E) {  // (rows without an env hold the dummy's observation: finite, and no row reads another)
+    float o[NO];
+    make_obs<KIND>(e, o);  // what the step that left this state returned (tennis_step / end_agent_step / restart_episode: make_obs all)
+#pragma unroll
+    for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+  }
+  __syncthreads();  // barrier 0: the outline table and the observations the first step acts on are in LDS
+  KParams Pl = A.P;  // (the substep's constants in vector registers: see tb_policy_rollout_kernel)
+#if TB_HINT_POLICY_VGPR_PARAMS
+#define TB_PIN(f) asm volatile("" : "+v"(Pl.f))
+  TB_PIN(dt); TB_PIN(gravity); TB_PIN(lin_damp); TB_PIN(ang_damp); TB_PIN(lin_damp_quad); TB_PIN(ang_damp_quad); TB_PIN(max_ang_step); TB_PIN(contact_threshold);
+  TB_PIN(racket_inv_mass); TB_PIN(racket_inertia[0]); TB_PIN(racket_inertia[1]); TB_PIN(racket_inertia[2]);
+  TB_PIN(racket_inv_inertia[0]); TB_PIN(racket_inv_inertia[1]); TB_PIN(racket_inv_inertia[2]);
+  TB_PIN(racket_half_thick); TB_PIN(hull_margin); TB_PIN(hull_bound_radius); TB_PIN(ball_inv_mass); TB_PIN(ball_radius); TB_PIN(magnus_k); TB_PIN(static_top);
+#undef TB_PIN
+#endif
+  constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);  // tb_policy_rollout_kernel<KIND, 1>'s
+  TB_DIAG_STAMPS_BEGIN(st);
+  for (int t = 0; t < S.n_steps; ++t) {
+    if (!uniform) sac_actor_stage<KIND>(S.actor, s_obs, s_h1, s_h2, s_head, wave, g, er);
+    float eps[NA], a[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) { eps[k] = 0.0f; a[k] = 0.0f; }
+    if (live) {  // while the head runs
+      if (uniform) policy_uniform<NA>(A.pol_seed, A.env_id_base + (unsigned long long)i, e.episode, e.step_count, a);
+      else policy_draw<KIND>(A, i, e, eps);
+    }
+    __syncthreads();  // barrier 3: the head is in LDS
+    float o[NO], rew = 0.0f;
+    bool d = false;
+    const size_t row = (size_t)t * A.n + i;
+    if (env_wave) {
+      if (live) {
+        if (!uniform) {
+#pragma unroll
+          for (int k = 0; k < NA; ++k) {
+            float ls;
+            a[k] = sac_squash_sample(s_head[lane * 16 + k], s_head[lane * 16 + 8 + k], eps[k], ls);
+          }
+        }
+        float oi[NO];
+#pragma unroll
+        for (int k = 0; k < NO; ++k) oi[k] = s_obs[lane * NO + k];
+        write_obs<KIND>(S.obs, row, oi);
+      }
+      int ns = 1;
+      bool parked = false;
+      // (every lane of the wave, dummies included: the substep's outline sweep is shared among all 64, SF_WIDE)
+      if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
+      else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
+      if (live) {
+        end_agent_step<KIND, RG, true>(A, i, e, M, parked, ns, row, o, d, cnt);  // (a parked step's reward: the fast-forward's, into S.reward[row])
+        if (d) {  // (the host requires TB_F_AUTO_RESET)
+          cnt[5]++;
+          restart_episode<KIND>(A, s_hull + TB_HULL_KP, i, e, M, o);
+          any_reset = true;
+        }
+#pragma unroll
+        for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+      }
+    }
+    __syncthreads();  // barrier 4: the observations step t + 1 acts on are in LDS
+    if (live) {
+      store_row2<NA>(S.action, row, a);
+      if (S.eps) store_row2<NA>(S.eps, row, eps);
+      write_obs<KIND>(S.next_obs, row, o);
+      S.reward[row] = rew;
+      S.done[row] = d ? 1.0f : 0.0f;
+    }
+  }
+  if (live) save_env<KIND, RG>(A, i, e, M, any_reset, had_contacts);
   if (env_wave) flush_counters(A.counters, cnt);
   TB_DIAG_STAMPS_END(st);
 }

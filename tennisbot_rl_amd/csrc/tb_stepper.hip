@@ -1258,6 +1258,53 @@ int tb_sac_evaluate(TbHandle* h, const float* actor_dev, double* return_dev, int
   return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
 }
 
+// tb_policy_rollout's host path around tb_sac_collect_kernel (tb_sac.hpp): one launch, the caller's ring rows as outputs
+int tb_sac_collect(TbHandle* h, const float* actor_dev, int n_steps, int mode, uint64_t noise_seed, const TbSacCollectOut* out, void* stream) {
+  if (!h || !out) return fail(TB_E_INVAL, "tb_sac_collect: null argument");
+  if (out->struct_size != sizeof(TbSacCollectOut)) return fail(TB_E_INVAL, "tb_sac_collect: TbSacCollectOut.struct_size is not sizeof(TbSacCollectOut)");
+  if (!out->obs || !out->next_obs || !out->action || !out->reward || !out->done) return fail(TB_E_INVAL, "tb_sac_collect: a TbSacCollectOut array is null");
+  if (mode != TB_SAC_COLLECT_ACTOR && mode != TB_SAC_COLLECT_UNIFORM) return fail(TB_E_INVAL, "tb_sac_collect: unknown mode");
+  if (mode == TB_SAC_COLLECT_ACTOR && !actor_dev) return fail(TB_E_INVAL, "tb_sac_collect: actor_dev is null in actor mode");
+  if (n_steps < 1) return fail(TB_E_INVAL, "tb_sac_collect: n_steps must be >= 1");
+  if (!(h->kp.flags & TB_F_AUTO_RESET)) return fail(TB_E_UNSUPPORTED, "tb_sac_collect needs TB_F_AUTO_RESET (episodes must restart inside the launch)");
+  const bool swing = h->kind == TB_ENV_SWING;
+  if (swing && !(h->pipeline && h->phase.valid))
+    return fail(TB_E_UNSUPPORTED, "tb_sac_collect on SwingRacket-v0 needs tb_set_pipeline(h, 1) and episodes in lockstep (every env reset together): "
+                                  "the fast-forward that ends an episode cannot run inside a multi-step launch");
+  if (swing && h->phase.at + n_steps > kEpisodeSteps)
+    return fail(TB_E_INVAL, "tb_sac_collect on SwingRacket-v0: the launch must end where the episodes do at the latest (phase + n_steps <= 26)");
+  const uintptr_t row_align = swing ? 8 : 16;  // write_obs: float2 / float4 stores
+  if ((reinterpret_cast<uintptr_t>(out->obs) | reinterpret_cast<uintptr_t>(out->next_obs)) % row_align ||
+      (reinterpret_cast<uintptr_t>(out->action) | reinterpret_cast<uintptr_t>(out->eps_or_null)) % 8 ||
+      (reinterpret_cast<uintptr_t>(out->reward) | reinterpret_cast<uintptr_t>(out->done)) % sizeof(float))
+    return fail(TB_E_INVAL, "tb_sac_collect: obs / next_obs must be 16-byte aligned (SwingRacket-v0: 8), action / eps 8-byte, reward / done 4-byte");
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = count_first_substeps(h, n_steps, s)) return rc;
+  SacCollectArgs S;
+  memset(&S, 0, sizeof S);
+  S.actor = actor_dev; S.n_steps = n_steps; S.uniform = mode == TB_SAC_COLLECT_UNIFORM;
+  S.obs = out->obs; S.next_obs = out->next_obs; S.action = out->action; S.reward = out->reward; S.done = out->done; S.eps = out->eps_or_null;
+  KArgs a = base_args(h);
+  a.pol_seed = noise_seed; a.pol_deterministic = 0;
+  a.reward = out->reward; a.T = n_steps;  // (SwingRacket: the fast-forward's destination is the row of the launch's last step)
+  const bool may_park = swing && h->phase.launch_ends_episode(n_steps);
+  Park park;
+  if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
+  const bool rg = extended_contacts(h->kp);
+  void (*kern)(KArgs, SacCollectArgs) = swing ? (rg ? tb_sac_collect_kernel<TB_ENV_SWING, true> : tb_sac_collect_kernel<TB_ENV_SWING, false>)
+                                              : (rg ? tb_sac_collect_kernel<TB_ENV_TENNIS, true> : tb_sac_collect_kernel<TB_ENV_TENNIS, false>);
+  const unsigned groups = (unsigned)((h->n + TB_POLICY_SLICE - 1) / TB_POLICY_SLICE);
+  (void)hipGetLastError();
+  if (int rc = launch(kern, dim3(groups), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S)) return rc;  // (dynamic LDS: the env wave's columns)
+  if (int rc = finish_park(h, park, a, (size_t)h->n, s)) return rc;
+  if (swing) {
+    if (int rc = flush_all(h, s)) return rc;  // every output, the terminal reward included, is in place once `s` gets past here
+  }
+  h->phase.advance(n_steps);
+  return TB_OK;
+}
+
 // ------------------------------------------------------------------------------------------ the PPO learner (tb_learner.hpp)
 int tb_ppo_param_floats(int env_kind) {
   return env_kind == TB_ENV_SWING ? PpoLayout<TB_ENV_SWING>::P : env_kind == TB_ENV_TENNIS ? PpoLayout<TB_ENV_TENNIS>::P : TB_E_INVAL;

@@ -25,6 +25,7 @@ no torch fallback for the gradient step: a refused call raises. One rank only.
 """
 import copy
 import math
+import sys
 import time
 
 from .learner import flatten_parameters
@@ -41,6 +42,8 @@ BATCH_SIZE = {"SwingRacket-v0": 1100, "Tennisbot-v0": 256}   # train_swing.py:93
 # gradient 13 (critics forward 3, loss, their backward 3, the head's backward, the actor's backward 2 and weight gradients 3), Adam 2
 LAUNCHES_PER_STEP = 40
 EVAL_FORMS = ("torch", "fused")   # SACTrainer.evaluate_episodes: the torch actor between env steps / one tb_sac_evaluate launch
+COLLECT_FORMS = ("torch", "fused")   # SACTrainer.vector_step: the torch actor between single env steps / tb_sac_collect launches into the ring
+SWING_EPISODE_STEPS = 26
 ACTOR_NAMES = ("latent_pi.0.weight", "latent_pi.0.bias", "latent_pi.2.weight", "latent_pi.2.bias", "mu.weight", "mu.bias", "log_std.weight", "log_std.bias")
 CRITIC_NAMES = tuple("qf%d.%d.%s" % (q, layer, w) for q in (0, 1) for layer in (0, 2, 4) for w in ("weight", "bias"))
 
@@ -333,6 +336,24 @@ class ReplayBuffer:
         self.pos = (self.pos + n) % self.capacity
         self.size = min(self.capacity, self.size + n)
 
+    def reserve(self, n_steps, n_envs):
+        """views of the next n_steps * n_envs rows of (obs, next_obs, action, reward, done) for a producer that writes whole vector
+        steps in place (tb_sac_collect); the cursor and the fill advance as add() of as many rows would move them. The ring must
+        hold whole vector steps (capacity % n_envs == 0, the cursor on a step boundary) and the rows must not cross the wrap:
+        plan_collect_chunks cuts a request there."""
+        n_steps, n_envs = int(n_steps), int(n_envs)
+        if n_steps < 1 or n_envs < 1:
+            raise ValueError("ReplayBuffer.reserve: n_steps and n_envs must be >= 1")
+        if self.capacity % n_envs or self.pos % n_envs:
+            raise ValueError("ReplayBuffer.reserve: capacity %d and cursor %d must be multiples of n_envs = %d" % (self.capacity, self.pos, n_envs))
+        rows = n_steps * n_envs
+        if self.pos + rows > self.capacity:
+            raise ValueError("ReplayBuffer.reserve: %d rows from row %d would cross the wrap at %d" % (rows, self.pos, self.capacity))
+        views = tuple(a[self.pos:self.pos + rows] for a in self.arrays())
+        self.pos = (self.pos + rows) % self.capacity
+        self.size = min(self.capacity, self.size + rows)
+        return views
+
     def sample(self, n):
         if self.size < 1:
             raise ValueError("ReplayBuffer.sample: the buffer is empty")
@@ -349,11 +370,45 @@ class ReplayBuffer:
             dst[:self.size].copy_(src)
 
 
+def plan_collect_chunks(pos_rows, capacity_rows, n_steps, swing_phase_or_None, steps_to_learning_starts):
+    """The launch sizes, in env steps, of a fused collect of n_steps env steps. Rows are VECTOR steps here: the ring's cursor and
+    capacity divided by num_envs. A launch ends at the ring's wrap (its rows are contiguous), at SwingRacket's episode end (26 -
+    phase: the launch that ends the episodes parks them; None for Tennisbot) and at the step where num_timesteps reaches
+    learning_starts (steps_to_learning_starts env steps from now, <= 0 or None: already past), so that uniform and actor
+    launches change over at the timestep where the torch form does. Pure: no device, no trainer."""
+    pos, cap, left = int(pos_rows), int(capacity_rows), int(n_steps)
+    if cap < 1 or not 0 <= pos < cap:
+        raise ValueError("plan_collect_chunks: the cursor %d is not inside a ring of %d vector steps" % (pos, cap))
+    if left < 1:
+        raise ValueError("plan_collect_chunks: n_steps must be >= 1")
+    phase = None if swing_phase_or_None is None else int(swing_phase_or_None)
+    if phase is not None and not 0 <= phase < SWING_EPISODE_STEPS:
+        raise ValueError("plan_collect_chunks: SwingRacket's episode phase must be in [0, %d), not %d (envs out of lockstep?)" % (SWING_EPISODE_STEPS, phase))
+    to_ls = 0 if steps_to_learning_starts is None else max(0, int(steps_to_learning_starts))
+    chunks = []
+    while left > 0:
+        c = min(left, cap - pos)
+        if phase is not None:
+            c = min(c, SWING_EPISODE_STEPS - phase)
+        if to_ls > 0:
+            c = min(c, to_ls)
+            to_ls -= c
+        if phase is not None:
+            phase = (phase + c) % SWING_EPISODE_STEPS
+        chunks.append(c)
+        left -= c
+        pos = (pos + c) % cap
+    return chunks
+
+
 class SACTrainer:
     """SAC over a BatchedEnv. Collect: one BatchedEnv.step of every env with the torch actor (uniform actions in [-1, 1] while
     num_timesteps < learning_starts), the transitions into the replay ring; then `gradient_steps` fused gradient steps (default
     num_envs: one per collected transition, the update-to-data ratio of the reference's single env). The env is not pipelined, so
     SwingRacket's terminal reward is complete when its transition is stored. hp: learning_rate, gamma, tau (SAC_DEFAULTS).
+    collect_form "fused" (default "torch"): a vector step is collect_steps env steps in tb_sac_collect launches, the learner's flat
+    actor vector inside, every row written in place into the ring (its capacity rounded down to whole vector steps; SwingRacket's
+    env pipelined; noise keyed by the trainer's seed, not drawn from torch's RNG), then gradient_steps * collect_steps gradient steps.
     What another algorithm with the same loop changes is in the class attributes (tqc.TQCTrainer)."""
 
     LEARNER, DEFAULTS = FusedSAC, SAC_DEFAULTS
@@ -362,12 +417,17 @@ class SACTrainer:
     ALGO, NETS = "SAC", "SB3's MlpPolicy [256, 256]"          # the words of the two messages
 
     def __init__(self, env_id="SwingRacket-v0", num_envs=256, batch_size=None, gradient_steps=None, buffer_size=1_000_000, learning_starts=100, seed=0, params=None,
-                 device=None, eval_form="torch", **hp):
+                 device=None, eval_form="torch", collect_form="torch", collect_steps=1, **hp):
         import torch
         self.torch = torch
         if eval_form not in EVAL_FORMS:
             raise ValueError("%s: eval_form must be one of %s, not %r" % (type(self).__name__, EVAL_FORMS, eval_form))
         self.eval_form = eval_form
+        if collect_form not in COLLECT_FORMS:
+            raise ValueError("%s: collect_form must be one of %s, not %r" % (type(self).__name__, COLLECT_FORMS, collect_form))
+        if int(collect_steps) < 1:
+            raise ValueError("%s: collect_steps must be >= 1, not %r" % (type(self).__name__, collect_steps))
+        self.collect_form, self.collect_steps = collect_form, int(collect_steps)
         dist = torch.distributed
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise ValueError("%s runs on one rank (world size %d): multi-rank %s is not provided" % (type(self).__name__, dist.get_world_size(), self.ALGO))
@@ -380,7 +440,19 @@ class SACTrainer:
         self.batch_size = int(batch_size or self.default_batch(env_id))
         self.gradient_steps = self.num_envs if gradient_steps is None else int(gradient_steps)
         self.learning_starts = int(learning_starts)
-        self.env = BatchedEnv(kind, self.num_envs, device=device, seed=seed, params=params, track_terminal_obs=False, pipeline=False)
+        fused = collect_form == "fused"
+        if fused:   # the ring holds whole vector steps: tb_sac_collect writes [S][N] rows in place
+            rounded = int(buffer_size) // self.num_envs * self.num_envs
+            if rounded < self.num_envs:
+                raise ValueError("%s: collect_form='fused' needs a buffer_size of at least num_envs = %d, not %d" % (type(self).__name__, self.num_envs, buffer_size))
+            if rounded != int(buffer_size):
+                print("%s: collect_form='fused' rounds buffer_size %d down to %d, a multiple of num_envs = %d" % (type(self).__name__, buffer_size, rounded, self.num_envs),
+                      file=sys.stderr)
+            buffer_size = rounded
+        # fused collect on SwingRacket: the launch that ends the episodes parks them for the pipeline's fast-forward
+        self.env = BatchedEnv(kind, self.num_envs, device=device, seed=seed, params=params, track_terminal_obs=False, pipeline=fused and kind == ENV_SWING)
+        # the fused collect's noise key: from the trainer's seed alone (episode and step live in the env's state words, which a checkpoint holds)
+        self._collect_seed = (int(seed) * 0x9E3779B97F4A7C15 + 0x53414343) & 0xFFFFFFFFFFFFFFFF
         self.device = self.env.device
         O, A = self.env.obs_dim, self.env.act_dim
         torch.manual_seed(seed)
@@ -408,6 +480,8 @@ class SACTrainer:
                 a, _ = self.actor.sample(self.obs, t.randn((self.num_envs, self.env.act_dim), device=self.device))
             a = a.contiguous()
             obs, r, d = self.env.step(a)    # not pipelined: r holds SwingRacket's terminal reward already
+            if self.env.pipeline:            # (this form on a trainer built for the fused one: the terminal reward is written late)
+                self.env.flush()
             df = d.float()
             self.replay.add(self.obs, obs, a, r, df)   # (a done row's obs is the next episode's first: its bootstrap is selected away)
             self._ep_return += r
@@ -417,6 +491,34 @@ class SACTrainer:
             self.obs = obs
         self.num_timesteps += self.num_envs
         return a, obs, r, d
+
+    def collect_fused(self, n_steps=None):
+        """`n_steps` (default: collect_steps) steps of every env in as few tb_sac_collect launches as plan_collect_chunks allows, the
+        actor inside (uniform actions while num_timesteps < learning_starts), every row written straight into the replay ring:
+        no torch forward, no copy, nothing drawn from torch's RNG. Returns (action, obs, reward, done) of the last step, done as
+        0.0 / 1.0 (views of the ring)."""
+        t, N, O, A = self.torch, self.num_envs, self.env.obs_dim, self.env.act_dim
+        S = self.collect_steps if n_steps is None else int(n_steps)
+        phase = self.env.phase() if self.kind == ENV_SWING else None
+        to_ls = -(-(self.learning_starts - self.num_timesteps) // N)   # env steps until num_timesteps >= learning_starts (ceil)
+        out = None
+        for c in plan_collect_chunks(self.replay.pos // N, self.replay.capacity // N, S, phase, to_ls):
+            uniform = self.num_timesteps < self.learning_starts
+            views = self.replay.reserve(c, N)
+            self.env.sac_collect(None if uniform else self._learner.pi.flat, c, views, seed=self._collect_seed, uniform=uniform)   # (the vector the kernels train)
+            obs, next_obs, action, reward, done = views
+            reward, done = reward.view(c, N), done.view(c, N)
+            with t.no_grad():
+                for k in range(c):   # collect()'s float sums, step by step
+                    r, df = reward[k], done[k]
+                    self._ep_return += r
+                    self._ep_stats[0] += df.sum()
+                    self._ep_stats[1] += (self._ep_return * df).sum()
+                    self._ep_return *= 1.0 - df
+            self.obs = next_obs.view(c, N, O)[c - 1].clone()   # (a copy: the ring's row is overwritten one lap later)
+            self.num_timesteps += c * N
+            out = (action.view(c, N, A)[c - 1], self.obs, reward[c - 1], done[c - 1])
+        return out
 
     def train(self, gradient_steps=None):
         """`gradient_steps` fused steps on fresh samples; indices and noise are drawn in bulk. Returns the number of steps issued."""
@@ -433,7 +535,14 @@ class SACTrainer:
         return G
 
     def vector_step(self):
-        """collect one step of every env, then (past learning_starts) the gradient steps; returns collect's (action, obs, reward, done)"""
+        """collect one step of every env, then (past learning_starts) the gradient steps; returns collect's (action, obs, reward, done).
+        collect_form "fused": collect_steps env steps (collect_fused), then gradient_steps * collect_steps gradient steps --
+        gradient_steps stays "per env step"."""
+        if self.collect_form == "fused":
+            out = self.collect_fused()
+            if self.num_timesteps > self.learning_starts:
+                self.train(self.gradient_steps * self.collect_steps)
+            return out
         out = self.collect()
         if self.num_timesteps > self.learning_starts:
             self.train()
@@ -482,6 +591,8 @@ class SACTrainer:
                 else:
                     a, _ = self.actor.sample(self.obs, t.randn((self.num_envs, self.env.act_dim), device=self.device))
                 self.obs, r, d = self.env.step(a.contiguous())
+                if self.env.pipeline:   # (a trainer built for the fused collect: SwingRacket's terminal reward is written late)
+                    self.env.flush()
                 total += r.sum(); eps += d.float().sum()
         self._ep_return.zero_()
         return float(total) / max(float(eps), 1.0)

@@ -101,6 +101,8 @@ def load_library():
     L.tb_policy_evaluate.restype = i32
     L.tb_sac_evaluate.argtypes = [vp, vp, vp, vp, u64, i32, ctypes.POINTER(TbSacEvalTrace), vp]
     L.tb_sac_evaluate.restype = i32
+    L.tb_sac_collect.argtypes = [vp, vp, i32, i32, u64, ctypes.POINTER(TbSacCollectOut), vp]
+    L.tb_sac_collect.restype = i32
     f32, f64, i64 = ctypes.c_float, ctypes.c_double, ctypes.c_longlong
     L.tb_ppo_param_floats.argtypes = [i32]
     L.tb_ppo_param_floats.restype = i32
@@ -213,6 +215,15 @@ class TbSacEvalTrace(ctypes.Structure):
     """include/tb_stepper.h TbSacEvalTrace: optional per-step record of tb_sac_evaluate"""
     _fields_ = [("struct_size", ctypes.c_size_t), ("max_steps", ctypes.c_int), ("obs", ctypes.c_void_p), ("eps", ctypes.c_void_p),
                 ("actions", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p)]
+
+
+class TbSacCollectOut(ctypes.Structure):
+    """include/tb_stepper.h TbSacCollectOut: the [S][N] rows tb_sac_collect writes (pointers into the caller's replay ring)"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("obs", ctypes.c_void_p), ("next_obs", ctypes.c_void_p), ("action", ctypes.c_void_p),
+                ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p), ("eps_or_null", ctypes.c_void_p)]
+
+
+SAC_COLLECT_ACTOR, SAC_COLLECT_UNIFORM = 0, 1   # include/tb_stepper.h TB_SAC_COLLECT_*
 
 
 def _check(L, rc, what):
@@ -596,6 +607,35 @@ class BatchedEnv:
         _check(self.L, self.L.tb_sac_evaluate(self._h, w.data_ptr(), ret.data_ptr(), length.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                               1 if deterministic else 0, None if tr is None else ctypes.byref(tr), self._stream()), "tb_sac_evaluate")
         return (ret, length, rec) if trace else (ret, length)
+
+    def sac_collect(self, actor_flat, n_steps, out_views, seed=0, uniform=False, eps=None):
+        """n_steps agent steps of every env from where it stands, in one launch with the SAC / TQC actor inside, every transition
+        written as a replay ring stores it (tb_sac_collect). actor_flat: the flat TB_SAC_ACTOR vector, or None with uniform=True
+        (actions uniform in [-1, 1), from the Philox words of the same keys). out_views = (obs, next_obs, action, reward, done):
+        contiguous float32 tensors [S, N, O], [S, N, O], [S, N, A], [S, N], [S, N] on this device (S * N leading rows also do:
+        views of a ring), done as 0.0 / 1.0; eps: optional [S, N, A] for the noise drawn. Envs that finish restart inside the
+        launch and the state is written back, as n_steps calls of step() would leave it. SwingRacket-v0 needs pipeline=True, envs
+        in lockstep and phase() + n_steps <= 26; every output is complete in stream order on return (no flush() needed)."""
+        t, n, S = self.torch, self.num_envs, int(n_steps)
+        if S < 1:
+            raise ValueError("n_steps must be >= 1")
+        if len(out_views) != 5:
+            raise ValueError("out_views must be (obs, next_obs, action, reward, done)")
+        dims = (self.obs_dim, self.obs_dim, self.act_dim, None, None)
+        names = ("obs", "next_obs", "action", "reward", "done")
+        views = list(zip(names, out_views, dims)) + ([("eps", eps, self.act_dim)] if eps is not None else [])
+        for name, x, k in views:
+            if not isinstance(x, t.Tensor) or x.device != self.device or x.dtype != t.float32 or not x.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 tensor on %s" % (name, self.device))
+            if x.numel() != S * n * (k or 1) or (k is not None and x.shape[-1] != k):
+                raise ValueError("%s must hold %d x %d rows%s, got %s" % (name, S, n, "" if k is None else " of %d" % k, tuple(x.shape)))
+        w = None
+        if not uniform:
+            w = self._check_tensor(actor_flat, (self.sac_actor_floats(),), t.float32, "actor_flat")
+        out = TbSacCollectOut(ctypes.sizeof(TbSacCollectOut), *(x.data_ptr() for x in out_views), None if eps is None else eps.data_ptr())
+        _check(self.L, self.L.tb_sac_collect(self._h, None if w is None else w.data_ptr(), S, SAC_COLLECT_UNIFORM if uniform else SAC_COLLECT_ACTOR,
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(out), self._stream()), "tb_sac_collect")
+        self._steps_issued += S
 
     def capture(self, fn):
         """Capture `fn()` -- a fixed sequence of step()/step_ptrs()/RolloutBuffer.step_into calls on

@@ -7,7 +7,8 @@ as HIP kernels (tennisbot_rl_amd/sac.py, csrc/tb_sac.hpp).
 
 Hyper-parameters are SB3 1.8.0's SAC defaults as the reference leaves them (lr 3e-4, gamma 0.99, tau 0.005, ent_coef "auto",
 buffer_size 1e6, learning_starts 100). One vector step collects --num-envs transitions and runs --gradient-steps gradient steps
-(default: one per transition, the reference's update-to-data ratio). Checkpoints hold the learner, the replay ring AND the env
+(default: one per transition, the reference's update-to-data ratio); with --collect-form fused it is --collect-steps env steps in
+one launch and --gradient-steps gradient steps per env step. Checkpoints hold the learner, the replay ring AND the env
 batch state. One rank only. TQC (train_swing.py only) is train_tqc.py.
 """
 import argparse
@@ -43,13 +44,16 @@ def off_policy_parser(description, algo, batch_help, total_default, total_help):
     add_schedule_arguments(ap)
     ap.add_argument("--eval-form", choices=["torch", "fused"], default="torch", help="how --eval-freq's whole episodes run: `torch` steps a separate batch with "
                     "the torch actor; `fused` runs every episode of a batch in one launch with the actor inside (tb_sac_evaluate)")
+    ap.add_argument("--collect-form", choices=["torch", "fused"], default="torch", help="how transitions are collected: `torch` runs the torch actor between "
+                    "single env steps; `fused` runs --collect-steps env steps in one launch with the actor inside, straight into the replay ring (tb_sac_collect)")
+    ap.add_argument("--collect-steps", type=int, default=1, help="env steps per vector step with --collect-form fused (--gradient-steps stays per env step)")
     return ap
 
 
 def trainer_arguments(args):
     """the trainer's keyword arguments that come straight from the parsed command line"""
     return dict(num_envs=args.num_envs, batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
-                learning_starts=args.learning_starts, seed=args.seed, eval_form=args.eval_form)
+                learning_starts=args.learning_starts, seed=args.seed, eval_form=args.eval_form, collect_form=args.collect_form, collect_steps=args.collect_steps)
 
 
 def off_policy_main(argv, script, algo, trainer, description, batch_help, total_default, total_help, total_by_env):

@@ -348,8 +348,12 @@ int tb_policy_rollout(TbHandle *h, int n_steps, const float *weights_dev, const 
  * the towers' first layer takes the A-wide feature as a 16-wide input (k(4u + r, g) = 16u + 4g + r, zero for k >= A).
  * tb_policy_step_net / tb_policy_rollout_net: tb_policy_step / tb_policy_rollout with that network; sampling, noise keys,
  * clipping, episode ends and every output are theirs. The un-suffixed names are the TB_NET_DEFAULT calls.
+ * TB_NET_MLP64, SwingRacket-v0 only: SB3's MlpPolicy default, pi = vf = [64, 64] tanh (6 -> 64 -> 64 -> 6 and -> 1), what the
+ * reference's `train_swing.py -s trpo` trains (train_swing.py:101-102). Blob: 11560 floats in TB_NET_DEFAULT's layout -- pi
+ * tower, vf tower, log_std padded to 8; the first layer has two k-chunks (O = 6 padded to 8). On Tennisbot-v0 TB_NET_DEFAULT
+ * already is that architecture, so (TB_ENV_TENNIS, TB_NET_MLP64) is refused like every other unbuilt pair.
  */
-enum { TB_NET_DEFAULT = 0, TB_NET_TUNED = 1 };
+enum { TB_NET_DEFAULT = 0, TB_NET_TUNED = 1, TB_NET_MLP64 = 2 };
 int tb_policy_blob_floats(int env_kind, int net);
 int tb_policy_step_net(TbHandle *h, int net, const float *weights_dev, const float *obs_in_dev, float *actions_dev,
                        float *raw_actions_dev, float *logp_dev, float *value_dev, float *obs_dev,
@@ -539,6 +543,9 @@ int tb_ppo_apply(int env_kind, int device, void *stream, int phases, const void 
  * extractor too: a partial vector holds the pi wave's extractor share in the extractor's slots and the vf wave's in a second
  * region, and TB_PPO_REDUCE adds the two float64 sums (pi's first), so the result is as reproducible as the default nets'.
  * TB_PPO_VALUE_ONLY is refused for it (TB_E_UNSUPPORTED): the extractor is shared, there is no critic-only slot range.
+ * TB_NET_MLP64 (SwingRacket-v0): 9677 floats in the order of the default nets, log_std [6] | policy_net W0 [64][6] b0 W1 [64][64]
+ * b1 | value_net_body, the same | action_net W [6][64] b | value_net W [1][64] b -- named_parameters() of
+ * ppo.build_actor_critic(6, 6, (64, 64)). The towers are separate: TB_PPO_VALUE_ONLY is offered.
  * tb_ppo_gae does not depend on the network. Other (kind, net) pairs: TB_E_PARAMS.
  */
 int tb_ppo_param_floats_net(int env_kind, int net);
@@ -582,6 +589,20 @@ int tb_trpo_search(int env_kind, int device, void *stream, const float *obs_dev,
                    const float *old_logp_dev, const float *adv_dev, long long n_rows, const int64_t *idx_dev, int batch,
                    const float *params_dev, const float *direction_dev, int n_params, const float *steps_dev, int n_candidates,
                    double *out_dev, void *workspace_dev, size_t workspace_bytes);
+/*
+ * The same two calls and their workspace queries for a network given by name (the names above are the TB_NET_DEFAULT calls):
+ * TB_NET_MLP64 on SwingRacket-v0, vectors of tb_ppo_param_floats_net(kind, net) floats. TB_NET_TUNED is refused (TB_E_PARAMS): the
+ * tuned network's shared extractor has no instantiation of these kernels.
+ */
+long long tb_trpo_fvp_workspace_bytes_net(int env_kind, int net, int n_idx);
+long long tb_trpo_search_workspace_bytes_net(int env_kind, int net, int batch, int n_candidates);
+int tb_trpo_fvp_net(int env_kind, int net, int device, void *stream, const float *obs_dev, long long n_rows, const int64_t *idx_dev,
+                    int n_idx, const float *params_dev, const float *vec_dev, int n_params, float damping, float *out_dev,
+                    void *workspace_dev, size_t workspace_bytes);
+int tb_trpo_search_net(int env_kind, int net, int device, void *stream, const float *obs_dev, const float *raw_actions_dev,
+                       const float *old_logp_dev, const float *adv_dev, long long n_rows, const int64_t *idx_dev, int batch,
+                       const float *params_dev, const float *direction_dev, int n_params, const float *steps_dev, int n_candidates,
+                       double *out_dev, void *workspace_dev, size_t workspace_bytes);
 
 /*
  * The SAC learner (csrc/tb_sac.hpp; tennisbot_rl_amd/sac.py is the caller): SB3 1.8.0's SAC with MlpPolicy, [256, 256] ReLU nets,

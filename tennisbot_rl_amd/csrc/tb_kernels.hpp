@@ -1068,7 +1068,7 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
     regs.load(A.pol_weights, tower, lane);
     __syncthreads();
     for (int t = 0; t < A.T; ++t) {
-      float x0[TowerRegs<KIND>::NC0], out[4];
+      float x0[policy_nc0<KIND>()], out[4];
       if (t == 0) policy_inputs<KIND>(A.pol_obs + (size_t)env_c * NO, lane, x0);
       else policy_inputs<KIND>(s_obs + slot * NO, lane, x0);
 #ifdef TB_DIAG_NO_TOWERS  // timing-only (tools/diag/r04_policy_ablate.py): RESULTS ARE WRONG
@@ -1201,7 +1201,7 @@ __global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double
     regs.load(A.pol_weights, 0, lane);
     __syncthreads();  // the outline table and the episodes' first observations are in LDS
     for (int t = 0;; ++t) {
-      float x0[TowerRegs<KIND>::NC0], out[4];
+      float x0[policy_nc0<KIND>()], out[4];
       policy_inputs<KIND>(s_obs + slot * NO, lane, x0);
       regs.apply(x0, out);
       if (grp < 2) *reinterpret_cast<float4*>(s_mean + slot * 8 + grp * 4) = make_float4(out[0], out[1], out[2], out[3]);

@@ -29,8 +29,8 @@ constexpr int TB_PPO_HALF = TB_PPO_SHARE / 2;
 constexpr int TB_PPO_STAT_BLOCKS = 64;  // partial sums of the advantage statistics
 constexpr float TB_LN_SQRT_2PI = 0.9189385332046727f;
 
-template <int KIND> struct PpoLayout {
-  using N = PolicyNet<KIND>;
+template <int KIND, int NET = TB_NET_DEFAULT> struct PpoLayout {
+  using N = PolicyNet<KIND, NET>;
   static constexpr int O = Dims<KIND>::O, A = Dims<KIND>::A, NH = N::NH, LAST = N::LAST;
   static constexpr int BODY = N::H0 * (O + 1) + N::H1 * (N::H0 + 1) + (NH == 3 ? N::H2 * (N::H1 + 1) : 0);
   static constexpr int LOG_STD = 0, PI = A, VF = PI + BODY, PI_HEAD = VF + BODY, VF_HEAD = PI_HEAD + A * (LAST + 1);
@@ -256,10 +256,10 @@ __global__ __launch_bounds__(256) void tb_ppo_adv_stats_kernel(const float* adv,
 }
 
 // one tower of one half share. PI: the policy tower (logp, ratio, clipped surrogate, d log_std); else the value tower
-template <int KIND, bool PI>
+template <int KIND, bool PI, int NET = TB_NET_DEFAULT>
 TB_DEV void ppo_tower(const PpoGradArgs& a, float* buf, int lane, int first, float* part) {
-  using L = PpoLayout<KIND>;
-  using N = PolicyNet<KIND>;
+  using L = PpoLayout<KIND, NET>;
+  using N = PolicyNet<KIND, NET>;
   constexpr int O = L::O, NA = L::A, NH = L::NH, HOUT = PI ? NA : 1;
   const int g = lane >> 4, e = lane & 15, B = a.batch;
   const float* body = a.params + (PI ? L::PI : L::VF);
@@ -411,23 +411,23 @@ TB_DEV void ppo_tower(const PpoGradArgs& a, float* buf, int lane, int first, flo
   if (lane == 0) part[L::P + (PI ? 0 : 1)] = stat;
 }
 
-template <int KIND>
+template <int KIND, int NET = TB_NET_DEFAULT>
 __global__ __launch_bounds__(256) void tb_ppo_grad_kernel(const PpoGradArgs a) {
   __shared__ __attribute__((aligned(16))) float s_buf[4 * 512];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = wave & 1;
   const int first = blockIdx.x * TB_PPO_SHARE + half * TB_PPO_HALF;
-  float* part = a.partials + (size_t)(2 * blockIdx.x + half) * PpoLayout<KIND>::STRIDE;
-  if (wave < 2) ppo_tower<KIND, true>(a, s_buf + wave * 512, lane, first, part);
-  else ppo_tower<KIND, false>(a, s_buf + wave * 512, lane, first, part);
+  float* part = a.partials + (size_t)(2 * blockIdx.x + half) * PpoLayout<KIND, NET>::STRIDE;
+  if (wave < 2) ppo_tower<KIND, true, NET>(a, s_buf + wave * 512, lane, first, part);
+  else ppo_tower<KIND, false, NET>(a, s_buf + wave * 512, lane, first, part);
 }
 
 // gradient[p] = sum of the partials in a fixed order (float64: four runs of n_part / 4, then (0 + 1) + (2 + 3)); log_std's
 // entropy term; the minibatch's three statistics. 64 parameters per block. value_only: grad's policy slots (log_std, PI,
 // PI_HEAD) are left as they are.
-template <int KIND>
+template <int KIND, int NET = TB_NET_DEFAULT>
 __global__ __launch_bounds__(256) void tb_ppo_reduce_kernel(const float* partials, int n_part, int batch, const float* params, float ent_coef, float* grad,
                                                             float* stats, int value_only) {
-  using L = PpoLayout<KIND>;
+  using L = PpoLayout<KIND, NET>;
   __shared__ double s_sum[4][64];
   const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;
   double s = 0.0;

@@ -28,16 +28,21 @@ namespace {
 // Blob, per tower and layer: bias tiles [ceil(out/16)][4 lane groups][4 regs], then weight fragments
 // [ceil(out/16)][chunks][64 lanes] -- i.e. exactly what lane l loads at index l; heads padded to 16 outputs,
 // the first layer's k padded to a multiple of 4 with zeros.
-template <int KIND> struct PolicyNet;
-template <> struct PolicyNet<TB_ENV_SWING> { static constexpr int NH = 3, H0 = 32, H1 = 64, H2 = 32, LAST = 32; };
-template <> struct PolicyNet<TB_ENV_TENNIS> { static constexpr int NH = 2, H0 = 64, H1 = 64, H2 = 64, LAST = 64; };
+// keyed by (kind, net): every kind's own network, and SB3's default [64, 64] on SwingRacket-v0 (TB_NET_MLP64: what the reference's
+// `train_swing.py -s trpo` trains, train_swing.py:101-102 -- Tennisbot's default network IS that architecture)
+template <int KIND, int NET = TB_NET_DEFAULT> struct PolicyNet;
+template <> struct PolicyNet<TB_ENV_SWING, TB_NET_DEFAULT> { static constexpr int NH = 3, H0 = 32, H1 = 64, H2 = 32, LAST = 32; };
+template <> struct PolicyNet<TB_ENV_TENNIS, TB_NET_DEFAULT> { static constexpr int NH = 2, H0 = 64, H1 = 64, H2 = 64, LAST = 64; };
+template <> struct PolicyNet<TB_ENV_SWING, TB_NET_MLP64> { static constexpr int NH = 2, H0 = 64, H1 = 64, H2 = 64, LAST = 64; };
 constexpr int layer_floats(int in, int out) { return ((out + 15) / 16) * (16 + ((in + 3) / 4) * 64); }
-template <int KIND> constexpr int tower_floats() {  // hidden layers + the (padded) head
-  using N = PolicyNet<KIND>;
+template <int KIND, int NET = TB_NET_DEFAULT> constexpr int tower_floats() {  // hidden layers + the (padded) head
+  using N = PolicyNet<KIND, NET>;
   return layer_floats(Dims<KIND>::O, N::H0) + layer_floats(N::H0, N::H1) + (N::NH == 3 ? layer_floats(N::H1, N::H2) : 0) + layer_floats(N::LAST, 16);
 }
-template <int KIND> constexpr int policy_floats() { return 2 * tower_floats<KIND>() + (Dims<KIND>::A + 3) / 4 * 4; }
+template <int KIND, int NET = TB_NET_DEFAULT> constexpr int policy_floats() { return 2 * tower_floats<KIND, NET>() + (Dims<KIND>::A + 3) / 4 * 4; }
 constexpr int TB_POLICY_SLICE = 16;  // envs per tower wave
+// k-chunks of a first layer: the observation padded to a multiple of 4 -- a property of the env kind, whatever the network
+template <int KIND> constexpr int policy_nc0() { return (Dims<KIND>::O + 3) / 4; }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // tanh(x) = 1 - 2 / (e^(2x) + 1) on the hardware exp2 / rcp units (1 ulp each): absolute error < 3e-7,
@@ -90,10 +95,10 @@ struct LayerRegs {
 // one tower for 16 envs: lane l works on env (l & 15); out[0..3] = head rows 4 (l >> 4) + 0..3 of that env. Every operand
 // of the tower is requested by load() up front (one VGPR per fragment): the loads of the later layers land while the
 // earlier ones compute (policy_tower), or stay resident across the steps of a rollout launch (tb_policy_rollout_kernel).
-template <int KIND> struct TowerRegs;
-template <> struct TowerRegs<TB_ENV_SWING> {  // 6 -> 32 -> 64 -> 32 -> head
+template <int KIND, int NET = TB_NET_DEFAULT> struct TowerRegs;
+template <> struct TowerRegs<TB_ENV_SWING, TB_NET_DEFAULT> {  // 6 -> 32 -> 64 -> 32 -> head
   using N = PolicyNet<TB_ENV_SWING>;
-  static constexpr int O = Dims<TB_ENV_SWING>::O, NC0 = (O + 3) / 4;
+  static constexpr int O = Dims<TB_ENV_SWING>::O, NC0 = policy_nc0<TB_ENV_SWING>();
   LayerRegs<2, NC0> l0;
   LayerRegs<4, 8> l1;
   LayerRegs<2, 16> l2;
@@ -112,9 +117,27 @@ template <> struct TowerRegs<TB_ENV_SWING> {  // 6 -> 32 -> 64 -> 32 -> head
     lh.template apply<ACT_NONE>(h2, out);
   }
 };
-template <> struct TowerRegs<TB_ENV_TENNIS> {  // 12 -> 64 -> 64 -> head
+template <> struct TowerRegs<TB_ENV_TENNIS, TB_NET_DEFAULT> {  // 12 -> 64 -> 64 -> head
   using N = PolicyNet<TB_ENV_TENNIS>;
-  static constexpr int O = Dims<TB_ENV_TENNIS>::O, NC0 = (O + 3) / 4;
+  static constexpr int O = Dims<TB_ENV_TENNIS>::O, NC0 = policy_nc0<TB_ENV_TENNIS>();
+  LayerRegs<4, NC0> l0;
+  LayerRegs<4, 16> l1;
+  LayerRegs<1, 16> lh;
+  TB_DEV void load(const float* g, int lane) {
+    l0.load(g, lane); g += layer_floats(O, N::H0);
+    l1.load(g, lane); g += layer_floats(N::H0, N::H1);
+    lh.load(g, lane);
+  }
+  TB_DEV void apply(const float (&x0)[NC0], float (&out)[4]) const {
+    float h0[16], h1[16];
+    l0.template apply<ACT_TANH>(x0, h0);
+    l1.template apply<ACT_TANH>(h0, h1);
+    lh.template apply<ACT_NONE>(h1, out);
+  }
+};
+template <> struct TowerRegs<TB_ENV_SWING, TB_NET_MLP64> {  // 6 -> 64 -> 64 -> head: two k-chunks in front (O = 6 padded to 8)
+  using N = PolicyNet<TB_ENV_SWING, TB_NET_MLP64>;
+  static constexpr int O = Dims<TB_ENV_SWING>::O, NC0 = policy_nc0<TB_ENV_SWING>();
   LayerRegs<4, NC0> l0;
   LayerRegs<4, 16> l1;
   LayerRegs<1, 16> lh;
@@ -183,16 +206,16 @@ struct TunedTower {  // feature tile -> 32 -> 64 -> 32 -> head, ReLU
 // tower; for the tuned network the trunk in front of it -- both tower waves of a slice evaluate the trunk, the same
 // instructions on the same operands, so the two see the same feature bits)
 template <int KIND, int NET> struct PolicyBlob {
-  static_assert(NET == TB_NET_DEFAULT, "the tuned network is Tennisbot's");
-  static constexpr int PI = 0, TOWER = tower_floats<KIND>(), LOG_STD = 2 * TOWER, TOTAL = policy_floats<KIND>();
+  static_assert(NET == TB_NET_DEFAULT || (NET == TB_NET_MLP64 && KIND == TB_ENV_SWING), "the tuned network is Tennisbot's, the [64, 64] one SwingRacket's");
+  static constexpr int PI = 0, TOWER = tower_floats<KIND, NET>(), LOG_STD = 2 * TOWER, TOTAL = policy_floats<KIND, NET>();
 };
 template <> struct PolicyBlob<TB_ENV_TENNIS, TB_NET_TUNED> {
   static constexpr int PI = tuned_trunk_floats(), TOWER = tuned_tower_floats(), LOG_STD = PI + 2 * TOWER, TOTAL = LOG_STD + 4;
 };
 template <int KIND, int NET> struct PolicyRegs {
-  TowerRegs<KIND> t;
-  TB_DEV void load(const float* blob, int tower, int lane) { t.load(blob + tower * tower_floats<KIND>(), lane); }
-  TB_DEV void apply(const float (&x0)[TowerRegs<KIND>::NC0], float (&out)[4]) const { t.apply(x0, out); }
+  TowerRegs<KIND, NET> t;
+  TB_DEV void load(const float* blob, int tower, int lane) { t.load(blob + tower * tower_floats<KIND, NET>(), lane); }
+  TB_DEV void apply(const float (&x0)[TowerRegs<KIND, NET>::NC0], float (&out)[4]) const { t.apply(x0, out); }
 };
 template <> struct PolicyRegs<TB_ENV_TENNIS, TB_NET_TUNED> {
   using B = PolicyBlob<TB_ENV_TENNIS, TB_NET_TUNED>;
@@ -211,11 +234,11 @@ template <> struct PolicyRegs<TB_ENV_TENNIS, TB_NET_TUNED> {
 
 // the first layer's B operand of this lane: obs[4 ch + (lane >> 4)] of its env, 0 beyond the observation
 template <int KIND>
-TB_DEV void policy_inputs(const float* obs_row, int lane, float (&x0)[TowerRegs<KIND>::NC0]) {
+TB_DEV void policy_inputs(const float* obs_row, int lane, float (&x0)[policy_nc0<KIND>()]) {
   constexpr int NO = Dims<KIND>::O;
   const int grp = lane >> 4;
 #pragma unroll
-  for (int ch = 0; ch < TowerRegs<KIND>::NC0; ++ch) {
+  for (int ch = 0; ch < policy_nc0<KIND>(); ++ch) {
     if ((NO & 3) == 0 || ch < NO / 4) x0[ch] = obs_row[4 * ch + grp];
     else x0[ch] = 4 * ch + grp < NO ? obs_row[4 * ch + grp] : 0.0f;
   }
@@ -263,7 +286,7 @@ TB_DEV void policy_towers(const KArgs& A, float* s_mean) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 4;
   const int slot = wave * TB_POLICY_SLICE + (lane & 15), env = blockIdx.x * 64 + slot;
   const int env_c = env < A.n ? env : A.n - 1;
-  float x0[TowerRegs<KIND>::NC0], mean[4], val[4];
+  float x0[policy_nc0<KIND>()], mean[4], val[4];
   policy_inputs<KIND>(A.pol_obs + (size_t)env_c * NO, lane, x0);
   if constexpr (NET == TB_NET_TUNED) {  // the trunk once, its feature tile into both towers
     using B = PolicyBlob<KIND, NET>;
@@ -281,9 +304,9 @@ TB_DEV void policy_towers(const KArgs& A, float* s_mean) {
     pi.apply(feat, mean);
     vf.apply(feat, val);
   } else {
-    TowerRegs<KIND> pi, vf;
+    TowerRegs<KIND, NET> pi, vf;
     pi.load(A.pol_weights, lane);
-    vf.load(A.pol_weights + tower_floats<KIND>(), lane);
+    vf.load(A.pol_weights + tower_floats<KIND, NET>(), lane);
     __builtin_amdgcn_sched_barrier(0);  // keeps the scheduler from sinking each load down to its MFMA
     pi.apply(x0, mean);
     vf.apply(x0, val);

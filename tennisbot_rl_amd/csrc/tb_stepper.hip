@@ -369,6 +369,10 @@ StepKernel step_kernel_of(bool multi, bool rg, bool pol, int net) {
     if (pol && net == TB_NET_TUNED)
       return multi ? nullptr : rg ? tb_step_kernel<KIND, LEAN, false, true, true, false, TB_NET_TUNED> : tb_step_kernel<KIND, LEAN, false, false, true, false, TB_NET_TUNED>;
   }
+  if constexpr (KIND == TB_ENV_SWING) {
+    if (pol && net == TB_NET_MLP64)
+      return multi ? nullptr : rg ? tb_step_kernel<KIND, LEAN, false, true, true, false, TB_NET_MLP64> : tb_step_kernel<KIND, LEAN, false, false, true, false, TB_NET_MLP64>;
+  }
   if (net != TB_NET_DEFAULT) return nullptr;
   if (pol) return multi ? nullptr : rg ? tb_step_kernel<KIND, LEAN, false, true, true> : tb_step_kernel<KIND, LEAN, false, false, true>;
   if (multi) return rg ? tb_step_kernel<KIND, LEAN, true, true> : tb_step_kernel<KIND, LEAN, true, false>;
@@ -677,7 +681,8 @@ int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, f
   const int E = narrow ? TB_POLICY_SLICE : 3 * TB_POLICY_SLICE;
   dim3 grid((unsigned)((h->n + E - 1) / E)), block(narrow ? 192 : 448);
   const bool rg = extended_contacts(h->kp);
-  const ArgsKernel kern = swing                     ? policy_rollout_kernel<TB_ENV_SWING>(narrow ? 1 : 3, rg)
+  const ArgsKernel kern = swing ? (pol.net == TB_NET_MLP64 ? policy_rollout_kernel<TB_ENV_SWING, TB_NET_MLP64>(narrow ? 1 : 3, rg)
+                                                           : policy_rollout_kernel<TB_ENV_SWING>(narrow ? 1 : 3, rg))
                           : pol.net == TB_NET_TUNED ? policy_rollout_kernel<TB_ENV_TENNIS, TB_NET_TUNED>(narrow ? 1 : 3, rg)
                                                     : policy_rollout_kernel<TB_ENV_TENNIS>(narrow ? 1 : 3, rg);
   if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_rollout_kernel instantiation for this variant");
@@ -1057,18 +1062,32 @@ int tb_policy_floats(int env_kind) {
 }
 
 namespace {
-// the (kind, net) pairs the policy kernels are built for: every kind's own network, and Tennisbot's tuned one
+// the (kind, net) pairs the policy kernels are built for: every kind's own network, Tennisbot's tuned one, SwingRacket's [64, 64]
 int policy_net_ok(int env_kind, int net, const char* who) {
-  if (net == TB_NET_DEFAULT || (net == TB_NET_TUNED && env_kind == TB_ENV_TENNIS)) return TB_OK;
-  char msg[160];
-  snprintf(msg, sizeof msg, "%s: net %d is not built for env kind %d (TB_NET_TUNED is Tennisbot-v0's; every kind has TB_NET_DEFAULT)", who, net, env_kind);
+  if (net == TB_NET_DEFAULT || (net == TB_NET_TUNED && env_kind == TB_ENV_TENNIS) || (net == TB_NET_MLP64 && env_kind == TB_ENV_SWING)) return TB_OK;
+  char msg[256];
+  if (net == TB_NET_MLP64 && env_kind == TB_ENV_TENNIS)
+    snprintf(msg, sizeof msg, "%s: TB_NET_MLP64 is SwingRacket-v0's; on Tennisbot-v0 TB_NET_DEFAULT is that net (pi = vf = [64, 64], tanh)", who);
+  else
+    snprintf(msg, sizeof msg, "%s: net %d is not built for env kind %d (TB_NET_TUNED is Tennisbot-v0's, TB_NET_MLP64 SwingRacket-v0's; every kind has TB_NET_DEFAULT)", who,
+             net, env_kind);
   return fail(TB_E_PARAMS, msg);
+}
+// the TRPO kernels': the above without the tuned network (its shared extractor has no instantiation of them)
+int trpo_net_ok(int env_kind, int net, const char* who) {
+  if (net == TB_NET_TUNED) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: TB_NET_TUNED is not built for the TRPO kernels (TB_NET_DEFAULT, or TB_NET_MLP64 on SwingRacket-v0)", who);
+    return fail(TB_E_PARAMS, msg);
+  }
+  return policy_net_ok(env_kind, net, who);
 }
 }  // namespace
 
 int tb_policy_blob_floats(int env_kind, int net) {
   if (env_kind != TB_ENV_SWING && env_kind != TB_ENV_TENNIS) return TB_E_INVAL;
   if (int rc = policy_net_ok(env_kind, net, "tb_policy_blob_floats")) return rc;
+  if (net == TB_NET_MLP64) return PolicyBlob<TB_ENV_SWING, TB_NET_MLP64>::TOTAL;
   return net == TB_NET_TUNED ? PolicyBlob<TB_ENV_TENNIS, TB_NET_TUNED>::TOTAL : tb_policy_floats(env_kind);
 }
 
@@ -1181,6 +1200,8 @@ namespace {
 // tb_policy_evaluate_kernel<KIND, RG, NET>: the (kind, RG, net) combinations of tb_policy_rollout_kernel
 using EvalKernel = void (*)(KArgs, double*, int32_t*);
 EvalKernel policy_evaluate_kernel(int kind, bool rg, int net) {
+  if (kind == TB_ENV_SWING && net == TB_NET_MLP64)
+    return rg ? tb_policy_evaluate_kernel<TB_ENV_SWING, true, TB_NET_MLP64> : tb_policy_evaluate_kernel<TB_ENV_SWING, false, TB_NET_MLP64>;
   if (kind == TB_ENV_SWING) return rg ? tb_policy_evaluate_kernel<TB_ENV_SWING, true> : tb_policy_evaluate_kernel<TB_ENV_SWING, false>;
   if (net == TB_NET_TUNED) return rg ? tb_policy_evaluate_kernel<TB_ENV_TENNIS, true, TB_NET_TUNED> : tb_policy_evaluate_kernel<TB_ENV_TENNIS, false, TB_NET_TUNED>;
   return rg ? tb_policy_evaluate_kernel<TB_ENV_TENNIS, true> : tb_policy_evaluate_kernel<TB_ENV_TENNIS, false>;
@@ -1309,17 +1330,34 @@ int tb_sac_collect(TbHandle* h, const float* actor_dev, int n_steps, int mode, u
 int tb_ppo_param_floats(int env_kind) {
   return env_kind == TB_ENV_SWING ? PpoLayout<TB_ENV_SWING>::P : env_kind == TB_ENV_TENNIS ? PpoLayout<TB_ENV_TENNIS>::P : TB_E_INVAL;
 }
+extern "C++" {
+namespace {
+// PpoLayout<KIND, NET> at run time, for the separate-tower nets: the flat vector's length and where its value slots lie. THE place
+// that maps a (kind, net) pair to a layout: a pair without an entry (the tuned net has TunedLayout, no critic-only range) gives P = 0.
+struct PpoDims { int P, VF, PI_HEAD, VF_HEAD; };
+template <int KIND, int NET> PpoDims ppo_dims_of() {
+  using L = PpoLayout<KIND, NET>;
+  return {L::P, L::VF, L::PI_HEAD, L::VF_HEAD};
+}
+PpoDims ppo_dims(int env_kind, int net) {
+  if (net == TB_NET_DEFAULT && env_kind == TB_ENV_SWING) return ppo_dims_of<TB_ENV_SWING, TB_NET_DEFAULT>();
+  if (net == TB_NET_DEFAULT && env_kind == TB_ENV_TENNIS) return ppo_dims_of<TB_ENV_TENNIS, TB_NET_DEFAULT>();
+  if (net == TB_NET_MLP64 && env_kind == TB_ENV_SWING) return ppo_dims_of<TB_ENV_SWING, TB_NET_MLP64>();
+  return {0, 0, 0, 0};
+}
+}  // namespace
+}  // extern "C++"
 int tb_ppo_param_floats_net(int env_kind, int net) {
   if (!kind_ok(env_kind)) return TB_E_INVAL;
   if (int rc = policy_net_ok(env_kind, net, "tb_ppo_param_floats_net")) return rc;
-  return net == TB_NET_TUNED ? TunedLayout::P : tb_ppo_param_floats(env_kind);
+  return net == TB_NET_TUNED ? TunedLayout::P : ppo_dims(env_kind, net).P;
 }
 int tb_ppo_rows_per_workgroup(void) { return TB_PPO_SHARE; }
 
 static size_t ppo_partials(int batch) { return 2 * (((size_t)batch + TB_PPO_SHARE - 1) / TB_PPO_SHARE); }
 static constexpr size_t kPpoStatBytes = sizeof(double) * 2 * TB_PPO_STAT_BLOCKS;
 // floats of one partial vector: the gradient and the two statistics; the tuned net's also hold the vf waves' extractor share
-static size_t ppo_partial_stride(int env_kind, int net) { return net == TB_NET_TUNED ? (size_t)TunedLayout::STRIDE : (size_t)tb_ppo_param_floats(env_kind) + 2; }
+static size_t ppo_partial_stride(int env_kind, int net) { return net == TB_NET_TUNED ? (size_t)TunedLayout::STRIDE : (size_t)tb_ppo_param_floats_net(env_kind, net) + 2; }
 
 long long tb_ppo_workspace_bytes_net(int env_kind, int net, int batch) {
   if (!kind_ok(env_kind) || batch < 2) return fail(TB_E_INVAL, "tb_ppo_workspace_bytes: unknown env kind, or batch < 2");
@@ -1374,7 +1412,7 @@ int tb_ppo_grad_net(int env_kind, int net, int device, void* stream, const float
   if (int rc = policy_net_ok(env_kind, net, "tb_ppo_grad")) return rc;
   if (!obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !returns_dev || !idx_dev || !params_dev || !workspace_dev)
     return fail(TB_E_INVAL, "tb_ppo_grad: null argument");
-  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_ppo_grad: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_ppo_grad: n_params is not tb_ppo_param_floats_net(env_kind, net)");
   if (n_rows < 1 || batch < 2) return fail(TB_E_INVAL, "tb_ppo_grad: n_rows must be >= 1 and batch >= 2 (the unbiased std of one row is undefined)");
   if (misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) || misaligned(returns_dev, 4) ||
       misaligned(params_dev, 4))
@@ -1391,6 +1429,7 @@ int tb_ppo_grad_net(int env_kind, int net, int device, void* stream, const float
   if (int rc = launch(tb_ppo_adv_stats_kernel, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
   const dim3 grid((unsigned)(ppo_partials(batch) / 2));
   if (net == TB_NET_TUNED) return launch(tb_ppo_grad_tuned_kernel, grid, dim3(256), 0, s, a);
+  if (net == TB_NET_MLP64) return launch(tb_ppo_grad_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, a);
   return env_kind == TB_ENV_SWING ? launch(tb_ppo_grad_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a) : launch(tb_ppo_grad_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a);
 }
 
@@ -1411,7 +1450,7 @@ int tb_ppo_apply_net(int env_kind, int net, int device, void* stream, int phases
     return fail(TB_E_INVAL, "tb_ppo_apply: phases must be TB_PPO_REDUCE, TB_PPO_STEP or both, with or without TB_PPO_VALUE_ONLY");
   const int value_only = (phases & TB_PPO_VALUE_ONLY) != 0;
   if (!params_dev || !grad_dev) return fail(TB_E_INVAL, "tb_ppo_apply: null argument");
-  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_ppo_apply: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_ppo_apply: n_params is not tb_ppo_param_floats_net(env_kind, net)");
   if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(stats_dev, 4))
     return fail(TB_E_INVAL, "tb_ppo_apply: a float array is not 4-byte aligned");
   if (phases & TB_PPO_REDUCE) {
@@ -1433,6 +1472,9 @@ int tb_ppo_apply_net(int env_kind, int net, int device, void* stream, int phases
     const dim3 grid((unsigned)((n_params + 2 + 63) / 64));
     if (net == TB_NET_TUNED) {
       if (int rc = launch(tb_ppo_reduce_tuned_kernel, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev)) return rc;
+    } else if (net == TB_NET_MLP64) {
+      if (int rc = launch(tb_ppo_reduce_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only))
+        return rc;
     } else if (int rc = env_kind == TB_ENV_SWING ? launch(tb_ppo_reduce_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only)
                                           : launch(tb_ppo_reduce_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only))
       return rc;
@@ -1441,11 +1483,9 @@ int tb_ppo_apply_net(int env_kind, int net, int device, void* stream, int phases
     const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
     int lo0 = 0, hi0 = n_params, lo1 = 0, hi1 = 0;
     if (value_only) {
-      const bool swing = env_kind == TB_ENV_SWING;
-      lo0 = swing ? PpoLayout<TB_ENV_SWING>::VF : PpoLayout<TB_ENV_TENNIS>::VF;
-      hi0 = swing ? PpoLayout<TB_ENV_SWING>::PI_HEAD : PpoLayout<TB_ENV_TENNIS>::PI_HEAD;
-      lo1 = swing ? PpoLayout<TB_ENV_SWING>::VF_HEAD : PpoLayout<TB_ENV_TENNIS>::VF_HEAD;
-      hi1 = n_params;
+      const PpoDims d = ppo_dims(env_kind, net);
+      if (d.P != n_params) return fail(TB_E_UNSUPPORTED, "tb_ppo_apply: no critic-only slot range for this (kind, net) pair");
+      lo0 = d.VF; hi0 = d.PI_HEAD; lo1 = d.VF_HEAD; hi1 = d.P;
     }
     return launch(tb_ppo_step_kernel, dim3(1), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, (float)world, max_grad_norm, lr,
                   beta1, beta2, eps, c1, c2, lo0, hi0, lo1, hi1);
@@ -1459,27 +1499,39 @@ int tb_trpo_search_rows_per_workgroup(void) { return TB_TRPO_SEARCH_SHARE; }
 
 static size_t trpo_search_shares(int batch) { return ((size_t)batch + TB_TRPO_SEARCH_SHARE - 1) / TB_TRPO_SEARCH_SHARE; }
 
-long long tb_trpo_fvp_workspace_bytes(int env_kind, int n_idx) {
+long long tb_trpo_fvp_workspace_bytes_net(int env_kind, int net, int n_idx) {
   if (!kind_ok(env_kind) || n_idx < 1) return fail(TB_E_INVAL, "tb_trpo_fvp_workspace_bytes: unknown env kind, or n_idx < 1");
-  return (long long)(sizeof(float) * ppo_partials(n_idx) * (size_t)tb_ppo_param_floats(env_kind));
+  if (int rc = trpo_net_ok(env_kind, net, "tb_trpo_fvp_workspace_bytes_net")) return rc;
+  return (long long)(sizeof(float) * ppo_partials(n_idx) * (size_t)tb_ppo_param_floats_net(env_kind, net));
 }
-long long tb_trpo_search_workspace_bytes(int env_kind, int batch, int n_candidates) {
+long long tb_trpo_fvp_workspace_bytes(int env_kind, int n_idx) { return tb_trpo_fvp_workspace_bytes_net(env_kind, TB_NET_DEFAULT, n_idx); }
+long long tb_trpo_search_workspace_bytes_net(int env_kind, int net, int batch, int n_candidates) {
   if (!kind_ok(env_kind) || batch < 2 || n_candidates < 1 || n_candidates > TB_TRPO_MAX_CANDIDATES)
     return fail(TB_E_INVAL, "tb_trpo_search_workspace_bytes: unknown env kind, batch < 2, or n_candidates outside 1 .. 64");
+  if (int rc = trpo_net_ok(env_kind, net, "tb_trpo_search_workspace_bytes_net")) return rc;
   return (long long)(kPpoStatBytes + sizeof(double) * 2 * trpo_search_shares(batch) * (size_t)n_candidates);
+}
+long long tb_trpo_search_workspace_bytes(int env_kind, int batch, int n_candidates) {
+  return tb_trpo_search_workspace_bytes_net(env_kind, TB_NET_DEFAULT, batch, n_candidates);
 }
 
 int tb_trpo_fvp(int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int n_idx, const float* params_dev,
                 const float* vec_dev, int n_params, float damping, float* out_dev, void* workspace_dev, size_t workspace_bytes) {
+  return tb_trpo_fvp_net(env_kind, TB_NET_DEFAULT, device, stream, obs_dev, n_rows, idx_dev, n_idx, params_dev, vec_dev, n_params, damping, out_dev, workspace_dev,
+                         workspace_bytes);
+}
+int tb_trpo_fvp_net(int env_kind, int net, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int n_idx,
+                    const float* params_dev, const float* vec_dev, int n_params, float damping, float* out_dev, void* workspace_dev, size_t workspace_bytes) {
   if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_trpo_fvp: unknown env kind");
+  if (int rc = trpo_net_ok(env_kind, net, "tb_trpo_fvp")) return rc;
   if (!obs_dev || !idx_dev || !params_dev || !vec_dev || !out_dev || !workspace_dev) return fail(TB_E_INVAL, "tb_trpo_fvp: null argument");
-  if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_trpo_fvp: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_trpo_fvp: n_params is not tb_ppo_param_floats_net(env_kind, net)");
   if (n_rows < 1 || n_idx < 1) return fail(TB_E_INVAL, "tb_trpo_fvp: n_rows and n_idx must be >= 1");
   if (misaligned(obs_dev, 4) || misaligned(params_dev, 4) || misaligned(vec_dev, 4) || misaligned(out_dev, 4))
     return fail(TB_E_INVAL, "tb_trpo_fvp: a float array is not 4-byte aligned");
   if (misaligned(idx_dev, 8) || misaligned(workspace_dev, 8)) return fail(TB_E_INVAL, "tb_trpo_fvp: idx and the workspace must be 8-byte aligned");
   if (vec_dev == out_dev) return fail(TB_E_INVAL, "tb_trpo_fvp: out_dev must not be vec_dev");
-  if ((long long)workspace_bytes < tb_trpo_fvp_workspace_bytes(env_kind, n_idx)) return fail(TB_E_INVAL, "tb_trpo_fvp: the workspace is smaller than tb_trpo_fvp_workspace_bytes");
+  if ((long long)workspace_bytes < tb_trpo_fvp_workspace_bytes_net(env_kind, net, n_idx)) return fail(TB_E_INVAL, "tb_trpo_fvp: the workspace is smaller than tb_trpo_fvp_workspace_bytes");
   if (int rc = ppo_device(device, "tb_trpo_fvp: device index out of range")) return rc;
   DeviceGuard g(device);
   if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
@@ -1487,6 +1539,10 @@ int tb_trpo_fvp(int env_kind, int device, void* stream, const float* obs_dev, lo
   const int n_part = (int)ppo_partials(n_idx);
   TrpoFvpArgs a = {obs_dev, (const long long*)idx_dev, params_dev, vec_dev, (float*)workspace_dev, n_rows, n_idx};
   const dim3 grid((unsigned)(n_part / 2)), rgrid((unsigned)((n_params + 63) / 64));
+  if (net == TB_NET_MLP64) {
+    if (int rc = launch(tb_trpo_fvp_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(128), 0, s, a)) return rc;
+    return launch(tb_trpo_fvp_reduce_kernel<TB_ENV_SWING, TB_NET_MLP64>, rgrid, dim3(256), 0, s, (const float*)workspace_dev, n_part, n_idx, vec_dev, damping, out_dev);
+  }
   const bool swing = env_kind == TB_ENV_SWING;
   if (int rc = swing ? launch(tb_trpo_fvp_kernel<TB_ENV_SWING>, grid, dim3(128), 0, s, a) : launch(tb_trpo_fvp_kernel<TB_ENV_TENNIS>, grid, dim3(128), 0, s, a)) return rc;
   return swing ? launch(tb_trpo_fvp_reduce_kernel<TB_ENV_SWING>, rgrid, dim3(256), 0, s, (const float*)workspace_dev, n_part, n_idx, vec_dev, damping, out_dev)
@@ -1496,10 +1552,17 @@ int tb_trpo_fvp(int env_kind, int device, void* stream, const float* obs_dev, lo
 int tb_trpo_search(int env_kind, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev, const float* adv_dev,
                    long long n_rows, const int64_t* idx_dev, int batch, const float* params_dev, const float* direction_dev, int n_params,
                    const float* steps_dev, int n_candidates, double* out_dev, void* workspace_dev, size_t workspace_bytes) {
+  return tb_trpo_search_net(env_kind, TB_NET_DEFAULT, device, stream, obs_dev, raw_actions_dev, old_logp_dev, adv_dev, n_rows, idx_dev, batch, params_dev, direction_dev,
+                            n_params, steps_dev, n_candidates, out_dev, workspace_dev, workspace_bytes);
+}
+int tb_trpo_search_net(int env_kind, int net, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev,
+                       const float* adv_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* params_dev, const float* direction_dev, int n_params,
+                       const float* steps_dev, int n_candidates, double* out_dev, void* workspace_dev, size_t workspace_bytes) {
   if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_trpo_search: unknown env kind");
+  if (int rc = trpo_net_ok(env_kind, net, "tb_trpo_search")) return rc;
   if (!obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !idx_dev || !params_dev || !direction_dev || !steps_dev || !out_dev || !workspace_dev)
     return fail(TB_E_INVAL, "tb_trpo_search: null argument");
-  if (n_params != tb_ppo_param_floats(env_kind)) return fail(TB_E_INVAL, "tb_trpo_search: n_params is not tb_ppo_param_floats(env_kind)");
+  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_trpo_search: n_params is not tb_ppo_param_floats_net(env_kind, net)");
   if (n_rows < 1 || batch < 2) return fail(TB_E_INVAL, "tb_trpo_search: n_rows must be >= 1 and batch >= 2 (the unbiased std of one row is undefined)");
   if (n_candidates < 1 || n_candidates > TB_TRPO_MAX_CANDIDATES) return fail(TB_E_INVAL, "tb_trpo_search: n_candidates must be 1 .. 64");
   if (misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) || misaligned(params_dev, 4) ||
@@ -1507,7 +1570,7 @@ int tb_trpo_search(int env_kind, int device, void* stream, const float* obs_dev,
     return fail(TB_E_INVAL, "tb_trpo_search: a float array is not 4-byte aligned");
   if (misaligned(idx_dev, 8) || misaligned(workspace_dev, 8) || misaligned(out_dev, 8))
     return fail(TB_E_INVAL, "tb_trpo_search: idx, out and the workspace must be 8-byte aligned");
-  if ((long long)workspace_bytes < tb_trpo_search_workspace_bytes(env_kind, batch, n_candidates))
+  if ((long long)workspace_bytes < tb_trpo_search_workspace_bytes_net(env_kind, net, batch, n_candidates))
     return fail(TB_E_INVAL, "tb_trpo_search: the workspace is smaller than tb_trpo_search_workspace_bytes");
   if (int rc = ppo_device(device, "tb_trpo_search: device index out of range")) return rc;
   DeviceGuard g(device);
@@ -1519,7 +1582,9 @@ int tb_trpo_search(int env_kind, int device, void* stream, const float* obs_dev,
   TrpoSearchArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, (const long long*)idx_dev, params_dev, direction_dev, steps_dev, sums, partials, n_rows, batch};
   if (int rc = launch(tb_ppo_adv_stats_kernel, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
   const dim3 grid((unsigned)shares, (unsigned)n_candidates);
-  if (int rc = env_kind == TB_ENV_SWING ? launch(tb_trpo_search_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a) : launch(tb_trpo_search_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a))
+  if (int rc = net == TB_NET_MLP64            ? launch(tb_trpo_search_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, a)
+               : env_kind == TB_ENV_SWING ? launch(tb_trpo_search_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a)
+                                          : launch(tb_trpo_search_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a))
     return rc;
   return launch(tb_trpo_search_reduce_kernel, dim3((unsigned)n_candidates), dim3(256), 0, s, (const double*)partials, shares, batch, out_dev);
 }

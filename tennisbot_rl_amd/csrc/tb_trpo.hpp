@@ -2,7 +2,8 @@
 // ppo_transpose, ppo_tanh / ppo_dtanh, tb_ppo_adv_stats_kernel). Device code only; included by tb_stepper.hip after tb_learner.hpp.
 // The rule is the reference's agent.py (TRPOAgent; cited by line in tennisbot_rl_amd/trpo.py). Policy tower only: the LOG_STD,
 // PI and PI_HEAD slots of the flat parameter vector. Every vector (v, F v, the search direction) is a full flat vector of
-// PpoLayout::P floats; the value slots are ignored on input and written as 0.
+// PpoLayout::P floats; the value slots are ignored on input and written as 0. Instantiated per (kind, net) like the learner's kernels:
+// both kinds' default nets and SwingRacket's [64, 64] (TB_NET_MLP64), which takes the NH == 2 paths of Tennisbot's default net.
 //
 // tb_trpo_fvp_kernel: F v = (1/m) sum_rows J^T diag(sigma^-2) J v over m rows of an index vector, J = d mean / d theta -- the
 // Hessian of KL(old || new) at theta, which agent.py:144-167 obtains by double backprop (second-order and cross terms vanish at
@@ -93,10 +94,10 @@ struct TrpoFvpArgs {
   int m;
 };
 
-template <int KIND>
+template <int KIND, int NET = TB_NET_DEFAULT>
 __global__ __launch_bounds__(128) void tb_trpo_fvp_kernel(const TrpoFvpArgs a) {
-  using L = PpoLayout<KIND>;
-  using N = PolicyNet<KIND>;
+  using L = PpoLayout<KIND, NET>;
+  using N = PolicyNet<KIND, NET>;
   constexpr int O = L::O, NA = L::A, NH = L::NH;
   using L0 = TrpoLayer<O, N::H0, true>;
   using L1 = TrpoLayer<N::H0, N::H1, false>;
@@ -203,9 +204,9 @@ __global__ __launch_bounds__(128) void tb_trpo_fvp_kernel(const TrpoFvpArgs a) {
 // out[p] = (float)(sum of the partials / m) + damping v[p] on the network's policy slots (float64 sum in the fixed order of
 // tb_ppo_reduce_kernel; the two float32 roundings of the damping term are separate: fvp(d) == fvp(0) + fl(d v) bit for bit),
 // 2 v[p] + damping v[p] on log_std (the Gaussian's own Fisher block: exact), 0 on the value slots. 64 parameters per block.
-template <int KIND>
+template <int KIND, int NET = TB_NET_DEFAULT>
 __global__ __launch_bounds__(256) void tb_trpo_fvp_reduce_kernel(const float* partials, int n_part, int m, const float* vec, float damping, float* out) {
-  using L = PpoLayout<KIND>;
+  using L = PpoLayout<KIND, NET>;
   __shared__ double s_sum[4][64];
   const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;
   const bool net = (p >= L::PI && p < L::VF) || (p >= L::PI_HEAD && p < L::VF_HEAD);
@@ -267,10 +268,10 @@ struct TrpoFwd {
 };
 
 // the policy tower's forward pass at theta + step * direction
-template <int KIND>
+template <int KIND, int NET = TB_NET_DEFAULT>
 struct TrpoMean {
-  using L = PpoLayout<KIND>;
-  using N = PolicyNet<KIND>;
+  using L = PpoLayout<KIND, NET>;
+  using N = PolicyNet<KIND, NET>;
   using L0 = TrpoFwd<L::O, N::H0, true>;
   using L1 = TrpoFwd<N::H0, N::H1, false>;
   using L2 = TrpoFwd<N::H1, N::H2, false>;
@@ -316,15 +317,15 @@ struct TrpoSearchArgs {
   int batch;
 };
 
-template <int KIND>
+template <int KIND, int NET = TB_NET_DEFAULT>
 __global__ __launch_bounds__(256) void tb_trpo_search_kernel(const TrpoSearchArgs a) {
-  using L = PpoLayout<KIND>;
+  using L = PpoLayout<KIND, NET>;
   constexpr int O = L::O, NA = L::A;
   __shared__ double s_part[4][2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, e = lane & 15, B = a.batch;
   const int first = blockIdx.x * TB_TRPO_SEARCH_SHARE + wave * (TB_TRPO_SEARCH_SHARE / 4);
   const float step = a.steps[blockIdx.y];
-  TrpoMean<KIND> cur, cand;
+  TrpoMean<KIND, NET> cur, cand;
   cur.load(a.params, a.dir, 0.0f, lane);
   cand.load(a.params, a.dir, step, lane);
   double sx = 0.0, sq = 0.0;
@@ -347,10 +348,10 @@ __global__ __launch_bounds__(256) void tb_trpo_search_kernel(const TrpoSearchArg
     const bool valid = i0 + e < B;
     long long row = a.idx[valid ? i0 + e : B - 1];
     row = row < 0 ? 0 : row >= a.n_rows ? a.n_rows - 1 : row;
-    float x0[TrpoMean<KIND>::L0::NC];
+    float x0[TrpoMean<KIND, NET>::L0::NC];
     const float* orow = a.obs + (size_t)row * O;
 #pragma unroll
-    for (int c = 0; c < TrpoMean<KIND>::L0::NC; ++c) x0[c] = 4 * c + g < O ? orow[4 * c + g] : 0.0f;
+    for (int c = 0; c < TrpoMean<KIND, NET>::L0::NC; ++c) x0[c] = 4 * c + g < O ? orow[4 * c + g] : 0.0f;
     const f32x4 mu = cur.mean(x0), mu2 = cand.mean(x0);
     float lp = 0.0f, kl = 0.0f;
 #pragma unroll

@@ -71,12 +71,13 @@ class _EpisodeEvaluator:
 
 
 class PolicyEvaluator(_EpisodeEvaluator):
-    """n_envs evaluation envs of their own for the fused policy networks (PPO / TRPO; NET_DEFAULT or Tennisbot's NET_TUNED); weights:
+    """n_envs evaluation envs of their own for the fused policy networks (PPO / TRPO; NET_DEFAULT, Tennisbot's NET_TUNED or SwingRacket's NET_MLP64); weights:
     the packed blob of ppo.pack_policy"""
 
     def __init__(self, kind, n_envs=64, seed=0, params=None, options=None, device=None, net=NET_DEFAULT, env_id_base=EVAL_ENV_ID_BASE):
+        from .stepper import check_net
+        self.net = check_net(kind, net)
         super().__init__(kind, n_envs, seed, params, options, device, env_id_base)
-        self.net = int(net)
 
     def _launch(self, packed_weights, deterministic):
         return self.env.policy_evaluate(packed_weights, seed=self.noise_seed, deterministic=deterministic, net=self.net)

@@ -60,7 +60,8 @@ class FusedLearner:
         import torch
         from .ppo import policy_net_of
         self.torch, self.kind, self.policy, self.opt, self.hp = torch, int(kind), policy, opt, hp
-        self.net = policy_net_of(policy)  # NET_TUNED for build_tuned_actor_critic's module: its own gradient kernel, shared-trunk partials
+        # NET_TUNED for build_tuned_actor_critic's module: its own gradient kernel, shared-trunk partials; NET_MLP64 for SwingRacket's [64, 64]
+        self.net = policy_net_of(policy)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise StepperError("FusedLearner needs a GPU (there is no CPU fallback)")

@@ -18,7 +18,9 @@ TB_HULL_REC = 8
 ENV_SWING = 0   # SwingRacket-v0, tennisbot/__init__.py:8-11
 ENV_TENNIS = 1  # Tennisbot-v0,   tennisbot/__init__.py:3-6
 NET_DEFAULT = 0  # include/tb_stepper.h TB_NET_*: the env kind's own policy network ...
-NET_TUNED = 1    # ... and Tennisbot's `train.py -s tuned_ppo` network (ppo.build_tuned_actor_critic)
+NET_TUNED = 1    # ... Tennisbot's `train.py -s tuned_ppo` network (ppo.build_tuned_actor_critic) ...
+NET_MLP64 = 2    # ... and SB3's MlpPolicy default pi = vf = [64, 64] on SwingRacket-v0 (the reference's `train_swing.py -s trpo`, :101-102)
+NET_NAMES = {NET_DEFAULT: "default", NET_TUNED: "tuned", NET_MLP64: "mlp64"}  # PPOTrainer(policy=...), the scripts' --net, checkpoints
 
 F_AUTO_RESET = 0x1
 F_NET = 0x2

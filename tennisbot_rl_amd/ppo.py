@@ -15,13 +15,16 @@ import time
 
 import numpy as np
 
-from .params import ACT_DIM, ENV_SWING, ENV_TENNIS, NET_DEFAULT, NET_TUNED, OBS_DIM
+from .params import ACT_DIM, ENV_SWING, ENV_TENNIS, NET_DEFAULT, NET_MLP64, NET_NAMES, NET_TUNED, OBS_DIM
 from .rollout import RolloutBuffer
 from .stepper import ENV_IDS, BatchedEnv, StepperError
 
 # hyper-parameters of the reference scripts (and SB3 1.8.0 defaults where they are silent)
 SWING_DEFAULTS = dict(net_arch=(32, 64, 32), ent_coef=0.002, learning_rate=3e-4)   # train_swing.py:80-91
 TENNIS_DEFAULTS = dict(net_arch=(64, 64), ent_coef=0.01, learning_rate=3e-4)        # train.py:4-33,104-110
+# SB3's MlpPolicy as `TRPO("MlpPolicy", env)` gets it (train_swing.py:101-102 passes no policy_kwargs): pi = vf = [64, 64], tanh; SB3's
+# on-policy ent_coef default 0. policy="mlp64" (NET_MLP64), SwingRacket-v0 only -- Tennisbot's default network already is this one.
+SB3_SWING_DEFAULTS = dict(net_arch=(64, 64), ent_coef=0.0, learning_rate=3e-4)
 # `train.py -s tuned_ppo` (train.py:112-127): ReLU, a shared features extractor obs -> 64 -> act_dim (train.py:54-67,116-118), pi = vf =
 # [32, 64, 32]; ent_coef is SB3's default 0. The reference also passes n_epochs = int(1e6 / 500) = 2000 (train.py:76-78,126), recorded
 # here as `reference_n_epochs`: PPOTrainer keeps COMMON's 10 unless n_epochs is given -- 2000 epochs over a 4096-env rollout is not a
@@ -159,8 +162,14 @@ def build_tuned_actor_critic(obs_dim, act_dim, net_arch=(32, 64, 32), extractor_
 
 
 def policy_net_of(policy):
-    """NET_TUNED for build_tuned_actor_critic's module, NET_DEFAULT for build_actor_critic's"""
-    return NET_TUNED if hasattr(policy, "features_extractor") else NET_DEFAULT
+    """NET_TUNED for build_tuned_actor_critic's module; for build_actor_critic's NET_MLP64 when it is SwingRacket's [64, 64]
+    (6 inputs: Tennisbot's [64, 64] has 12 and is its NET_DEFAULT), else NET_DEFAULT"""
+    if hasattr(policy, "features_extractor"):
+        return NET_TUNED
+    lin = [m for m in policy.policy_net if hasattr(m, "in_features")]
+    if lin and lin[0].in_features == OBS_DIM[ENV_SWING] and [m.out_features for m in lin] == list(SB3_SWING_DEFAULTS["net_arch"]):
+        return NET_MLP64
+    return NET_DEFAULT
 
 
 def _blob_layers(policy):
@@ -256,19 +265,24 @@ class PPOTrainer:
         self.torch = torch
         if learner not in ("torch", "fused"):
             raise ValueError("learner must be 'torch' or 'fused', not %r" % (learner,))
-        if policy not in ("default", "tuned"):
-            raise ValueError("policy must be 'default' or 'tuned', not %r" % (policy,))
+        if policy not in ("default", "tuned", "mlp64"):
+            raise ValueError("policy must be 'default', 'tuned' or 'mlp64', not %r" % (policy,))
         kind = ENV_IDS[env_id]
         # policy="tuned": the reference's `train.py -s tuned_ppo` network and hyper-parameters (TUNED_TENNIS_DEFAULTS), Tennisbot-v0 only
         tuned = policy == "tuned"
         if tuned and kind != ENV_TENNIS:
             raise ValueError("policy='tuned' is Tennisbot-v0's network (the reference's train.py -s tuned_ppo), not %s's" % env_id)
-        self.net = NET_TUNED if tuned else NET_DEFAULT
-        arch_defaults = TUNED_TENNIS_DEFAULTS if tuned else SWING_DEFAULTS if kind == ENV_SWING else TENNIS_DEFAULTS
+        # policy="mlp64": SB3's default [64, 64] on SwingRacket-v0 (SB3_SWING_DEFAULTS), what the reference's `train_swing.py -s trpo` trains
+        mlp64 = policy == "mlp64"
+        if mlp64 and kind != ENV_SWING:
+            raise ValueError("policy='mlp64' (NET_MLP64) is SwingRacket-v0's; on %s policy='default' (NET_DEFAULT) is that net: pi = vf = [64, 64], tanh" % env_id)
+        arch_defaults = TUNED_TENNIS_DEFAULTS if tuned else SB3_SWING_DEFAULTS if mlp64 else SWING_DEFAULTS if kind == ENV_SWING else TENNIS_DEFAULTS
         d = dict(arch_defaults)
         d.update(COMMON)
         d.update(hp)
         self.hp = d
+        if mlp64 and tuple(d["net_arch"]) != tuple(SB3_SWING_DEFAULTS["net_arch"]):   # the name IS the architecture: nothing else may carry it
+            raise ValueError("policy='mlp64' is net_arch %s; for net_arch %s leave policy='default'" % (tuple(SB3_SWING_DEFAULTS["net_arch"]), tuple(d["net_arch"])))
         dist = torch.distributed
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank() if self.world > 1 else 0
@@ -289,6 +303,10 @@ class PPOTrainer:
             self.policy = build_tuned_actor_critic(OBS_DIM[kind], ACT_DIM[kind], tuple(d["net_arch"]), int(d["extractor_hidden"])).to(self.device)
         else:
             self.policy = build_actor_critic(OBS_DIM[kind], ACT_DIM[kind], tuple(d["net_arch"])).to(self.device)
+        # the net the kernels, the learner and the checkpoint go by: what the MODULE is (policy_net_of), one source for all three. With
+        # policy="default" and net_arch=(64, 64) on SwingRacket-v0 that is NET_MLP64 too (collected unfused, as that combination always was)
+        self.net = policy_net_of(self.policy)
+        assert not (tuned or mlp64) or self.net == (NET_TUNED if tuned else NET_MLP64)
         torch.manual_seed(seed + 1000 * (self.rank + 1))  # ... but rank-local exploration noise
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=d["learning_rate"], eps=1e-5)
         # minibatches of <= 65536 rows. (The reference's batch_size = n_steps = 1100 is its whole 1-env rollout, ONE minibatch per
@@ -326,7 +344,7 @@ class PPOTrainer:
         self._learner = None
         if learner == "fused":
             if not self.fused:
-                raise ValueError("learner='fused' needs the architecture the kernels are instantiated for (fused=True and the env's default net_arch, or policy='tuned' as it is)")
+                raise ValueError("learner='fused' needs the architecture the kernels are instantiated for (fused=True and the env's default net_arch, or policy='tuned' / 'mlp64' as it is)")
             from .learner import FusedLearner
             self._learner = FusedLearner(kind, self.policy, self.opt, self.hp, self.device)
 
@@ -540,10 +558,12 @@ class PPOTrainer:
         train_swing.py:115-117; SURVEY.md section 5 asks for env state as well)"""
         w, d = self.env.get_state_words()
         self.torch.save({"policy": self.policy.state_dict(), "optimizer": self.opt.state_dict(), "num_timesteps": self.num_timesteps,
-                         "env_words": w.cpu(), "env_done": d.cpu(), "hp": self.hp}, path)
+                         "env_words": w.cpu(), "env_done": d.cpu(), "hp": self.hp, "net": NET_NAMES[self.net]}, path)
 
     def load(self, path):
         ck = self.torch.load(path, map_location=self.device, weights_only=True)
+        if ck.get("net", NET_NAMES[self.net]) != NET_NAMES[self.net]:  # (checkpoints from before the field: the state dict's shapes decide)
+            raise ValueError("%s holds a checkpoint of the %r network; this trainer's network is %r" % (path, ck["net"], NET_NAMES[self.net]))
         self.policy.load_state_dict(ck["policy"]); self.opt.load_state_dict(ck["optimizer"])
         self.num_timesteps = int(ck["num_timesteps"])
         self.env.set_state_words(ck["env_words"].to(self.device), ck["env_done"].to(self.device))

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from .params import (ACT_DIM, COUNTER_NAMES, ENV_SWING, ENV_TENNIS, F_AUTO_RESET, N_COUNTERS, NET_DEFAULT, NET_TUNED, OBS_DIM,  # noqa: F401
+from .params import (ACT_DIM, COUNTER_NAMES, ENV_SWING, ENV_TENNIS, F_AUTO_RESET, N_COUNTERS, NET_DEFAULT, NET_MLP64, NET_TUNED, OBS_DIM,  # noqa: F401
                      STATE_ROWS, STATE_WORDS, TbOptions, TbParams, default_params, make_options)
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtb_stepper.so")
@@ -136,6 +136,14 @@ def load_library():
     L.tb_trpo_fvp.restype = i32
     L.tb_trpo_search.argtypes = [i32, i32, vp] + [vp] * 4 + [i64, vp, i32, vp, vp, i32, vp, i32, vp, vp, ctypes.c_size_t]
     L.tb_trpo_search.restype = i32
+    L.tb_trpo_fvp_workspace_bytes_net.argtypes = [i32, i32, i32]
+    L.tb_trpo_fvp_workspace_bytes_net.restype = i64
+    L.tb_trpo_search_workspace_bytes_net.argtypes = [i32, i32, i32, i32]
+    L.tb_trpo_search_workspace_bytes_net.restype = i64
+    L.tb_trpo_fvp_net.argtypes = [i32, i32, i32, vp, vp, i64, vp, i32, vp, vp, i32, f32, vp, vp, ctypes.c_size_t]
+    L.tb_trpo_fvp_net.restype = i32
+    L.tb_trpo_search_net.argtypes = [i32, i32, i32, vp] + [vp] * 4 + [i64, vp, i32, vp, vp, i32, vp, i32, vp, vp, ctypes.c_size_t]
+    L.tb_trpo_search_net.restype = i32
     L.tb_sac_param_floats.argtypes = [i32, i32]
     L.tb_sac_param_floats.restype = i32
     L.tb_sac_rows_per_workgroup.argtypes = []
@@ -229,6 +237,14 @@ SAC_COLLECT_ACTOR, SAC_COLLECT_UNIFORM = 0, 1   # include/tb_stepper.h TB_SAC_CO
 def _check(L, rc, what):
     if rc != 0:
         raise StepperError("%s failed (%d): %s" % (what, rc, L.tb_last_error().decode()))
+
+
+def check_net(kind, net):
+    """the library's refusal of (Tennisbot-v0, NET_MLP64) as a ValueError, before any call: that pair is not a missing kernel but
+    another name for what NET_DEFAULT already is there"""
+    if int(net) == NET_MLP64 and int(kind) == ENV_TENNIS:
+        raise ValueError("NET_MLP64 is SwingRacket-v0's; on Tennisbot-v0 NET_DEFAULT (TB_NET_DEFAULT) is that net: pi = vf = [64, 64], tanh")
+    return int(net)
 
 
 class StepGraph:
@@ -424,8 +440,9 @@ class BatchedEnv:
         self._steps_issued += int(n_steps)
 
     def policy_floats(self, net=NET_DEFAULT):
-        """length of the packed policy blob tb_policy_step expects for this env kind and network (NET_DEFAULT, or Tennisbot's NET_TUNED)"""
-        nf = int(self.L.tb_policy_blob_floats(self.kind, int(net)))
+        """length of the packed policy blob tb_policy_step expects for this env kind and network (NET_DEFAULT, Tennisbot's NET_TUNED,
+        SwingRacket's NET_MLP64)"""
+        nf = int(self.L.tb_policy_blob_floats(self.kind, check_net(self.kind, net)))
         if nf < 0:
             _check(self.L, nf, "tb_policy_blob_floats")
         return nf

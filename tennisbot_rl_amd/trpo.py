@@ -27,17 +27,44 @@ Deviations from agent.py, all of them:
   * The ratio's old log-probability is the rollout's own (as in the PPO learner), and the CG rows are the first 0.1 n entries of
     a device-side torch.randperm instead of numpy's choice.
 
-An update issues no host synchronisation before its single read of the statistics. One rank only, and only the env's default
-net_arch (the kernels are instantiated for it). There is no torch fallback: a refused call raises, as in learner.py.
+An update issues no host synchronisation before its single read of the statistics. One rank only, and only the architectures
+the kernels are instantiated for: the env's default net_arch, or policy="mlp64" (NET_MLP64: SB3's [64, 64] on SwingRacket-v0).
+There is no torch fallback: a refused call raises, as in learner.py.
+
+form="sb3": sb3_contrib's TRPO, what the reference's `train_swing.py -s trpo` runs (train_swing.py:101-102, `TRPO("MlpPolicy", env)`).
+The same six steps on the same kernels with sb3_contrib's constants (SB3_TRPO_DEFAULTS) and its acceptance rule:
+  2'. every row takes part in the Fisher-vector products (cg_state_percent = 1.0: sub_sampling_factor = 1), cg_damping = 0.1.
+  3'. 15 CG iterations.
+  4'. beta = sqrt(2 delta / x^T (F + damping I) x): what step 4 computes already (tb_trpo_fvp adds the damping term).
+  5'. theta_k = theta + beta 0.8^k x, k = 0 .. 9. The first k with finite entries, KL_k < delta and L_k > L_0 is taken, BOTH tests strict;
+      L_0 is the surrogate at theta. It comes out of the search launch itself: a zero step stands in front of the candidates (K + 1
+      <= 64 entries), whose KL is exactly 0.0 by the kernel's construction. select_candidate_sb3 chooses, on the device; a rejected
+      step leaves theta bit-identical.
+  6'. The critic: n_epochs = 10 (n_critic_updates) of Adam at learning_rate 1e-3 on the plain MSE (vf_coef = 1.0), gae_lambda 0.95,
+      gamma 0.99, advantages normalised over the rollout, NO gradient-norm clip: max_grad_norm = inf, with which tb_ppo_apply's clip
+      factor is exactly 1.0f and the gradient keeps its bits (tests/test_gpu_mlp64_learner.py).
+Left to the script: num_envs, n_steps and the critic's minibatch size. sb3_contrib's 2048 steps of ONE env and its 128-row minibatches
+are sized for one env, not for 4096 of them.
+Deviations from sb3_contrib's TRPO.train, all of them:
+  * CG's early exit at a residual below cg_tolerance is the device-side freeze above: the iterations run on, nothing moves.
+  * The ratio's old log-probability is the rollout's own (as in the PPO learner), not a second forward pass of the old policy.
+  * log_std is inside the natural gradient with its exact Fisher block 2 I (sb3_contrib differentiates the KL through it as well).
+  * The critic's minibatches are the script's (above); sb3_contrib's early stop of the critic does not exist, there is none to port.
 """
 from .learner import TB_PPO_REDUCE, TB_PPO_STEP, FusedLearner, flatten_parameters, parameter_offsets
-from .ppo import SWING_DEFAULTS, TENNIS_DEFAULTS, PPOTrainer
+from .ppo import SB3_SWING_DEFAULTS, SWING_DEFAULTS, TENNIS_DEFAULTS, PPOTrainer
 from .params import ENV_SWING
 from .stepper import ENV_IDS, StepperError, _check
 
 TB_PPO_VALUE_ONLY = 4
 TRPO_DEFAULTS = dict(kl_delta=0.01, cg_iterations=10, cg_damping=0.001, cg_tolerance=1e-10, cg_state_percent=0.1,   # agent.py:17-18
                      search_candidates=10, search_decay=1.5)                                                      # agent.py:112-113
+# [3P-recalled] sb3_contrib 1.8.0, TRPO.__init__'s defaults (the package is not installed here: a host that has it corrects them in
+# this one place). search_decay 1.25 = 1 / line_search_shrinking_factor 0.8; cg_state_percent 1.0 = sub_sampling_factor 1;
+# search_candidates = line_search_max_iter; cg_iterations = cg_max_steps; kl_delta = target_kl; n_epochs = n_critic_updates.
+SB3_TRPO_DEFAULTS = dict(kl_delta=0.01, cg_iterations=15, cg_damping=0.1, cg_tolerance=1e-10, cg_state_percent=1.0, search_candidates=10, search_decay=1.25,
+                         n_epochs=10, learning_rate=1e-3, vf_coef=1.0, gae_lambda=0.95, gamma=0.99, max_grad_norm=float("inf"))
+FORMS = ("agent", "sb3")
 
 
 def select_candidate(torch, table, delta):
@@ -50,18 +77,34 @@ def select_candidate(torch, table, delta):
     return torch.where(first < K, first, torch.full_like(first, -1))
 
 
+def select_candidate_sb3(torch, table, delta):
+    """sb3_contrib's rule. table [K + 1, 2] = (L, KL), row 0 the zero step (L_0, 0.0), rows 1 .. K the candidates: the first candidate
+    k (0-based among the candidates) that is finite with KL_k < delta and L_k > L_0 -- both strict -- or -1; a 0-d int64 tensor on
+    the table's device"""
+    K = table.shape[0] - 1
+    L0, L, KL = table[0, 0], table[1:, 0], table[1:, 1]
+    ok = torch.isfinite(L) & torch.isfinite(KL) & (KL < delta) & (L > L0)
+    first = torch.where(ok, torch.arange(K, device=table.device), torch.full((K,), K, device=table.device)).min()
+    return torch.where(first < K, first, torch.full_like(first, -1))
+
+
 class FusedTRPO(FusedLearner):
     """GAE (inherited), the trust-region policy step and the critic's epochs on the device for one policy / optimiser pair"""
 
-    def __init__(self, kind, policy, opt, hp, device):
+    def __init__(self, kind, policy, opt, hp, device, form="agent"):
         if hasattr(policy, "features_extractor"):
             raise ValueError("FusedTRPO needs the env's default net_arch: its kernels are not instantiated for the tuned network")
-        for k, v in TRPO_DEFAULTS.items():        # filled in place: hp stays the caller's dict, as with FusedLearner, so a later
-            hp.setdefault(k, v)                   # change of trainer.hp reaches the learner
+        if form not in FORMS:
+            raise ValueError("form must be 'agent' or 'sb3', not %r" % (form,))
+        self.form = form
+        for k, v in (SB3_TRPO_DEFAULTS if form == "sb3" else TRPO_DEFAULTS).items():  # filled in place: hp stays the caller's dict, as with
+            if k in TRPO_DEFAULTS:                                                    # FusedLearner, so a later change of trainer.hp reaches the learner
+                hp.setdefault(k, v)
         super().__init__(kind, policy, opt, hp, device)
         t = self.torch
-        if not 1 <= int(self.hp["search_candidates"]) <= 64 or int(self.hp["cg_iterations"]) < 1 or not 0.0 < float(self.hp["cg_state_percent"]) <= 1.0:
-            raise ValueError("FusedTRPO: search_candidates 1 .. 64, cg_iterations >= 1 and 0 < cg_state_percent <= 1 expected")
+        self._zero = 1 if form == "sb3" else 0    # entries in front of the candidates: sb3's zero step, whose L is L_0
+        if not 1 <= int(self.hp["search_candidates"]) <= 64 - self._zero or int(self.hp["cg_iterations"]) < 1 or not 0.0 < float(self.hp["cg_state_percent"]) <= 1.0:
+            raise ValueError("FusedTRPO: search_candidates 1 .. 64 (form='sb3': 63, the zero step being one entry), cg_iterations >= 1 and 0 < cg_state_percent <= 1 expected")
         self.mask = t.zeros(self.n_params, dtype=t.float32, device=self.device)   # 1 on theta's slots
         for name, (off, n) in parameter_offsets(policy).items():
             if name == "log_std" or name.startswith("policy_net.") or name.startswith("action_net."):
@@ -69,7 +112,7 @@ class FusedTRPO(FusedLearner):
         z = lambda n, dt=t.float32: t.zeros(n, dtype=dt, device=self.device)  # noqa: E731
         self._g, self._gstats, self._fv, self._fx = z(self.n_params), z(3), z(self.n_params), z(self.n_params)
         K = int(self.hp["search_candidates"])
-        self.table = z((K, 2), t.float64)
+        self.table = z((K + self._zero, 2), t.float64)
         self._decay = t.tensor([float(self.hp["search_decay"]) ** -k for k in range(K)], dtype=t.float64, device=self.device)
         self.report = z(5, t.float64)
         self._fvp_ws = self._search_ws = self._rows = None
@@ -87,8 +130,8 @@ class FusedTRPO(FusedLearner):
         obs, vec = self._float(obs, "obs"), self._float(vec, "vec")
         if out.dtype != self.torch.float32 or out.device != self.flat.device or not out.is_contiguous() or out.numel() != self.n_params or vec.numel() != self.n_params:
             raise ValueError("fvp: vec and out must be contiguous float32 vectors of %d floats on %s" % (self.n_params, self.flat.device))
-        self._fvp_ws = ws = self._grow(self._fvp_ws, self.lib.tb_trpo_fvp_workspace_bytes(self.kind, int(m)), "tb_trpo_fvp_workspace_bytes")
-        _check(self.lib, self.lib.tb_trpo_fvp(self.kind, self._dev(), self._stream(), obs.data_ptr(), int(obs.shape[0]), idx_ptr, int(m), self.flat.data_ptr(),
+        self._fvp_ws = ws = self._grow(self._fvp_ws, self.lib.tb_trpo_fvp_workspace_bytes_net(self.kind, self.net, int(m)), "tb_trpo_fvp_workspace_bytes")
+        _check(self.lib, self.lib.tb_trpo_fvp_net(self.kind, self.net, self._dev(), self._stream(), obs.data_ptr(), int(obs.shape[0]), idx_ptr, int(m), self.flat.data_ptr(),
                                               vec.data_ptr(), self.n_params, float(self.hp["cg_damping"] if damping is None else damping), out.data_ptr(),
                                               ws.data_ptr(), ws.numel() * 8), "tb_trpo_fvp")
         return out
@@ -102,8 +145,8 @@ class FusedTRPO(FusedLearner):
         if direction.numel() != self.n_params:
             raise ValueError("search: the direction must hold %d floats" % self.n_params)
         out = out if out is not None else t.zeros((K, 2), dtype=t.float64, device=self.device)
-        self._search_ws = ws = self._grow(self._search_ws, self.lib.tb_trpo_search_workspace_bytes(self.kind, int(batch), K), "tb_trpo_search_workspace_bytes")
-        _check(self.lib, self.lib.tb_trpo_search(self.kind, self._dev(), self._stream(), obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), int(n_rows),
+        self._search_ws = ws = self._grow(self._search_ws, self.lib.tb_trpo_search_workspace_bytes_net(self.kind, self.net, int(batch), K), "tb_trpo_search_workspace_bytes")
+        _check(self.lib, self.lib.tb_trpo_search_net(self.kind, self.net, self._dev(), self._stream(), obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), int(n_rows),
                                                  idx_ptr, int(batch), self.flat.data_ptr(), direction.data_ptr(), self.n_params, steps.data_ptr(), K, out.data_ptr(),
                                                  ws.data_ptr(), ws.numel() * 8), "tb_trpo_search")
         return out
@@ -115,9 +158,9 @@ class FusedTRPO(FusedLearner):
         obs, act, old_logp, adv, returns = arrays
         ws = self.workspace(batch)
         wb = ws.numel() * 8
-        _check(L, L.tb_ppo_grad(self.kind, dev, s, obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), returns.data_ptr(), n_rows, idx_ptr, batch,
+        _check(L, L.tb_ppo_grad_net(self.kind, self.net, dev, s, obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), returns.data_ptr(), n_rows, idx_ptr, batch,
                                 self.flat.data_ptr(), self.n_params, float("inf"), 0.0, ws.data_ptr(), wb), "tb_ppo_grad")
-        _check(L, L.tb_ppo_apply(self.kind, dev, s, TB_PPO_REDUCE, ws.data_ptr(), wb, batch, self.flat.data_ptr(), self._g.data_ptr(), None, None, self.n_params,
+        _check(L, L.tb_ppo_apply_net(self.kind, self.net, dev, s, TB_PPO_REDUCE, ws.data_ptr(), wb, batch, self.flat.data_ptr(), self._g.data_ptr(), None, None, self.n_params,
                                  self._gstats.data_ptr(), 0.0, 1.0, 1, 0.0, 0.9, 0.999, 1e-5, 1), "tb_ppo_apply")
         return -self._g * self.mask
 
@@ -152,10 +195,12 @@ class FusedTRPO(FusedLearner):
         xFx = xf.double().dot(self.fvp(arrays[0], cg_ptr, m, xf, self._fx).double())
         beta = t.sqrt(2.0 * float(hp["kl_delta"]) / xFx)
         steps = (beta * self._decay).float()
+        if self._zero:                                # form="sb3": the zero step in front, table[0] = (L_0, 0.0)
+            steps = t.cat([t.zeros(1, dtype=t.float32, device=self.device), steps])
         self.search(arrays, n_rows, all_ptr, n_rows, xf, steps, out=self.table)
-        k = select_candidate(t, self.table, float(hp["kl_delta"]))
+        k = (select_candidate_sb3 if self._zero else select_candidate)(t, self.table, float(hp["kl_delta"]))
         accepted = k >= 0
-        kk = k.clamp(min=0).view(1)                   # (gather / index_select: indexing with a 0-d tensor would read it on the host)
+        kk = (k.clamp(min=0) + self._zero).view(1)    # (gather / index_select: indexing with a 0-d tensor would read it on the host)
         moved = self.flat + steps.gather(0, kk) * xf  # the product and the sum rounded separately: what the search kernel evaluated
         self.flat.copy_(t.where(accepted, moved, self.flat))
         row = self.table.index_select(0, kk)[0]
@@ -167,10 +212,10 @@ class FusedTRPO(FusedLearner):
         obs, act, old_logp, adv, returns = arrays
         ws = self.workspace(batch)
         wb = ws.numel() * 8
-        _check(L, L.tb_ppo_grad(self.kind, dev, s, obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), returns.data_ptr(), n_rows, idx_ptr, batch,
+        _check(L, L.tb_ppo_grad_net(self.kind, self.net, dev, s, obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), returns.data_ptr(), n_rows, idx_ptr, batch,
                                 self.flat.data_ptr(), self.n_params, float(hp["clip_range"]), float(hp["vf_coef"]), ws.data_ptr(), wb), "tb_ppo_grad")
         g = self.opt.param_groups[0]
-        _check(L, L.tb_ppo_apply(self.kind, dev, s, TB_PPO_REDUCE | TB_PPO_STEP | TB_PPO_VALUE_ONLY, ws.data_ptr(), wb, batch, self.flat.data_ptr(), self.grad.data_ptr(),
+        _check(L, L.tb_ppo_apply_net(self.kind, self.net, dev, s, TB_PPO_REDUCE | TB_PPO_STEP | TB_PPO_VALUE_ONLY, ws.data_ptr(), wb, batch, self.flat.data_ptr(), self.grad.data_ptr(),
                                  self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.n_params, self.stats.data_ptr(), float(hp["ent_coef"]),
                                  float(hp["max_grad_norm"]), 1, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), int(step)), "tb_ppo_apply")
 
@@ -214,18 +259,28 @@ class FusedTRPO(FusedLearner):
 
 class TRPOTrainer(PPOTrainer):
     """TRPO over a BatchedEnv: PPOTrainer's collect, GAE and critic; the policy moves by FusedTRPO's trust-region step.
-    hp: kl_delta, cg_iterations, cg_damping, cg_state_percent (TRPO_DEFAULTS) beside PPOTrainer's."""
+    hp: kl_delta, cg_iterations, cg_damping, cg_state_percent (TRPO_DEFAULTS) beside PPOTrainer's.
+    form="agent": the reference's agent.py; form="sb3": sb3_contrib's TRPO with SB3_TRPO_DEFAULTS as the preset of every hyper-parameter
+    it names (an explicit keyword wins). policy="mlp64": SB3's [64, 64] on SwingRacket-v0 -- with form="sb3" the reference's
+    `train_swing.py -s trpo`."""
 
-    def __init__(self, env_id="SwingRacket-v0", num_envs=4096, n_steps=104, device=None, seed=0, batch_size=None, **kw):
+    def __init__(self, env_id="SwingRacket-v0", num_envs=4096, n_steps=104, device=None, seed=0, batch_size=None, form="agent", **kw):
         import torch
         dist = torch.distributed
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise ValueError("TRPOTrainer runs on one rank (world size %d): multi-rank TRPO is not provided" % dist.get_world_size())
-        default_arch = tuple((SWING_DEFAULTS if ENV_IDS[env_id] == ENV_SWING else TENNIS_DEFAULTS)["net_arch"])
-        if tuple(kw.get("net_arch", default_arch)) != default_arch or not kw.get("fused", True) or kw.get("policy", "default") != "default":
-            raise ValueError("TRPOTrainer needs the env's default net_arch %s and the fused rollout: its kernels are instantiated for that architecture" % (default_arch,))
+        if form not in FORMS:
+            raise ValueError("form must be 'agent' or 'sb3', not %r" % (form,))
+        mlp64 = kw.get("policy", "default") == "mlp64"   # (on another env than SwingRacket-v0: PPOTrainer's refusal, by name)
+        default_arch = tuple((SB3_SWING_DEFAULTS if mlp64 else SWING_DEFAULTS if ENV_IDS[env_id] == ENV_SWING else TENNIS_DEFAULTS)["net_arch"])
+        if tuple(kw.get("net_arch", default_arch)) != default_arch or not kw.get("fused", True) or kw.get("policy", "default") not in ("default", "mlp64"):
+            raise ValueError("TRPOTrainer needs the env's default net_arch %s (or policy='mlp64' on SwingRacket-v0) and the fused rollout: its kernels are "
+                             "instantiated for those architectures" % (default_arch,))
         if kw.pop("learner", "fused") != "fused":
             raise ValueError("TRPOTrainer has no torch learner")
+        if form == "sb3":
+            kw = dict(SB3_TRPO_DEFAULTS, **kw)
         super().__init__(env_id, num_envs, n_steps, device, seed, batch_size, learner="torch", **kw)
+        self.form = form
         self.hp = dict(TRPO_DEFAULTS, **self.hp)
-        self._learner = FusedTRPO(ENV_IDS[env_id], self.policy, self.opt, self.hp, self.device)
+        self._learner = FusedTRPO(ENV_IDS[env_id], self.policy, self.opt, self.hp, self.device, form=form)

@@ -7,6 +7,10 @@ both sides of every timed region, one warm-up each, then the median of --runs ru
 and optimiser state. Prints one JSON line (and writes it to --out); exits 1 if the fused update is slower than the torch form.
 
     python tools/trpo_rate.py [--env SwingRacket-v0] [--num-envs 4096] [--n-steps 104] [--runs 5] [--out profiles/r10_trpo_rate.json]
+    python tools/trpo_rate.py --net mlp64 --form sb3 --out profiles/r17_trpo_sb3_rate.json   # sb3_contrib's form on SB3's [64, 64] net
+
+--form sb3: both sides run sb3_contrib's update (tennisbot_rl_amd/trpo.py): its constants, and the acceptance KL < delta and L > L_0,
+the torch side measuring L_0 with one more forward pass in front of the search.
 """
 import argparse
 import copy
@@ -73,11 +77,13 @@ def torch_update(torch, tr, adv, returns):
             q.copy_(vec[off:off + q.numel()].view(q.shape))
             off += q.numel()
 
+    sb3 = getattr(tr, "form", "agent") == "sb3"
     with torch.no_grad():
+        L0 = float(surrogate()) if sb3 else 0.0
         for k in range(int(hp["search_candidates"])):
             set_theta(start + step * x)
             kl, L = float(kl_to(all_mean, ls0, obs)), float(surrogate())
-            if kl == kl and L == L and kl <= hp["kl_delta"] and L >= 0:
+            if kl == kl and L == L and abs(kl) != float("inf") and abs(L) != float("inf") and ((kl < hp["kl_delta"] and L > L0) if sb3 else (kl <= hp["kl_delta"] and L >= 0)):
                 accepted = k
                 break
             step /= hp["search_decay"]
@@ -103,13 +109,15 @@ def main():
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--n-steps", type=int, default=104)
     ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--net", default="default", choices=["default", "mlp64"], help="mlp64: SB3's [64, 64] on SwingRacket-v0")
+    ap.add_argument("--form", default="agent", choices=["agent", "sb3"], help="the update both sides run: agent.py's or sb3_contrib's")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs < 5:
         ap.error("--runs must be at least 5 (a median of fewer says little)")
     import torch
     from tennisbot_rl_amd.trpo import TRPOTrainer
-    tr = TRPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device="cuda:0", seed=0)
+    tr = TRPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device="cuda:0", seed=0, policy=args.net, form=args.form)
     tr.collect()
     adv, returns = tr.advantages(tr.last_value)
     torch.cuda.synchronize()
@@ -130,7 +138,7 @@ def main():
             s, stats[name] = run(fn)
             if k:
                 times[name].append(s)
-    out = {"tool": "trpo_rate", "env": args.env, "num_envs": args.num_envs, "n_steps": args.n_steps, "rows": args.num_envs * args.n_steps,
+    out = {"tool": "trpo_rate", "env": args.env, "num_envs": args.num_envs, "n_steps": args.n_steps, "net": args.net, "form": args.form, "rows": args.num_envs * args.n_steps,
            "cg_rows": int(tr.hp["cg_state_percent"] * args.num_envs * args.n_steps), "batch_size": tr.batch_size, "n_epochs": tr.hp["n_epochs"], "runs": args.runs,
            "device": torch.cuda.get_device_name(0)}
     for name in ("torch", "fused"):

@@ -5,6 +5,7 @@ report how it does) on the batched MI355X envs -- headless only, many episodes a
   python validate_swing.py -m model/ppo_SwingRacket-v0.pt            # a checkpoint of train_swing.py
   python validate_swing.py --reference-policy                        # the reference's shipped ppo_swing weights
   python validate_swing.py --env Tennisbot-v0 -m model/ppo_Tennisbot-v0.pt --steps 1000
+  python validate_swing.py --net mlp64 -m model/trpo_SwingRacket-v0.pt  # a checkpoint of train_swing.py -s trpo --trpo-form sb3 --net mlp64
 
 Like `model.predict(ob)` in validate_swing.py:35 the policy acts stochastically unless --deterministic.
 """
@@ -22,6 +23,7 @@ def main():
     ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
     ap.add_argument("-m", "--model_file", type=str, default="", help="checkpoint written by train_swing.py --save")
     ap.add_argument("--reference-policy", action="store_true", help="tests/golden/ppo_swing_policy.npz (exported from backup_models/ppo_swing.zip)")
+    ap.add_argument("--net", default="default", choices=["default", "mlp64"], help="the network the checkpoint holds (train_swing.py --net); mlp64: SwingRacket-v0 only")
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=104, help="agent steps per env (4 SwingRacket episodes)")
     ap.add_argument("--deterministic", action="store_true")
@@ -33,7 +35,7 @@ def main():
     import torch
     from tennisbot_rl_amd.ppo import PPOTrainer, pack_policy
 
-    tr = PPOTrainer(args.env, num_envs=args.num_envs, n_steps=26, device="cuda:0", seed=args.seed, graph=False)
+    tr = PPOTrainer(args.env, num_envs=args.num_envs, n_steps=26, device="cuda:0", seed=args.seed, graph=False, policy=args.net)
     if args.reference_policy:
         tr.policy.load_sb3_arrays(dict(np.load(os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz"))))
     elif args.model_file:
@@ -45,7 +47,7 @@ def main():
     ret = torch.zeros(args.num_envs, device=env.device)
     finished, total = [], 0
     for t in range(args.steps):
-        (obs, rew, done), _ = env.policy_step(blob, obs, seed=args.seed + 1, deterministic=args.deterministic)
+        (obs, rew, done), _ = env.policy_step(blob, obs, seed=args.seed + 1, deterministic=args.deterministic, net=tr.net)
         env.flush()
         ret += rew
         d = done.bool()

@@ -4,6 +4,7 @@
   python train_swing.py                      # PPO on SwingRacket-v0, 4096 envs on cuda:0
   python train_swing.py --env Tennisbot-v0 --curri
   torchrun --nproc-per-node 8 train_swing.py # one process per GPU, sharded envs
+  python train_swing.py -s trpo --trpo-form sb3 --net mlp64   # the reference's `-s trpo`: sb3_contrib's TRPO on SB3's [64, 64] net
 
 Hyper-parameters follow train_swing.py:46-50,80-91 (net_arch pi=vf=[32,64,32], ent_coef 0.002,
 total_timesteps 2e6) and train.py:76-80,104-110 (Tennisbot: 64-64, ent_coef 0.01, 1e6); the
@@ -30,7 +31,18 @@ def racket_scale_for(progress_percent):
     return 1.0
 
 
-def main():
+TRPO_FLAGS = ("kl_delta", "cg_iterations", "cg_damping", "cg_state_percent")
+
+
+def trpo_keywords(args):
+    """TRPOTrainer's keywords from the command line: the form, the net, and of the four trust-region flags only those given explicitly --
+    the others are left to the form's preset (trpo.TRPO_DEFAULTS / trpo.SB3_TRPO_DEFAULTS), so a flag always wins over it"""
+    kw = dict(form=args.trpo_form, policy=args.net)
+    kw.update({k: getattr(args, k) for k in TRPO_FLAGS if getattr(args, k) is not None})
+    return kw
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
     ap.add_argument("--num-envs", type=int, default=4096)
@@ -42,27 +54,41 @@ def main():
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
     ap.add_argument("--gui", action="store_true", help="accepted for CLI compatibility; there is no GUI")
     ap.add_argument("-s", "--select", default="ppo", help="ppo or trpo (train_swing.py:102; tennisbot_rl_amd/trpo.py); sac and tqc have their own scripts, train_sac.py and train_tqc.py")
-    ap.add_argument("--kl-delta", type=float, default=0.01, help="trpo: the trust region's KL bound (agent.py:17)")
-    ap.add_argument("--cg-iterations", type=int, default=10, help="trpo: conjugate-gradient iterations")
-    ap.add_argument("--cg-damping", type=float, default=0.001, help="trpo: damping added to the Fisher-vector product")
-    ap.add_argument("--cg-state-percent", type=float, default=0.1, help="trpo: share of the rollout's rows the Fisher-vector products run over")
+    ap.add_argument("--trpo-form", default="agent", choices=["agent", "sb3"],
+                    help="trpo: agent = the reference's agent.py (TRPOAgent); sb3 = sb3_contrib's TRPO, what the reference's train_swing.py -s trpo runs (tennisbot_rl_amd/trpo.py)")
+    ap.add_argument("--net", default="default", choices=["default", "mlp64"],
+                    help="mlp64: SB3's MlpPolicy default pi = vf = [64, 64] on SwingRacket-v0 (on Tennisbot-v0 the default net is that one)")
+    ap.add_argument("--kl-delta", type=float, default=None, help="trpo: the trust region's KL bound (default 0.01, agent.py:17; sb3: 0.01)")
+    ap.add_argument("--cg-iterations", type=int, default=None, help="trpo: conjugate-gradient iterations (default 10; sb3: 15)")
+    ap.add_argument("--cg-damping", type=float, default=None, help="trpo: damping added to the Fisher-vector product (default 0.001; sb3: 0.1)")
+    ap.add_argument("--cg-state-percent", type=float, default=None, help="trpo: share of the rollout's rows the Fisher-vector products run over (default 0.1; sb3: 1.0)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (court.urdf:19-24; TB_F_RACKET_GROUND, opt-in: DESIGN.md section 3)")
     ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact (rollingFriction=.001 in racket.py:43-45, objects.py:29-31,48-50)")
     ap.add_argument("--no-fused", action="store_true", help="run the policy as torch modules between env steps instead of inside the step kernel")
     ap.add_argument("--learner", default=None, choices=["torch", "fused"], help="ppo (default torch): fused = GAE, minibatch gradient and Adam as HIP kernels (tennisbot_rl_amd/learner.py); trpo has the fused learner only")
     ap.add_argument("--log-json", type=str, default=None)
-    from tennisbot_rl_amd.evaluation import add_schedule_arguments, resolve_load, schedule_from_args
+    from tennisbot_rl_amd.evaluation import add_schedule_arguments
     add_schedule_arguments(ap)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.select not in ("ppo", "trpo"):
         sys.exit("only -s ppo and -s trpo are implemented on the batched envs by this script. SAC: train_sac.py; TQC: train_tqc.py")
     if args.select == "trpo" and args.learner == "torch":
         sys.exit("-s trpo has no torch learner: its update runs as HIP kernels (leave --learner out, or --learner fused)")
     if args.select == "trpo" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("-s trpo runs on one rank: multi-rank TRPO is not provided")
+    if args.select != "trpo" and args.trpo_form != "agent":
+        sys.exit("--trpo-form belongs to -s trpo")
+    if args.net == "mlp64" and args.env != "SwingRacket-v0":
+        sys.exit("--net mlp64 is SwingRacket-v0's: on Tennisbot-v0 the default net already is SB3's [64, 64]")
     if args.save is None:
         args.save = "./model/%s_%%s.pt" % args.select
+    return args
+
+
+def main():
+    from tennisbot_rl_amd.evaluation import resolve_load, schedule_from_args
+    args = parse_args()
 
     import torch
     from tennisbot_rl_amd.ppo import PPOTrainer
@@ -81,10 +107,10 @@ def main():
     if args.select == "trpo":
         from tennisbot_rl_amd.trpo import TRPOTrainer
         tr = TRPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed, fused=not args.no_fused,
-                         params=params, kl_delta=args.kl_delta, cg_iterations=args.cg_iterations, cg_damping=args.cg_damping, cg_state_percent=args.cg_state_percent)
+                         params=params, **trpo_keywords(args))
     else:
         tr = PPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed,
-                        fused=not args.no_fused, params=params, learner=args.learner or "torch")
+                        fused=not args.no_fused, params=params, learner=args.learner or "torch", policy=args.net)
     if args.load_reference:
         import numpy as np
         tr.policy.load_sb3_arrays(dict(np.load(os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz"))))

@@ -603,6 +603,20 @@ int tb_trpo_search_net(int env_kind, int net, int device, void *stream, const fl
                        const float *old_logp_dev, const float *adv_dev, long long n_rows, const int64_t *idx_dev, int batch,
                        const float *params_dev, const float *direction_dev, int n_params, const float *steps_dev, int n_candidates,
                        double *out_dev, void *workspace_dev, size_t workspace_bytes);
+/*
+ * tb_trpo_returns: agent.py's critic-free estimator (agent.py:193-230, 264-268), the discounted return-to-go of the episodes that
+ * ended inside the rollout. rewards / dones are [T][n] with tb_ppo_gae's step strides (0 = contiguous) and its refusals. With L_e the
+ * last step of env e whose done != 0 (-1: none), row (t, e) -- flat index t n + e -- is FINISHED iff t <= L_e. On finished rows
+ * R[t] = r[t] where done[t], else r[t] + discount R[t + 1]: carried in float64, the product and the sum rounded separately, rounded
+ * to float32 once at the store (a plain numpy float64 loop gives the same bits). Unfinished rows hold 0.0f. returns is contiguous
+ * [T][n]; idx[0 .. *count) holds the flat indices of the finished rows in ascending order, entries from *count on are not written
+ * (idx needs room for T n entries); count is ONE int64 on the device. Four launches, no atomics: the same inputs give the same
+ * bits. Workspace: tb_trpo_returns_workspace_bytes(n_steps, n_envs), 8-byte aligned. The network plays no part.
+ */
+long long tb_trpo_returns_workspace_bytes(int n_steps, int n_envs);
+int tb_trpo_returns(int env_kind, int device, void *stream, int n_steps, int n_envs, const float *rewards_dev,
+                    size_t reward_step_stride_bytes, const uint8_t *dones_dev, size_t done_step_stride_bytes, double discount,
+                    float *returns_dev, int64_t *idx_dev, int64_t *count_dev, void *workspace_dev, size_t workspace_bytes);
 
 /*
  * The SAC learner (csrc/tb_sac.hpp; tennisbot_rl_amd/sac.py is the caller): SB3 1.8.0's SAC with MlpPolicy, [256, 256] ReLU nets,

@@ -1589,6 +1589,50 @@ int tb_trpo_search_net(int env_kind, int net, int device, void* stream, const fl
   return launch(tb_trpo_search_reduce_kernel, dim3((unsigned)n_candidates), dim3(256), 0, s, (const double*)partials, shares, batch, out_dev);
 }
 
+// the workspace of tb_trpo_returns: the [T][chunks] table of counts / offsets (int64), then L_e (int32 [n])
+static long long trpo_return_chunks(int n_envs) { return ((long long)n_envs + 63) / 64; }
+long long tb_trpo_returns_workspace_bytes(int n_steps, int n_envs) {
+  if (n_steps < 1 || n_envs < 1) return fail(TB_E_INVAL, "tb_trpo_returns_workspace_bytes: n_steps and n_envs must be >= 1");
+  return 8 * (long long)n_steps * trpo_return_chunks(n_envs) + 8 * (((long long)n_envs + 1) / 2);
+}
+
+int tb_trpo_returns(int env_kind, int device, void* stream, int n_steps, int n_envs, const float* rewards_dev, size_t reward_step_stride_bytes,
+                    const uint8_t* dones_dev, size_t done_step_stride_bytes, double discount, float* returns_dev, int64_t* idx_dev, int64_t* count_dev,
+                    void* workspace_dev, size_t workspace_bytes) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_trpo_returns: unknown env kind");
+  if (!rewards_dev || !dones_dev || !returns_dev || !idx_dev || !count_dev || !workspace_dev) return fail(TB_E_INVAL, "tb_trpo_returns: null argument");
+  if (n_steps < 1 || n_envs < 1) return fail(TB_E_INVAL, "tb_trpo_returns: n_steps and n_envs must be >= 1");
+  if (misaligned(rewards_dev, 4) || misaligned(returns_dev, 4)) return fail(TB_E_INVAL, "tb_trpo_returns: a float array is not 4-byte aligned");
+  if (misaligned(idx_dev, 8) || misaligned(count_dev, 8) || misaligned(workspace_dev, 8))
+    return fail(TB_E_INVAL, "tb_trpo_returns: idx, count and the workspace must be 8-byte aligned");
+  size_t rs = (size_t)n_envs, ds = (size_t)n_envs;
+  if (reward_step_stride_bytes) {
+    if (reward_step_stride_bytes % sizeof(float) || reward_step_stride_bytes < sizeof(float) * (size_t)n_envs)
+      return fail(TB_E_INVAL, "tb_trpo_returns: the rewards' step stride must be a multiple of 4 bytes and hold n_envs floats");
+    rs = reward_step_stride_bytes / sizeof(float);
+  }
+  if (done_step_stride_bytes) {
+    if (done_step_stride_bytes < (size_t)n_envs) return fail(TB_E_INVAL, "tb_trpo_returns: the dones' step stride is shorter than n_envs bytes");
+    ds = done_step_stride_bytes;
+  }
+  if ((long long)n_steps * trpo_return_chunks(n_envs) > 0x7fffffffLL) return fail(TB_E_INVAL, "tb_trpo_returns: n_steps * ceil(n_envs / 64) must be below 2^31");
+  if ((long long)workspace_bytes < tb_trpo_returns_workspace_bytes(n_steps, n_envs))
+    return fail(TB_E_INVAL, "tb_trpo_returns: the workspace is smaller than tb_trpo_returns_workspace_bytes");
+  if (int rc = ppo_device(device, "tb_trpo_returns: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = (int)trpo_return_chunks(n_envs);
+  const long long entries = (long long)n_steps * chunks;
+  long long* table = (long long*)workspace_dev;
+  int* last = (int*)(table + entries);
+  const dim3 waves((unsigned)((entries + 3) / 4));
+  if (int rc = launch(tb_trpo_returns_kernel, dim3((unsigned)chunks), dim3(64), 0, s, n_steps, n_envs, rewards_dev, rs, dones_dev, ds, discount, returns_dev, last)) return rc;
+  if (int rc = launch(tb_trpo_finished_count_kernel, waves, dim3(256), 0, s, n_steps, n_envs, chunks, (const int*)last, table)) return rc;
+  if (int rc = launch(tb_trpo_finished_scan_kernel, dim3(1), dim3(1024), 0, s, entries, table, (long long*)count_dev)) return rc;
+  return launch(tb_trpo_finished_scatter_kernel, waves, dim3(256), 0, s, n_steps, n_envs, chunks, (const int*)last, (const long long*)table, (long long*)idx_dev);
+}
+
 // --------------------------------------------------------------------------------------------- the SAC and TQC learners (tb_sac.hpp, tb_tqc.hpp)
 // Every stage is written once, as a template over an algorithm descriptor (SacAlgo, TqcAlgo); the C entry points forward to it.
 extern "C++" {

@@ -144,6 +144,10 @@ def load_library():
     L.tb_trpo_fvp_net.restype = i32
     L.tb_trpo_search_net.argtypes = [i32, i32, i32, vp] + [vp] * 4 + [i64, vp, i32, vp, vp, i32, vp, i32, vp, vp, ctypes.c_size_t]
     L.tb_trpo_search_net.restype = i32
+    L.tb_trpo_returns_workspace_bytes.argtypes = [i32, i32]
+    L.tb_trpo_returns_workspace_bytes.restype = i64
+    L.tb_trpo_returns.argtypes = [i32, i32, vp, i32, i32, vp, ctypes.c_size_t, vp, ctypes.c_size_t, f64, vp, vp, vp, vp, ctypes.c_size_t]
+    L.tb_trpo_returns.restype = i32
     L.tb_sac_param_floats.argtypes = [i32, i32]
     L.tb_sac_param_floats.restype = i32
     L.tb_sac_rows_per_workgroup.argtypes = []

@@ -11,6 +11,11 @@ and optimiser state. Prints one JSON line (and writes it to --out); exits 1 if t
 
 --form sb3: both sides run sb3_contrib's update (tennisbot_rl_amd/trpo.py): its constants, and the acceptance KL < delta and L > L_0,
 the torch side measuring L_0 with one more forward pass in front of the search.
+
+    python tools/trpo_rate.py --form agent_returns --out profiles/r18_trpo_returns_rate.json
+
+--form agent_returns: no torch side. One update of the critic-free form beside one of form="agent", both fused, alternating in one
+process, and one tb_trpo_returns call beside one tb_ppo_gae call at the same shape (returns_rate). No pass/fail threshold: exits 0.
 """
 import argparse
 import copy
@@ -103,6 +108,63 @@ def torch_update(torch, tr, adv, returns):
     return {"accepted_k": accepted, "value_loss": float(loss.detach()) / hp["vf_coef"]}
 
 
+def returns_rate(args):
+    """--form agent_returns: one update of form="agent_returns" (no critic) beside one of form="agent" (GAE, the critic's epochs), each
+    on its own trainer's collected rollout at the same shape, alternating in this one process; and the estimators alone, one
+    tb_trpo_returns call beside one tb_ppo_gae call (20 calls each, alternating, a synchronisation on both sides). Medians; no
+    threshold: the two updates do different work, the figures are what each costs."""
+    import torch
+    from tennisbot_rl_amd.trpo import TRPOTrainer
+    kw = dict(num_envs=args.num_envs, n_steps=args.n_steps, device="cuda:0", seed=0, policy=args.net)
+    trainers = {"agent": TRPOTrainer(args.env, form="agent", **kw), "agent_returns": TRPOTrainer(args.env, form="agent_returns", **kw)}
+    inputs, start = {}, {}
+    for name, tr in trainers.items():
+        tr.collect()
+        inputs[name] = tr.advantages(tr.last_value)
+        start[name] = copy.deepcopy(tr.policy.state_dict()), copy.deepcopy(tr.opt.state_dict())
+    torch.cuda.synchronize()
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        result = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, result
+
+    times, stats = {name: [] for name in trainers}, {}
+    for k in range(args.runs + 1):            # run 0 of each is the warm-up
+        for name, tr in trainers.items():
+            tr.policy.load_state_dict(start[name][0]); tr.opt.load_state_dict(copy.deepcopy(start[name][1]))
+            s, stats[name] = timed(lambda: tr.update(*inputs[name]))
+            if k:
+                times[name].append(s)
+    estimator = {name: [] for name in trainers}
+    for k in range(21):
+        for name, tr in trainers.items():
+            s, _ = timed(lambda: tr.advantages(tr.last_value))
+            if k:
+                estimator[name].append(s)
+    rows = args.num_envs * args.n_steps
+    out = {"tool": "trpo_rate", "env": args.env, "num_envs": args.num_envs, "n_steps": args.n_steps, "net": args.net, "form": "agent_returns", "rows": rows,
+           "finished_rows": stats["agent_returns"]["finished_rows"], "finished_share": stats["agent_returns"]["finished_share"], "runs": args.runs,
+           "agent_batch_size": trainers["agent"].batch_size, "agent_n_epochs": trainers["agent"].hp["n_epochs"], "device": torch.cuda.get_device_name(0)}
+    for name in trainers:
+        out[name + "_update_s"] = statistics.median(times[name])
+        out[name + "_runs_s"] = [round(s, 6) for s in times[name]]
+        out[name + "_last_stats"] = {k: v for k, v in stats[name].items() if v == v}   # (the critic-free form's value_loss is NaN: left out)
+    out["tb_trpo_returns_call_s"] = statistics.median(estimator["agent_returns"])
+    out["tb_ppo_gae_call_s"] = statistics.median(estimator["agent"])
+    out["estimator_calls"] = 20
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    for tr in trainers.values():
+        tr.env.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
@@ -110,11 +172,14 @@ def main():
     ap.add_argument("--n-steps", type=int, default=104)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--net", default="default", choices=["default", "mlp64"], help="mlp64: SB3's [64, 64] on SwingRacket-v0")
-    ap.add_argument("--form", default="agent", choices=["agent", "sb3"], help="the update both sides run: agent.py's or sb3_contrib's")
+    ap.add_argument("--form", default="agent", choices=["agent", "sb3", "agent_returns"],
+                    help="the update both sides run: agent.py's or sb3_contrib's; agent_returns: the critic-free form beside form=agent, both fused, no threshold")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs < 5:
         ap.error("--runs must be at least 5 (a median of fewer says little)")
+    if args.form == "agent_returns":
+        return returns_rate(args)
     import torch
     from tennisbot_rl_amd.trpo import TRPOTrainer
     tr = TRPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device="cuda:0", seed=0, policy=args.net, form=args.form)

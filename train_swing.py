@@ -5,6 +5,7 @@
   python train_swing.py --env Tennisbot-v0 --curri
   torchrun --nproc-per-node 8 train_swing.py # one process per GPU, sharded envs
   python train_swing.py -s trpo --trpo-form sb3 --net mlp64   # the reference's `-s trpo`: sb3_contrib's TRPO on SB3's [64, 64] net
+  python train_swing.py -s trpo --trpo-form agent_returns     # agent.py's own estimator: discounted returns of finished episodes, no critic
 
 Hyper-parameters follow train_swing.py:46-50,80-91 (net_arch pi=vf=[32,64,32], ent_coef 0.002,
 total_timesteps 2e6) and train.py:76-80,104-110 (Tennisbot: 64-64, ent_coef 0.01, 1e6); the
@@ -31,12 +32,12 @@ def racket_scale_for(progress_percent):
     return 1.0
 
 
-TRPO_FLAGS = ("kl_delta", "cg_iterations", "cg_damping", "cg_state_percent")
+TRPO_FLAGS = ("kl_delta", "cg_iterations", "cg_damping", "cg_state_percent", "discount", "log_std_step", "step_rows")
 
 
 def trpo_keywords(args):
-    """TRPOTrainer's keywords from the command line: the form, the net, and of the four trust-region flags only those given explicitly --
-    the others are left to the form's preset (trpo.TRPO_DEFAULTS / trpo.SB3_TRPO_DEFAULTS), so a flag always wins over it"""
+    """TRPOTrainer's keywords from the command line: the form, the net, and of the trust-region flags only those given explicitly --
+    the others are left to the form's preset (trpo.TRPO_DEFAULTS / trpo.SB3_TRPO_DEFAULTS / trpo.AGENT_PY_DEFAULTS), so a flag always wins over it"""
     kw = dict(form=args.trpo_form, policy=args.net)
     kw.update({k: getattr(args, k) for k in TRPO_FLAGS if getattr(args, k) is not None})
     return kw
@@ -54,14 +55,20 @@ def parse_args(argv=None):
     ap.add_argument("--curri", action="store_true", help="curriculum learning: size change of racket (Tennisbot-v0)")
     ap.add_argument("--gui", action="store_true", help="accepted for CLI compatibility; there is no GUI")
     ap.add_argument("-s", "--select", default="ppo", help="ppo or trpo (train_swing.py:102; tennisbot_rl_amd/trpo.py); sac and tqc have their own scripts, train_sac.py and train_tqc.py")
-    ap.add_argument("--trpo-form", default="agent", choices=["agent", "sb3"],
-                    help="trpo: agent = the reference's agent.py (TRPOAgent); sb3 = sb3_contrib's TRPO, what the reference's train_swing.py -s trpo runs (tennisbot_rl_amd/trpo.py)")
+    ap.add_argument("--trpo-form", default="agent", choices=["agent", "sb3", "agent_returns"],
+                    help="trpo: agent = the reference's agent.py (TRPOAgent) with GAE and a critic; sb3 = sb3_contrib's TRPO, what the reference's train_swing.py -s trpo runs; "
+                         "agent_returns = agent.py's own estimator, discounted returns of finished episodes and no critic (tennisbot_rl_amd/trpo.py)")
     ap.add_argument("--net", default="default", choices=["default", "mlp64"],
                     help="mlp64: SB3's MlpPolicy default pi = vf = [64, 64] on SwingRacket-v0 (on Tennisbot-v0 the default net is that one)")
     ap.add_argument("--kl-delta", type=float, default=None, help="trpo: the trust region's KL bound (default 0.01, agent.py:17; sb3: 0.01)")
     ap.add_argument("--cg-iterations", type=int, default=None, help="trpo: conjugate-gradient iterations (default 10; sb3: 15)")
     ap.add_argument("--cg-damping", type=float, default=None, help="trpo: damping added to the Fisher-vector product (default 0.001; sb3: 0.1)")
     ap.add_argument("--cg-state-percent", type=float, default=None, help="trpo: share of the rollout's rows the Fisher-vector products run over (default 0.1; sb3: 1.0)")
+    ap.add_argument("--discount", type=float, default=None, help="trpo, agent_returns: the returns' discount (default 0.98, agent.py:17)")
+    ap.add_argument("--log-std-step", default=None, choices=["natural", "raw"],
+                    help="trpo: natural = log_std inside the natural gradient; raw = moved by the surrogate's raw gradient, agent.py:120,136 (default natural; agent_returns: raw)")
+    ap.add_argument("--step-rows", default=None, choices=["cg", "all"],
+                    help="trpo: the rows of the x^T F x behind the step size: the CG rows, or all rows as agent.py:110-111 (default cg; agent_returns: all)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--racket-ground", action="store_true", help="also simulate racket<->court contact (court.urdf:19-24; TB_F_RACKET_GROUND, opt-in: DESIGN.md section 3)")
     ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact (rollingFriction=.001 in racket.py:43-45, objects.py:29-31,48-50)")
@@ -79,6 +86,10 @@ def parse_args(argv=None):
         sys.exit("-s trpo runs on one rank: multi-rank TRPO is not provided")
     if args.select != "trpo" and args.trpo_form != "agent":
         sys.exit("--trpo-form belongs to -s trpo")
+    if args.select != "trpo" and (args.discount is not None or args.log_std_step or args.step_rows):
+        sys.exit("--discount, --log-std-step and --step-rows belong to -s trpo")
+    if args.discount is not None and args.trpo_form != "agent_returns":
+        sys.exit("--discount belongs to --trpo-form agent_returns (the other forms discount with PPO's gamma)")
     if args.net == "mlp64" and args.env != "SwingRacket-v0":
         sys.exit("--net mlp64 is SwingRacket-v0's: on Tennisbot-v0 the default net already is SB3's [64, 64]")
     if args.save is None:

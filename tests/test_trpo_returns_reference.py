@@ -3,6 +3,9 @@ needs no GPU:
 
   * the float64 reference (returns, finished-row mask, index list) against agent.py's per-episode loop (agent.py:253-279, 264-268) run
     env by env over ragged synthetic episodes: the same rows, the same bits;
+  * the restatement of the four launches (kernel_reference, compact_by_table) against that definition, past one scan pass too; the
+    value fixtures hold what they are named for and agree with agent.py's loop where they are finite; each of the seven mutants
+    (a kernel that is subtly wrong) is rejected by the fixture named for it in tests/test_gpu_trpo_returns_edges.py;
   * the host side of the C ABI: the symbols, the workspace query, every refusal (tb_ppo_gae's conventions);
   * AGENT_PY_DEFAULTS is the list of the issue, cited to agent.py; an explicit keyword and a command-line flag beat it;
   * the raw log_std direction and the skip rule on hand-made inputs;
@@ -68,6 +71,169 @@ def test_the_discount_is_a_parameter_and_the_rounding_is_single():
     _, mask, _ = rr.returns_reference(rewards, dones)
     assert not np.array_equal(np.where(mask, R32, 0).astype(np.float32), a.astype(np.float32))
     assert np.allclose(one[0, 1], rewards[:, 1].astype(np.float64).sum(), rtol=1e-12)
+
+
+# --------------------------------------------------------------------------------- the launches restated, the fixtures, the mutants
+SCAN_SHAPES = [(1025, 1), (2048, 1), (33, 2000), (17, 4097)]     # tests/test_gpu_trpo_returns_edges.py: past one scan pass of 1024 entries
+OLD_SHAPES = [(1, 1), (2, 63), (27, 64), (27, 65), (53, 130), (3, 4097)]   # tests/test_gpu_trpo_returns.py
+
+
+def u32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def definition(rewards, dones, discount=rr.DISCOUNT):
+    """returns_reference in the shape of kernel_reference's result"""
+    with np.errstate(all="ignore"):
+        R, mask, idx = rr.returns_reference(rewards, dones, discount)
+        return np.where(mask, R, 0.0).astype(np.float32), idx, len(idx)
+
+
+def same(a, b):
+    """bit for bit where the first is not NaN, NaN where it is; the same list and count"""
+    nan = np.isnan(a[0])
+    return np.array_equal(nan, np.isnan(b[0])) and np.array_equal(u32(a[0])[~nan], u32(b[0])[~nan]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+
+
+@pytest.mark.parametrize("T,n", SCAN_SHAPES + [(78, 1100), (104, 4096)])
+def test_compact_by_table_is_flatnonzero(T, n):
+    entries = T * ((n + 63) // 64)
+    assert entries > rr.SCAN_PASS
+    for p, which in enumerate(rr.PATTERNS):
+        if T * n > 10 ** 5 and which not in ("bernoulli", "last-step"):
+            continue
+        mask = np.zeros((T, n), bool)
+        d = rr.patterns(T, n, which, seed=7 + p) != 0
+        for e in range(n):
+            ends = np.flatnonzero(d[:, e])
+            if len(ends):
+                mask[:ends[-1] + 1, e] = True
+        want = np.flatnonzero(mask.reshape(-1))
+        assert np.array_equal(rr.compact_by_table(mask), want), (T, n, which)
+        if T * n <= 10 ** 5:
+            for pass_entries in (1, 7, 64, entries - 1, entries, entries + 1):
+                assert np.array_equal(rr.compact_by_table(mask, pass_entries), want), (T, n, which, pass_entries)
+        # without the carry the list is another one as soon as a set row lies behind the first pass
+        entry = np.arange(T)[:, None] * ((n + 63) // 64) + np.arange(n)[None, :] // 64
+        if mask[entry >= rr.SCAN_PASS].any():
+            assert not np.array_equal(rr.compact_by_table(mask, carry=False), want), (T, n, which)
+
+
+@pytest.mark.parametrize("T,n", OLD_SHAPES[:5] + [(1025, 1), (33, 2000)])
+def test_kernel_reference_is_the_definition(T, n):
+    for p, which in enumerate(rr.PATTERNS):
+        rewards, dones = rr.rollout_rewards(T, n, seed=p), rr.patterns(T, n, which, seed=7 + p)
+        got, want = rr.kernel_reference(rewards, dones), definition(rewards, dones)
+        assert not rr.differs(got, want), (T, n, which)
+        assert not rr.differs(rr.kernel_reference(rewards, dones, 0.5), definition(rewards, dones, 0.5))
+
+
+def test_value_fixtures_hold_what_they_are_named_for():
+    fx = rr.value_fixtures()
+    assert set(fx) == set(rr.VALUE_FIXTURES) and len(fx) == len(rr.VALUE_FIXTURES) == 8
+    T, n = rr.VALUE_T, rr.VALUE_N
+    clean = np.arange(n) % 3 == 2
+    plain = definition(rr.rollout_rewards(T, n, 0), fx["overflow"][1])
+    for name, (rewards, dones, discount) in fx.items():
+        assert rewards.shape == dones.shape == (T, n) and rewards.dtype == np.float32 and dones.dtype == np.uint8
+        want = definition(rewards, dones, discount)
+        assert same(want, rr.kernel_reference(rewards, dones, discount)), name
+        assert np.isfinite(want[0][:, clean]).all() and np.isfinite(want[0][:9]).all() and np.isfinite(want[0][18:]).all(), name   # what is special stays in its episode
+        if name != "done_bytes" and name != "nonfinite":
+            assert np.array_equal(want[1], plain[1]), name                  # values never move the mask
+        if name in rr.FINITE_VALUE_FIXTURES:                                # agent.py's own loop, float64 bit for bit
+            with np.errstate(all="ignore"):
+                R, mask, idx = rr.returns_reference(rewards, dones, discount)
+                theirs = rr.agent_py_returns(rewards, dones, discount)
+            flat = R.reshape(-1)
+            assert sorted(theirs) == list(idx)
+            assert all(flat[i] == v and math.copysign(1.0, flat[i]) == math.copysign(1.0, v) for i, v in theirs.items()), name
+    with np.errstate(all="ignore"):
+        R = {k: rr.returns_reference(*v)[0] for k, v in fx.items()}
+    stored = {k: definition(*v)[0] for k, v in fx.items()}
+    for name in ("overflow", "overflow_and_back"):
+        over = np.abs(R[name]) > rr.F32_MAX
+        assert np.isfinite(R[name]).all() and over.any() and (stored[name][over] == np.inf).any() and (stored[name][over] == -np.inf).any()
+    back = (np.abs(R["overflow_and_back"][1:]) > rr.F32_MAX) & (np.abs(R["overflow_and_back"][:-1]) < rr.F32_MAX) & (R["overflow_and_back"][:-1] != 0)
+    assert back.sum() >= 40 and np.isfinite(stored["overflow_and_back"][:-1][back]).all() and (np.abs(stored["overflow_and_back"][:-1][back]) > 1e38).all()
+    s, S = stored["subnormal"], R["subnormal"]
+    sub = (s != 0) & (np.abs(s) < rr.F32_TINY)
+    assert (sub & (s > 0)).sum() > 100 and (sub & (s < 0)).sum() > 100
+    assert (np.abs(fx["subnormal"][0][9:18, ~clean]) < rr.F32_TINY).all() and fx["subnormal"][0][9:18, ~clean].all()
+    tiny = (S != 0) & (np.abs(S) < 2.0 ** -150)
+    assert (tiny & (S > 0)).any() and (tiny & (S < 0)).any() and not s[tiny].any()
+    assert set(u32(s[tiny])) == {0, 0x80000000}                            # the zero keeps the sign
+    z = stored["signed_zero"]
+    assert (u32(z[16:18, ~clean]) == 0x80000000).all() and (u32(z[14:16, ~clean]) == 0).all() and (u32(z[8, ~clean]) == 0x80000000).all()
+    assert (u32(fx["signed_zero"][0][20:, 0::2]) == 0x80000000).all() and (u32(z[18:, 0::2]) == 0).all()
+    nf = stored["nonfinite"]
+    e = np.arange(n)
+    assert np.isnan(nf[9:14, e % 6 == 0]).all() and (nf[9:14, e % 6 == 1] == np.inf).all() and (nf[9:14, e % 6 == 3] == -np.inf).all()
+    assert np.isnan(nf[9:14, e % 6 == 4]).all() and (nf[14, e % 6 == 4] == np.inf).all() and np.isfinite(nf[14:18, e % 6 != 4]).all()
+    assert np.isnan(fx["nonfinite"][0][20, 2]) and not nf[18:, 2].any() and len(definition(*fx["nonfinite"])[1]) == T * n - 9
+    assert set(np.unique(fx["done_bytes"][1])) == {0, 1, 2, 0x80, 0xFF}
+    d0 = stored["discount_0"]
+    assert np.isnan(d0[9:13, ~clean]).all() and np.isinf(d0[13, ~clean]).all() and np.array_equal(u32(d0[:18, clean]), u32(fx["discount_0"][0][:18, clean] + np.float32(0.0)))
+    assert np.allclose(R["discount_1"][9], fx["discount_1"][0][9:18].astype(np.float64).sum(0), rtol=1e-9, atol=1e-9)
+
+
+def test_tie_fixture_separates_the_two_roundings():
+    assert rr.tie_discounts() >= 2
+    seen = set()
+    for i in range(rr.tie_discounts()):
+        rewards, dones, discount = rr.tie_fixture(i)
+        seen.add(discount)
+        n = rewards.shape[1]
+        assert rewards.shape == (2, n) and n >= 65 and dones[1].all() and not dones[0].any() and 0.0 < discount < 1.0
+        sep, fused = rr.kernel_reference(rewards, dones, discount), rr.Mutant("fused")(rewards, dones, discount)
+        assert not rr.differs(sep, definition(rewards, dones, discount))
+        assert (u32(sep[0][0]) != u32(fused[0][0])).all(), "tie fixture %d: an env does not tell the fused form apart" % i
+        assert np.array_equal(u32(sep[0][1]), u32(fused[0][1])) and np.array_equal(sep[1], fused[1])
+        print("tie fixture %d: discount %r, r1 = %g, %d envs" % (i, discount, rewards[1, 0], n))
+    assert len(seen) == rr.tie_discounts()
+    # the issue's example
+    r = np.array([[16777256.0], [5.0]], np.float32)
+    d = np.array([[0], [1]], np.uint8)
+    assert rr.kernel_reference(r, d, 0.20000000037252905)[0][0, 0] == 16777256.0 and rr.Mutant("fused")(r, d, 0.20000000037252905)[0][0, 0] == 16777258.0
+
+
+def rejecting_inputs(name):
+    """the table of the module docstring of tests/test_gpu_trpo_returns_edges.py: the fixture that rejects each mutant"""
+    fx = rr.value_fixtures()
+    if name == "no_carry":
+        return rr.rollout_rewards(1025, 1, 0), rr.patterns(1025, 1, "last-step"), rr.DISCOUNT
+    if name == "fused":
+        return rr.tie_fixture(0)
+    if name == "first_done":
+        return rr.rollout_rewards(27, 65, 4), rr.patterns(27, 65, "bernoulli", seed=11), rr.DISCOUNT
+    if name == "unfinished_keep":
+        dones = rr.patterns(27, 65, "last-step")
+        dones[26, 64] = 0                                   # last-step minus one env: its rows hold 0.0, whatever R the lane carries
+        return rr.rollout_rewards(27, 65, 1), dones, rr.DISCOUNT
+    return fx[{"float32_carry": "overflow_and_back", "done_is_one": "done_bytes", "flush_subnormal": "subnormal"}[name]]
+
+
+@pytest.mark.parametrize("name", rr.MUTANTS)
+def test_every_mutant_is_rejected_by_its_fixture(name):
+    rewards, dones, discount = rejecting_inputs(name)
+    want, got = rr.kernel_reference(rewards, dones, discount), rr.Mutant(name)(rewards, dones, discount)
+    assert not rr.differs(want, definition(rewards, dones, discount))
+    assert np.isfinite(got[0]).all() or name == "float32_carry"
+    assert rr.differs(got, want), "the mutant %s passes the fixture named for it" % name
+    if name == "no_carry":
+        assert want[2] == 1025 and got[2] == 1 and np.array_equal(u32(got[0]), u32(want[0]))
+    if name == "first_done":
+        assert (rr.patterns(27, 65, "bernoulli", seed=11).sum(0) >= 2).any()
+
+
+def test_the_older_fixtures_do_not_see_a_fused_recurrence():
+    """printed, not asserted: fl(r + discount R') and r + fl(discount R') part after the float32 store only beside a float32 tie"""
+    apart = 0
+    for T, n in OLD_SHAPES:
+        for p, which in enumerate(rr.PATTERNS):
+            rewards, dones = rr.rollout_rewards(T, n, seed=p), rr.patterns(T, n, which, seed=7 + p)
+            apart += int(rr.differs(rr.kernel_reference(rewards, dones), rr.Mutant("fused")(rewards, dones)))
+    print("rollout_rewards fixtures that tell the fused recurrence apart: %d of %d" % (apart, len(OLD_SHAPES) * len(rr.PATTERNS)))
 
 
 # ------------------------------------------------------------------------------------------------------ the host side of the ABI

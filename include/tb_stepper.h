@@ -710,6 +710,37 @@ int tb_tqc_actor_grad(int env_kind, int device, void *stream, int batch, const f
                       double *stats_dev, void *workspace_dev, size_t workspace_bytes);
 
 /*
+ * rgb_array frames of env states (csrc/tb_render.hpp states the whole rule: camera, primitives, shading, exceptional values): what
+ * the reference's render() set out to do (tennisbot_env.py:263-288 builds a camera at the racket and leaves getCameraImage
+ * commented out; validate.py / validate_swing.py open PyBullet's GUI). One launch casts one primary ray per pixel of every image
+ * against the ground and net boxes, the SwingRacket-v0 goal cylinder, the ball and the racket's extruded hull (hull_margin, court
+ * lines and textures, and a racket shadow are not drawn), in the conventions of the tb_ppo_* block: no handle, caller-owned device
+ * buffers, refusals before any launch, complete in stream order on `stream`.
+ *   words_dev: [tb_state_words(kind)][n_envs] in tb_get_state's layout; only read. Image k shows env env_idx[k] (any order,
+ *     repeats allowed, values outside [0, n_envs) clamped), or env k when env_idx is null (then n_images <= n_envs).
+ *   params: the scene (ground_half, net_half and TB_F_NET, goal_*, ball_radius, racket_half_thick, hull_bound_radius, hull_edges)
+ *     and, on SwingRacket-v0, racket_scale; a Tennisbot-v0 env is drawn at the scale in its own TB_W_TN_SCALE word.
+ *   camera: origin top-left, x to the right; the ray of pixel (i, j) passes through its centre (i + 0.5, j + 0.5).
+ *   rgb_dev uint8 [n_images][H][W][3]; id_dev_or_null uint8 [n_images][H][W]: 0 sky, 1 ground, 2 net, 3 goal, 4 ball, 5 racket;
+ *   depth_dev_or_null float32 [n_images][H][W]: the ray parameter along the unit direction, +inf for sky.
+ * A primitive whose state is not finite is not drawn; no output is ever NaN, out of 0..5, or a negative depth.
+ * TB_E_INVAL (and a tb_last_error text): null params / words / camera / rgb, n_hull outside [3, TB_MAX_HULL], a size < 1 (or a
+ * side > 16384), struct_size != sizeof(TbCamera), a camera vector that is not finite, eye == target, up zero or parallel to the
+ * view direction, light_dir zero, fov_y_deg outside (0, 180), follow not 0 or 1, a misaligned words / env_idx / depth pointer.
+ */
+typedef struct TbCamera {
+  uint32_t struct_size;             /* sizeof(TbCamera) */
+  float eye[3], target[3], up[3];   /* up need not be orthogonal to the view direction */
+  float fov_y_deg;                  /* vertical field of view, (0, 180) */
+  int32_t follow;                   /* 1: eye and target are offsets from EACH env's racket COM */
+  float light_dir[3];               /* towards the light; normalised by the library */
+} TbCamera;
+int tb_render(int env_kind, int device, void *stream, const TbParams *params,
+              const uint32_t *words_dev /* [tb_state_words][n_envs], tb_get_state's layout */, int n_envs,
+              const int32_t *env_idx_dev_or_null, int n_images, const TbCamera *camera, int width, int height,
+              uint8_t *rgb_dev, uint8_t *id_dev_or_null, float *depth_dev_or_null);
+
+/*
  * Pipelined fast-forward (SwingRacket-v0 with TB_F_AUTO_RESET; HIP streams, no reference
  * counterpart). The <= 775-substep fast-forward of swingracket_env.py:105-141 takes no
  * agent input, and the next episode does not depend on its outcome. With the pipeline

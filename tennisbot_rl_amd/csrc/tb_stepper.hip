@@ -30,6 +30,7 @@
 #include "tb_trpo.hpp"
 #include "tb_sac.hpp"
 #include "tb_tqc.hpp"
+#include "tb_render.hpp"
 
 using namespace tb;
 
@@ -2013,6 +2014,69 @@ int tb_diag_stream_copy(const uint32_t* src_dev, uint32_t* dst_dev, int n, int r
   hipLaunchKernelGGL(tb_diag_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src_dev, dst_dev, n, rows);
   HIP_TRY(hipGetLastError());
   return TB_OK;
+}
+
+// ------------------------------------------------------------------------------------------ tb_render (csrc/tb_render.hpp)
+int tb_render(int env_kind, int device, void* stream, const TbParams* params, const uint32_t* words_dev, int n_envs, const int32_t* env_idx_dev_or_null,
+              int n_images, const TbCamera* camera, int width, int height, uint8_t* rgb_dev, uint8_t* id_dev_or_null, float* depth_dev_or_null) {
+  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_render: unknown env kind");
+  if (!params || !words_dev || !camera || !rgb_dev) return fail(TB_E_INVAL, "tb_render: null argument (params, words, camera and rgb are required)");
+  if (params->n_hull < 3 || params->n_hull > TB_MAX_HULL) return fail(TB_E_INVAL, "tb_render: TbParams.n_hull must be in [3, 64]");
+  if (n_envs < 1 || n_images < 1 || width < 1 || height < 1) return fail(TB_E_INVAL, "tb_render: n_envs, n_images, width and height must be >= 1");
+  if (width > 16384 || height > 16384) return fail(TB_E_INVAL, "tb_render: width and height must be <= 16384");
+  if (!env_idx_dev_or_null && n_images > n_envs) return fail(TB_E_INVAL, "tb_render: without env_idx image k shows env k: n_images must be <= n_envs");
+  if (camera->struct_size != sizeof(TbCamera)) return fail(TB_E_INVAL, "tb_render: TbCamera.struct_size is not sizeof(TbCamera)");
+  if (misaligned(words_dev, 4) || misaligned(env_idx_dev_or_null, 4) || misaligned(depth_dev_or_null, 4)) return fail(TB_E_INVAL, "tb_render: words, env_idx and depth must be 4-byte aligned");
+  const int tiles_x = (width + 7) / 8, tiles = tiles_x * ((height + 7) / 8);
+  if ((long long)tiles * n_images > 0x7fffffffLL) return fail(TB_E_INVAL, "tb_render: more than 2^31 - 1 tiles in one call");
+  // the camera basis, float64 (tb_render.hpp, THE RULE)
+  RenderCam cam;
+  double f[3], r[3], u[3], l[3], fl = 0.0, ul = 0.0, ll = 0.0, rl = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    if (!isfinite(camera->eye[i]) || !isfinite(camera->target[i]) || !isfinite(camera->up[i]) || !isfinite(camera->light_dir[i]))
+      return fail(TB_E_INVAL, "tb_render: a camera vector is not finite");
+    f[i] = (double)camera->target[i] - (double)camera->eye[i];
+    fl += f[i] * f[i]; ul += (double)camera->up[i] * camera->up[i]; ll += (double)camera->light_dir[i] * camera->light_dir[i];
+  }
+  if (!(fl > 0.0)) return fail(TB_E_INVAL, "tb_render: eye == target");
+  if (!(ul > 0.0)) return fail(TB_E_INVAL, "tb_render: up is the zero vector");
+  if (!(ll > 0.0)) return fail(TB_E_INVAL, "tb_render: light_dir is the zero vector");
+  if (!(camera->fov_y_deg > 0.0f && camera->fov_y_deg < 180.0f)) return fail(TB_E_INVAL, "tb_render: fov_y_deg must be in (0, 180)");
+  if (camera->follow != 0 && camera->follow != 1) return fail(TB_E_INVAL, "tb_render: follow must be 0 or 1");
+  fl = sqrt(fl);
+  for (int i = 0; i < 3; ++i) f[i] /= fl;
+  r[0] = f[1] * camera->up[2] - f[2] * camera->up[1]; r[1] = f[2] * camera->up[0] - f[0] * camera->up[2]; r[2] = f[0] * camera->up[1] - f[1] * camera->up[0];
+  for (int i = 0; i < 3; ++i) rl += r[i] * r[i];
+  if (!(rl > 1e-12 * ul)) return fail(TB_E_INVAL, "tb_render: up is parallel to the view direction");
+  rl = sqrt(rl);
+  for (int i = 0; i < 3; ++i) r[i] /= rl;
+  u[0] = r[1] * f[2] - r[2] * f[1]; u[1] = r[2] * f[0] - r[0] * f[2]; u[2] = r[0] * f[1] - r[1] * f[0];
+  const double th = tan(0.5 * (double)camera->fov_y_deg * 3.14159265358979323846 / 180.0), tw = th * (double)width / (double)height;
+  ll = sqrt(ll);
+  for (int i = 0; i < 3; ++i) {
+    l[i] = camera->light_dir[i] / ll;
+    cam.eye[i] = camera->eye[i]; cam.fwd[i] = (float)f[i]; cam.right[i] = (float)(tw * r[i]); cam.up[i] = (float)(th * u[i]); cam.light[i] = (float)l[i];
+  }
+  cam.follow = camera->follow;
+  RenderScene sc;
+  for (int i = 0; i < 3; ++i) { sc.ground_half[i] = params->ground_half[i]; sc.net_half[i] = params->net_half[i]; }
+  sc.goal_radius = params->goal_radius; sc.goal_half_len = params->goal_half_len; sc.ball_radius = params->ball_radius;
+  sc.half_thick = params->racket_half_thick; sc.bound_radius = params->hull_bound_radius; sc.racket_scale = params->racket_scale;
+  sc.n_hull = params->n_hull; sc.flags = params->flags;
+  RenderHull hull;
+  for (int i = 0; i < TB_MAX_HULL; ++i) {
+    const bool in = i < params->n_hull;
+    hull.e[i] = make_float4(in ? params->hull_edges[i][0] : 0.0f, in ? params->hull_edges[i][1] : 0.0f, in ? params->hull_edges[i][2] : 0.0f, in ? params->hull_edges[i][3] : 0.0f);
+  }
+  if (int rc = ppo_device(device, "tb_render: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  const dim3 grid((unsigned)(tiles * n_images)), block(64);
+  if (env_kind == TB_ENV_SWING)
+    return launch(tb_render_kernel<TB_ENV_SWING>, grid, block, 0, (hipStream_t)stream, cam, sc, hull, words_dev, n_envs, env_idx_dev_or_null, width, height, tiles_x, tiles,
+                  rgb_dev, id_dev_or_null, depth_dev_or_null);
+  return launch(tb_render_kernel<TB_ENV_TENNIS>, grid, block, 0, (hipStream_t)stream, cam, sc, hull, words_dev, n_envs, env_idx_dev_or_null, width, height, tiles_x, tiles,
+                rgb_dev, id_dev_or_null, depth_dev_or_null);
 }
 
 int tb_diag_two_wave_gate(TbHandle* h, uint8_t* out_dev, void* stream) {

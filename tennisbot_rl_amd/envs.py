@@ -8,6 +8,9 @@
     / train.py:104-110 consumes it unchanged where stable-baselines3 is installed.
   * `make(id, **kwargs)` / `register_with_gym()`: the ids of tennisbot/__init__.py:3-11.
 
+`render(mode='rgb_array')` / `get_images()` give frames ray-cast on the GPU (BatchedEnv.render, csrc/tb_render.hpp); `metadata` keeps
+listing 'human' only, as the reference's does, and render() / render(mode='human') stay no-ops: there is no window.
+
 `gym` / `gymnasium` / `stable_baselines3` are optional (none is installed in the build
 image): spaces fall back to a minimal `Box`, the VecEnv to a plain class with SB3's method
 set. All arithmetic still happens in the HIP library; these classes only marshal.
@@ -86,7 +89,7 @@ class _SingleEnv(_Base):
 
     def __init__(self, use_gui=False, device=None, seed=0, params=None):
         if use_gui:
-            warnings.warn("use_gui=True: the batched stepper has no GUI (PyBullet's GUI client is not reproduced)")
+            warnings.warn("use_gui=True: the batched stepper has no GUI (PyBullet's GUI client is not reproduced); render(mode='rgb_array') gives frames")
         self.action_space, self.observation_space = spaces_for(self._kind)
         self.np_random = np.random.default_rng()
         self._batch = BatchedEnv(self._kind, 1, device=device, seed=seed, params=params, auto_reset=False)
@@ -107,8 +110,13 @@ class _SingleEnv(_Base):
     def close(self):
         self._batch.close()
 
-    def render(self, mode='human'):
-        pass
+    def render(self, mode='human', camera=None, width=96, height=64):
+        """mode='human' (the default, and the only mode `metadata` lists, as in the reference): a no-op, there is no window.
+        mode='rgb_array': the env as it stands as an H x W x 3 uint8 numpy array, ray-cast on the GPU (BatchedEnv.render);
+        camera: stepper.Camera(...) / default_camera(kind) / racket_view(...), default default_camera(kind)."""
+        if mode != 'rgb_array':
+            return None
+        return self._batch.render(camera=camera, width=width, height=height)[0].cpu().numpy()
 
     def get_state(self):
         return self._batch.get_state()
@@ -192,6 +200,21 @@ def register_with_gym():
     return True
 
 
+def tile_images(images):
+    """[H, W, 3] frames -> one [rows H, cols W, 3] image, near-square: cols = ceil(sqrt(N)), rows = ceil(N / cols), frame k at tile
+    (k // cols, k % cols); tiles beyond N stay black"""
+    images = [np.asarray(im) for im in images]
+    n = len(images)
+    h, w, c = images[0].shape
+    cols = int(np.ceil(np.sqrt(n)))
+    rows = (n + cols - 1) // cols
+    out = np.zeros((rows * h, cols * w, c), images[0].dtype)
+    for k, im in enumerate(images):
+        r, q = divmod(k, cols)
+        out[r * h:(r + 1) * h, q * w:(q + 1) * w] = im
+    return out
+
+
 try:  # optional: real SB3 base class when available so isinstance checks pass
     from stable_baselines3.common.vec_env import VecEnv as _VecEnvBase  # type: ignore
 except Exception:  # pragma: no cover - depends on the host
@@ -249,11 +272,16 @@ class TennisbotVecEnv(_VecEnvBase):
     def seed(self, seed=None):
         return [seed] * self.num_envs
 
-    def render(self, mode='human'):
-        pass
+    def render(self, mode='human', camera=None, width=96, height=64):
+        """mode='human' (the default, the only mode `metadata` lists): a no-op. mode='rgb_array': every env's frame (get_images)
+        tiled into one uint8 image, SB3's tile_images arrangement: ceil(sqrt(N)) columns, row-major, unused tiles black."""
+        if mode != 'rgb_array':
+            return None
+        return tile_images(self.get_images(camera=camera, width=width, height=height))
 
-    def get_images(self):
-        return []
+    def get_images(self, camera=None, width=96, height=64):
+        """one H x W x 3 uint8 numpy array per env, ray-cast on the GPU in one launch (BatchedEnv.render)"""
+        return list(self.batch.render(camera=camera, width=width, height=height).cpu().numpy())
 
     def _indices(self, indices):
         if indices is None:

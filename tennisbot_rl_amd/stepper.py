@@ -3,7 +3,7 @@ stepped in lockstep on one MI355X.
 
 This is the measured path: `step(actions)` takes and returns device tensors and never
 synchronises with the host. torch is used for device memory and streams only; all
-arithmetic happens in libtb_stepper.so (hand-written HIP: csrc/tb_kernels.hpp, tb_device.hpp, tb_policy.hpp; host side csrc/tb_stepper.hip). There is
+arithmetic happens in libtb_stepper.so (hand-written HIP: csrc/tb_kernels.hpp, tb_device.hpp, tb_policy.hpp, tb_render.hpp; host side csrc/tb_stepper.hip). There is
 no CPU or eager-PyTorch fallback: if the library or a GPU is missing, construction raises.
 
 Reference counterparts: `SwingRacketEnv` (tennisbot/envs/swingracket_env.py:24-192) and
@@ -171,6 +171,8 @@ def load_library():
     for sac, tqc in ((L.tb_sac_actor_forward, L.tb_tqc_actor_forward), (L.tb_sac_targets, L.tb_tqc_targets), (L.tb_sac_critic_grad, L.tb_tqc_critic_grad),
                      (L.tb_sac_actor_grad, L.tb_tqc_actor_grad)):   # the same signatures
         tqc.argtypes, tqc.restype = sac.argtypes, i32
+    L.tb_render.argtypes = [i32, i32, vp, ctypes.POINTER(TbParams), vp, i32, vp, i32, ctypes.POINTER(TbCamera), i32, i32, vp, vp, vp]
+    L.tb_render.restype = i32
     L.tb_phase.argtypes = [vp]
     L.tb_phase.restype = i32
     L.tb_phase_advance.argtypes = [vp, i32]
@@ -236,6 +238,85 @@ class TbSacCollectOut(ctypes.Structure):
 
 
 SAC_COLLECT_ACTOR, SAC_COLLECT_UNIFORM = 0, 1   # include/tb_stepper.h TB_SAC_COLLECT_*
+
+
+class TbCamera(ctypes.Structure):
+    """include/tb_stepper.h TbCamera: the view of tb_render"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("eye", ctypes.c_float * 3), ("target", ctypes.c_float * 3), ("up", ctypes.c_float * 3),
+                ("fov_y_deg", ctypes.c_float), ("follow", ctypes.c_int32), ("light_dir", ctypes.c_float * 3)]
+
+
+DEFAULT_LIGHT = (0.3, -0.5, 0.8)
+RENDER_IDS = ("sky", "ground", "net", "goal", "ball", "racket")   # the id layer of tb_render
+
+
+def Camera(eye, target, up=(0.0, 0.0, 1.0), fov_y_deg=60.0, follow=False, light_dir=DEFAULT_LIGHT):
+    """A TbCamera. follow=True: eye and target are offsets from EACH env's racket COM. Bad values (eye == target, up parallel to the
+    view, fov outside (0, 180)) are refused by the library when the camera is used."""
+    c = TbCamera()
+    c.struct_size = ctypes.sizeof(TbCamera)
+    for i in range(3):
+        c.eye[i], c.target[i], c.up[i], c.light_dir[i] = float(eye[i]), float(target[i]), float(up[i]), float(light_dir[i])
+    c.fov_y_deg, c.follow = float(fov_y_deg), 1 if follow else 0
+    return c
+
+
+def default_camera(kind):
+    """The view that shows what a policy does, for each env its own: a follow camera behind and above the env's racket, looking past it
+    down the court towards the net (SwingRacket-v0: and the goal beyond it; Tennisbot-v0: towards the incoming ball). The rackets
+    spawn anywhere in a 5 m x 8 m (10 m) region (swingracket_env.py:161-162, tennisbot_env.py:227-228), which no fixed camera
+    shows at a readable size: court_camera() is that fixed overview."""
+    if isinstance(kind, str):
+        kind = ENV_IDS[kind]
+    if kind == ENV_SWING:
+        return Camera((3.5, -2.0, 2.2), (-3.0, 0.5, 0.2), follow=True)
+    return Camera((3.0, -1.5, 1.5), (-2.0, 0.3, -0.2), follow=True)
+
+
+def court_camera():
+    """a fixed view of the whole court from beside the racket's end"""
+    return Camera((20.0, -11.0, 8.0), (1.0, 0.0, 0.0))
+
+
+def racket_view(racket_pos, racket_quat):
+    """The camera the reference's render() builds (tennisbot_env.py:263-279): at the racket with z = 0.2, looking along the body x
+    axis, the body z axis up, fov 80. It needs the orientation, so it is built per call from ONE env's state (get_state()'s
+    racket_pos[i], racket_quat[i])."""
+    x, y, z, w = (float(v) for v in racket_quat)
+    ex = (1 - 2 * (y * y + z * z), 2 * (x * y + z * w), 2 * (x * z - y * w))   # R [1, 0, 0]
+    ez = (2 * (x * z + y * w), 2 * (y * z - x * w), 1 - 2 * (x * x + y * y))   # R [0, 0, 1]
+    eye = (float(racket_pos[0]), float(racket_pos[1]), 0.2)
+    return Camera(eye, tuple(e + d for e, d in zip(eye, ex)), up=ez, fov_y_deg=80.0)
+
+
+def render_words(kind, params, words, indices=None, camera=None, width=96, height=64, layers=False):
+    """tb_render on a state-word block: words int32 / uint32 [W, N] on a GPU (get_state_words' layout) -> uint8 [K, H, W, 3] on the same
+    device; with layers=True also ids uint8 [K, H, W] (RENDER_IDS) and depth float32 [K, H, W] (+inf: sky). indices: the envs to show (a
+    sequence or an integer tensor; any order, repeats allowed, out-of-range values clamped), default all. Stream-ordered, no host sync."""
+    import torch as t
+    L = load_library()
+    if isinstance(kind, str):
+        kind = ENV_IDS[kind]
+    if not isinstance(words, t.Tensor) or words.device.type != "cuda" or words.dim() != 2 or words.shape[0] != STATE_WORDS[kind] or not words.is_contiguous():
+        raise ValueError("words must be a contiguous [%d, N] tensor on the GPU" % STATE_WORDS[kind])
+    if words.element_size() != 4:
+        raise TypeError("words must hold 32-bit words")
+    n = int(words.shape[1])
+    idx = None
+    if indices is not None:
+        idx = indices if isinstance(indices, t.Tensor) else t.as_tensor(np.asarray(indices, dtype=np.int64).reshape(-1))
+        idx = idx.to(device=words.device, dtype=t.int32).contiguous()
+    K = n if idx is None else int(idx.numel())
+    cam = camera if camera is not None else default_camera(kind)
+    W, H = int(width), int(height)
+    shape = (K, max(H, 0), max(W, 0))   # a size < 1 is the library's to refuse
+    rgb = t.empty(shape + (3,), dtype=t.uint8, device=words.device)
+    ids = t.empty(shape, dtype=t.uint8, device=words.device) if layers else None
+    depth = t.empty(shape, dtype=t.float32, device=words.device) if layers else None
+    _check(L, L.tb_render(int(kind), words.device.index, ctypes.c_void_p(t.cuda.current_stream(words.device).cuda_stream), ctypes.byref(params),
+                          words.data_ptr(), n, None if idx is None else idx.data_ptr(), K, ctypes.byref(cam), W, H, rgb.data_ptr(),
+                          None if ids is None else ids.data_ptr(), None if depth is None else depth.data_ptr()), "tb_render")
+    return (rgb, ids, depth) if layers else rgb
 
 
 def _check(L, rc, what):
@@ -738,6 +819,15 @@ class BatchedEnv:
         else:
             rows = [0, 1, 2, 7, 8, 9, 13, 14, 15, 16, 17, 18]
         return f[rows].t().contiguous()
+
+    def render(self, indices=None, camera=None, width=96, height=64, layers=False):
+        """rgb_array frames of the envs as they stand (tb_render: one ray per pixel against ground, net, goal, ball and racket, one
+        launch for every image). Returns uint8 [K, H, W, 3] on the device, K = len(indices) or num_envs; with layers=True also ids
+        uint8 [K, H, W] (RENDER_IDS) and depth float32 [K, H, W] (+inf: sky). camera: Camera(...) / default_camera(kind) /
+        racket_view(...). It works from get_state_words() -- on a pipelined SwingRacket handle that joins the outstanding
+        fast-forwards, as every state read does -- and writes nothing of the env: state, counters and the next step are untouched."""
+        w, _ = self.get_state_words()
+        return render_words(self.kind, self.params, w, indices=indices, camera=camera, width=width, height=height, layers=layers)
 
     def set_params(self, params):
         p = params.copy()

@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Look at a policy: step K envs through whole episodes, render every AGENT step on the GPU (BatchedEnv.render, tb_render: one ray per
+pixel against ground, net, goal, ball and racket) and write the tiled frames as a GIF.
+
+  python tools/render_episode.py --reference-policy --envs 4 --out swing.gif     # the reference's shipped ppo_swing weights
+  python tools/render_episode.py -m model/ppo_SwingRacket-v0.pt --out swing.gif  # a checkpoint of train_swing.py
+  python tools/render_episode.py --env Tennisbot-v0 --random --steps 200 --out tennis.gif --camera court
+
+Only the agent steps are rendered. A SwingRacket-v0 episode is 25 swing steps and one last step whose ball flight (up to 775
+physics substeps) runs inside the fast-forward: those substeps are not visible from outside, so the flight itself is NOT in the
+film -- the last frame of an episode shows the state the next episode starts from. Tennisbot-v0 steps one substep per agent step,
+so its film is complete. Without PIL the frames are written as an .npy stack [T, H, W, 3] instead, and the tool says so.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
+    ap.add_argument("-m", "--model_file", type=str, default="", help="checkpoint written by train_swing.py / train.py --save")
+    ap.add_argument("--reference-policy", action="store_true", help="tests/golden/ppo_swing_policy.npz (exported from backup_models/ppo_swing.zip)")
+    ap.add_argument("--random", action="store_true", help="uniform random actions instead of a policy")
+    ap.add_argument("--net", default="default", choices=["default", "tuned", "mlp64"], help="the network the checkpoint holds")
+    ap.add_argument("--envs", type=int, default=4, help="envs stepped and shown side by side (tiled near-square)")
+    ap.add_argument("--episodes", type=int, default=2, help="whole SwingRacket-v0 episodes (26 agent steps each); Tennisbot-v0: see --steps")
+    ap.add_argument("--steps", type=int, default=0, help="agent steps to film (default: 26 x --episodes; Tennisbot-v0: 300)")
+    ap.add_argument("--width", type=int, default=192)
+    ap.add_argument("--height", type=int, default=128)
+    ap.add_argument("--camera", default="default", choices=["default", "court", "racket"],
+                    help="default: from behind each env's own racket (stepper.default_camera); court: the fixed overview; racket: the reference's render() camera "
+                         "(tennisbot_env.py:263-279: at the racket, z = 0.2, along its body x axis, fov 80), built from env 0's state")
+    ap.add_argument("--fps", type=float, default=12.0)
+    ap.add_argument("--deterministic", action="store_true")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default="episode.gif")
+    args = ap.parse_args()
+    if sum([bool(args.model_file), args.reference_policy, args.random]) != 1:
+        sys.exit("give exactly one of -m <checkpoint>, --reference-policy, --random")
+
+    import numpy as np
+    import torch
+    from tennisbot_rl_amd import stepper
+    from tennisbot_rl_amd.envs import tile_images
+
+    swing = args.env == "SwingRacket-v0"
+    steps = args.steps or (26 * args.episodes if swing else 300)
+    if args.random:
+        env = stepper.BatchedEnv(args.env, args.envs, device="cuda:0", seed=args.seed)
+        obs, blob, net = env.reset(), None, None
+        gen = torch.Generator(device="cpu").manual_seed(args.seed)
+    else:
+        from tennisbot_rl_amd.ppo import PPOTrainer, pack_policy
+        tr = PPOTrainer(args.env, num_envs=args.envs, n_steps=26, device="cuda:0", seed=args.seed, graph=False, policy=args.net)
+        if args.reference_policy:
+            tr.policy.load_sb3_arrays(dict(np.load(os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz"))))
+        else:
+            tr.load(args.model_file)
+        env, blob, obs, net = tr.env, pack_policy(tr.policy), tr.obs_in, tr.net
+
+    def camera():
+        if args.camera == "court":
+            return stepper.court_camera()
+        if args.camera == "racket":
+            st = env.get_state()
+            return stepper.racket_view(st["racket_pos"][0], st["racket_quat"][0])
+        return stepper.default_camera(env.kind)
+
+    def frame():
+        return tile_images(list(env.render(camera=camera(), width=args.width, height=args.height).cpu().numpy()))
+
+    frames, ret, finished = [frame()], torch.zeros(args.envs, device=env.device), []
+    for t in range(steps):
+        if args.random:
+            a = (torch.rand((args.envs, env.act_dim), generator=gen) * 2 - 1).to(env.device)
+            obs, rew, done = env.step(a)
+        else:
+            (obs, rew, done), _ = env.policy_step(blob, obs, seed=args.seed + 1, deterministic=args.deterministic, net=net)
+        if env.pipeline:
+            env.flush()
+        ret += rew
+        d = done.bool()
+        if bool(d.any()):
+            finished.append(ret[d].cpu().numpy())
+            ret[d] = 0.0
+        frames.append(frame())
+    if finished:
+        r = np.concatenate(finished)
+        print("%d episodes: mean reward %.3f, goal hits (reward >= 50) %.1f %%" % (r.size, r.mean(), 100.0 * (r >= 50).mean()))
+    stack = np.stack(frames)
+    try:
+        from PIL import Image
+    except Exception:
+        out = os.path.splitext(args.out)[0] + ".npy"
+        np.save(out, stack)
+        print("PIL is not installed: wrote the %d frames as a uint8 array %s to %s instead of a GIF" % (len(frames), stack.shape, out))
+        return
+    images = [Image.fromarray(f) for f in stack]
+    images[0].save(args.out, save_all=True, append_images=images[1:], duration=max(1, int(round(1000.0 / args.fps))), loop=0)
+    print("wrote %d frames of %d x %d (%d envs) to %s" % (len(frames), stack.shape[2], stack.shape[1], args.envs, args.out))
+
+
+if __name__ == "__main__":
+    main()

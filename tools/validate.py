@@ -33,7 +33,7 @@ def main(argv=None):
     ap.add_argument("--racket-scale", type=float, default=1.0, help="the racket size to validate on (train.py --curri ends at 1)")
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--headless", action="store_true", help="accepted for CLI compatibility; there is no GUI")
+    ap.add_argument("--headless", action="store_true", help="accepted for CLI compatibility; there is no GUI (tools/render_episode.py films a policy)")
     args = ap.parse_args(argv)
     if args.select in ("sac", "tqc") and args.env is None:
         ap.error("-s %s needs --env: its checkpoints exist for both env ids" % args.select)

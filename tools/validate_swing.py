@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--steps", type=int, default=104, help="agent steps per env (4 SwingRacket episodes)")
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--headless", action="store_true", help="accepted for CLI compatibility; there is no GUI")
+    ap.add_argument("--headless", action="store_true", help="accepted for CLI compatibility; there is no GUI (tools/render_episode.py films a policy)")
     args = ap.parse_args()
 
     import numpy as np

@@ -157,8 +157,7 @@ TB_DEV void es_normalise(double& n, double* mean, double* mdiff, const float* o,
 template <int KIND, bool RG>
 __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
   using N = EsNet<KIND>;
-  constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O;
-  constexpr int T_MAX = KIND == TB_ENV_SWING ? 26 : 1001;  // every episode is over by then (26 steps; step_count > 1000)
+  constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, T_MAX = episode_cap(KIND);
   __shared__ float4 s_hull[TB_HULL_LDS];
   __shared__ __attribute__((aligned(16))) float s_w[TB_ES_LDS_MEMBERS * N::PP];
   __shared__ float s_ring[N::RING * 64];
@@ -180,10 +179,8 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
   float* ring = s_ring + lane;
 
   EnvRegs e;
-  idle_env(e);
-  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);  // the state tb_reset just wrote: the episode's start, no contacts cached
   Manifold M;
-  init_manifold(M, lane, 64, !es_rows_in_registers(KIND, RG));
+  enter_env_wave<KIND>(A, i, live, lane, !es_rows_in_registers(KIND, RG), e, M);  // the state tb_reset just wrote: the episode's start, no contacts cached
   uint32_t cnt[TB_N_COUNTERS] = {};
   KParams Pl = A.P;
   double nrm = 0.0, mean[NO], mdiff[NO];
@@ -191,17 +188,15 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
   for (int k = 0; k < NO; ++k) { mean[k] = 0.0; mdiff[k] = 0.0; }
   float o[NO];
   make_obs<KIND>(e, o);
-  bool active = live;
-  double ret = 0.0;
-  int len = 0;
-  constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (es_rows_in_registers(KIND, RG) ? SF_REGROWS : 0u);
+  EpisodeTally ep = {live, 0.0, 0};
+  constexpr unsigned FORM = loop_step_form(RG, true, es_rows_in_registers(KIND, RG));
   TB_DIAG_STAMPS_BEGIN(st);  // (the substep's stamps: the diagnostic build compiles every kernel that steps envs)
-  for (int t = 0; t < T_MAX && __ballot(active) != 0ull; ++t) {
+  for (int t = 0; t < T_MAX && __ballot(ep.active) != 0ull; ++t) {
     float a[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) a[k] = 0.0f;
-    const bool rec = active && t < E.t_max;
-    if (active) {
+    const bool rec = ep.active && t < E.t_max;
+    if (ep.active) {
       float x[NO], raw[NA];
       es_normalise<NO>(nrm, mean, mdiff, o, x);
       es_net_step<KIND>(W, x, ring, t, raw);
@@ -217,28 +212,17 @@ __global__ void __launch_bounds__(64) tb_es_rollout_kernel(KArgs A, EsArgs E) {
     }
     int ns = 1;
     bool d = false, parked = false;
-    float rew;
-    // (every lane of the wave, idle ones included: the substep's outline sweep is shared among all 64, SF_WIDE)
-    if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
-    else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
-    if (active) {
+    float rew = env_wave_step<KIND, FORM>(Pl, s_hull, e, M, a, o, ns, d, parked, cnt TB_STAMP_PASS);
+    if (ep.active) {
       end_agent_step<KIND, RG, false>(A, i, e, M, parked, ns, (size_t)i, o, d, cnt);  // (tb_es_evaluate claims a slot for every env)
-      if (parked) rew = 0.0f;  // the 26th step: its reward is the fast-forward's, folded in after the flush
-      else ret += (double)rew;
-      len = t + 1;
+      rew = tally_step(ep, t, rew, parked, d, e, M, cnt);
       if (rec) {
         E.t_rew[(size_t)t * A.n + i] = rew;
         E.t_done[(size_t)t * A.n + i] = d ? 1 : 0;
       }
-      if (d) {
-        cnt[5]++;
-        active = false;
-        idle_env(e);  // from here on this lane steps the dummy
-        M.n = 0; M.deep = 0;
-      }
     }
   }
-  if (live) { E.ret[i] = ret; E.len[i] = len; }
+  if (live) { E.ret[i] = ep.ret; E.len[i] = ep.len; }
   flush_counters(A.counters, cnt);
   TB_DIAG_STAMPS_END(st);
 }

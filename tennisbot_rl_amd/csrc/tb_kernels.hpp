@@ -1052,6 +1052,94 @@ TB_DEV void idle_env(EnvRegs& e) {
   e.step_count = -(1 << 30); e.episode = 0u; e.done = TB_DONE_NO;
 }
 constexpr int policy_rollout_lds_words(int kind, bool rg) { return lds_words(!policy_rollout_rows_in_registers(kind), rg); }
+
+// ---- THE ENV WAVE of the kernels that step envs in a loop with a network in front of them: tb_policy_rollout_kernel,
+// tb_policy_evaluate_kernel, tb_es_rollout_kernel (tb_es.hpp), tb_sac_evaluate_kernel and tb_sac_collect_kernel (tb_sac.hpp). The pieces
+// below are what those five share; none of them holds a barrier: every __syncthreads() is written out where the kernel documents it.
+
+// the substep's form in these kernels: the cold contact path; WIDE: the outline sweep shared among the wave's 64 lanes
+constexpr unsigned loop_step_form(bool rg, bool wide, bool rows_in_registers) {
+  return (rg ? SF_RG : 0u) | SF_COLD | (wide ? SF_WIDE : 0u) | (rows_in_registers ? SF_REGROWS : 0u);
+}
+// the whole-episode kernels' trip limit: every episode is over by then (SwingRacket: exactly 26 agent steps; Tennisbot: step_count > 1000)
+constexpr int episode_cap(int kind) { return kind == TB_ENV_SWING ? 26 : 1001; }
+
+// The free-flight constants of the substep as VECTOR registers for the whole launch. As kernel arguments they are scalar loads
+// that the compiler, at its SGPR limit in these kernels, re-issues inside the per-step loop (two dozen of them, each behind a wait
+// the lone env wave cannot hide); the env wave has ~300 vector registers to spare, and a value that went through an empty asm
+// cannot be fetched again.
+TB_DEV void pin_substep_params(KParams& Pl) {
+#if TB_HINT_POLICY_VGPR_PARAMS
+#define TB_PIN(f) asm volatile("" : "+v"(Pl.f))
+  TB_PIN(dt); TB_PIN(gravity); TB_PIN(lin_damp); TB_PIN(ang_damp); TB_PIN(lin_damp_quad); TB_PIN(ang_damp_quad); TB_PIN(max_ang_step); TB_PIN(contact_threshold);
+  TB_PIN(racket_inv_mass); TB_PIN(racket_inertia[0]); TB_PIN(racket_inertia[1]); TB_PIN(racket_inertia[2]);
+  TB_PIN(racket_inv_inertia[0]); TB_PIN(racket_inv_inertia[1]); TB_PIN(racket_inv_inertia[2]);
+  TB_PIN(racket_half_thick); TB_PIN(hull_margin); TB_PIN(hull_bound_radius); TB_PIN(ball_inv_mass); TB_PIN(ball_radius); TB_PIN(magnus_k); TB_PIN(static_top);
+#undef TB_PIN
+#endif
+}
+
+// entering the wave: a lane with an env loads it, every other lane holds the dummy; the lane's LDS column
+template <int KIND>
+TB_DEV void enter_env_wave(const KArgs& A, int i, bool live, int lane, bool rows_in_lds, EnvRegs& e, Manifold& M) {
+  idle_env(e);
+  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);
+  init_manifold(M, lane, 64, rows_in_lds);
+}
+// the lane's observation row, where the network's waves read it
+template <int NO>
+TB_DEV void publish_obs(float* s_obs, int lane, const float* o) {
+#pragma unroll
+  for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+}
+
+// one agent step of every lane of the wave, dummies included (SwingRacket never loops in here: it parks, see tb_step_kernel<LEAN>)
+template <int KIND, unsigned FORM>
+TB_DEV float env_wave_step(const KParams& Pl, const float4* s_hull, EnvRegs& e, Manifold& M, const float* a, float* o, int& ns, bool& d, bool& parked,
+                           uint32_t* cnt TB_STAMP_ARG) {
+  if (KIND == TB_ENV_SWING) return swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
+  return tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
+}
+
+// a collect loop's episode end (the host requires TB_F_AUTO_RESET): o becomes the next episode's first observation
+template <int KIND>
+TB_DEV void restart_on_done(const KArgs& A, const float4* s_hull, int i, EnvRegs& e, Manifold& M, float* o, uint32_t* cnt, bool& any_reset) {
+  cnt[5]++;
+  restart_episode<KIND>(A, s_hull + TB_HULL_KP, i, e, M, o);
+  any_reset = true;
+}
+
+// A whole-episode loop's account of one lane: every env runs from the state tb_reset wrote through its first `done`; the return is
+// summed in float64 in step order.
+struct EpisodeTally { bool active; double ret; int len; };
+// step t of an active lane, behind its end_agent_step. A parked step (SwingRacket's 26th) adds nothing: its reward is the
+// fast-forward's, folded in after the flush (tb_es_fold_kernel). On done the lane steps the dummy from here on. Returns the reward
+// as a trace records it.
+TB_DEV float tally_step(EpisodeTally& ep, int t, float rew, bool parked, bool d, EnvRegs& e, Manifold& M, uint32_t* cnt) {
+  if (parked) rew = 0.0f;
+  else ep.ret += (double)rew;
+  ep.len = t + 1;
+  if (d) {
+    cnt[5]++;
+    ep.active = false;
+    idle_env(e);
+    M.n = 0; M.deep = 0;
+  }
+  return rew;
+}
+
+// THE LOOP EXIT of a whole-episode kernel with several waves. All waves must leave the loop at the same t, or one of them waits at a
+// barrier the others never reach. The decision is therefore ONE value: after step t the env wave computes __ballot(active) != 0 and
+// its lane 0 writes it to the LDS word s_go (vote_go) BEFORE the barrier "the observations after step t are in LDS". Every wave reads
+// s_go only AFTER that barrier, and every wave evaluates the same expression (loop_goes_on), t + 1 < cap && s_go: the same t, the same
+// word, hence the same verdict. The word is next written in iteration t + 1, which the env wave does only behind a barrier that
+// every other wave reaches after its read of s_go in iteration t. So no reader can see the next value early or lose the current one.
+TB_DEV void vote_go(int& s_go, int lane, bool active) {
+  const bool go = __ballot(active) != 0ull;
+  if (lane == 0) s_go = go ? 1 : 0;
+}
+TB_DEV bool loop_goes_on(const int& s_go, int t, int cap) { return t + 1 < cap && __builtin_amdgcn_readfirstlane(s_go) != 0; }
+
 template <int KIND, int S, bool RG, int NET = TB_NET_DEFAULT>
 __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KArgs A) {
   constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE * S;
@@ -1089,10 +1177,8 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   // never reaches an episode end. It touches nothing, asks for nothing and is never stored -- but its lane is IN the substep, so the
   // racket narrowphase can share the outline sweeps of the asking envs among all 64 lanes (outline_sweep_rows).
   EnvRegs e;
-  idle_env(e);
-  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);
   Manifold M;
-  init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
+  enter_env_wave<KIND>(A, i, live, lane, !policy_rollout_rows_in_registers(KIND), e, M);
   const bool had_contacts = load_contacts<RG>(A, i, live, M);
   uint32_t cnt[TB_N_COUNTERS] = {};
   bool any_reset = false;
@@ -1101,19 +1187,8 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   float stdv[NA], lstd[NA];
 #pragma unroll
   for (int k = 0; k < NA; ++k) { lstd[k] = A.pol_weights[PolicyBlob<KIND, NET>::LOG_STD + k]; stdv[k] = expf(lstd[k]); }
-  // The free-flight constants of the substep as VECTOR registers for the whole launch. As kernel arguments they are scalar loads
-  // that the compiler, at its SGPR limit in this kernel, re-issues inside the per-step loop (two dozen of them, each behind a wait
-  // the lone env wave cannot hide); the env wave has ~300 vector registers to spare, and a value that went through an empty asm
-  // cannot be fetched again.
   KParams Pl = A.P;
-#if TB_HINT_POLICY_VGPR_PARAMS
-#define TB_PIN(f) asm volatile("" : "+v"(Pl.f))
-  TB_PIN(dt); TB_PIN(gravity); TB_PIN(lin_damp); TB_PIN(ang_damp); TB_PIN(lin_damp_quad); TB_PIN(ang_damp_quad); TB_PIN(max_ang_step); TB_PIN(contact_threshold);
-  TB_PIN(racket_inv_mass); TB_PIN(racket_inertia[0]); TB_PIN(racket_inertia[1]); TB_PIN(racket_inertia[2]);
-  TB_PIN(racket_inv_inertia[0]); TB_PIN(racket_inv_inertia[1]); TB_PIN(racket_inv_inertia[2]);
-  TB_PIN(racket_half_thick); TB_PIN(hull_margin); TB_PIN(hull_bound_radius); TB_PIN(ball_inv_mass); TB_PIN(ball_radius); TB_PIN(magnus_k); TB_PIN(static_top);
-#undef TB_PIN
-#endif
+  pin_substep_params(Pl);
   for (int t = 0; t < A.T; ++t) {
     float eps[NA];
     if (live) policy_draw<KIND>(A, i, e, eps);  // while the towers run
@@ -1131,23 +1206,17 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
       //  env wave, 4096 envs: each lane sweeping for itself 570-574, one query at a time over 64 lanes 592-595 -> 622, four at a time 644 M env
       //  steps/s; 48 envs per wave, 16384 envs: for itself 1036 -> 1057 M -- there the one-query form had lost, 461 -> 426 M at 4096 envs)
       //  (not with 48 envs per wave AND the extended contact set: at that instantiation's 256-VGPR limit the shared sweep's edge records spill)
-      constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | (S == 1 || !RG ? SF_WIDE : 0u) | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);
+      constexpr unsigned FORM = loop_step_form(RG, S == 1 || !RG, policy_rollout_rows_in_registers(KIND));
 #ifdef TB_DIAG_NO_ENVSTEP  // timing-only (tools/diag/r04_policy_ablate.py): RESULTS ARE WRONG
       rew = a[0]; e.step_count += 1;
       if (KIND == TB_ENV_TENNIS) make_obs<KIND>(e, o);
 #else
-      if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);  // never loops in here: see tb_step_kernel<LEAN>
-      else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
+      rew = env_wave_step<KIND, FORM>(Pl, s_hull, e, M, a, o, ns, d, parked, cnt TB_STAMP_PASS);
 #endif
       if (live) {
         end_agent_step<KIND, RG, true>(A, i, e, M, parked, ns, (size_t)t * A.st_rew + i, o, d, cnt);
-        if (d) {  // (rollouts require TB_F_AUTO_RESET)
-          cnt[5]++;
-          restart_episode<KIND>(A, s_hull + TB_HULL_KP, i, e, M, o);
-          any_reset = true;
-        }
-#pragma unroll
-        for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+        if (d) restart_on_done<KIND>(A, s_hull, i, e, M, o, cnt, any_reset);
+        publish_obs<NO>(s_obs, lane, o);
       }
       // The towers wait for the observations only: THEY are in LDS now. The step's rows go to memory behind the barrier, while
       // the towers already run step t + 1 (the env wave's next stop is the barrier behind their means: ~1.2 us away).
@@ -1177,18 +1246,14 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
 // where tb_reset left it. Sampling, noise keys and clipping are policy_draw / policy_sample_regs: per env the actions are those of
 // tb_policy_step, step after step. SwingRacket's 26th step parks its fast-forward as in tb_es_rollout_kernel (the host folds the
 // terminal reward in afterwards). Static contact rows: where tb_policy_rollout_kernel keeps them.
-// THE LOOP EXIT. Both waves must leave the loop at the same t, or one of them waits at a barrier the other never reaches. The
-// decision is therefore ONE value: after step t the env wave computes go = (__ballot(active) != 0) and its lane 0 writes it to the
-// LDS word s_go BEFORE the barrier "the observations after step t are in LDS". Both waves read s_go only AFTER that barrier, and both
-// evaluate the same expression, t + 1 < T_MAX && s_go: the same t, the same word, hence the same verdict. The word is next written
-// in iteration t + 1, which the env wave does only after the barrier "the action means of step t + 1 are in LDS" -- and the tower
-// wave arrives at that barrier after its read of s_go in iteration t. So no reader can see the next value early or lose the
-// current one. s_mean and s_obs are handed over as in tb_policy_rollout_kernel. Barriers per wave: one behind the set-up, then two
-// per iteration on every path (the exit, by s_go or by T_MAX, is behind an iteration's second barrier in both roles).
+// THE LOOP EXIT is vote_go / loop_goes_on (the proof is there): the env wave votes in front of the barrier "the observations after step
+// t are in LDS", both waves test behind it; the barrier that guards the next vote is "the action means of step t + 1 are in LDS",
+// which the tower wave reaches after its test of iteration t. s_mean and s_obs are handed over as in tb_policy_rollout_kernel.
+// Barriers per wave: one behind the set-up, then two per iteration on every path (the exit, by s_go or by the cap, is behind an
+// iteration's second barrier in both roles).
 template <int KIND, bool RG, int NET = TB_NET_DEFAULT>
 __global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double* ret_out, int32_t* len_out) {
-  constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE;
-  constexpr int T_MAX = KIND == TB_ENV_SWING ? 26 : 1001;  // tb_es_rollout_kernel's: every episode is over by then
+  constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE, T_MAX = episode_cap(KIND);
   __shared__ float4 s_hull[TB_HULL_LDS];
   __shared__ __attribute__((aligned(16))) float s_mean[E * 8];
   __shared__ __attribute__((aligned(16))) float s_obs[E * NO];
@@ -1207,80 +1272,53 @@ __global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double
       if (grp < 2) *reinterpret_cast<float4*>(s_mean + slot * 8 + grp * 4) = make_float4(out[0], out[1], out[2], out[3]);
       __syncthreads();  // the action means of step t are in LDS
       __syncthreads();  // the observations after step t, and s_go, are in LDS
-      if (!(t + 1 < T_MAX && __builtin_amdgcn_readfirstlane(s_go) != 0)) break;
+      if (!loop_goes_on(s_go, t, T_MAX)) break;
     }
     return;
   }
   const int i = blockIdx.x * E + lane;
   const bool live = lane < E && i < A.n;
   EnvRegs e;
-  idle_env(e);
-  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);  // the state tb_reset just wrote: the episode's start, no contacts cached
   Manifold M;
-  init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
+  enter_env_wave<KIND>(A, i, live, lane, !policy_rollout_rows_in_registers(KIND), e, M);  // the state tb_reset just wrote: the episode's start, no contacts cached
   uint32_t cnt[TB_N_COUNTERS] = {};
   {
     float o[NO];
     make_obs<KIND>(e, o);
-    if (live) {
-#pragma unroll
-      for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
-    }
+    if (live) publish_obs<NO>(s_obs, lane, o);
   }
   __syncthreads();  // the outline table and the episodes' first observations are in LDS
   float stdv[NA], lstd[NA];
 #pragma unroll
   for (int k = 0; k < NA; ++k) { lstd[k] = A.pol_weights[PolicyBlob<KIND, NET>::LOG_STD + k]; stdv[k] = expf(lstd[k]); }
-  KParams Pl = A.P;  // (the substep's constants in vector registers: see tb_policy_rollout_kernel)
-#if TB_HINT_POLICY_VGPR_PARAMS
-#define TB_PIN(f) asm volatile("" : "+v"(Pl.f))
-  TB_PIN(dt); TB_PIN(gravity); TB_PIN(lin_damp); TB_PIN(ang_damp); TB_PIN(lin_damp_quad); TB_PIN(ang_damp_quad); TB_PIN(max_ang_step); TB_PIN(contact_threshold);
-  TB_PIN(racket_inv_mass); TB_PIN(racket_inertia[0]); TB_PIN(racket_inertia[1]); TB_PIN(racket_inertia[2]);
-  TB_PIN(racket_inv_inertia[0]); TB_PIN(racket_inv_inertia[1]); TB_PIN(racket_inv_inertia[2]);
-  TB_PIN(racket_half_thick); TB_PIN(hull_margin); TB_PIN(hull_bound_radius); TB_PIN(ball_inv_mass); TB_PIN(ball_radius); TB_PIN(magnus_k); TB_PIN(static_top);
-#undef TB_PIN
-#endif
-  bool active = live;
-  double ret = 0.0;
-  int len = 0;
-  constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);  // tb_policy_rollout_kernel<KIND, 1>'s
+  KParams Pl = A.P;
+  pin_substep_params(Pl);
+  EpisodeTally ep = {live, 0.0, 0};
+  constexpr unsigned FORM = loop_step_form(RG, true, policy_rollout_rows_in_registers(KIND));
   TB_DIAG_STAMPS_BEGIN(st);
   for (int t = 0;; ++t) {
     float eps[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) eps[k] = 0.0f;
-    if (active) policy_draw<KIND>(A, i, e, eps);  // while the tower runs
+    if (ep.active) policy_draw<KIND>(A, i, e, eps);  // while the tower runs
     __syncthreads();  // the action means of step t are in LDS
     float a[NA], raw[NA], o[NO];
 #pragma unroll
     for (int k = 0; k < NA; ++k) { a[k] = 0.0f; raw[k] = 0.0f; }
-    if (active) (void)policy_sample_regs<NA>(s_mean + lane * 8, eps, stdv, lstd, raw, a);
+    if (ep.active) (void)policy_sample_regs<NA>(s_mean + lane * 8, eps, stdv, lstd, raw, a);
     int ns = 1;
     bool d = false, parked = false;
-    float rew;
-    // (every lane of the wave, dummies included: the substep's outline sweep is shared among all 64, SF_WIDE)
-    if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
-    else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
-    if (active) {
+    const float rew = env_wave_step<KIND, FORM>(Pl, s_hull, e, M, a, o, ns, d, parked, cnt TB_STAMP_PASS);
+    if (ep.active) {
       end_agent_step<KIND, RG, false>(A, i, e, M, parked, ns, (size_t)i, o, d, cnt);  // (tb_policy_evaluate claims a slot for every env)
-      if (!parked) ret += (double)rew;  // the 26th step's reward is the fast-forward's, folded in after the flush
-      len = t + 1;
-      if (d) {
-        cnt[5]++;
-        active = false;
-        idle_env(e);  // from here on this lane steps the dummy
-        M.n = 0; M.deep = 0;
-      } else {
-#pragma unroll
-        for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
-      }
+      (void)tally_step(ep, t, rew, parked, d, e, M, cnt);
+      if (!d) publish_obs<NO>(s_obs, lane, o);
     }
-    const bool go = __ballot(active) != 0ull;
-    if (lane == 0) s_go = go ? 1 : 0;
+    vote_go(s_go, lane, ep.active);
     __syncthreads();  // the observations after step t, and s_go, are in LDS
-    if (!(t + 1 < T_MAX && __builtin_amdgcn_readfirstlane(s_go) != 0)) break;
+    if (!loop_goes_on(s_go, t, T_MAX)) break;
   }
-  if (live) { ret_out[i] = ret; len_out[i] = len; }
+  if (live) { ret_out[i] = ep.ret; len_out[i] = ep.len; }
   flush_counters(A.counters, cnt);
   TB_DIAG_STAMPS_END(st);
 }

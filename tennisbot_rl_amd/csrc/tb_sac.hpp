@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void sac_polyak_kernel(const float* params, fl
 }
 
 // ------------------------------------------------------------------------------- whole episodes in one launch (tb_sac_evaluate)
-// tb_policy_evaluate_kernel's env side with SAC's / TQC's 256-wide actor inside the episode loop. A workgroup owns 16 envs and is
+// The whole-episode env wave (tb_kernels.hpp) with SAC's / TQC's 256-wide actor inside the episode loop. A workgroup owns 16 envs and is
 // FOUR waves, one per SIMD (__launch_bounds__(256): the env wave keeps the register budget it has in tb_policy_evaluate_kernel).
 // Waves 0-3 share the actor; wave 3 is also the env wave: the 16 envs' state in its registers, lanes >= 16 and lanes whose episode
 // is over step the dummy (idle_env). The actor does not fit registers or LDS (283 KB): its weights stream from global memory (L2)
@@ -387,7 +387,8 @@ __global__ __launch_bounds__(256) void sac_polyak_kernel(const float* params, fl
 //   (2)     all: s_h2 = relu(W1 s_h1 + b1)                                                             -> barrier 2  "h2 is in LDS"
 //   (3)     wave 0: s_head mu, wave 1: s_head log_std (from s_h2); env wave: draws the noise           -> barrier 3  "the head is in LDS"
 //   (4)     env wave: sample (s_head), trace (s_obs), env step, s_obs of the live envs, lane 0: s_go   -> barrier 4  "obs and s_go are in LDS"
-//           all: leave unless t + 1 < T_MAX && s_go -- the same t and the same word in every wave, hence the same verdict.
+//           all: leave unless loop_goes_on (tb_kernels.hpp, with the proof that every wave reaches the same verdict; the env wave's
+//           vote_go is in (4), the barrier that guards the next vote is barrier 3 of t + 1).
 // Who may overwrite what: s_h1 is next written in (1) of t + 1, behind barrier 4, its readers ((2) of t) are in front of barrier
 // 2; s_h2 is next written behind barrier 1 of t + 1, its readers ((3) of t) are in front of barrier 3; s_head is next written
 // behind barrier 2 of t + 1, its reader ((4) of t) is in front of barrier 4; s_obs and s_go are written behind barrier 3 only,
@@ -484,7 +485,7 @@ __global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalAr
   using L = SacLayout<KIND>;
   constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE, ENV_WAVE = 3;
   static_assert(NA == L::A && NO == L::O && E == 16 && NA <= 8, "the actor's rows are the envs of one slice");
-  constexpr int T_MAX = KIND == TB_ENV_SWING ? 26 : 1001;  // tb_es_rollout_kernel's: every episode is over by then
+  constexpr int T_MAX = episode_cap(KIND);
   __shared__ float4 s_hull[TB_HULL_LDS];
   __shared__ __attribute__((aligned(16))) float s_obs[E * NO];
   __shared__ __attribute__((aligned(16))) float s_h1[E * SAC_EV_STRIDE];
@@ -497,45 +498,33 @@ __global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalAr
   const int i = blockIdx.x * E + lane;
   const bool live = env_wave && lane < E && i < A.n;
   EnvRegs e;
-  idle_env(e);
-  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);  // the state tb_reset just wrote: the episode's start, no contacts cached
   Manifold M;
-  init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
+  enter_env_wave<KIND>(A, i, live, lane, !policy_rollout_rows_in_registers(KIND), e, M);  // the state tb_reset just wrote: the episode's start, no contacts cached
   uint32_t cnt[TB_N_COUNTERS] = {};
   if (env_wave && lane < E) {  // (rows without an env hold the dummy's observation: finite, and no row reads another)
     float o[NO];
     make_obs<KIND>(e, o);
-#pragma unroll
-    for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+    publish_obs<NO>(s_obs, lane, o);
   }
   __syncthreads();  // barrier 0: the outline table and the episodes' first observations are in LDS
-  KParams Pl = A.P;  // (the substep's constants in vector registers: see tb_policy_rollout_kernel)
-#if TB_HINT_POLICY_VGPR_PARAMS
-#define TB_PIN(f) asm volatile("" : "+v"(Pl.f))
-  TB_PIN(dt); TB_PIN(gravity); TB_PIN(lin_damp); TB_PIN(ang_damp); TB_PIN(lin_damp_quad); TB_PIN(ang_damp_quad); TB_PIN(max_ang_step); TB_PIN(contact_threshold);
-  TB_PIN(racket_inv_mass); TB_PIN(racket_inertia[0]); TB_PIN(racket_inertia[1]); TB_PIN(racket_inertia[2]);
-  TB_PIN(racket_inv_inertia[0]); TB_PIN(racket_inv_inertia[1]); TB_PIN(racket_inv_inertia[2]);
-  TB_PIN(racket_half_thick); TB_PIN(hull_margin); TB_PIN(hull_bound_radius); TB_PIN(ball_inv_mass); TB_PIN(ball_radius); TB_PIN(magnus_k); TB_PIN(static_top);
-#undef TB_PIN
-#endif
-  bool active = live;
-  double ret = 0.0;
-  int len = 0;
-  constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);  // tb_policy_evaluate_kernel's
+  KParams Pl = A.P;
+  pin_substep_params(Pl);
+  EpisodeTally ep = {live, 0.0, 0};
+  constexpr unsigned FORM = loop_step_form(RG, true, policy_rollout_rows_in_registers(KIND));
   TB_DIAG_STAMPS_BEGIN(st);
   for (int t = 0;; ++t) {
     sac_actor_stage<KIND>(S.actor, s_obs, s_h1, s_h2, s_head, wave, g, er);
     float eps[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) eps[k] = 0.0f;
-    if (env_wave && active) policy_draw<KIND>(A, i, e, eps);  // while the head runs
+    if (env_wave && ep.active) policy_draw<KIND>(A, i, e, eps);  // while the head runs
     __syncthreads();  // barrier 3: the head is in LDS
     if (env_wave) {
       float a[NA], o[NO];
 #pragma unroll
       for (int k = 0; k < NA; ++k) a[k] = 0.0f;
-      const bool rec = active && t < S.t_max;
-      if (active) {
+      const bool rec = ep.active && t < S.t_max;
+      if (ep.active) {
 #pragma unroll
         for (int k = 0; k < NA; ++k) {
           float ls;
@@ -551,36 +540,22 @@ __global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalAr
       }
       int ns = 1;
       bool d = false, parked = false;
-      float rew;
-      // (every lane of the wave, dummies included: the substep's outline sweep is shared among all 64, SF_WIDE)
-      if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
-      else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
-      if (active) {
+      float rew = env_wave_step<KIND, FORM>(Pl, s_hull, e, M, a, o, ns, d, parked, cnt TB_STAMP_PASS);
+      if (ep.active) {
         end_agent_step<KIND, RG, false>(A, i, e, M, parked, ns, (size_t)i, o, d, cnt);  // (tb_sac_evaluate claims a slot for every env)
-        if (parked) rew = 0.0f;  // the 26th step: its reward is the fast-forward's, folded in after the flush
-        else ret += (double)rew;
-        len = t + 1;
+        rew = tally_step(ep, t, rew, parked, d, e, M, cnt);
         if (rec) {
           S.t_rew[(size_t)t * A.n + i] = rew;
           S.t_done[(size_t)t * A.n + i] = d ? 1 : 0;
         }
-        if (d) {
-          cnt[5]++;
-          active = false;
-          idle_env(e);  // from here on this lane steps the dummy
-          M.n = 0; M.deep = 0;
-        } else {
-#pragma unroll
-          for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
-        }
+        if (!d) publish_obs<NO>(s_obs, lane, o);
       }
-      const bool go = __ballot(active) != 0ull;
-      if (lane == 0) s_go = go ? 1 : 0;
+      vote_go(s_go, lane, ep.active);
     }
     __syncthreads();  // barrier 4: the observations after step t, and s_go, are in LDS
-    if (!(t + 1 < T_MAX && __builtin_amdgcn_readfirstlane(s_go) != 0)) break;
+    if (!loop_goes_on(s_go, t, T_MAX)) break;
   }
-  if (live) { S.ret[i] = ret; S.len[i] = len; }
+  if (live) { S.ret[i] = ep.ret; S.len[i] = ep.len; }
   if (env_wave) flush_counters(A.counters, cnt);
   TB_DIAG_STAMPS_END(st);
 }
@@ -628,30 +603,20 @@ __global__ void __launch_bounds__(256) tb_sac_collect_kernel(KArgs A, SacCollect
   const int i = blockIdx.x * E + lane;
   const bool live = env_wave && lane < E && i < A.n;
   EnvRegs e;
-  idle_env(e);
-  if (live) load_env<KIND>(A.words, A.done_state, A.n, i, e);
   Manifold M;
-  init_manifold(M, lane, 64, !policy_rollout_rows_in_registers(KIND));
+  enter_env_wave<KIND>(A, i, live, lane, !policy_rollout_rows_in_registers(KIND), e, M);
   const bool had_contacts = load_contacts<RG>(A, i, live, M);
   uint32_t cnt[TB_N_COUNTERS] = {};
   bool any_reset = false;
   if (env_wave && lane < E) {  // (rows without an env hold the dummy's observation: finite, and no row reads another)
     float o[NO];
     make_obs<KIND>(e, o);  // what the step that left this state returned (tennis_step / end_agent_step / restart_episode: make_obs all)
-#pragma unroll
-    for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+    publish_obs<NO>(s_obs, lane, o);
   }
   __syncthreads();  // barrier 0: the outline table and the observations the first step acts on are in LDS
-  KParams Pl = A.P;  // (the substep's constants in vector registers: see tb_policy_rollout_kernel)
-#if TB_HINT_POLICY_VGPR_PARAMS
-#define TB_PIN(f) asm volatile("" : "+v"(Pl.f))
-  TB_PIN(dt); TB_PIN(gravity); TB_PIN(lin_damp); TB_PIN(ang_damp); TB_PIN(lin_damp_quad); TB_PIN(ang_damp_quad); TB_PIN(max_ang_step); TB_PIN(contact_threshold);
-  TB_PIN(racket_inv_mass); TB_PIN(racket_inertia[0]); TB_PIN(racket_inertia[1]); TB_PIN(racket_inertia[2]);
-  TB_PIN(racket_inv_inertia[0]); TB_PIN(racket_inv_inertia[1]); TB_PIN(racket_inv_inertia[2]);
-  TB_PIN(racket_half_thick); TB_PIN(hull_margin); TB_PIN(hull_bound_radius); TB_PIN(ball_inv_mass); TB_PIN(ball_radius); TB_PIN(magnus_k); TB_PIN(static_top);
-#undef TB_PIN
-#endif
-  constexpr unsigned FORM = (RG ? SF_RG : 0u) | SF_COLD | SF_WIDE | (policy_rollout_rows_in_registers(KIND) ? SF_REGROWS : 0u);  // tb_policy_rollout_kernel<KIND, 1>'s
+  KParams Pl = A.P;
+  pin_substep_params(Pl);
+  constexpr unsigned FORM = loop_step_form(RG, true, policy_rollout_rows_in_registers(KIND));
   TB_DIAG_STAMPS_BEGIN(st);
   for (int t = 0; t < S.n_steps; ++t) {
     if (!uniform) sac_actor_stage<KIND>(S.actor, s_obs, s_h1, s_h2, s_head, wave, g, er);
@@ -682,18 +647,11 @@ __global__ void __launch_bounds__(256) tb_sac_collect_kernel(KArgs A, SacCollect
       }
       int ns = 1;
       bool parked = false;
-      // (every lane of the wave, dummies included: the substep's outline sweep is shared among all 64, SF_WIDE)
-      if (KIND == TB_ENV_SWING) rew = swing_step<FORM>(Pl, s_hull, e, M, a, ns, cnt, true, parked TB_STAMP_PASS);
-      else rew = tennis_step<FORM>(Pl, s_hull, e, M, a, o, d, cnt TB_STAMP_PASS);
+      rew = env_wave_step<KIND, FORM>(Pl, s_hull, e, M, a, o, ns, d, parked, cnt TB_STAMP_PASS);
       if (live) {
         end_agent_step<KIND, RG, true>(A, i, e, M, parked, ns, row, o, d, cnt);  // (a parked step's reward: the fast-forward's, into S.reward[row])
-        if (d) {  // (the host requires TB_F_AUTO_RESET)
-          cnt[5]++;
-          restart_episode<KIND>(A, s_hull + TB_HULL_KP, i, e, M, o);
-          any_reset = true;
-        }
-#pragma unroll
-        for (int k = 0; k < NO; ++k) s_obs[lane * NO + k] = o[k];
+        if (d) restart_on_done<KIND>(A, s_hull, i, e, M, o, cnt, any_reset);
+        publish_obs<NO>(s_obs, lane, o);
       }
     }
     __syncthreads();  // barrier 4: the observations step t + 1 acts on are in LDS

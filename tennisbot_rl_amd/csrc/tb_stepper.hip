@@ -20,6 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
+#include <type_traits>
 
 #include "../../include/tb_stepper.h"
 #include "tb_device.hpp"
@@ -149,6 +150,7 @@ int capture_status(hipStream_t s, hipStreamCaptureStatus* st) { *st = hipStreamC
 #define TB_DEFER_MAX_ENVS 131072  // deferred stragglers: a small-batch scheme (large batches run the fast-forward in phases)
 #define TB_TWO_WAVE_MAX_ENVS 16384  // the two-wave step kernel up to here (auto)
 constexpr int kEpisodeSteps = 26;  // a SwingRacket episode is exactly this many agent steps (the kernels keep their own 25 / 26)
+static_assert(kEpisodeSteps == episode_cap(TB_ENV_SWING), "the whole-episode kernels' trip limit is the episode's length");
 constexpr size_t kSealedWord = (size_t)TB_N_COUNTERS * TB_COUNTER_SHARDS;  // the counter block: [TB_COUNTER_SHARDS][TB_N_COUNTERS] ...
 constexpr size_t kCounterWords = kSealedWord + 1;  // ... + one word: substeps booked by the pool's sealed-fate exit
 
@@ -361,7 +363,6 @@ size_t pool_rec(const TbHandle* h) { return extended_contacts(h->kp) ? ff_rec<tr
 // any other is null (nothing is built for it) and its launch fails.
 using StepKernel = void (*)(const uint32_t*, const uint8_t*, const float*, const float4*, int, int, KArgs);
 using ArgsKernel = void (*)(KArgs);
-using ArgsKernel2 = void (*)(KArgs, EsArgs);
 
 // tb_step_kernel<KIND, LEAN, MULTI, RG, POLICY>; the fused policy step runs one step per launch (Tennisbot: with either network)
 template <int KIND, bool LEAN>
@@ -394,11 +395,26 @@ ArgsKernel ff_kernel(bool rg, bool big, bool esc, bool pool) {
   return big ? tb_ff_kernel<false, true> : tb_ff_kernel<false, false>;
 }
 
-// tb_policy_rollout_kernel<KIND, S, RG, NET>: every combination (S = 1 or 3 env slices per workgroup)
-template <int KIND, int NET = TB_NET_DEFAULT>
-ArgsKernel policy_rollout_kernel(int slices, bool rg) {
-  if (slices == 1) return rg ? tb_policy_rollout_kernel<KIND, 1, true, NET> : tb_policy_rollout_kernel<KIND, 1, false, NET>;
-  return slices == 3 ? (rg ? tb_policy_rollout_kernel<KIND, 3, true, NET> : tb_policy_rollout_kernel<KIND, 3, false, NET>) : nullptr;
+// The loop kernels' selectors. `pick` is a generic lambda that names the kernel template once, with its parameters taken from the
+// types of its arguments: [](auto K, auto R) { return tb_es_rollout_kernel<K.value, R.value>; }
+template <int V> using Int = std::integral_constant<int, V>;
+// (kind, RG): tb_es_rollout_kernel, tb_sac_evaluate_kernel, tb_sac_collect_kernel
+template <class F>
+auto kernel_of_kind_rg(int kind, bool rg, F pick) {
+  if (kind == TB_ENV_SWING) return rg ? pick(Int<TB_ENV_SWING>{}, std::true_type{}) : pick(Int<TB_ENV_SWING>{}, std::false_type{});
+  return rg ? pick(Int<TB_ENV_TENNIS>{}, std::true_type{}) : pick(Int<TB_ENV_TENNIS>{}, std::false_type{});
+}
+// (kind, net, RG): tb_policy_evaluate_kernel, tb_policy_rollout_kernel. THE (kind, net) PAIRS THESE LAUNCHES ARE BUILT FOR: every kind's
+// own network, SwingRacket's [64, 64], Tennisbot's tuned one -- the pairs policy_net_ok lets through; any other is null, and its launch
+// a refusal.
+template <class F>
+auto kernel_of_kind_net_rg(int kind, int net, bool rg, F pick) -> decltype(pick(Int<TB_ENV_SWING>{}, Int<TB_NET_DEFAULT>{}, std::false_type{})) {
+  const auto with_rg = [&](auto K, auto N) { return rg ? pick(K, N, std::true_type{}) : pick(K, N, std::false_type{}); };
+  if (kind == TB_ENV_SWING && net == TB_NET_DEFAULT) return with_rg(Int<TB_ENV_SWING>{}, Int<TB_NET_DEFAULT>{});
+  if (kind == TB_ENV_SWING && net == TB_NET_MLP64) return with_rg(Int<TB_ENV_SWING>{}, Int<TB_NET_MLP64>{});
+  if (kind == TB_ENV_TENNIS && net == TB_NET_DEFAULT) return with_rg(Int<TB_ENV_TENNIS>{}, Int<TB_NET_DEFAULT>{});
+  if (kind == TB_ENV_TENNIS && net == TB_NET_TUNED) return with_rg(Int<TB_ENV_TENNIS>{}, Int<TB_NET_TUNED>{});
+  return nullptr;
 }
 
 // the fast-forward family's one launch: one-wave workgroups on stream q
@@ -665,33 +681,91 @@ int launch_step(TbHandle* h, int T, const float* actions, float* obs, float* rew
   return TB_OK;
 }
 
+// ---- the two host paths of the kernels that step envs in a loop with a network in front of them (tb_kernels.hpp, "THE ENV WAVE")
+int refusal(int code, const char* who, const char* what) {
+  char msg[320];
+  snprintf(msg, sizeof msg, "%s%s", who, what);
+  return fail(code, msg);
+}
+// the workgroups of the kernels whose env wave holds one slice of TB_POLICY_SLICE envs (their dynamic LDS: that wave's columns)
+dim3 slice_groups(const TbHandle* h) { return dim3((unsigned)((h->n + TB_POLICY_SLICE - 1) / TB_POLICY_SLICE)); }
+
+// WHOLE EPISODES of every env, one launch (tb_es_evaluate, tb_policy_evaluate, tb_sac_evaluate; `who` names the entry point, which has
+// checked its own arguments: nothing is allocated, reset or launched before this). Every env is reset, runs through its first `done`,
+// and the state words are not written: on return every env is at its episode's start, phase 0, as tb_reset left it. SwingRacket's
+// 26th step parks its fast-forward, whose reward goes to d_es_rew; behind the flush tb_es_fold_kernel adds it to return_dev, and to
+// row 25 of a trace's reward (trace_rew, of trace_steps rows) that reaches so far. `issue(a, rg, s)` is the one kernel launch.
+template <class Launch>
+int run_whole_episodes(TbHandle* h, const char* who, const PolicyIO* pol, double* return_dev, int trace_steps, float* trace_rew, void* stream, Launch issue) {
+  const bool swing = h->kind == TB_ENV_SWING;
+  if (swing && !h->pipeline)
+    return refusal(TB_E_UNSUPPORTED, who, " on SwingRacket-v0 needs tb_set_pipeline(h, 1): the 26th step's fast-forward runs on the pipeline's kernels");
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (swing && !h->d_es_rew) HIP_TRY(hipMalloc((void**)&h->d_es_rew, sizeof(float) * (size_t)h->n));
+  if (int rc = tb_reset(h, nullptr, nullptr, stream)) return rc;  // (flushes the pipeline; every env in lockstep at phase 0)
+  KArgs a = base_args(h);
+  if (pol) pol->apply(a);
+  a.reward = h->d_es_rew;  // (SwingRacket: the fast-forward's destination for the 26th step's reward)
+  Park park;
+  if (int rc = claim_park(h, swing, a, s, &park)) return rc;  // (a slot for every env)
+  (void)hipGetLastError();
+  if (int rc = issue(a, extended_contacts(h->kp), s)) return rc;
+  if (swing) {
+    if (int rc = finish_park(h, park, a, 0, s)) return rc;
+    if (int rc = flush_all(h, s)) return rc;  // every fast-forward's reward is in d_es_rew once `s` gets past here
+    float* const last_rew = trace_steps >= kEpisodeSteps ? trace_rew : nullptr;  // (a trace that reaches the episode's last step)
+    if (int rc = launch(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n, last_rew)) return rc;
+  }
+  return TB_OK;
+}
+
+// T STEPS FROM THE HANDLE'S STATE, one launch, episodes restarting inside it (tb_policy_rollout's launches, tb_sac_collect). What
+// both refuse:
+int refuse_steps_from_state(const TbHandle* h, const char* who) {
+  if (!(h->kp.flags & TB_F_AUTO_RESET)) return refusal(TB_E_UNSUPPORTED, who, " needs TB_F_AUTO_RESET (episodes must restart inside the launch)");
+  if (h->kind == TB_ENV_SWING && !(h->pipeline && h->phase.valid))
+    return refusal(TB_E_UNSUPPORTED, who, " on SwingRacket-v0 needs tb_set_pipeline(h, 1) and episodes in lockstep (every env reset together): "
+                                          "the fast-forward that ends an episode cannot run inside a multi-step launch");
+  return TB_OK;
+}
+// SwingRacket: the caller keeps T inside the episode, so only a launch that ends where the episodes do parks anything; the parked
+// step's reward goes to row T - 1 of a.reward (rows reward_step_stride apart). `issue(a, rg)` is the one kernel launch. flush: every
+// output, the terminal reward included, is in place once `s` gets past the call.
+template <class Launch>
+int run_steps_from_state(TbHandle* h, int T, KArgs a, size_t reward_step_stride, bool flush, hipStream_t s, Launch issue) {
+  if (int rc = count_first_substeps(h, T, s)) return rc;
+  const bool swing = h->kind == TB_ENV_SWING;
+  const bool may_park = swing && h->phase.launch_ends_episode(T);
+  Park park;
+  if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
+  (void)hipGetLastError();
+  if (int rc = issue(a, extended_contacts(h->kp))) return rc;
+  if (int rc = finish_park(h, park, a, reward_step_stride, s)) return rc;
+  if (flush && swing) {
+    if (int rc = flush_all(h, s)) return rc;
+  }
+  h->phase.advance(T);
+  return TB_OK;
+}
+
 // one launch of tb_policy_rollout_kernel over T steps; SwingRacket: T ends where the episode does
 int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, float* reward, uint8_t* done, const size_t* st /*element strides*/,
                           hipStream_t s) {
-  if (int rc = count_first_substeps(h, T, s)) return rc;
   KArgs a = base_args(h);
   pol.apply(a);
   a.obs = obs; a.reward = reward; a.done_out = done; a.T = T;
   a.st_act = st[0]; a.st_raw = st[1]; a.st_logp = st[2]; a.st_val = st[3]; a.st_obs = st[4]; a.st_rew = st[5]; a.st_done = st[6];
-  const bool swing = h->kind == TB_ENV_SWING;
-  const bool may_park = swing && h->phase.launch_ends_episode(T);  // (the caller checked pipeline, lockstep phase and that T stays inside the episode)
-  Park park;
-  if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
-  // 16 envs per workgroup (3 waves) while every workgroup still gets a CU of its own, else 48 (7 waves): see the kernel
-  const bool narrow = h->opt.policy_slices ? h->opt.policy_slices == 1 : h->n <= 4096;
-  const int E = narrow ? TB_POLICY_SLICE : 3 * TB_POLICY_SLICE;
-  dim3 grid((unsigned)((h->n + E - 1) / E)), block(narrow ? 192 : 448);
-  const bool rg = extended_contacts(h->kp);
-  const ArgsKernel kern = swing ? (pol.net == TB_NET_MLP64 ? policy_rollout_kernel<TB_ENV_SWING, TB_NET_MLP64>(narrow ? 1 : 3, rg)
-                                                           : policy_rollout_kernel<TB_ENV_SWING>(narrow ? 1 : 3, rg))
-                          : pol.net == TB_NET_TUNED ? policy_rollout_kernel<TB_ENV_TENNIS, TB_NET_TUNED>(narrow ? 1 : 3, rg)
-                                                    : policy_rollout_kernel<TB_ENV_TENNIS>(narrow ? 1 : 3, rg);
-  if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_rollout_kernel instantiation for this variant");
-  (void)hipGetLastError();
-  if (int rc = launch(kern, grid, block, dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a)) return rc;  // (the env wave's columns)
-  if (int rc = finish_park(h, park, a, st[5], s)) return rc;
-  h->phase.advance(T);
-  return TB_OK;
+  return run_steps_from_state(h, T, a, st[5], false, s, [&](const KArgs& k, bool rg) {
+    // 16 envs per workgroup (3 waves) while every workgroup still gets a CU of its own, else 48 (7 waves): see the kernel
+    const bool narrow = h->opt.policy_slices ? h->opt.policy_slices == 1 : h->n <= 4096;
+    const int E = narrow ? TB_POLICY_SLICE : 3 * TB_POLICY_SLICE;
+    const ArgsKernel kern = kernel_of_kind_net_rg(h->kind, pol.net, rg, [&](auto K, auto N, auto R) -> ArgsKernel {
+      return narrow ? tb_policy_rollout_kernel<K.value, 1, R.value, N.value> : tb_policy_rollout_kernel<K.value, 3, R.value, N.value>;
+    });
+    if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_rollout_kernel instantiation for this variant");
+    return launch(kern, dim3((unsigned)((h->n + E - 1) / E)), dim3(narrow ? 192 : 448), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, k);  // (the env wave's columns)
+  });
 }
 
 // every fast-forward's result in place, then `bytes` of device memory read back; the host has them on return
@@ -1120,11 +1194,8 @@ int tb_policy_rollout_net(TbHandle* h, int net, int n_steps, const float* weight
     return fail(TB_E_INVAL, "tb_policy_rollout: null argument");
   if (n_steps < 1) return fail(TB_E_INVAL, "tb_policy_rollout: n_steps must be >= 1");
   if (int rc = policy_net_ok(h->kind, net, "tb_policy_rollout")) return rc;
-  if (!(h->kp.flags & TB_F_AUTO_RESET)) return fail(TB_E_UNSUPPORTED, "tb_policy_rollout needs TB_F_AUTO_RESET (episodes must restart inside the launch)");
+  if (int rc = refuse_steps_from_state(h, "tb_policy_rollout")) return rc;
   const bool swing = h->kind == TB_ENV_SWING;
-  if (swing && !(h->pipeline && h->phase.valid))
-    return fail(TB_E_UNSUPPORTED, "tb_policy_rollout on SwingRacket-v0 needs tb_set_pipeline(h, 1) and episodes in lockstep (every env reset together): "
-                                  "the fast-forward that ends an episode cannot run inside a multi-step launch");
   const size_t n = (size_t)h->n, A = swing ? TB_SWING_ACT_DIM : TB_TENNIS_ACT_DIM, O = swing ? TB_SWING_OBS_DIM : TB_TENNIS_OBS_DIM;
   size_t st[7] = {n * A, n * A, n, n, n * O, n, n};  // elements per step: actions, raw, logp, value, obs, reward, done
   if (step_strides_bytes) {
@@ -1160,11 +1231,8 @@ int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t 
   if (!h || !weights_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_es_evaluate: null argument");
   if (n_members < 1 || envs_per_member < 1 || (long long)n_members * envs_per_member != h->n)
     return fail(TB_E_INVAL, "tb_es_evaluate: n_members * envs_per_member must equal n_envs (both >= 1)");
-  const bool swing = h->kind == TB_ENV_SWING;
   if (weights_stride_floats % 4 || weights_stride_floats < (size_t)tb_es_floats(h->kind) || reinterpret_cast<uintptr_t>(weights_dev) % 16)
     return fail(TB_E_INVAL, "tb_es_evaluate: the weights' row stride must be a multiple of 4 floats and >= tb_es_floats, the base 16-byte aligned");
-  if (swing && !h->pipeline)
-    return fail(TB_E_UNSUPPORTED, "tb_es_evaluate on SwingRacket-v0 needs tb_set_pipeline(h, 1): the 26th step's fast-forward runs on the pipeline's kernels");
   EsArgs E;
   memset(&E, 0, sizeof E);
   E.weights = weights_dev; E.stride = weights_stride_floats; E.per_member = envs_per_member; E.ret = return_dev; E.len = length_dev;
@@ -1175,77 +1243,29 @@ int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t 
     E.t_max = trace->max_steps; E.t_net_in = trace->net_in; E.t_obs = trace->obs; E.t_act = trace->actions; E.t_raw = trace->raw;
     E.t_rew = trace->reward; E.t_done = trace->done;
   }
-  DeviceGuard g(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  if (swing && !h->d_es_rew) HIP_TRY(hipMalloc((void**)&h->d_es_rew, sizeof(float) * (size_t)h->n));
-  if (int rc = tb_reset(h, nullptr, nullptr, stream)) return rc;  // (flushes the pipeline; every env in lockstep at phase 0)
-  KArgs a = base_args(h);
-  a.reward = h->d_es_rew;  // (SwingRacket: the fast-forward's destination for the 26th step's reward)
-  Park park;
-  if (int rc = claim_park(h, swing, a, s, &park)) return rc;
-  const bool rg = extended_contacts(h->kp);
-  ArgsKernel2 kern = swing ? (rg ? tb_es_rollout_kernel<TB_ENV_SWING, true> : tb_es_rollout_kernel<TB_ENV_SWING, false>)
-                           : (rg ? tb_es_rollout_kernel<TB_ENV_TENNIS, true> : tb_es_rollout_kernel<TB_ENV_TENNIS, false>);
-  (void)hipGetLastError();
-  if (int rc = launch(kern, dim3((unsigned)((h->n + 63) / 64)), dim3(64), dyn_lds(es_lds_words(h->kind, rg), 64), s, a, E)) return rc;
-  if (swing) {
-    if (int rc = finish_park(h, park, a, 0, s)) return rc;
-    if (int rc = flush_all(h, s)) return rc;  // every fast-forward's reward is in d_es_rew once `s` gets past here
-    float* const last_rew = E.t_max >= kEpisodeSteps ? E.t_rew : nullptr;  // (a trace that reaches the episode's last step)
-    if (int rc = launch(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n, last_rew)) return rc;
-  }
-  return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
+  return run_whole_episodes(h, "tb_es_evaluate", nullptr, return_dev, E.t_max, E.t_rew, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
+    const auto kern = kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_es_rollout_kernel<K.value, R.value>; });
+    return launch(kern, dim3((unsigned)((h->n + 63) / 64)), dim3(64), dyn_lds(es_lds_words(h->kind, rg), 64), s, a, E);
+  });
 }
-
-namespace {
-// tb_policy_evaluate_kernel<KIND, RG, NET>: the (kind, RG, net) combinations of tb_policy_rollout_kernel
-using EvalKernel = void (*)(KArgs, double*, int32_t*);
-EvalKernel policy_evaluate_kernel(int kind, bool rg, int net) {
-  if (kind == TB_ENV_SWING && net == TB_NET_MLP64)
-    return rg ? tb_policy_evaluate_kernel<TB_ENV_SWING, true, TB_NET_MLP64> : tb_policy_evaluate_kernel<TB_ENV_SWING, false, TB_NET_MLP64>;
-  if (kind == TB_ENV_SWING) return rg ? tb_policy_evaluate_kernel<TB_ENV_SWING, true> : tb_policy_evaluate_kernel<TB_ENV_SWING, false>;
-  if (net == TB_NET_TUNED) return rg ? tb_policy_evaluate_kernel<TB_ENV_TENNIS, true, TB_NET_TUNED> : tb_policy_evaluate_kernel<TB_ENV_TENNIS, false, TB_NET_TUNED>;
-  return rg ? tb_policy_evaluate_kernel<TB_ENV_TENNIS, true> : tb_policy_evaluate_kernel<TB_ENV_TENNIS, false>;
-}
-}  // namespace
 
 int tb_policy_evaluate(TbHandle* h, int net, const float* weights_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
                        void* stream) {
   if (!h || !weights_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_policy_evaluate: null argument");
   if (int rc = policy_net_ok(h->kind, net, "tb_policy_evaluate")) return rc;
-  const bool swing = h->kind == TB_ENV_SWING;
-  if (swing && !h->pipeline)
-    return fail(TB_E_UNSUPPORTED, "tb_policy_evaluate on SwingRacket-v0 needs tb_set_pipeline(h, 1): the 26th step's fast-forward runs on the pipeline's kernels");
-  DeviceGuard g(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  if (swing && !h->d_es_rew) HIP_TRY(hipMalloc((void**)&h->d_es_rew, sizeof(float) * (size_t)h->n));
-  if (int rc = tb_reset(h, nullptr, nullptr, stream)) return rc;  // (flushes the pipeline; every env in lockstep at phase 0)
-  KArgs a = base_args(h);
-  a.pol_weights = weights_dev; a.pol_seed = noise_seed; a.pol_deterministic = deterministic;
-  a.reward = h->d_es_rew;  // (SwingRacket: the fast-forward's destination for the 26th step's reward)
-  Park park;
-  if (int rc = claim_park(h, swing, a, s, &park)) return rc;
-  const bool rg = extended_contacts(h->kp);
-  const unsigned groups = (unsigned)((h->n + TB_POLICY_SLICE - 1) / TB_POLICY_SLICE);
-  (void)hipGetLastError();
-  if (int rc = launch(policy_evaluate_kernel(h->kind, rg, net), dim3(groups), dim3(128), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, return_dev,
-                      length_dev))
-    return rc;  // (dynamic LDS: the env wave's columns)
-  if (swing) {
-    if (int rc = finish_park(h, park, a, 0, s)) return rc;
-    if (int rc = flush_all(h, s)) return rc;  // every fast-forward's reward is in d_es_rew once `s` gets past here
-    if (int rc = launch(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n, (float*)nullptr)) return rc;
-  }
-  return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
+  PolicyIO pol = {};
+  pol.weights = weights_dev; pol.seed = noise_seed; pol.deterministic = deterministic; pol.net = net;
+  return run_whole_episodes(h, "tb_policy_evaluate", &pol, return_dev, 0, nullptr, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
+    const auto kern = kernel_of_kind_net_rg(h->kind, net, rg, [](auto K, auto N, auto R) { return tb_policy_evaluate_kernel<K.value, R.value, N.value>; });
+    if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_evaluate_kernel instantiation for this variant");
+    return launch(kern, slice_groups(h), dim3(128), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, return_dev, length_dev);
+  });
 }
 
-// tb_policy_evaluate's body with SAC's / TQC's actor inside the loop (tb_sac.hpp, tb_sac_evaluate_kernel), four waves per 16 envs
+// SAC's / TQC's actor inside the episode loop (tb_sac.hpp, tb_sac_evaluate_kernel), four waves per 16 envs
 int tb_sac_evaluate(TbHandle* h, const float* actor_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
                     const TbSacEvalTrace* trace, void* stream) {
   if (!h || !actor_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_sac_evaluate: null argument");
-  const bool swing = h->kind == TB_ENV_SWING;
-  if (swing && !h->pipeline)
-    return fail(TB_E_UNSUPPORTED, "tb_sac_evaluate on SwingRacket-v0 needs tb_set_pipeline(h, 1): the 26th step's fast-forward runs on the pipeline's kernels");
   SacEvalArgs S;
   memset(&S, 0, sizeof S);
   S.actor = actor_dev; S.ret = return_dev; S.len = length_dev;
@@ -1256,31 +1276,15 @@ int tb_sac_evaluate(TbHandle* h, const float* actor_dev, double* return_dev, int
       S.t_max = trace->max_steps; S.t_obs = trace->obs; S.t_eps = trace->eps; S.t_act = trace->actions; S.t_rew = trace->reward; S.t_done = trace->done;
     }
   }
-  DeviceGuard g(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  if (swing && !h->d_es_rew) HIP_TRY(hipMalloc((void**)&h->d_es_rew, sizeof(float) * (size_t)h->n));
-  if (int rc = tb_reset(h, nullptr, nullptr, stream)) return rc;  // (flushes the pipeline; every env in lockstep at phase 0)
-  KArgs a = base_args(h);
-  a.pol_seed = noise_seed; a.pol_deterministic = deterministic;
-  a.reward = h->d_es_rew;  // (SwingRacket: the fast-forward's destination for the 26th step's reward)
-  Park park;
-  if (int rc = claim_park(h, swing, a, s, &park)) return rc;
-  const bool rg = extended_contacts(h->kp);
-  void (*kern)(KArgs, SacEvalArgs) = swing ? (rg ? tb_sac_evaluate_kernel<TB_ENV_SWING, true> : tb_sac_evaluate_kernel<TB_ENV_SWING, false>)
-                                           : (rg ? tb_sac_evaluate_kernel<TB_ENV_TENNIS, true> : tb_sac_evaluate_kernel<TB_ENV_TENNIS, false>);
-  const unsigned groups = (unsigned)((h->n + TB_POLICY_SLICE - 1) / TB_POLICY_SLICE);
-  (void)hipGetLastError();
-  if (int rc = launch(kern, dim3(groups), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S)) return rc;  // (dynamic LDS: the env wave's columns)
-  if (swing) {
-    if (int rc = finish_park(h, park, a, 0, s)) return rc;
-    if (int rc = flush_all(h, s)) return rc;  // every fast-forward's reward is in d_es_rew once `s` gets past here
-    float* const last_rew = S.t_max >= kEpisodeSteps ? S.t_rew : nullptr;  // (a trace that reaches the episode's last step)
-    if (int rc = launch(tb_es_fold_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->d_es_rew, return_dev, h->n, last_rew)) return rc;
-  }
-  return TB_OK;  // (the state words were not written: every env is at its episode's start, phase 0, as tb_reset left it)
+  PolicyIO pol = {};
+  pol.seed = noise_seed; pol.deterministic = deterministic;
+  return run_whole_episodes(h, "tb_sac_evaluate", &pol, return_dev, S.t_max, S.t_rew, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
+    const auto kern = kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_sac_evaluate_kernel<K.value, R.value>; });
+    return launch(kern, slice_groups(h), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S);
+  });
 }
 
-// tb_policy_rollout's host path around tb_sac_collect_kernel (tb_sac.hpp): one launch, the caller's ring rows as outputs
+// tb_sac_collect_kernel (tb_sac.hpp): one launch, the caller's ring rows as outputs
 int tb_sac_collect(TbHandle* h, const float* actor_dev, int n_steps, int mode, uint64_t noise_seed, const TbSacCollectOut* out, void* stream) {
   if (!h || !out) return fail(TB_E_INVAL, "tb_sac_collect: null argument");
   if (out->struct_size != sizeof(TbSacCollectOut)) return fail(TB_E_INVAL, "tb_sac_collect: TbSacCollectOut.struct_size is not sizeof(TbSacCollectOut)");
@@ -1288,11 +1292,8 @@ int tb_sac_collect(TbHandle* h, const float* actor_dev, int n_steps, int mode, u
   if (mode != TB_SAC_COLLECT_ACTOR && mode != TB_SAC_COLLECT_UNIFORM) return fail(TB_E_INVAL, "tb_sac_collect: unknown mode");
   if (mode == TB_SAC_COLLECT_ACTOR && !actor_dev) return fail(TB_E_INVAL, "tb_sac_collect: actor_dev is null in actor mode");
   if (n_steps < 1) return fail(TB_E_INVAL, "tb_sac_collect: n_steps must be >= 1");
-  if (!(h->kp.flags & TB_F_AUTO_RESET)) return fail(TB_E_UNSUPPORTED, "tb_sac_collect needs TB_F_AUTO_RESET (episodes must restart inside the launch)");
+  if (int rc = refuse_steps_from_state(h, "tb_sac_collect")) return rc;
   const bool swing = h->kind == TB_ENV_SWING;
-  if (swing && !(h->pipeline && h->phase.valid))
-    return fail(TB_E_UNSUPPORTED, "tb_sac_collect on SwingRacket-v0 needs tb_set_pipeline(h, 1) and episodes in lockstep (every env reset together): "
-                                  "the fast-forward that ends an episode cannot run inside a multi-step launch");
   if (swing && h->phase.at + n_steps > kEpisodeSteps)
     return fail(TB_E_INVAL, "tb_sac_collect on SwingRacket-v0: the launch must end where the episodes do at the latest (phase + n_steps <= 26)");
   const uintptr_t row_align = swing ? 8 : 16;  // write_obs: float2 / float4 stores
@@ -1302,7 +1303,6 @@ int tb_sac_collect(TbHandle* h, const float* actor_dev, int n_steps, int mode, u
     return fail(TB_E_INVAL, "tb_sac_collect: obs / next_obs must be 16-byte aligned (SwingRacket-v0: 8), action / eps 8-byte, reward / done 4-byte");
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = count_first_substeps(h, n_steps, s)) return rc;
   SacCollectArgs S;
   memset(&S, 0, sizeof S);
   S.actor = actor_dev; S.n_steps = n_steps; S.uniform = mode == TB_SAC_COLLECT_UNIFORM;
@@ -1310,21 +1310,10 @@ int tb_sac_collect(TbHandle* h, const float* actor_dev, int n_steps, int mode, u
   KArgs a = base_args(h);
   a.pol_seed = noise_seed; a.pol_deterministic = 0;
   a.reward = out->reward; a.T = n_steps;  // (SwingRacket: the fast-forward's destination is the row of the launch's last step)
-  const bool may_park = swing && h->phase.launch_ends_episode(n_steps);
-  Park park;
-  if (int rc = claim_park(h, may_park, a, s, &park)) return rc;
-  const bool rg = extended_contacts(h->kp);
-  void (*kern)(KArgs, SacCollectArgs) = swing ? (rg ? tb_sac_collect_kernel<TB_ENV_SWING, true> : tb_sac_collect_kernel<TB_ENV_SWING, false>)
-                                              : (rg ? tb_sac_collect_kernel<TB_ENV_TENNIS, true> : tb_sac_collect_kernel<TB_ENV_TENNIS, false>);
-  const unsigned groups = (unsigned)((h->n + TB_POLICY_SLICE - 1) / TB_POLICY_SLICE);
-  (void)hipGetLastError();
-  if (int rc = launch(kern, dim3(groups), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S)) return rc;  // (dynamic LDS: the env wave's columns)
-  if (int rc = finish_park(h, park, a, (size_t)h->n, s)) return rc;
-  if (swing) {
-    if (int rc = flush_all(h, s)) return rc;  // every output, the terminal reward included, is in place once `s` gets past here
-  }
-  h->phase.advance(n_steps);
-  return TB_OK;
+  return run_steps_from_state(h, n_steps, a, (size_t)h->n, true, s, [&](const KArgs& k, bool rg) {
+    const auto kern = kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_sac_collect_kernel<K.value, R.value>; });
+    return launch(kern, slice_groups(h), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, k, S);
+  });
 }
 
 // ------------------------------------------------------------------------------------------ the PPO learner (tb_learner.hpp)

@@ -741,6 +741,37 @@ int tb_render(int env_kind, int device, void *stream, const TbParams *params,
               uint8_t *rgb_dev, uint8_t *id_dev_or_null, float *depth_dev_or_null);
 
 /*
+ * The flight of a SwingRacket-v0 ball, substep by substep (csrc/tb_trace.hpp): ONE agent step of caller-owned states, with the states it
+ * passes through stored as frames. The reference shows the flight in PyBullet's GUI (validate_swing.py); the fast-forward of
+ * swingracket_env.py:105-141 runs up to 775 substeps inside env.step(), of which tb_step returns the reward, the terminal observation
+ * and a count.
+ *   words_dev [tb_state_words][n_rows] and done_dev [n_rows]: the states, in tb_get_state's layout; only read. actions_dev [n_rows][6].
+ *   For every row, reward / substeps / done_out / obs (the observation of the final state; optional) are what this sequence gives, bit
+ *   for bit: tb_set_state(words, done), then tb_step(actions), on a handle with the same parameters and no TB_F_AUTO_RESET. A restored
+ *   state starts with empty racket<->court caches, and so does the trace. The frames are the states that step passed through.
+ * Which substeps become frames. Number the substeps of the call s = 1 .. ns: s = 1 is the agent's substep, ns what tb_step reports in
+ * substeps_dev (1 .. 776; 1 for a row that starts no flight: step count below 25, or a non-zero done byte). The sampled set is
+ * {1 + j stride : j >= 0, 1 + j stride <= ns} plus ns itself, in increasing order: m = 1 + (ns - 1) / stride + ((ns - 1) % stride != 0).
+ *   m <= max_frames: row k < m holds the state after the k-th sampled substep, rows m .. max_frames - 1 copies of the final state.
+ *   m >  max_frames: rows 0 .. max_frames - 2 hold the first max_frames - 1 samples, row max_frames - 1 the state after substep ns.
+ *   The last stored row is always the final state and no byte of frames_dev stays unwritten; n_frames_dev[i] = m in both cases (as
+ *   snprintf reports the length it needed). A row's step-count word is the input step count + s; the episode word is unchanged: the
+ *   trace never resets an env, whatever TB_F_AUTO_RESET says.
+ *   frames_dev is [max_frames][tb_state_words][n_rows]: frames_dev + row * tb_state_words * n_rows is a words_dev for tb_render.
+ * The handle supplies the parameters, the outline table and the device, and nothing else: the call does not touch its env state,
+ * caches, counters, episode phase, pipeline slots or pool, and it does not flush. n_rows is independent of the handle's n_envs. The
+ * call is complete in stream order on `stream`.
+ * TB_E_INVAL before any launch, with "tb_swing_trace" in tb_last_error: a null handle or a null pointer other than obs, a Tennisbot-v0
+ * handle (there every agent step is one substep and is visible as it is), n_rows < 1 (or > 2^25), stride < 1, max_frames < 1, a
+ * pointer that is not 4-byte aligned (actions and obs: 8-byte, rows are accessed two floats at a time).
+ */
+int tb_swing_trace(TbHandle *h, const uint32_t *words_dev, const uint8_t *done_dev, int n_rows,
+                   const float *actions_dev /* [n_rows][6] */, int stride, int max_frames,
+                   uint32_t *frames_dev /* [max_frames][tb_state_words][n_rows] */, int32_t *n_frames_dev,
+                   float *reward_dev, int32_t *substeps_dev, uint8_t *done_out_dev,
+                   float *obs_dev_or_null /* [n_rows][6]: the observation of the final state */, void *stream);
+
+/*
  * Pipelined fast-forward (SwingRacket-v0 with TB_F_AUTO_RESET; HIP streams, no reference
  * counterpart). The <= 775-substep fast-forward of swingracket_env.py:105-141 takes no
  * agent input, and the next episode does not depend on its outcome. With the pipeline

@@ -6,7 +6,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = [os.path.join(_HERE, "csrc", "tb_stepper.hip")]
-HEADERS = [os.path.join(_HERE, "csrc", "tb_kernels.hpp"), os.path.join(_HERE, "csrc", "tb_device.hpp"), os.path.join(_HERE, "csrc", "tb_policy.hpp"), os.path.join(_HERE, "csrc", "tb_diag.hpp"), os.path.join(_HERE, "csrc", "tb_es.hpp"), os.path.join(_HERE, "csrc", "tb_learner.hpp"), os.path.join(_HERE, "csrc", "tb_trpo.hpp"), os.path.join(_HERE, "csrc", "tb_sac.hpp"), os.path.join(_HERE, "csrc", "tb_tqc.hpp"), os.path.join(_HERE, "csrc", "tb_render.hpp"),
+HEADERS = [os.path.join(_HERE, "csrc", "tb_kernels.hpp"), os.path.join(_HERE, "csrc", "tb_device.hpp"), os.path.join(_HERE, "csrc", "tb_policy.hpp"), os.path.join(_HERE, "csrc", "tb_diag.hpp"), os.path.join(_HERE, "csrc", "tb_es.hpp"), os.path.join(_HERE, "csrc", "tb_learner.hpp"), os.path.join(_HERE, "csrc", "tb_trpo.hpp"), os.path.join(_HERE, "csrc", "tb_sac.hpp"), os.path.join(_HERE, "csrc", "tb_tqc.hpp"), os.path.join(_HERE, "csrc", "tb_render.hpp"), os.path.join(_HERE, "csrc", "tb_trace.hpp"),
            os.path.join(_HERE, "..", "include", "tb_stepper.h")]
 OUTPUT = os.path.join(_HERE, "libtb_stepper.so")
 

@@ -32,6 +32,7 @@
 #include "tb_sac.hpp"
 #include "tb_tqc.hpp"
 #include "tb_render.hpp"
+#include "tb_trace.hpp"
 
 using namespace tb;
 
@@ -2066,6 +2067,32 @@ int tb_render(int env_kind, int device, void* stream, const TbParams* params, co
                   rgb_dev, id_dev_or_null, depth_dev_or_null);
   return launch(tb_render_kernel<TB_ENV_TENNIS>, grid, block, 0, (hipStream_t)stream, cam, sc, hull, words_dev, n_envs, env_idx_dev_or_null, width, height, tiles_x, tiles,
                 rgb_dev, id_dev_or_null, depth_dev_or_null);
+}
+
+// ------------------------------------------------------------------------------------------ tb_swing_trace (csrc/tb_trace.hpp)
+int tb_swing_trace(TbHandle* h, const uint32_t* words_dev, const uint8_t* done_dev, int n_rows, const float* actions_dev, int stride, int max_frames,
+                   uint32_t* frames_dev, int32_t* n_frames_dev, float* reward_dev, int32_t* substeps_dev, uint8_t* done_out_dev, float* obs_dev_or_null,
+                   void* stream) {
+  if (!h) return fail(TB_E_INVAL, "tb_swing_trace: null handle");
+  if (!words_dev || !done_dev || !actions_dev || !frames_dev || !n_frames_dev || !reward_dev || !substeps_dev || !done_out_dev)
+    return fail(TB_E_INVAL, "tb_swing_trace: null argument (only obs may be null)");
+  if (h->kind != TB_ENV_SWING) return fail(TB_E_INVAL, "tb_swing_trace: a SwingRacket-v0 handle is required (every Tennisbot-v0 agent step is one substep, visible as it is)");
+  if (n_rows < 1 || stride < 1 || max_frames < 1) return fail(TB_E_INVAL, "tb_swing_trace: n_rows, stride and max_frames must be >= 1");
+  if (n_rows > (1 << 25)) return fail(TB_E_INVAL, "tb_swing_trace: n_rows must be <= 2^25");  // (32-bit row offsets inside a frame: see row_word)
+  if (misaligned(words_dev, 4) || misaligned(frames_dev, 4) || misaligned(n_frames_dev, 4) || misaligned(reward_dev, 4) || misaligned(substeps_dev, 4))
+    return fail(TB_E_INVAL, "tb_swing_trace: words, frames, n_frames, reward and substeps must be 4-byte aligned");
+  if (misaligned(actions_dev, 8) || misaligned(obs_dev_or_null, 8)) return fail(TB_E_INVAL, "tb_swing_trace: actions and obs must be 8-byte aligned (rows are accessed two floats at a time)");
+  DeviceGuard g(h->device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  TraceArgs a;
+  memset(&a, 0, sizeof a);
+  a.P = h->kp; a.hull = h->d_hull;
+  a.words = words_dev; a.done = done_dev; a.actions = actions_dev;
+  a.frames = frames_dev; a.n_frames = n_frames_dev; a.reward = reward_dev; a.substeps = substeps_dev; a.done_out = done_out_dev; a.obs = obs_dev_or_null;
+  a.n = n_rows; a.stride = stride; a.max_frames = max_frames;
+  const bool rg = extended_contacts(h->kp);
+  const dim3 grid((unsigned)((n_rows + 63) / 64));
+  return launch(rg ? tb_swing_trace_kernel<true> : tb_swing_trace_kernel<false>, grid, dim3(64), dyn_lds(ff_lds_words(rg, false), 64), (hipStream_t)stream, a);
 }
 
 int tb_diag_two_wave_gate(TbHandle* h, uint8_t* out_dev, void* stream) {

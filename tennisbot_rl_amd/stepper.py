@@ -3,7 +3,7 @@ stepped in lockstep on one MI355X.
 
 This is the measured path: `step(actions)` takes and returns device tensors and never
 synchronises with the host. torch is used for device memory and streams only; all
-arithmetic happens in libtb_stepper.so (hand-written HIP: csrc/tb_kernels.hpp, tb_device.hpp, tb_policy.hpp, tb_render.hpp; host side csrc/tb_stepper.hip). There is
+arithmetic happens in libtb_stepper.so (hand-written HIP: csrc/tb_kernels.hpp, tb_device.hpp, tb_policy.hpp, tb_render.hpp, tb_trace.hpp; host side csrc/tb_stepper.hip). There is
 no CPU or eager-PyTorch fallback: if the library or a GPU is missing, construction raises.
 
 Reference counterparts: `SwingRacketEnv` (tennisbot/envs/swingracket_env.py:24-192) and
@@ -173,6 +173,8 @@ def load_library():
         tqc.argtypes, tqc.restype = sac.argtypes, i32
     L.tb_render.argtypes = [i32, i32, vp, ctypes.POINTER(TbParams), vp, i32, vp, i32, ctypes.POINTER(TbCamera), i32, i32, vp, vp, vp]
     L.tb_render.restype = i32
+    L.tb_swing_trace.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.tb_swing_trace.restype = i32
     L.tb_phase.argtypes = [vp]
     L.tb_phase.restype = i32
     L.tb_phase_advance.argtypes = [vp, i32]
@@ -317,6 +319,25 @@ def render_words(kind, params, words, indices=None, camera=None, width=96, heigh
                           words.data_ptr(), n, None if idx is None else idx.data_ptr(), K, ctypes.byref(cam), W, H, rgb.data_ptr(),
                           None if ids is None else ids.data_ptr(), None if depth is None else depth.data_ptr()), "tb_render")
     return (rgb, ids, depth) if layers else rgb
+
+
+TRACE_MAX_SUBSTEPS = 776   # a SwingRacket-v0 step: the agent's substep + at most 775 of the fast-forward (swingracket_env.py:105-129)
+
+
+def trace_frame_substeps(ns, stride, max_frames):
+    """tb_swing_trace's sampling rule (include/tb_stepper.h) in plain Python: the substep numbers s, 1-based, of the max_frames stored
+    rows of an env whose step ran ns substeps. The samples are 1, 1 + stride, 1 + 2 stride, ... <= ns, then ns itself; where they
+    fit, the rows behind them repeat ns, and where they do not, the last row is ns all the same. n_frames reports how many samples
+    there were: 1 + (ns - 1) // stride + ((ns - 1) % stride != 0), whether they fit or not."""
+    ns, stride, F = int(ns), int(stride), int(max_frames)
+    if ns < 1 or stride < 1 or F < 1:
+        raise ValueError("ns, stride and max_frames must be >= 1")
+    samples = list(range(1, ns + 1, stride))
+    if samples[-1] != ns:
+        samples.append(ns)
+    if len(samples) <= F:
+        return samples + [ns] * (F - len(samples))
+    return samples[:F - 1] + [ns]
 
 
 def _check(L, rc, what):
@@ -828,6 +849,46 @@ class BatchedEnv:
         fast-forwards, as every state read does -- and writes nothing of the env: state, counters and the next step are untouched."""
         w, _ = self.get_state_words()
         return render_words(self.kind, self.params, w, indices=indices, camera=camera, width=width, height=height, layers=layers)
+
+    def trace_step(self, actions, stride=8, words=None, done=None, max_frames=None):
+        """One SwingRacket-v0 agent step with the states it passes through (tb_swing_trace): the 26th step's fast-forward -- the ball's
+        whole flight, up to 775 substeps -- sampled every `stride` substeps. words / done: the states to step, int32 [W, K] and uint8
+        [K] in get_state_words' layout (done=None: all running); words=None traces this env's own current state, read as
+        get_state_words reads it (a pipelined handle joins its outstanding fast-forwards first). actions: float32 [K, 6]. Nothing of
+        this env changes: state, counters, phase and the next step are what they were. Returns a dict of device tensors, complete in
+        stream order: frames int32 [F, W, K] (F = max_frames, default 2 + 775 // stride: any flight and a row to spare; frames[k]
+        feeds render_words as it is), n_frames int32 [K] (samples per env, trace_frame_substeps' rule; rows behind them repeat the
+        final state), and reward float32 [K], substeps int32 [K], done uint8 [K], obs float32 [K, 6] -- what set_state_words(words,
+        done) and step(actions) give on an env without auto-reset, bit for bit."""
+        if self.kind != ENV_SWING:
+            raise ValueError("trace_step is SwingRacket-v0's: every Tennisbot-v0 agent step is one substep and is visible as it is")
+        t = self.torch
+        stride = int(stride)
+        F = 2 + (TRACE_MAX_SUBSTEPS - 1) // max(stride, 1) if max_frames is None else int(max_frames)
+        if words is None:
+            if done is not None:
+                raise ValueError("done belongs to words: give both, or neither to trace the env's own state")
+            w, d = self.get_state_words()
+        else:
+            w = words if isinstance(words, t.Tensor) else t.from_numpy(np.ascontiguousarray(words).view(np.int32))
+            w = w.to(self.device)
+            if w.dim() != 2 or w.shape[0] != self.words or w.element_size() != 4 or not w.is_contiguous():
+                raise ValueError("words must be a contiguous [%d, K] tensor of 32-bit words" % self.words)
+            if done is None:
+                d = t.zeros(int(w.shape[1]), dtype=t.uint8, device=self.device)
+            else:
+                d = done if isinstance(done, t.Tensor) else t.from_numpy(np.ascontiguousarray(done, np.uint8))
+                d = self._check_tensor(d.to(self.device).contiguous(), (int(w.shape[1]),), t.uint8, "done")
+        K = int(w.shape[1])
+        a = self._check_tensor(actions, (K, self.act_dim), t.float32, "actions")
+        out = dict(frames=t.empty((max(F, 0), self.words, K), dtype=t.int32, device=self.device),   # (a size < 1 is the library's to refuse)
+                   n_frames=t.empty(K, dtype=t.int32, device=self.device), reward=t.empty(K, dtype=t.float32, device=self.device),
+                   substeps=t.empty(K, dtype=t.int32, device=self.device), done=t.empty(K, dtype=t.uint8, device=self.device),
+                   obs=t.empty((K, self.obs_dim), dtype=t.float32, device=self.device))
+        _check(self.L, self.L.tb_swing_trace(self._h, w.data_ptr(), d.data_ptr(), K, a.data_ptr(), stride, F, out["frames"].data_ptr(),
+                                             out["n_frames"].data_ptr(), out["reward"].data_ptr(), out["substeps"].data_ptr(),
+                                             out["done"].data_ptr(), out["obs"].data_ptr(), self._stream()), "tb_swing_trace")
+        return out
 
     def set_params(self, params):
         p = params.copy()

@@ -6,10 +6,15 @@ pixel against ground, net, goal, ball and racket) and write the tiled frames as 
   python tools/render_episode.py -m model/ppo_SwingRacket-v0.pt --out swing.gif  # a checkpoint of train_swing.py
   python tools/render_episode.py --env Tennisbot-v0 --random --steps 200 --out tennis.gif --camera court
 
-Only the agent steps are rendered. A SwingRacket-v0 episode is 25 swing steps and one last step whose ball flight (up to 775
-physics substeps) runs inside the fast-forward: those substeps are not visible from outside, so the flight itself is NOT in the
-film -- the last frame of an episode shows the state the next episode starts from. Tennisbot-v0 steps one substep per agent step,
-so its film is complete. Without PIL the frames are written as an .npy stack [T, H, W, 3] instead, and the tool says so.
+Without --flight only the agent steps are rendered. A SwingRacket-v0 episode is 25 swing steps and one last step whose ball flight (up
+to 775 physics substeps) runs inside the fast-forward; the frame after that step shows the state the next episode starts from.
+--flight puts the flight into the film: the state before the episodes' last step is kept on the device, the step is taken as always,
+and BatchedEnv.trace_step (tb_swing_trace) re-runs it from the kept state with the actions the step used, storing the state every
+--flight-stride substeps; those rows are rendered between the last swing frame and the next episode's first, each tile showing its
+own env's row (an env that has landed keeps showing its final state while the others still fly). The trace's reward must equal the
+step's bit for bit, or the tool exits non-zero. Flight frames use the fixed court overview unless --camera is given: the follow
+camera loses a ball that flies 15 m. Tennisbot-v0 steps one substep per agent step, so its film is complete and --flight does
+nothing there. Without PIL the frames are written as an .npy stack [T, H, W, 3] instead, and the tool says so.
 """
 import argparse
 import os
@@ -32,9 +37,11 @@ def main():
     ap.add_argument("--steps", type=int, default=0, help="agent steps to film (default: 26 x --episodes; Tennisbot-v0: 300)")
     ap.add_argument("--width", type=int, default=192)
     ap.add_argument("--height", type=int, default=128)
-    ap.add_argument("--camera", default="default", choices=["default", "court", "racket"],
+    ap.add_argument("--camera", default=None, choices=["default", "court", "racket"],
                     help="default: from behind each env's own racket (stepper.default_camera); court: the fixed overview; racket: the reference's render() camera "
                          "(tennisbot_env.py:263-279: at the racket, z = 0.2, along its body x axis, fov 80), built from env 0's state")
+    ap.add_argument("--flight", action="store_true", help="SwingRacket-v0: film the ball flight inside each episode's last step too (tb_swing_trace)")
+    ap.add_argument("--flight-stride", type=int, default=8, help="physics substeps between two flight frames")
     ap.add_argument("--fps", type=float, default=12.0)
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
@@ -49,6 +56,9 @@ def main():
     from tennisbot_rl_amd.envs import tile_images
 
     swing = args.env == "SwingRacket-v0"
+    if args.flight and not swing:
+        print("--flight does nothing on Tennisbot-v0: every agent step is one substep, the film is complete as it is")
+    flight = args.flight and swing
     steps = args.steps or (26 * args.episodes if swing else 300)
     if args.random:
         env = stepper.BatchedEnv(args.env, args.envs, device="cuda:0", seed=args.seed)
@@ -63,26 +73,48 @@ def main():
             tr.load(args.model_file)
         env, blob, obs, net = tr.env, pack_policy(tr.policy), tr.obs_in, tr.net
 
-    def camera():
-        if args.camera == "court":
+    def camera(words=None, name=args.camera or "default"):
+        if name == "court":
             return stepper.court_camera()
-        if args.camera == "racket":
-            st = env.get_state()
-            return stepper.racket_view(st["racket_pos"][0], st["racket_quat"][0])
+        if name == "racket":
+            if words is None:
+                st = env.get_state()
+                return stepper.racket_view(st["racket_pos"][0], st["racket_quat"][0])
+            w0 = words[:7, 0].view(torch.float32).cpu().numpy()   # env 0's racket position and orientation in this row
+            return stepper.racket_view(w0[:3], w0[3:7])
         return stepper.default_camera(env.kind)
 
     def frame():
         return tile_images(list(env.render(camera=camera(), width=args.width, height=args.height).cpu().numpy()))
 
+    def flight_frames(words, done, actions, rew):
+        """the ending step once more from the kept state, traced: its rows as tiled frames"""
+        tr = env.trace_step(actions, stride=args.flight_stride, words=words, done=done)
+        if not torch.equal(tr["reward"].view(torch.int32), rew.view(torch.int32)):
+            sys.exit("the trace's reward differs from the step's: %s vs %s" % (tr["reward"].cpu().numpy(), rew.cpu().numpy()))
+        ns, r = tr["substeps"].cpu().numpy(), tr["reward"].cpu().numpy()
+        print("flight: substeps %s, goal hits (reward >= 50) %d of %d" % (" ".join(str(int(x)) for x in ns), int((r >= 50).sum()), r.size))
+        out = []
+        for k in range(int(tr["n_frames"].max())):
+            row = tr["frames"][k]
+            rgb = stepper.render_words(env.kind, env.params, row, camera=camera(row, args.camera or "court"), width=args.width, height=args.height)
+            out.append(tile_images(list(rgb.cpu().numpy())))
+        return out
+
     frames, ret, finished = [frame()], torch.zeros(args.envs, device=env.device), []
     for t in range(steps):
+        ends = flight and t % 26 == 25   # every SwingRacket-v0 episode is 26 agent steps, and the envs were reset together
+        if ends:
+            kept = env.get_state_words()
         if args.random:
             a = (torch.rand((args.envs, env.act_dim), generator=gen) * 2 - 1).to(env.device)
             obs, rew, done = env.step(a)
         else:
-            (obs, rew, done), _ = env.policy_step(blob, obs, seed=args.seed + 1, deterministic=args.deterministic, net=net)
+            (obs, rew, done), (a, _, _, _) = env.policy_step(blob, obs, seed=args.seed + 1, deterministic=args.deterministic, net=net)
         if env.pipeline:
             env.flush()
+        if ends:
+            frames += flight_frames(kept[0], kept[1], a, rew)
         ret += rew
         d = done.bool()
         if bool(d.any()):

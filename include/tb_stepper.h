@@ -415,6 +415,29 @@ int tb_policy_evaluate(TbHandle *h, int net, const float *weights_dev, double *r
                        uint64_t noise_seed, int deterministic, void *stream);
 
 /*
+ * tb_policy_evaluate for a POPULATION of networks, one launch (csrc/tb_kernels.hpp, tb_policy_evaluate_members_kernel): a
+ * checkpoint tournament, or the population of an evolution strategy on the MlpPolicy actor. A workgroup still owns 16 envs; they
+ * all belong to one member, whose blob its tower wave keeps in registers -- 16 envs against one weight fragment on the matrix cores.
+ *   weights_dev: n_members blobs of tb_policy_blob_floats(kind, net) floats in pack_policy's layout, weights_stride_floats apart:
+ *     a multiple of 4 and >= the blob length; the base 16-byte aligned. Floats between the end of a blob and the next row are
+ *     never read. Env i uses member i / envs_per_member; n_members * envs_per_member must equal n_envs, and envs_per_member
+ *     must be a multiple of tb_policy_member_granule() (16: the envs of a tower wave).
+ * Everything else is tb_policy_evaluate's contract: the call resets first (call k is episode k), return_dev [n_envs] is the float64
+ * sum of the float32 rewards in step order through the first done, length_dev [n_envs] the episode length in agent steps; no state
+ * word is written and the phase is 0 on return; SwingRacket-v0 needs tb_set_pipeline(h, 1) (TB_E_UNSUPPORTED otherwise) and its
+ * terminal reward is folded in behind the flush; the kernel counts its counters; results are complete in stream order. Per env, the
+ * actions are bit for bit those of tb_policy_step_net with that member's blob, and log_std is that member's -- so row m equals
+ * tb_policy_evaluate with blob m on a handle of envs_per_member envs whose env_id_base is this handle's + m * envs_per_member.
+ * Null h / weights_dev / return_dev / length_dev, n_members < 1, envs_per_member < 1 or not a multiple of the granule, a
+ * product other than n_envs, a stride below the blob length or not a multiple of 4, a misaligned base: TB_E_INVAL; a (kind, net)
+ * pair that is not built: TB_E_PARAMS. A refusal launches, resets and writes nothing.
+ */
+int tb_policy_member_granule(void);
+int tb_policy_evaluate_members(TbHandle *h, int net, const float *weights_dev, int n_members, size_t weights_stride_floats,
+                               int envs_per_member, double *return_dev, int32_t *length_dev, uint64_t noise_seed,
+                               int deterministic, void *stream);
+
+/*
  * Whole-episode evaluation of a SAC / TQC actor (the two share it): one launch runs every env's whole episode with the
  * 256-wide actor inside (csrc/tb_sac.hpp, tb_sac_evaluate_kernel: 16 envs per four-wave workgroup, weights streamed from L2).
  *   actor_dev: the flat TB_SAC_ACTOR vector, tb_sac_param_floats(kind, TB_SAC_ACTOR) floats, as the learner trains it.

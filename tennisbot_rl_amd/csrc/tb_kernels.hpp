@@ -1251,8 +1251,21 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
 // which the tower wave reaches after its test of iteration t. s_mean and s_obs are handed over as in tb_policy_rollout_kernel.
 // Barriers per wave: one behind the set-up, then two per iteration on every path (the exit, by s_go or by the cap, is behind an
 // iteration's second barrier in both roles).
-template <int KIND, bool RG, int NET = TB_NET_DEFAULT>
-__global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double* ret_out, int32_t* len_out) {
+//
+// THE MEMBERS FORM (tb_policy_evaluate_members: a population of networks, one launch) is this kernel with ONE more argument, a
+// PolicyMembers: A.pol_weights then holds the members' blobs `stride` floats apart, env i is member i / per_member's, and per_member
+// is a multiple of TB_POLICY_SLICE (the host refuses anything else), so the 16 envs of a workgroup share ONE member. Its index is a
+// function of blockIdx.x and two kernel arguments alone: the blob's address stays in scalar registers like A.pol_weights itself.
+// The tower wave loads that blob's pi tower (the matrix cores' 16 x 16 x 4 tile: 16 envs against one weight fragment), the env wave
+// its log_std; floats between the blobs are never read. The loop, the barriers and the exit are the same lines. The argument is a
+// trailing pack, empty or one PolicyMembers, so that tb_policy_evaluate_kernel<KIND, RG, NET> remains the kernel it was, argument
+// list included.
+struct PolicyMembers { size_t stride; int per_member; };
+TB_DEV size_t member_blob_offset(const PolicyMembers& mb) { return (size_t)((blockIdx.x * (unsigned)TB_POLICY_SLICE) / (unsigned)mb.per_member) * mb.stride; }
+template <int KIND, bool RG, int NET = TB_NET_DEFAULT, class... MEMBERS>
+__global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double* ret_out, int32_t* len_out, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PolicyMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) A.pol_weights += member_blob_offset(members...);
   constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE, T_MAX = episode_cap(KIND);
   __shared__ float4 s_hull[TB_HULL_LDS];
   __shared__ __attribute__((aligned(16))) float s_mean[E * 8];

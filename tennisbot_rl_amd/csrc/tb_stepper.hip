@@ -1263,6 +1263,27 @@ int tb_policy_evaluate(TbHandle* h, int net, const float* weights_dev, double* r
   });
 }
 
+// a population of blobs through the same launch (tb_policy_evaluate_members_kernel): a workgroup's 16 envs belong to one member
+int tb_policy_member_granule(void) { return TB_POLICY_SLICE; }
+int tb_policy_evaluate_members(TbHandle* h, int net, const float* weights_dev, int n_members, size_t weights_stride_floats, int envs_per_member,
+                               double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic, void* stream) {
+  if (!h || !weights_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_policy_evaluate_members: null argument");
+  if (int rc = policy_net_ok(h->kind, net, "tb_policy_evaluate_members")) return rc;
+  if (n_members < 1 || envs_per_member < 1 || envs_per_member % TB_POLICY_SLICE)
+    return fail(TB_E_INVAL, "tb_policy_evaluate_members: n_members must be >= 1 and envs_per_member a positive multiple of tb_policy_member_granule() (16)");
+  if ((long long)n_members * envs_per_member != h->n) return fail(TB_E_INVAL, "tb_policy_evaluate_members: n_members * envs_per_member must equal n_envs");
+  if (weights_stride_floats % 4 || weights_stride_floats < (size_t)tb_policy_blob_floats(h->kind, net) || reinterpret_cast<uintptr_t>(weights_dev) % 16)
+    return fail(TB_E_INVAL, "tb_policy_evaluate_members: the weights' row stride must be a multiple of 4 floats and >= tb_policy_blob_floats, the base 16-byte aligned");
+  PolicyIO pol = {};
+  pol.weights = weights_dev; pol.seed = noise_seed; pol.deterministic = deterministic; pol.net = net;
+  return run_whole_episodes(h, "tb_policy_evaluate_members", &pol, return_dev, 0, nullptr, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
+    const auto kern = kernel_of_kind_net_rg(h->kind, net, rg, [](auto K, auto N, auto R) { return tb_policy_evaluate_kernel<K.value, R.value, N.value, PolicyMembers>; });
+    if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_evaluate_kernel members instantiation for this variant");
+    return launch(kern, slice_groups(h), dim3(128), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, return_dev, length_dev,
+                  PolicyMembers{weights_stride_floats, envs_per_member});
+  });
+}
+
 // SAC's / TQC's actor inside the episode loop (tb_sac.hpp, tb_sac_evaluate_kernel), four waves per 16 envs
 int tb_sac_evaluate(TbHandle* h, const float* actor_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
                     const TbSacEvalTrace* trace, void* stream) {

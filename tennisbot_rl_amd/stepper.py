@@ -99,6 +99,10 @@ def load_library():
     L.tb_es_evaluate.restype = i32
     L.tb_policy_evaluate.argtypes = [vp, i32, vp, vp, vp, u64, i32, vp]
     L.tb_policy_evaluate.restype = i32
+    L.tb_policy_member_granule.argtypes = []
+    L.tb_policy_member_granule.restype = i32
+    L.tb_policy_evaluate_members.argtypes = [vp, i32, vp, i32, ctypes.c_size_t, i32, vp, vp, u64, i32, vp]
+    L.tb_policy_evaluate_members.restype = i32
     L.tb_sac_evaluate.argtypes = [vp, vp, vp, vp, u64, i32, ctypes.POINTER(TbSacEvalTrace), vp]
     L.tb_sac_evaluate.restype = i32
     L.tb_sac_collect.argtypes = [vp, vp, i32, i32, u64, ctypes.POINTER(TbSacCollectOut), vp]
@@ -702,6 +706,41 @@ class BatchedEnv:
         _check(self.L, self.L.tb_policy_evaluate(self._h, int(net), w.data_ptr(), ret.data_ptr(), length.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                  1 if deterministic else 0, self._stream()), "tb_policy_evaluate")
         return ret, length
+
+    def policy_member_granule(self):
+        """envs_per_member of policy_evaluate_members must be a multiple of this (16: the envs of one tower wave)"""
+        return int(self.L.tb_policy_member_granule())
+
+    def policy_evaluate_members(self, weights, envs_per_member, seed=0, deterministic=False, net=NET_DEFAULT):
+        """policy_evaluate for a population of networks in one launch (tb_policy_evaluate_members). weights: [M, stride] float32 on
+        this device, row m the packed blob of member m (`ppo.pack_policy`; `policy_es.pack_policy_members` for perturbations of one
+        policy), stride a multiple of 4 and >= policy_floats(net); M * envs_per_member == num_envs and env i uses member
+        i // envs_per_member; envs_per_member must be a multiple of policy_member_granule(). A misaligned, non-contiguous or
+        short-stride input is re-packed first, as es_evaluate does. Sampling, noise keys, the reset in front and the state
+        afterwards are policy_evaluate's: row m is what policy_evaluate(weights[m]) gives on a batch of envs_per_member envs at
+        env_id_base + m * envs_per_member. Returns (returns float64 [M, R], lengths int32 [M, R]), complete in stream order."""
+        t, n = self.torch, self.num_envs
+        R, G = int(envs_per_member), self.policy_member_granule()
+        if R < 1 or R % G:
+            raise ValueError("envs_per_member must be a positive multiple of policy_member_granule() (%d), got %d" % (G, R))
+        if n % R:
+            raise ValueError("envs_per_member must divide num_envs (%d)" % n)
+        M, P = n // R, self.policy_floats(net)
+        if not isinstance(weights, t.Tensor) or weights.dim() != 2 or weights.shape[0] != M:
+            raise ValueError("weights must be a [%d, stride] tensor" % M)
+        if weights.device != self.device or weights.dtype != t.float32:
+            raise ValueError("weights must be float32 on %s" % self.device)
+        if weights.shape[1] < P:
+            raise ValueError("weights rows must hold the %d floats of a packed policy, got %d" % (P, weights.shape[1]))
+        if weights.shape[1] % 4 or not weights.is_contiguous() or weights.data_ptr() % 16:
+            w = t.zeros((M, (P + 3) // 4 * 4), dtype=t.float32, device=self.device)
+            w[:, :P] = weights[:, :P]
+            weights = w
+        ret = t.empty(n, dtype=t.float64, device=self.device)
+        length = t.empty(n, dtype=t.int32, device=self.device)
+        _check(self.L, self.L.tb_policy_evaluate_members(self._h, int(net), weights.data_ptr(), M, weights.shape[1], R, ret.data_ptr(), length.data_ptr(),
+                                                         int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if deterministic else 0, self._stream()), "tb_policy_evaluate_members")
+        return ret.view(M, R), length.view(M, R)
 
     def sac_actor_floats(self):
         """Floats of the flat SAC / TQC actor vector for this env kind (70668 SwingRacket-v0, 70148 Tennisbot-v0)"""

@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""A checkpoint tournament in one launch: every checkpoint is one MEMBER of a BatchedEnv.policy_evaluate_members call
+(tb_policy_evaluate_members), its whole episodes run side by side with the others', and a table sorted by mean return comes out.
+
+  python tools/rank_checkpoints.py model/rl_model_*_steps.pt model/best_model.pt
+  python tools/rank_checkpoints.py --env Tennisbot-v0 --net tuned --episodes-per-member 1024 model/*.pt
+  python tools/rank_checkpoints.py reference model/ppo_SwingRacket-v0.pt     # `reference`: tests/golden/ppo_swing_policy.npz
+
+Checkpoints: what train_swing.py / train.py (PPO, TRPO) and train_es.py --policy mlp write (their "policy" entry), or an .npz of
+SB3-named arrays. All must hold the network --net names.
+
+MEMBERS SEE DIFFERENT EPISODES. Resets and exploration noise are keyed by the global env id, and every member has env ids of its
+own, so no two checkpoints play the same balls: the table's means are estimates from independent samples, to be compared THROUGH
+THEIR STANDARD ERRORS (the `sem` column: std / sqrt(episodes)). Two means closer than a few standard errors are not ranked by this
+table; raise --episodes-per-member. Like `model.predict(ob)` in the reference the policies act stochastically unless --deterministic.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+GRANULE = 16      # tb_policy_member_granule(): episodes per member and launch come in multiples of it
+MAX_ENVS = 65536  # envs of the evaluation batch at the most: more episodes are more launches
+
+
+def plan(n_members, episodes_per_member, granule=GRANULE, max_envs=MAX_ENVS):
+    """(envs per member and launch, launches): the episodes asked for, rounded up to whole launches of a batch of at most max_envs
+    envs; a member's envs are a multiple of the granule"""
+    want = -(-int(episodes_per_member) // granule) * granule
+    per_launch = max(granule, min(want, max_envs // max(n_members, 1) // granule * granule))
+    return per_launch, -(-want // per_launch)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("checkpoints", nargs="+", metavar="CKPT", help="checkpoint files; `reference`: the reference's shipped ppo_swing policy")
+    ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
+    ap.add_argument("--net", default="default", choices=["default", "tuned", "mlp64"], help="the network every checkpoint holds")
+    ap.add_argument("--episodes-per-member", type=int, default=256, help="episodes per checkpoint (rounded up to whole launches; members see DIFFERENT "
+                    "episodes: compare means through the sem column)")
+    ap.add_argument("--deterministic", action="store_true", help="act on the mean action")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--json", default=None, help="also write the table to this file")
+    args = ap.parse_args(argv)
+    if args.episodes_per_member < 1:
+        ap.error("--episodes-per-member must be >= 1")
+
+    import torch
+    from tennisbot_rl_amd.evaluation import EVAL_ENV_ID_BASE
+    from tennisbot_rl_amd.params import ENV_SWING, NET_NAMES
+    from tennisbot_rl_amd.policy_es import build_policy, load_init
+    from tennisbot_rl_amd.ppo import pack_policy
+    from tennisbot_rl_amd.stepper import ENV_IDS, BatchedEnv, check_net
+
+    kind = ENV_IDS[args.env]
+    net = check_net(kind, {v: k for k, v in NET_NAMES.items()}[args.net])
+    dev = torch.device("cuda", 0)
+    blobs = []
+    for path in args.checkpoints:
+        src = os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz") if path == "reference" else path
+        blobs.append(pack_policy(load_init(build_policy(kind, net), src).to(dev)))
+    weights = torch.stack(blobs)
+    M = len(blobs)
+    R, launches = plan(M, args.episodes_per_member)
+    env = BatchedEnv(kind, M * R, device=dev, seed=args.seed, env_id_base=EVAL_ENV_ID_BASE, track_terminal_obs=False, pipeline=kind == ENV_SWING)
+    assert R % env.policy_member_granule() == 0
+    noise_seed = (args.seed * 1000003 + 0x52414E4B) & 0xFFFFFFFFFFFFFFFF
+    rets, lens = [], []
+    for _ in range(launches):   # launch k is episode k of every env
+        r, ln = env.policy_evaluate_members(weights, R, seed=noise_seed, deterministic=args.deterministic, net=net)
+        rets.append(r); lens.append(ln)
+    ret, length = torch.cat(rets, dim=1), torch.cat(lens, dim=1).double()
+    n = ret.shape[1]
+    stats = torch.stack([ret.mean(1), ret.std(1, unbiased=True) / n ** 0.5 if n > 1 else torch.zeros(M, dtype=ret.dtype, device=dev), length.mean(1)]).cpu().tolist()   # one host read
+    env.close()
+    rows = sorted(({"checkpoint": p, "mean": stats[0][m], "sem": stats[1][m], "mean_length": stats[2][m], "episodes": n} for m, p in enumerate(args.checkpoints)),
+                  key=lambda r: -r["mean"])
+    print("%d checkpoints x %d episodes of %s (%s, %s), %d launch%s of %d envs" % (M, n, args.env, args.net, "deterministic" if args.deterministic else "stochastic",
+                                                                                 launches, "" if launches == 1 else "es", M * R))
+    print("members see DIFFERENT episodes: compare means through their standard errors (sem), not digit by digit")
+    print("%4s  %12s  %10s  %11s  %s" % ("rank", "mean return", "sem", "mean length", "checkpoint"))
+    for k, r in enumerate(rows):
+        print("%4d  %12.3f  %10.3f  %11.1f  %s" % (k + 1, r["mean"], r["sem"], r["mean_length"], r["checkpoint"]))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(rows, f, indent=1)
+    return rows
+
+
+if __name__ == "__main__":
+    main()

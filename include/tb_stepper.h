@@ -438,6 +438,23 @@ int tb_policy_evaluate_members(TbHandle *h, int net, const float *weights_dev, i
                                int deterministic, void *stream);
 
 /*
+ * tb_policy_rollout_net for a POPULATION of networks (csrc/tb_kernels.hpp, tb_policy_rollout_kernel's members form): the collect of
+ * a population of PPO learners, one launch per episode cut whatever the population's size. Everything is tb_policy_rollout_net's:
+ * arrays [n_steps][N][..], step strides, alignment, TB_F_AUTO_RESET and, on SwingRacket-v0, the pipeline and lockstep. The weights
+ * are tb_policy_evaluate_members': n_members blobs weights_stride_floats apart (a multiple of 4, >= the blob length, base 16-byte
+ * aligned; floats between blobs are never read), env i uses member i / envs_per_member, envs_per_member a multiple of
+ * tb_policy_member_granule(), n_members * envs_per_member == n_envs. The member belongs to a SLICE of 16 envs: at 48 envs per
+ * workgroup the three tower-wave pairs may hold three members' weights. Per env, every output is bit for bit what
+ * tb_policy_rollout_net gives with that member's blob on a handle of envs_per_member envs whose env_id_base is this handle's
+ * + m * envs_per_member. Refusals: tb_policy_evaluate_members' list and tb_policy_rollout_net's, with the same codes, named after
+ * this function; a refusal launches nothing and writes nothing.
+ */
+int tb_policy_rollout_members(TbHandle *h, int net, int n_steps, const float *weights_dev, int n_members, size_t weights_stride_floats,
+                              int envs_per_member, const float *obs_in_dev, float *actions_dev, float *raw_actions_dev, float *logp_dev,
+                              float *value_dev, float *obs_dev, float *reward_dev, uint8_t *done_dev, const size_t *step_strides_bytes,
+                              uint64_t noise_seed, int deterministic, void *stream);
+
+/*
  * Whole-episode evaluation of a SAC / TQC actor (the two share it): one launch runs every env's whole episode with the
  * 256-wide actor inside (csrc/tb_sac.hpp, tb_sac_evaluate_kernel: 16 envs per four-wave workgroup, weights streamed from L2).
  *   actor_dev: the flat TB_SAC_ACTOR vector, tb_sac_param_floats(kind, TB_SAC_ACTOR) floats, as the learner trains it.
@@ -581,6 +598,31 @@ int tb_ppo_apply_net(int env_kind, int net, int device, void *stream, int phases
                      int batch, float *params_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev, int n_params,
                      float *stats_dev, float ent_coef, float max_grad_norm, int world, float lr, float beta1, float beta2, float eps,
                      long long step);
+
+/*
+ * One minibatch step of a POPULATION of n_members learners in three launches (advantage sums + gradient, reduction, step), whatever
+ * n_members is: the kernels above with the member as a second grid axis. The flat rollout arrays are shared; member m reads the
+ * index row idx_dev + m * idx_stride (idx_stride >= batch), its parameter row params_dev + m * param_stride_floats
+ * (param_stride_floats >= n_params; grad and both moments use the same stride), hp_dev[m] (clip_range and vf_coef in the gradient,
+ * ent_coef in the reduction, lr in the step) and its workspace region, tb_ppo_members_workspace_stride_bytes(kind, net, batch)
+ * apart (a multiple of 8, >= tb_ppo_workspace_bytes_net). tb_ppo_apply_members always reduces and then steps: no world, no
+ * TB_PPO_VALUE_ONLY, no phases. After the pair, member m's grad, params, exp_avg, exp_avg_sq and stats [3] rows are bit for bit what
+ * tb_ppo_grad_net + tb_ppo_apply_net(TB_PPO_REDUCE | TB_PPO_STEP, world = 1) leave, given that member's row of each and its four
+ * scalars. Floats between rows are neither read nor written. Refused before the device is looked up: n_members outside
+ * [1, 65535], batch < 2, a null pointer, a float array not 4-byte aligned, idx / workspace / hp not 8-byte aligned, a stride that is
+ * too short, workspace_bytes < n_members * the stride, n_params other than tb_ppo_param_floats_net: TB_E_INVAL; a (kind, net) pair
+ * that is not built: TB_E_PARAMS.
+ */
+typedef struct TbPpoMemberHp { float clip_range, vf_coef, ent_coef, lr; } TbPpoMemberHp;   /* 16 bytes, device array [M] */
+long long tb_ppo_members_workspace_stride_bytes(int env_kind, int net, int batch);
+int tb_ppo_grad_members(int env_kind, int net, int device, void *stream, const float *obs_dev, const float *raw_actions_dev,
+                        const float *old_logp_dev, const float *adv_dev, const float *returns_dev, long long n_rows,
+                        const int64_t *idx_dev, size_t idx_stride, int batch, int n_members, const float *params_dev,
+                        size_t param_stride_floats, int n_params, const TbPpoMemberHp *hp_dev, void *workspace_dev, size_t workspace_bytes);
+int tb_ppo_apply_members(int env_kind, int net, int device, void *stream, const void *workspace_dev, size_t workspace_bytes,
+                         int batch, int n_members, float *params_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
+                         size_t param_stride_floats, int n_params, float *stats_dev /* [M][3] */, const TbPpoMemberHp *hp_dev,
+                         float max_grad_norm, float beta1, float beta2, float eps, long long step);
 
 /*
  * The TRPO learner's policy step (csrc/tb_trpo.hpp; tennisbot_rl_amd/trpo.py is the caller), in the conventions of the tb_ppo_*

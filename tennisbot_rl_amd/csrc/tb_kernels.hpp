@@ -1140,8 +1140,23 @@ TB_DEV void vote_go(int& s_go, int lane, bool active) {
 }
 TB_DEV bool loop_goes_on(const int& s_go, int t, int cap) { return t + 1 < cap && __builtin_amdgcn_readfirstlane(s_go) != 0; }
 
-template <int KIND, int S, bool RG, int NET = TB_NET_DEFAULT>
-__global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KArgs A) {
+// A POPULATION's blobs in one launch (tb_policy_evaluate_members, tb_policy_rollout_members): A.pol_weights holds the members' blobs
+// `stride` floats apart, env i is member i / per_member's, and per_member is a multiple of TB_POLICY_SLICE (the host refuses anything
+// else): the member is a property of a SLICE of 16 envs. An env beyond the batch counts as env n - 1, so nothing beyond the last
+// member's blob is read, and neither are the floats between blobs.
+struct PolicyMembers { size_t stride; int per_member; };
+TB_DEV int member_of_env(const PolicyMembers& mb, int env, int n) { return (int)((unsigned)(env < n ? env : n - 1) / (unsigned)mb.per_member); }
+
+// THE MEMBERS FORM (tb_policy_rollout_members: a population of PPO learners collects in one launch) is this kernel with ONE more
+// argument, a PolicyMembers, as a trailing pack -- empty, or that one -- so that tb_policy_rollout_kernel<KIND, S, RG, NET> remains the
+// kernel it was, argument list included. At S = 3 the three slices of a workgroup may belong to three members: each tower wave
+// (tower, slice) loads the blob of ITS slice's member -- the index is a function of blockIdx.x, the wave's number and kernel arguments,
+// made scalar by readfirstlane, so the blob's address stays in scalar registers like A.pol_weights itself -- and each lane of the env
+// wave, which holds up to 48 envs of up to three members, takes log_std from its own env's member. The loop, the barriers, the noise
+// keys, parking, restart on done, the counters and save_env are the lines below, untouched.
+template <int KIND, int S, bool RG, int NET = TB_NET_DEFAULT, class... MEMBERS>
+__global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KArgs A, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PolicyMembers");
   constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE * S;
   __shared__ float4 s_hull[TB_HULL_LDS];
   __shared__ __attribute__((aligned(16))) float s_mean[E * 8];
@@ -1153,7 +1168,10 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
     const int slot = slice * TB_POLICY_SLICE + (lane & 15), env = blockIdx.x * E + slot;
     const int env_c = env < A.n ? env : A.n - 1;
     PolicyRegs<KIND, NET> regs;
-    regs.load(A.pol_weights, tower, lane);
+    const float* blob = A.pol_weights;
+    if constexpr (sizeof...(MEMBERS) != 0)  // the slice's member: wave-uniform
+      blob += (size_t)__builtin_amdgcn_readfirstlane(member_of_env(members..., (int)blockIdx.x * E + slice * TB_POLICY_SLICE, A.n)) * (members.stride, ...);
+    regs.load(blob, tower, lane);
     __syncthreads();
     for (int t = 0; t < A.T; ++t) {
       float x0[policy_nc0<KIND>()], out[4];
@@ -1185,8 +1203,10 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
   TB_DIAG_STAMPS_BEGIN(st);
   __syncthreads();
   float stdv[NA], lstd[NA];
+  const float* blob = A.pol_weights;
+  if constexpr (sizeof...(MEMBERS) != 0) blob += (size_t)member_of_env(members..., i, A.n) * (members.stride, ...);  // this lane's env's member
 #pragma unroll
-  for (int k = 0; k < NA; ++k) { lstd[k] = A.pol_weights[PolicyBlob<KIND, NET>::LOG_STD + k]; stdv[k] = expf(lstd[k]); }
+  for (int k = 0; k < NA; ++k) { lstd[k] = blob[PolicyBlob<KIND, NET>::LOG_STD + k]; stdv[k] = expf(lstd[k]); }
   KParams Pl = A.P;
   pin_substep_params(Pl);
   for (int t = 0; t < A.T; ++t) {
@@ -1260,7 +1280,6 @@ __global__ void __launch_bounds__((2 * S + 1) * 64) tb_policy_rollout_kernel(KAr
 // its log_std; floats between the blobs are never read. The loop, the barriers and the exit are the same lines. The argument is a
 // trailing pack, empty or one PolicyMembers, so that tb_policy_evaluate_kernel<KIND, RG, NET> remains the kernel it was, argument
 // list included.
-struct PolicyMembers { size_t stride; int per_member; };
 TB_DEV size_t member_blob_offset(const PolicyMembers& mb) { return (size_t)((blockIdx.x * (unsigned)TB_POLICY_SLICE) / (unsigned)mb.per_member) * mb.stride; }
 template <int KIND, bool RG, int NET = TB_NET_DEFAULT, class... MEMBERS>
 __global__ void __launch_bounds__(128) tb_policy_evaluate_kernel(KArgs A, double* ret_out, int32_t* len_out, MEMBERS... members) {

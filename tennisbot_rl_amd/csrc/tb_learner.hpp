@@ -236,8 +236,31 @@ struct PpoGradArgs {
   float clip_range, vf_coef;
 };
 
+// ---- THE MEMBER AXIS (tb_ppo_grad_members / tb_ppo_apply_members: a population of PPO learners takes its minibatch step in three
+// launches, whatever its size). The flat rollout arrays are shared; a member's rows are picked by ITS index row. Per member: an
+// index row, a parameter / gradient / moment row, a workspace region (advantage sums, then partials), a statistics row [3] and a
+// hyper-parameter row (TbPpoMemberHp: clip_range, vf_coef, ent_coef, lr). Every kernel below takes the member as ONE trailing
+// argument, a PpoMembers, in a pack that is empty or holds that one: with the pack empty the kernel is what it was, argument list
+// included. With it, the member is blockIdx.y (blockIdx.x of the one-workgroup step kernel); a prologue offsets the member's own
+// pointers and takes its scalars from hp[member]; the body -- every reduction order, the absence of atomics, the arithmetic -- is the
+// same lines. The member index depends on the block index alone: every offset pointer stays scalar.
+struct PpoMembers {
+  const TbPpoMemberHp* hp;  // [M]
+  size_t idx_stride;        // int64 entries between index rows
+  size_t param_stride;      // floats between parameter (gradient, moment) rows
+  size_t ws_stride;         // bytes between workspace regions (a multiple of 8)
+};
+template <class T> TB_DEV T* ppo_member_bytes(T* p, size_t bytes) { return (T*)((const char*)p + bytes); }
+
 // sum and sum of squares of the minibatch's advantages, float64, one pair per block (fixed order inside a block)
-__global__ __launch_bounds__(256) void tb_ppo_adv_stats_kernel(const float* adv, const long long* idx, int batch, long long n_rows, double* out) {
+template <class... MEMBERS>
+__global__ __launch_bounds__(256) void tb_ppo_adv_stats_kernel(const float* adv, const long long* idx, int batch, long long n_rows, double* out, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PpoMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const PpoMembers mb = (members, ...);
+    idx += (size_t)blockIdx.y * mb.idx_stride;
+    out = ppo_member_bytes(out, (size_t)blockIdx.y * mb.ws_stride);
+  }
   __shared__ double s_x[256], s_q[256];
   double x = 0.0, q = 0.0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < batch; i += TB_PPO_STAT_BLOCKS * 256) {
@@ -411,8 +434,21 @@ TB_DEV void ppo_tower(const PpoGradArgs& a, float* buf, int lane, int first, flo
   if (lane == 0) part[L::P + (PI ? 0 : 1)] = stat;
 }
 
-template <int KIND, int NET = TB_NET_DEFAULT>
-__global__ __launch_bounds__(256) void tb_ppo_grad_kernel(const PpoGradArgs a) {
+// the member's view of the shared arguments: its index row, parameter row, workspace region (sums, then partials), clip_range, vf_coef
+TB_DEV void ppo_member_args(PpoGradArgs& a, const PpoMembers& mb) {
+  const size_t m = blockIdx.y;
+  a.idx += m * mb.idx_stride;
+  a.params += m * mb.param_stride;
+  a.adv_sums = ppo_member_bytes(a.adv_sums, m * mb.ws_stride);
+  a.partials = ppo_member_bytes(a.partials, m * mb.ws_stride);
+  a.clip_range = mb.hp[m].clip_range;
+  a.vf_coef = mb.hp[m].vf_coef;
+}
+
+template <int KIND, int NET = TB_NET_DEFAULT, class... MEMBERS>
+__global__ __launch_bounds__(256) void tb_ppo_grad_kernel(PpoGradArgs a, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PpoMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) ppo_member_args(a, members...);
   __shared__ __attribute__((aligned(16))) float s_buf[4 * 512];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = wave & 1;
   const int first = blockIdx.x * TB_PPO_SHARE + half * TB_PPO_HALF;
@@ -424,9 +460,21 @@ __global__ __launch_bounds__(256) void tb_ppo_grad_kernel(const PpoGradArgs a) {
 // gradient[p] = sum of the partials in a fixed order (float64: four runs of n_part / 4, then (0 + 1) + (2 + 3)); log_std's
 // entropy term; the minibatch's three statistics. 64 parameters per block. value_only: grad's policy slots (log_std, PI,
 // PI_HEAD) are left as they are.
-template <int KIND, int NET = TB_NET_DEFAULT>
+// the member's partials, parameter and gradient rows, statistics row, ent_coef
+TB_DEV void ppo_member_reduce(const PpoMembers& mb, const float*& partials, const float*& params, float& ent_coef, float*& grad, float*& stats) {
+  const size_t m = blockIdx.y;
+  partials = ppo_member_bytes(partials, m * mb.ws_stride);
+  params += m * mb.param_stride;
+  grad += m * mb.param_stride;
+  stats += 3 * m;
+  ent_coef = mb.hp[m].ent_coef;
+}
+
+template <int KIND, int NET = TB_NET_DEFAULT, class... MEMBERS>
 __global__ __launch_bounds__(256) void tb_ppo_reduce_kernel(const float* partials, int n_part, int batch, const float* params, float ent_coef, float* grad,
-                                                            float* stats, int value_only) {
+                                                            float* stats, int value_only, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PpoMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) ppo_member_reduce((members, ...), partials, params, ent_coef, grad, stats);
   using L = PpoLayout<KIND, NET>;
   __shared__ double s_sum[4][64];
   const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;
@@ -455,8 +503,18 @@ __global__ __launch_bounds__(256) void tb_ppo_reduce_kernel(const float* partial
 
 // grad /= world; the global norm (float64, fixed-order tree); torch's clip factor; Adam. One workgroup. Only the slots in
 // [lo0, hi0) or [lo1, hi1) take part, in the norm too (every slot: 0, P, 0, 0; the critic alone: the VF and VF_HEAD slots).
+// The members form: one workgroup per member (blockIdx.x), its four rows and its lr.
+template <class... MEMBERS>
 __global__ __launch_bounds__(1024) void tb_ppo_step_kernel(float* params, float* grad, float* m, float* v, int P, float world, float max_norm, float lr,
-                                                           float beta1, float beta2, float eps, float c1, float c2, int lo0, int hi0, int lo1, int hi1) {
+                                                           float beta1, float beta2, float eps, float c1, float c2, int lo0, int hi0, int lo1, int hi1,
+                                                           MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PpoMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const PpoMembers mb = (members, ...);
+    const size_t row = (size_t)blockIdx.x * mb.param_stride;
+    params += row; grad += row; m += row; v += row;
+    lr = mb.hp[blockIdx.x].lr;
+  }
   __shared__ double s_sq[1024];
   double sq = 0.0;
   for (int p = threadIdx.x; p < P; p += 1024) {
@@ -707,7 +765,10 @@ TB_DEV void ppo_tuned_tower(const PpoGradArgs& a, float* buf, float* wb_lds, int
 
 #undef TB_TUNED_STAGE
 
-__global__ __launch_bounds__(256) void tb_ppo_grad_tuned_kernel(const PpoGradArgs a) {
+template <class... MEMBERS>
+__global__ __launch_bounds__(256) void tb_ppo_grad_tuned_kernel(PpoGradArgs a, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PpoMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) ppo_member_args(a, members...);
   constexpr int NWB = PpoLayer<TunedNet::FH, TunedNet::F, false, false>::NWB + PpoLayer<TunedNet::H1, TunedNet::H2, false, false>::NWB;
   __shared__ __attribute__((aligned(16))) float s_buf[4 * 512];
   __shared__ float s_wb[4 * NWB * 64];  // per wave: the transposed fragments of the extractor's output layer and of the tower's third layer
@@ -720,8 +781,11 @@ __global__ __launch_bounds__(256) void tb_ppo_grad_tuned_kernel(const PpoGradArg
 
 // tb_ppo_reduce_kernel for the tuned net: the same fixed-order float64 sums per slot; an extractor slot is (the sum of the pi
 // waves' shares) + (the sum of the vf waves' shares, from the partials' second extractor region)
+template <class... MEMBERS>
 __global__ __launch_bounds__(256) void tb_ppo_reduce_tuned_kernel(const float* partials, int n_part, int batch, const float* params, float ent_coef, float* grad,
-                                                                  float* stats) {
+                                                                  float* stats, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PpoMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) ppo_member_reduce((members, ...), partials, params, ent_coef, grad, stats);
   using L = TunedLayout;
   __shared__ double s_sum[4][64], s_sum2[4][64];
   const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;

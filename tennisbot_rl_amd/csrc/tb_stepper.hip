@@ -750,9 +750,10 @@ int run_steps_from_state(TbHandle* h, int T, KArgs a, size_t reward_step_stride,
   return TB_OK;
 }
 
-// one launch of tb_policy_rollout_kernel over T steps; SwingRacket: T ends where the episode does
+// one launch of tb_policy_rollout_kernel over T steps; SwingRacket: T ends where the episode does. members: null, or the population
+// whose blobs pol.weights holds (the kernel's members form: the same grid, block and LDS)
 int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, float* reward, uint8_t* done, const size_t* st /*element strides*/,
-                          hipStream_t s) {
+                          hipStream_t s, const PolicyMembers* members = nullptr) {
   KArgs a = base_args(h);
   pol.apply(a);
   a.obs = obs; a.reward = reward; a.done_out = done; a.T = T;
@@ -761,6 +762,14 @@ int launch_policy_rollout(TbHandle* h, int T, const PolicyIO& pol, float* obs, f
     // 16 envs per workgroup (3 waves) while every workgroup still gets a CU of its own, else 48 (7 waves): see the kernel
     const bool narrow = h->opt.policy_slices ? h->opt.policy_slices == 1 : h->n <= 4096;
     const int E = narrow ? TB_POLICY_SLICE : 3 * TB_POLICY_SLICE;
+    if (members) {
+      using MembersKernel = void (*)(KArgs, PolicyMembers);
+      const MembersKernel kern = kernel_of_kind_net_rg(h->kind, pol.net, rg, [&](auto K, auto N, auto R) -> MembersKernel {
+        return narrow ? tb_policy_rollout_kernel<K.value, 1, R.value, N.value, PolicyMembers> : tb_policy_rollout_kernel<K.value, 3, R.value, N.value, PolicyMembers>;
+      });
+      if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_rollout_kernel members instantiation for this variant");
+      return launch(kern, dim3((unsigned)((h->n + E - 1) / E)), dim3(narrow ? 192 : 448), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, k, *members);
+    }
     const ArgsKernel kern = kernel_of_kind_net_rg(h->kind, pol.net, rg, [&](auto K, auto N, auto R) -> ArgsKernel {
       return narrow ? tb_policy_rollout_kernel<K.value, 1, R.value, N.value> : tb_policy_rollout_kernel<K.value, 3, R.value, N.value>;
     });
@@ -1188,27 +1197,36 @@ int tb_policy_rollout(TbHandle* h, int n_steps, const float* weights_dev, const 
   return tb_policy_rollout_net(h, TB_NET_DEFAULT, n_steps, weights_dev, obs_in_dev, actions_dev, raw_actions_dev, logp_dev, value_dev, obs_dev, reward_dev, done_dev,
                                step_strides_bytes, noise_seed, deterministic, stream);
 }
-int tb_policy_rollout_net(TbHandle* h, int net, int n_steps, const float* weights_dev, const float* obs_in_dev, float* actions_dev, float* raw_actions_dev,
-                          float* logp_dev, float* value_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, const size_t* step_strides_bytes,
-                          uint64_t noise_seed, int deterministic, void* stream) {
+namespace {
+// tb_policy_rollout_net and tb_policy_rollout_members (`who`; members: null, or the population -- n_members is only checked here)
+int policy_rollout(const char* who, TbHandle* h, int net, int n_steps, const float* weights_dev, const PolicyMembers* members, int n_members,
+                   const float* obs_in_dev, float* actions_dev, float* raw_actions_dev, float* logp_dev, float* value_dev, float* obs_dev, float* reward_dev,
+                   uint8_t* done_dev, const size_t* step_strides_bytes, uint64_t noise_seed, int deterministic, void* stream) {
   if (!h || !weights_dev || !obs_in_dev || !actions_dev || !raw_actions_dev || !logp_dev || !value_dev || !obs_dev || !reward_dev || !done_dev)
-    return fail(TB_E_INVAL, "tb_policy_rollout: null argument");
-  if (n_steps < 1) return fail(TB_E_INVAL, "tb_policy_rollout: n_steps must be >= 1");
-  if (int rc = policy_net_ok(h->kind, net, "tb_policy_rollout")) return rc;
-  if (int rc = refuse_steps_from_state(h, "tb_policy_rollout")) return rc;
+    return refusal(TB_E_INVAL, who, ": null argument");
+  if (n_steps < 1) return refusal(TB_E_INVAL, who, ": n_steps must be >= 1");
+  if (int rc = policy_net_ok(h->kind, net, who)) return rc;
+  if (members) {
+    if (n_members < 1 || members->per_member < 1 || members->per_member % TB_POLICY_SLICE)
+      return refusal(TB_E_INVAL, who, ": n_members must be >= 1 and envs_per_member a positive multiple of tb_policy_member_granule() (16)");
+    if ((long long)n_members * members->per_member != h->n) return refusal(TB_E_INVAL, who, ": n_members * envs_per_member must equal n_envs");
+    if (members->stride % 4 || members->stride < (size_t)tb_policy_blob_floats(h->kind, net) || reinterpret_cast<uintptr_t>(weights_dev) % 16)
+      return refusal(TB_E_INVAL, who, ": the weights' row stride must be a multiple of 4 floats and >= tb_policy_blob_floats, the base 16-byte aligned");
+  }
+  if (int rc = refuse_steps_from_state(h, who)) return rc;
   const bool swing = h->kind == TB_ENV_SWING;
   const size_t n = (size_t)h->n, A = swing ? TB_SWING_ACT_DIM : TB_TENNIS_ACT_DIM, O = swing ? TB_SWING_OBS_DIM : TB_TENNIS_OBS_DIM;
   size_t st[7] = {n * A, n * A, n, n, n * O, n, n};  // elements per step: actions, raw, logp, value, obs, reward, done
   if (step_strides_bytes) {
     for (int k = 0; k < 7; ++k) {
       const size_t el = k == 6 ? 1 : sizeof(float);
-      if (step_strides_bytes[k] % el) return fail(TB_E_INVAL, "tb_policy_rollout: a step stride is not a multiple of its element size");
+      if (step_strides_bytes[k] % el) return refusal(TB_E_INVAL, who, ": a step stride is not a multiple of its element size");
       if (step_strides_bytes[k]) st[k] = step_strides_bytes[k] / el;
     }
   }
   // action rows are written 8 bytes at a time (like the action rows tb_step reads): bases and step strides must keep them aligned
   if ((reinterpret_cast<uintptr_t>(actions_dev) | reinterpret_cast<uintptr_t>(raw_actions_dev)) % 8 || (st[0] * sizeof(float)) % 8 || (st[1] * sizeof(float)) % 8)
-    return fail(TB_E_INVAL, "tb_policy_rollout: actions / raw_actions and their step strides must be 8-byte aligned");
+    return refusal(TB_E_INVAL, who, ": actions / raw_actions and their step strides must be 8-byte aligned");
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const float* obs_in = obs_in_dev;
@@ -1216,11 +1234,26 @@ int tb_policy_rollout_net(TbHandle* h, int net, int n_steps, const float* weight
     const int chunk = swing ? h->phase.chunk(n_steps - t) : n_steps - t;
     PolicyIO pol = {weights_dev, obs_in, actions_dev + (size_t)t * st[0], raw_actions_dev + (size_t)t * st[1], logp_dev + (size_t)t * st[2],
                     value_dev + (size_t)t * st[3], noise_seed, deterministic, net};
-    if (int rc = launch_policy_rollout(h, chunk, pol, obs_dev + (size_t)t * st[4], reward_dev + (size_t)t * st[5], done_dev + (size_t)t * st[6], st, s)) return rc;
+    if (int rc = launch_policy_rollout(h, chunk, pol, obs_dev + (size_t)t * st[4], reward_dev + (size_t)t * st[5], done_dev + (size_t)t * st[6], st, s, members)) return rc;
     t += chunk;
     obs_in = obs_dev + (size_t)(t - 1) * st[4];  // the next launch acts on what this one observed last
   }
   return TB_OK;
+}
+}  // namespace
+int tb_policy_rollout_net(TbHandle* h, int net, int n_steps, const float* weights_dev, const float* obs_in_dev, float* actions_dev, float* raw_actions_dev,
+                          float* logp_dev, float* value_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, const size_t* step_strides_bytes,
+                          uint64_t noise_seed, int deterministic, void* stream) {
+  return policy_rollout("tb_policy_rollout", h, net, n_steps, weights_dev, nullptr, 0, obs_in_dev, actions_dev, raw_actions_dev, logp_dev, value_dev, obs_dev,
+                        reward_dev, done_dev, step_strides_bytes, noise_seed, deterministic, stream);
+}
+// a population's collect: the same launches with the kernel's members form
+int tb_policy_rollout_members(TbHandle* h, int net, int n_steps, const float* weights_dev, int n_members, size_t weights_stride_floats, int envs_per_member,
+                              const float* obs_in_dev, float* actions_dev, float* raw_actions_dev, float* logp_dev, float* value_dev, float* obs_dev,
+                              float* reward_dev, uint8_t* done_dev, const size_t* step_strides_bytes, uint64_t noise_seed, int deterministic, void* stream) {
+  const PolicyMembers members = {weights_stride_floats, envs_per_member};
+  return policy_rollout("tb_policy_rollout_members", h, net, n_steps, weights_dev, &members, n_members, obs_in_dev, actions_dev, raw_actions_dev, logp_dev, value_dev,
+                        obs_dev, reward_dev, done_dev, step_strides_bytes, noise_seed, deterministic, stream);
 }
 
 int tb_es_floats(int env_kind) {
@@ -1438,9 +1471,9 @@ int tb_ppo_grad_net(int env_kind, int net, int device, void* stream, const float
   double* sums = (double*)workspace_dev;
   PpoGradArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, (const long long*)idx_dev, params_dev, sums,
                    (float*)((char*)workspace_dev + kPpoStatBytes), n_rows, batch, clip_range, vf_coef};
-  if (int rc = launch(tb_ppo_adv_stats_kernel, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
+  if (int rc = launch(tb_ppo_adv_stats_kernel<>, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
   const dim3 grid((unsigned)(ppo_partials(batch) / 2));
-  if (net == TB_NET_TUNED) return launch(tb_ppo_grad_tuned_kernel, grid, dim3(256), 0, s, a);
+  if (net == TB_NET_TUNED) return launch(tb_ppo_grad_tuned_kernel<>, grid, dim3(256), 0, s, a);
   if (net == TB_NET_MLP64) return launch(tb_ppo_grad_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, a);
   return env_kind == TB_ENV_SWING ? launch(tb_ppo_grad_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a) : launch(tb_ppo_grad_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a);
 }
@@ -1483,7 +1516,7 @@ int tb_ppo_apply_net(int env_kind, int net, int device, void* stream, int phases
     const int n_part = (int)ppo_partials(batch);
     const dim3 grid((unsigned)((n_params + 2 + 63) / 64));
     if (net == TB_NET_TUNED) {
-      if (int rc = launch(tb_ppo_reduce_tuned_kernel, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev)) return rc;
+      if (int rc = launch(tb_ppo_reduce_tuned_kernel<>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev)) return rc;
     } else if (net == TB_NET_MLP64) {
       if (int rc = launch(tb_ppo_reduce_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only))
         return rc;
@@ -1499,10 +1532,90 @@ int tb_ppo_apply_net(int env_kind, int net, int device, void* stream, int phases
       if (d.P != n_params) return fail(TB_E_UNSUPPORTED, "tb_ppo_apply: no critic-only slot range for this (kind, net) pair");
       lo0 = d.VF; hi0 = d.PI_HEAD; lo1 = d.VF_HEAD; hi1 = d.P;
     }
-    return launch(tb_ppo_step_kernel, dim3(1), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, (float)world, max_grad_norm, lr,
+    return launch(tb_ppo_step_kernel<>, dim3(1), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, (float)world, max_grad_norm, lr,
                   beta1, beta2, eps, c1, c2, lo0, hi0, lo1, hi1);
   }
   return TB_OK;
+}
+
+// ---- a population's minibatch step (tb_learner.hpp, "THE MEMBER AXIS"): the same kernels with the member as a second grid axis
+long long tb_ppo_members_workspace_stride_bytes(int env_kind, int net, int batch) {
+  const long long one = tb_ppo_workspace_bytes_net(env_kind, net, batch);
+  return one < 0 ? one : (one + 7) / 8 * 8;
+}
+// what both calls refuse, before the device is looked up
+static int ppo_members_refused(const char* who, int env_kind, int net, int batch, int n_members, size_t param_stride_floats, int n_params, const void* hp_dev,
+                               const void* workspace_dev, size_t workspace_bytes) {
+  if (!kind_ok(env_kind)) return refusal(TB_E_INVAL, who, ": unknown env kind");
+  if (int rc = policy_net_ok(env_kind, net, who)) return rc;
+  if (n_members < 1 || n_members > 65535) return refusal(TB_E_INVAL, who, ": n_members must be in [1, 65535] (the member is a grid axis)");
+  if (batch < 2) return refusal(TB_E_INVAL, who, ": batch must be >= 2 (the unbiased std of one row is undefined)");
+  if (!hp_dev || !workspace_dev) return refusal(TB_E_INVAL, who, ": null argument");
+  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return refusal(TB_E_INVAL, who, ": n_params is not tb_ppo_param_floats_net(env_kind, net)");
+  if (param_stride_floats < (size_t)n_params) return refusal(TB_E_INVAL, who, ": param_stride_floats is shorter than n_params");
+  if (misaligned(hp_dev, 8) || misaligned(workspace_dev, 8)) return refusal(TB_E_INVAL, who, ": idx, hp and the workspace must be 8-byte aligned");
+  if (workspace_bytes / (size_t)n_members < (size_t)tb_ppo_members_workspace_stride_bytes(env_kind, net, batch))
+    return refusal(TB_E_INVAL, who, ": the workspace is smaller than n_members * tb_ppo_members_workspace_stride_bytes");
+  return TB_OK;
+}
+
+int tb_ppo_grad_members(int env_kind, int net, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev,
+                        const float* adv_dev, const float* returns_dev, long long n_rows, const int64_t* idx_dev, size_t idx_stride, int batch, int n_members,
+                        const float* params_dev, size_t param_stride_floats, int n_params, const TbPpoMemberHp* hp_dev, void* workspace_dev, size_t workspace_bytes) {
+  const char* const who = "tb_ppo_grad_members";
+  if (!obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !returns_dev || !idx_dev || !params_dev) return refusal(TB_E_INVAL, who, ": null argument");
+  if (int rc = ppo_members_refused(who, env_kind, net, batch, n_members, param_stride_floats, n_params, hp_dev, workspace_dev, workspace_bytes)) return rc;
+  if (n_rows < 1) return refusal(TB_E_INVAL, who, ": n_rows must be >= 1");
+  if (idx_stride < (size_t)batch) return refusal(TB_E_INVAL, who, ": idx_stride is shorter than batch");
+  if (misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) || misaligned(returns_dev, 4) ||
+      misaligned(params_dev, 4))
+    return refusal(TB_E_INVAL, who, ": a float array is not 4-byte aligned");
+  if (misaligned(idx_dev, 8)) return refusal(TB_E_INVAL, who, ": idx, hp and the workspace must be 8-byte aligned");
+  if (int rc = ppo_device(device, "tb_ppo_grad_members: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  hipStream_t s = (hipStream_t)stream;
+  double* sums = (double*)workspace_dev;
+  const PpoMembers mb = {hp_dev, idx_stride, param_stride_floats, (size_t)tb_ppo_members_workspace_stride_bytes(env_kind, net, batch)};
+  const PpoGradArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, (const long long*)idx_dev, params_dev, sums,
+                         (float*)((char*)workspace_dev + kPpoStatBytes), n_rows, batch, 0.0f, 0.0f};  // (clip_range, vf_coef: the member's, from hp)
+  const unsigned M = (unsigned)n_members;
+  if (int rc = launch(tb_ppo_adv_stats_kernel<PpoMembers>, dim3(TB_PPO_STAT_BLOCKS, M), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums, mb)) return rc;
+  const dim3 grid((unsigned)(ppo_partials(batch) / 2), M);
+  if (net == TB_NET_TUNED) return launch(tb_ppo_grad_tuned_kernel<PpoMembers>, grid, dim3(256), 0, s, a, mb);
+  if (net == TB_NET_MLP64) return launch(tb_ppo_grad_kernel<TB_ENV_SWING, TB_NET_MLP64, PpoMembers>, grid, dim3(256), 0, s, a, mb);
+  return env_kind == TB_ENV_SWING ? launch(tb_ppo_grad_kernel<TB_ENV_SWING, TB_NET_DEFAULT, PpoMembers>, grid, dim3(256), 0, s, a, mb)
+                                  : launch(tb_ppo_grad_kernel<TB_ENV_TENNIS, TB_NET_DEFAULT, PpoMembers>, grid, dim3(256), 0, s, a, mb);
+}
+
+int tb_ppo_apply_members(int env_kind, int net, int device, void* stream, const void* workspace_dev, size_t workspace_bytes, int batch, int n_members,
+                         float* params_dev, float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, size_t param_stride_floats, int n_params, float* stats_dev,
+                         const TbPpoMemberHp* hp_dev, float max_grad_norm, float beta1, float beta2, float eps, long long step) {
+  const char* const who = "tb_ppo_apply_members";
+  if (!params_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !stats_dev) return refusal(TB_E_INVAL, who, ": null argument");
+  if (int rc = ppo_members_refused(who, env_kind, net, batch, n_members, param_stride_floats, n_params, hp_dev, workspace_dev, workspace_bytes)) return rc;
+  if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(stats_dev, 4))
+    return refusal(TB_E_INVAL, who, ": a float array is not 4-byte aligned");
+  if (step < 1) return refusal(TB_E_INVAL, who, ": step must be >= 1");
+  if (int rc = ppo_device(device, "tb_ppo_apply_members: device index out of range")) return rc;
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  hipStream_t s = (hipStream_t)stream;
+  const PpoMembers mb = {hp_dev, 0, param_stride_floats, (size_t)tb_ppo_members_workspace_stride_bytes(env_kind, net, batch)};
+  const float* partials = (const float*)((const char*)workspace_dev + kPpoStatBytes);
+  const int n_part = (int)ppo_partials(batch);
+  const unsigned M = (unsigned)n_members;
+  const dim3 grid((unsigned)((n_params + 2 + 63) / 64), M);
+  const float* params = params_dev;
+  int rc;
+  if (net == TB_NET_TUNED) rc = launch(tb_ppo_reduce_tuned_kernel<PpoMembers>, grid, dim3(256), 0, s, partials, n_part, batch, params, 0.0f, grad_dev, stats_dev, mb);
+  else if (net == TB_NET_MLP64) rc = launch(tb_ppo_reduce_kernel<TB_ENV_SWING, TB_NET_MLP64, PpoMembers>, grid, dim3(256), 0, s, partials, n_part, batch, params, 0.0f, grad_dev, stats_dev, 0, mb);
+  else if (env_kind == TB_ENV_SWING) rc = launch(tb_ppo_reduce_kernel<TB_ENV_SWING, TB_NET_DEFAULT, PpoMembers>, grid, dim3(256), 0, s, partials, n_part, batch, params, 0.0f, grad_dev, stats_dev, 0, mb);
+  else rc = launch(tb_ppo_reduce_kernel<TB_ENV_TENNIS, TB_NET_DEFAULT, PpoMembers>, grid, dim3(256), 0, s, partials, n_part, batch, params, 0.0f, grad_dev, stats_dev, 0, mb);
+  if (rc) return rc;
+  const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
+  return launch(tb_ppo_step_kernel<PpoMembers>, dim3(M), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, 1.0f, max_grad_norm, 0.0f, beta1,
+                beta2, eps, c1, c2, 0, n_params, 0, 0, mb);
 }
 
 // ------------------------------------------------------------------------------------------- the TRPO learner (tb_trpo.hpp)
@@ -1592,7 +1705,7 @@ int tb_trpo_search_net(int env_kind, int net, int device, void* stream, const fl
   double* partials = (double*)((char*)workspace_dev + kPpoStatBytes);
   const int shares = (int)trpo_search_shares(batch);
   TrpoSearchArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, (const long long*)idx_dev, params_dev, direction_dev, steps_dev, sums, partials, n_rows, batch};
-  if (int rc = launch(tb_ppo_adv_stats_kernel, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
+  if (int rc = launch(tb_ppo_adv_stats_kernel<>, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
   const dim3 grid((unsigned)shares, (unsigned)n_candidates);
   if (int rc = net == TB_NET_MLP64            ? launch(tb_trpo_search_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, a)
                : env_kind == TB_ENV_SWING ? launch(tb_trpo_search_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a)

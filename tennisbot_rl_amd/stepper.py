@@ -103,6 +103,8 @@ def load_library():
     L.tb_policy_member_granule.restype = i32
     L.tb_policy_evaluate_members.argtypes = [vp, i32, vp, i32, ctypes.c_size_t, i32, vp, vp, u64, i32, vp]
     L.tb_policy_evaluate_members.restype = i32
+    L.tb_policy_rollout_members.argtypes = [vp, i32, i32, vp, i32, ctypes.c_size_t, i32] + [vp] * 8 + [ctypes.POINTER(ctypes.c_size_t), u64, i32, vp]
+    L.tb_policy_rollout_members.restype = i32
     L.tb_sac_evaluate.argtypes = [vp, vp, vp, vp, u64, i32, ctypes.POINTER(TbSacEvalTrace), vp]
     L.tb_sac_evaluate.restype = i32
     L.tb_sac_collect.argtypes = [vp, vp, i32, i32, u64, ctypes.POINTER(TbSacCollectOut), vp]
@@ -128,6 +130,12 @@ def load_library():
     L.tb_ppo_grad_net.restype = i32
     L.tb_ppo_apply_net.argtypes = [i32, i32, i32, vp, i32, vp, ctypes.c_size_t, i32] + [vp] * 4 + [i32, vp, f32, f32, i32, f32, f32, f32, f32, i64]
     L.tb_ppo_apply_net.restype = i32
+    L.tb_ppo_members_workspace_stride_bytes.argtypes = [i32, i32, i32]
+    L.tb_ppo_members_workspace_stride_bytes.restype = i64
+    L.tb_ppo_grad_members.argtypes = [i32, i32, i32, vp] + [vp] * 5 + [i64, vp, ctypes.c_size_t, i32, i32, vp, ctypes.c_size_t, i32, vp, vp, ctypes.c_size_t]
+    L.tb_ppo_grad_members.restype = i32
+    L.tb_ppo_apply_members.argtypes = [i32, i32, i32, vp, vp, ctypes.c_size_t, i32, i32] + [vp] * 4 + [ctypes.c_size_t, i32, vp, vp, f32, f32, f32, f32, i64]
+    L.tb_ppo_apply_members.restype = i32
     L.tb_trpo_rows_per_workgroup.argtypes = []
     L.tb_trpo_rows_per_workgroup.restype = i32
     L.tb_trpo_search_rows_per_workgroup.argtypes = []
@@ -652,6 +660,36 @@ class BatchedEnv:
             self._inflight.append(rew)
         return (obs, rew, done), (act, raw, logp, value)
 
+    def policy_rollout_members_ptrs(self, n_steps, weights_ptr, n_members, weights_stride, envs_per_member, obs_in_ptr, act_ptr, raw_ptr, logp_ptr, value_ptr,
+                                    obs_ptr, reward_ptr, done_ptr, strides_bytes, seed, deterministic=False, net=NET_DEFAULT):
+        """policy_rollout_ptrs for a population of networks (tb_policy_rollout_members): n_members blobs weights_stride floats
+        apart, env i runs with member i // envs_per_member's. Unchecked fast path, validated once by the caller."""
+        st = (ctypes.c_size_t * 7)(*[int(x) for x in strides_bytes])
+        rc = self.L.tb_policy_rollout_members(self._h, int(net), int(n_steps), weights_ptr, int(n_members), int(weights_stride), int(envs_per_member), obs_in_ptr,
+                                              act_ptr, raw_ptr, logp_ptr, value_ptr, obs_ptr, reward_ptr, done_ptr, st, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              1 if deterministic else 0, self.torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            _check(self.L, rc, "tb_policy_rollout_members")
+        self._steps_issued += int(n_steps)
+
+    def policy_rollout_members(self, weights, envs_per_member, obs_in, n_steps, seed=0, deterministic=False, net=NET_DEFAULT):
+        """policy_rollout for a population of networks, the same launches (tb_policy_rollout_members). weights: [M, stride] float32
+        on this device, row m the packed blob of member m, as policy_evaluate_members takes them (a misaligned, non-contiguous or
+        odd-stride input is re-packed first); M * envs_per_member == num_envs, env i uses member i // envs_per_member, and
+        envs_per_member must be a multiple of policy_member_granule(). Member m's env columns are what policy_rollout(weights[m])
+        gives on a batch of envs_per_member envs at env_id_base + m * envs_per_member. Returns policy_rollout's tuples."""
+        t, n, T = self.torch, self.num_envs, int(n_steps)
+        weights, M, R = self._members_weights(weights, envs_per_member, net)
+        oi = self._check_tensor(obs_in, (n, self.obs_dim), t.float32, "obs_in")
+        f = dict(dtype=t.float32, device=self.device)
+        obs, rew, done = t.empty((T, n, self.obs_dim), **f), t.empty((T, n), **f), t.empty((T, n), dtype=t.uint8, device=self.device)
+        act, raw, logp, value = t.empty((T, n, self.act_dim), **f), t.empty((T, n, self.act_dim), **f), t.empty((T, n), **f), t.empty((T, n), **f)
+        self.policy_rollout_members_ptrs(T, weights.data_ptr(), M, weights.shape[1], R, oi.data_ptr(), act.data_ptr(), raw.data_ptr(), logp.data_ptr(),
+                                         value.data_ptr(), obs.data_ptr(), rew.data_ptr(), done.data_ptr(), (0,) * 7, seed, deterministic, net)
+        if self.pipeline:
+            self._inflight.append(rew)
+        return (obs, rew, done), (act, raw, logp, value)
+
     def es_floats(self):
         """GatedCNN parameters per member for this env kind (766 SwingRacket-v0, 858 Tennisbot-v0)"""
         return int(self.L.tb_es_floats(self.kind))
@@ -711,14 +749,9 @@ class BatchedEnv:
         """envs_per_member of policy_evaluate_members must be a multiple of this (16: the envs of one tower wave)"""
         return int(self.L.tb_policy_member_granule())
 
-    def policy_evaluate_members(self, weights, envs_per_member, seed=0, deterministic=False, net=NET_DEFAULT):
-        """policy_evaluate for a population of networks in one launch (tb_policy_evaluate_members). weights: [M, stride] float32 on
-        this device, row m the packed blob of member m (`ppo.pack_policy`; `policy_es.pack_policy_members` for perturbations of one
-        policy), stride a multiple of 4 and >= policy_floats(net); M * envs_per_member == num_envs and env i uses member
-        i // envs_per_member; envs_per_member must be a multiple of policy_member_granule(). A misaligned, non-contiguous or
-        short-stride input is re-packed first, as es_evaluate does. Sampling, noise keys, the reset in front and the state
-        afterwards are policy_evaluate's: row m is what policy_evaluate(weights[m]) gives on a batch of envs_per_member envs at
-        env_id_base + m * envs_per_member. Returns (returns float64 [M, R], lengths int32 [M, R]), complete in stream order."""
+    def _members_weights(self, weights, envs_per_member, net):
+        """what both members calls ask of [M, stride] blobs; a misaligned, non-contiguous or odd-stride input is re-packed, as es_evaluate
+        does. Returns (weights, M, R)."""
         t, n = self.torch, self.num_envs
         R, G = int(envs_per_member), self.policy_member_granule()
         if R < 1 or R % G:
@@ -736,6 +769,18 @@ class BatchedEnv:
             w = t.zeros((M, (P + 3) // 4 * 4), dtype=t.float32, device=self.device)
             w[:, :P] = weights[:, :P]
             weights = w
+        return weights, M, R
+
+    def policy_evaluate_members(self, weights, envs_per_member, seed=0, deterministic=False, net=NET_DEFAULT):
+        """policy_evaluate for a population of networks in one launch (tb_policy_evaluate_members). weights: [M, stride] float32 on
+        this device, row m the packed blob of member m (`ppo.pack_policy`; `policy_es.pack_policy_members` for perturbations of one
+        policy), stride a multiple of 4 and >= policy_floats(net); M * envs_per_member == num_envs and env i uses member
+        i // envs_per_member; envs_per_member must be a multiple of policy_member_granule(). A misaligned, non-contiguous or
+        short-stride input is re-packed first, as es_evaluate does. Sampling, noise keys, the reset in front and the state
+        afterwards are policy_evaluate's: row m is what policy_evaluate(weights[m]) gives on a batch of envs_per_member envs at
+        env_id_base + m * envs_per_member. Returns (returns float64 [M, R], lengths int32 [M, R]), complete in stream order."""
+        t, n = self.torch, self.num_envs
+        weights, M, R = self._members_weights(weights, envs_per_member, net)
         ret = t.empty(n, dtype=t.float64, device=self.device)
         length = t.empty(n, dtype=t.int32, device=self.device)
         _check(self.L, self.L.tb_policy_evaluate_members(self._h, int(net), weights.data_ptr(), M, weights.shape[1], R, ret.data_ptr(), length.data_ptr(),

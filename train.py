@@ -4,6 +4,7 @@
   python train.py                                   # -s ppo: SB3's default 64-64 tanh MlpPolicy (train.py:104-110)
   python train.py -s tuned_ppo --curri              # the ReLU net with the shared features extractor (train.py:54-67,112-127)
   torchrun --nproc-per-node 8 train.py -s tuned_ppo # one process per GPU, sharded envs
+  python train.py -s tuned_ppo --population 4 --member-ent-coef 0,1e-3,3e-3,1e-2 --pbt-every 4   # 4 learners side by side, 1024 envs each
 
 `-s tuned_ppo` selects `PPOTrainer(policy="tuned")`: the network runs inside the rollout kernels (tb_policy_rollout_net with
 TB_NET_TUNED) and, with --learner fused, its update in the learner kernels (tb_ppo_grad_net / tb_ppo_apply_net). Hyper-parameters follow train.py (ppo.TENNIS_DEFAULTS / ppo.TUNED_TENNIS_DEFAULTS); the rollout is n_steps per
@@ -23,6 +24,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from tennisbot_rl_amd.evaluation import add_schedule_arguments, resolve_load, schedule_from_args  # noqa: E402
+from tennisbot_rl_amd.population import add_population_arguments, population_keywords  # noqa: E402
 from train_swing import racket_scale_for  # noqa: E402  (train.py:164-176, one table for both scripts)
 
 ENV_ID = "Tennisbot-v0"
@@ -44,9 +46,16 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-json", type=str, default=None)
     add_schedule_arguments(ap)
+    add_population_arguments(ap)
     args = ap.parse_args(argv)
     if args.select not in SELECT:
         sys.exit("-s %s: only ppo and tuned_ppo are implemented on the batched envs (trpo: train_swing.py). SAC: train_sac.py" % args.select)
+    try:
+        population = population_keywords(args, args.select)
+    except ValueError as exc:
+        sys.exit(str(exc))
+    if population is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("--population runs on one rank: multi-GPU populations are not provided")
 
     import torch
     from tennisbot_rl_amd.ppo import PPOTrainer
@@ -58,6 +67,16 @@ def main(argv=None):
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.distributed.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
     hp = {} if args.n_epochs is None else {"n_epochs": args.n_epochs}
+    if population is not None:
+        from tennisbot_rl_amd.population import PopulationPPO, run_population
+        pop = PopulationPPO(ENV_ID, n_steps=args.n_steps, net=SELECT[args.select], device=torch.device("cuda", local_rank), seed=args.seed, **population, **hp)
+        path = args.save or "./model/%s_%s.pt" % (args.select, ENV_ID)
+        if args.load:
+            pop.load(args.load)
+        history = run_population(pop, args.total_timesteps, path, save_freq=args.save_freq)
+        if args.log_json:
+            json.dump(history, open(args.log_json, "w"))
+        return
     tr = PPOTrainer(ENV_ID, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed,
                     learner=args.learner, policy=SELECT[args.select], **hp)
     path = args.save or "./model/%s_%s.pt" % (args.select, ENV_ID)

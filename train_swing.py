@@ -6,6 +6,7 @@
   torchrun --nproc-per-node 8 train_swing.py # one process per GPU, sharded envs
   python train_swing.py -s trpo --trpo-form sb3 --net mlp64   # the reference's `-s trpo`: sb3_contrib's TRPO on SB3's [64, 64] net
   python train_swing.py -s trpo --trpo-form agent_returns     # agent.py's own estimator: discounted returns of finished episodes, no critic
+  python train_swing.py --population 4 --member-lr 1e-4,3e-4,1e-3,3e-3 --pbt-every 4   # 4 PPO learners side by side, 1024 envs each
 
 Hyper-parameters follow train_swing.py:46-50,80-91 (net_arch pi=vf=[32,64,32], ent_coef 0.002,
 total_timesteps 2e6) and train.py:76-80,104-110 (Tennisbot: 64-64, ent_coef 0.01, 1e6); the
@@ -76,8 +77,16 @@ def parse_args(argv=None):
     ap.add_argument("--learner", default=None, choices=["torch", "fused"], help="ppo (default torch): fused = GAE, minibatch gradient and Adam as HIP kernels (tennisbot_rl_amd/learner.py); trpo has the fused learner only")
     ap.add_argument("--log-json", type=str, default=None)
     from tennisbot_rl_amd.evaluation import add_schedule_arguments
+    from tennisbot_rl_amd.population import add_population_arguments, population_keywords
     add_schedule_arguments(ap)
+    add_population_arguments(ap)
     args = ap.parse_args(argv)
+    try:
+        args.population_keywords = population_keywords(args, args.select)
+    except ValueError as exc:
+        sys.exit(str(exc))
+    if args.population_keywords is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("--population runs on one rank: multi-GPU populations are not provided")
     if args.select not in ("ppo", "trpo"):
         sys.exit("only -s ppo and -s trpo are implemented on the batched envs by this script. SAC: train_sac.py; TQC: train_tqc.py")
     if args.select == "trpo" and args.learner == "torch":
@@ -115,6 +124,17 @@ def main():
     if args.racket_ground or args.rolling_friction:
         from tennisbot_rl_amd.params import F_DEFAULT, F_RACKET_GROUND, default_params, reference_rolling_friction
         params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
+    if args.population_keywords is not None:
+        from tennisbot_rl_amd.population import PopulationPPO, run_population
+        pop = PopulationPPO(args.env, n_steps=args.n_steps, net=args.net, device=torch.device("cuda", local_rank), seed=args.seed, params=params,
+                            **args.population_keywords)
+        path = args.save % args.env if "%s" in args.save else args.save
+        if args.load:
+            pop.load(args.load)
+        history = run_population(pop, total, path, save_freq=args.save_freq)
+        if args.log_json:
+            json.dump(history, open(args.log_json, "w"))
+        return
     if args.select == "trpo":
         from tennisbot_rl_amd.trpo import TRPOTrainer
         tr = TRPOTrainer(args.env, num_envs=args.num_envs, n_steps=args.n_steps, device=torch.device("cuda", local_rank), seed=args.seed, fused=not args.no_fused,

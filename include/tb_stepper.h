@@ -485,6 +485,27 @@ int tb_sac_evaluate(TbHandle *h, const float *actor_dev, double *return_dev, int
                     int deterministic, const TbSacEvalTrace *trace_or_null, void *stream);
 
 /*
+ * tb_sac_evaluate for a POPULATION of actors, one launch (csrc/tb_sac.hpp, tb_sac_evaluate_kernel's members form): a tournament of
+ * the checkpoints train_sac.py / train_tqc.py write, or the runs of a seed sweep. A workgroup still owns 16 envs; they all belong
+ * to one member, whose vector its four waves stream -- 16 envs against one weight fragment on the matrix cores.
+ *   actors_dev: n_members flat TB_SAC_ACTOR vectors of tb_sac_param_floats(kind, TB_SAC_ACTOR) floats, actors_stride_floats
+ *     apart: a multiple of 4 and >= the vector's length; the base 16-byte aligned. Floats between the end of a vector and the next
+ *     row are never read. Env i uses the vector at actors_dev + (i / envs_per_member) * actors_stride_floats;
+ *     n_members * envs_per_member must equal n_envs, and envs_per_member must be a multiple of tb_policy_member_granule() (16).
+ * Everything else is tb_sac_evaluate's contract: the call resets first (call k is episode k), return_dev / length_dev [n_envs] as
+ * there, no state word is written and the phase is 0 on return; SwingRacket-v0 needs tb_set_pipeline(h, 1) (TB_E_UNSUPPORTED
+ * otherwise); results are complete in stream order; the optional trace has rows [T][n_envs] and changes no result. Per env, every
+ * result and every trace row is bit for bit what tb_sac_evaluate gives with that member's vector on a handle of envs_per_member
+ * envs whose env_id_base is this handle's + m * envs_per_member.
+ * Null h / actors_dev / return_dev / length_dev, n_members < 1, envs_per_member < 1 or not a multiple of the granule, a product
+ * other than n_envs, a stride below the vector's length or not a multiple of 4, a misaligned base, a trace whose struct_size is
+ * not sizeof(TbSacEvalTrace) or with a null array: TB_E_INVAL. A refusal launches, resets and writes nothing.
+ */
+int tb_sac_evaluate_members(TbHandle *h, const float *actors_dev, int n_members, size_t actors_stride_floats, int envs_per_member,
+                            double *return_dev, int32_t *length_dev, uint64_t noise_seed, int deterministic,
+                            const TbSacEvalTrace *trace_or_null, void *stream);
+
+/*
  * SAC / TQC collect: n_steps agent steps of every env with the 256-wide actor inside, one launch, every transition written as a
  * replay ring stores it (csrc/tb_sac.hpp, tb_sac_collect_kernel: tb_sac_evaluate_kernel's four-wave workgroup and actor stage
  * around tb_policy_rollout's env wave).

@@ -480,8 +480,18 @@ TB_DEV void sac_actor_stage(const float* actor, const float* s_obs, float* s_h1,
   }
 }
 
-template <int KIND, bool RG>
-__global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalArgs S) {
+// THE MEMBERS FORM (tb_sac_evaluate_members: a population of actors, one launch) is this kernel with ONE more argument, a
+// PolicyMembers (tb_kernels.hpp), as tb_policy_evaluate_kernel has it: S.actor then holds the members' flat vectors `stride` floats
+// apart, env i is member i / per_member's, and per_member is a multiple of TB_POLICY_SLICE (the host refuses anything else), so the
+// 16 envs of a workgroup -- the 16 rows of every MFMA tile of its four waves -- share ONE member. member_blob_offset is a function of
+// blockIdx.x and two kernel arguments alone: the vector's address stays in scalar registers like S.actor itself. Every weight address
+// is S.actor + a layout offset below the vector's length, so floats between two members' vectors are never read. The actor stage,
+// the barriers, the vote and the exit are the same lines. The argument is a trailing pack, empty or one PolicyMembers, so that
+// tb_sac_evaluate_kernel<KIND, RG> remains the kernel it was, argument list included.
+template <int KIND, bool RG, typename... MEMBERS>
+__global__ void __launch_bounds__(256) tb_sac_evaluate_kernel(KArgs A, SacEvalArgs S, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one PolicyMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) S.actor += member_blob_offset(members...);
   using L = SacLayout<KIND>;
   constexpr int NA = Dims<KIND>::A, NO = Dims<KIND>::O, E = TB_POLICY_SLICE, ENV_WAVE = 3;
   static_assert(NA == L::A && NO == L::O && E == 16 && NA <= 8, "the actor's rows are the envs of one slice");

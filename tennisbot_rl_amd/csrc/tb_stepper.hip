@@ -1317,25 +1317,51 @@ int tb_policy_evaluate_members(TbHandle* h, int net, const float* weights_dev, i
   });
 }
 
-// SAC's / TQC's actor inside the episode loop (tb_sac.hpp, tb_sac_evaluate_kernel), four waves per 16 envs
+// SAC's / TQC's actor inside the episode loop (tb_sac.hpp, tb_sac_evaluate_kernel), four waves per 16 envs. The kernel's arguments
+// from the caller's, the optional trace checked: ONE copy for tb_sac_evaluate and tb_sac_evaluate_members, `who` names the entry point
+namespace {
+int sac_eval_args(SacEvalArgs& S, const char* who, const float* actor_dev, double* return_dev, int32_t* length_dev, const TbSacEvalTrace* trace) {
+  memset(&S, 0, sizeof S);
+  S.actor = actor_dev; S.ret = return_dev; S.len = length_dev;
+  if (!trace) return TB_OK;
+  if (trace->struct_size != sizeof(TbSacEvalTrace)) return refusal(TB_E_INVAL, who, ": TbSacEvalTrace.struct_size is not sizeof(TbSacEvalTrace)");
+  if (trace->max_steps > 0) {
+    if (!trace->obs || !trace->eps || !trace->actions || !trace->reward || !trace->done) return refusal(TB_E_INVAL, who, ": a TbSacEvalTrace array is null");
+    S.t_max = trace->max_steps; S.t_obs = trace->obs; S.t_eps = trace->eps; S.t_act = trace->actions; S.t_rew = trace->reward; S.t_done = trace->done;
+  }
+  return TB_OK;
+}
+}  // namespace
 int tb_sac_evaluate(TbHandle* h, const float* actor_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
                     const TbSacEvalTrace* trace, void* stream) {
   if (!h || !actor_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_sac_evaluate: null argument");
   SacEvalArgs S;
-  memset(&S, 0, sizeof S);
-  S.actor = actor_dev; S.ret = return_dev; S.len = length_dev;
-  if (trace) {
-    if (trace->struct_size != sizeof(TbSacEvalTrace)) return fail(TB_E_INVAL, "tb_sac_evaluate: TbSacEvalTrace.struct_size is not sizeof(TbSacEvalTrace)");
-    if (trace->max_steps > 0) {
-      if (!trace->obs || !trace->eps || !trace->actions || !trace->reward || !trace->done) return fail(TB_E_INVAL, "tb_sac_evaluate: a TbSacEvalTrace array is null");
-      S.t_max = trace->max_steps; S.t_obs = trace->obs; S.t_eps = trace->eps; S.t_act = trace->actions; S.t_rew = trace->reward; S.t_done = trace->done;
-    }
-  }
+  if (int rc = sac_eval_args(S, "tb_sac_evaluate", actor_dev, return_dev, length_dev, trace)) return rc;
   PolicyIO pol = {};
   pol.seed = noise_seed; pol.deterministic = deterministic;
   return run_whole_episodes(h, "tb_sac_evaluate", &pol, return_dev, S.t_max, S.t_rew, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
     const auto kern = kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_sac_evaluate_kernel<K.value, R.value>; });
     return launch(kern, slice_groups(h), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S);
+  });
+}
+
+// a population of actors through the same launch (tb_sac_evaluate_kernel's members form): a workgroup's 16 envs belong to one member
+int tb_sac_evaluate_members(TbHandle* h, const float* actors_dev, int n_members, size_t actors_stride_floats, int envs_per_member, double* return_dev,
+                            int32_t* length_dev, uint64_t noise_seed, int deterministic, const TbSacEvalTrace* trace, void* stream) {
+  if (!h || !actors_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_sac_evaluate_members: null argument");
+  if (n_members < 1 || envs_per_member < 1 || envs_per_member % TB_POLICY_SLICE)
+    return fail(TB_E_INVAL, "tb_sac_evaluate_members: n_members must be >= 1 and envs_per_member a positive multiple of tb_policy_member_granule() (16)");
+  if ((long long)n_members * envs_per_member != h->n) return fail(TB_E_INVAL, "tb_sac_evaluate_members: n_members * envs_per_member must equal n_envs");
+  if (actors_stride_floats % 4 || actors_stride_floats < (size_t)tb_sac_param_floats(h->kind, TB_SAC_ACTOR) || reinterpret_cast<uintptr_t>(actors_dev) % 16)
+    return fail(TB_E_INVAL, "tb_sac_evaluate_members: the actors' row stride must be a multiple of 4 floats and >= tb_sac_param_floats(kind, 0), the base 16-byte aligned");
+  SacEvalArgs S;
+  if (int rc = sac_eval_args(S, "tb_sac_evaluate_members", actors_dev, return_dev, length_dev, trace)) return rc;
+  PolicyIO pol = {};
+  pol.seed = noise_seed; pol.deterministic = deterministic;
+  return run_whole_episodes(h, "tb_sac_evaluate_members", &pol, return_dev, S.t_max, S.t_rew, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
+    const auto kern = kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_sac_evaluate_kernel<K.value, R.value, PolicyMembers>; });
+    return launch(kern, slice_groups(h), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S,
+                  PolicyMembers{actors_stride_floats, envs_per_member});
   });
 }
 

@@ -91,6 +91,12 @@ def build_sac_modules(obs_dim, act_dim):
     return actor, critic, target
 
 
+def flatten_actor(state_dict):
+    """a SAC / TQC trainer checkpoint's `actor` state dict as the flat TB_SAC_ACTOR vector (ACTOR_NAMES order)"""
+    import torch
+    return torch.cat([state_dict[k].detach().reshape(-1).float() for k in ACTOR_NAMES]).contiguous()
+
+
 class _Flat:
     """one module's flat parameter vector with its gradient and Adam moments, and the optimiser whose state views them"""
 

@@ -107,6 +107,8 @@ def load_library():
     L.tb_policy_rollout_members.restype = i32
     L.tb_sac_evaluate.argtypes = [vp, vp, vp, vp, u64, i32, ctypes.POINTER(TbSacEvalTrace), vp]
     L.tb_sac_evaluate.restype = i32
+    L.tb_sac_evaluate_members.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, vp, vp, u64, i32, ctypes.POINTER(TbSacEvalTrace), vp]
+    L.tb_sac_evaluate_members.restype = i32
     L.tb_sac_collect.argtypes = [vp, vp, i32, i32, u64, ctypes.POINTER(TbSacCollectOut), vp]
     L.tb_sac_collect.restype = i32
     f32, f64, i64 = ctypes.c_float, ctypes.c_double, ctypes.c_longlong
@@ -679,7 +681,7 @@ class BatchedEnv:
         envs_per_member must be a multiple of policy_member_granule(). Member m's env columns are what policy_rollout(weights[m])
         gives on a batch of envs_per_member envs at env_id_base + m * envs_per_member. Returns policy_rollout's tuples."""
         t, n, T = self.torch, self.num_envs, int(n_steps)
-        weights, M, R = self._members_weights(weights, envs_per_member, net)
+        weights, M, R = self._members_weights(weights, envs_per_member, self.policy_floats(net))
         oi = self._check_tensor(obs_in, (n, self.obs_dim), t.float32, "obs_in")
         f = dict(dtype=t.float32, device=self.device)
         obs, rew, done = t.empty((T, n, self.obs_dim), **f), t.empty((T, n), **f), t.empty((T, n), dtype=t.uint8, device=self.device)
@@ -749,22 +751,22 @@ class BatchedEnv:
         """envs_per_member of policy_evaluate_members must be a multiple of this (16: the envs of one tower wave)"""
         return int(self.L.tb_policy_member_granule())
 
-    def _members_weights(self, weights, envs_per_member, net):
-        """what both members calls ask of [M, stride] blobs; a misaligned, non-contiguous or odd-stride input is re-packed, as es_evaluate
-        does. Returns (weights, M, R)."""
+    def _members_weights(self, weights, envs_per_member, P, what="a packed policy"):
+        """what the members calls ask of [M, stride] rows of P floats each (`what` names them); a misaligned, non-contiguous or odd-stride
+        input is re-packed, as es_evaluate does. Returns (weights, M, R)."""
         t, n = self.torch, self.num_envs
         R, G = int(envs_per_member), self.policy_member_granule()
         if R < 1 or R % G:
             raise ValueError("envs_per_member must be a positive multiple of policy_member_granule() (%d), got %d" % (G, R))
         if n % R:
             raise ValueError("envs_per_member must divide num_envs (%d)" % n)
-        M, P = n // R, self.policy_floats(net)
+        M, P = n // R, int(P)
         if not isinstance(weights, t.Tensor) or weights.dim() != 2 or weights.shape[0] != M:
             raise ValueError("weights must be a [%d, stride] tensor" % M)
         if weights.device != self.device or weights.dtype != t.float32:
             raise ValueError("weights must be float32 on %s" % self.device)
         if weights.shape[1] < P:
-            raise ValueError("weights rows must hold the %d floats of a packed policy, got %d" % (P, weights.shape[1]))
+            raise ValueError("weights rows must hold the %d floats of %s, got %d" % (P, what, weights.shape[1]))
         if weights.shape[1] % 4 or not weights.is_contiguous() or weights.data_ptr() % 16:
             w = t.zeros((M, (P + 3) // 4 * 4), dtype=t.float32, device=self.device)
             w[:, :P] = weights[:, :P]
@@ -780,7 +782,7 @@ class BatchedEnv:
         afterwards are policy_evaluate's: row m is what policy_evaluate(weights[m]) gives on a batch of envs_per_member envs at
         env_id_base + m * envs_per_member. Returns (returns float64 [M, R], lengths int32 [M, R]), complete in stream order."""
         t, n = self.torch, self.num_envs
-        weights, M, R = self._members_weights(weights, envs_per_member, net)
+        weights, M, R = self._members_weights(weights, envs_per_member, self.policy_floats(net))
         ret = t.empty(n, dtype=t.float64, device=self.device)
         length = t.empty(n, dtype=t.int32, device=self.device)
         _check(self.L, self.L.tb_policy_evaluate_members(self._h, int(net), weights.data_ptr(), M, weights.shape[1], R, ret.data_ptr(), length.data_ptr(),
@@ -804,16 +806,39 @@ class BatchedEnv:
         w = self._check_tensor(actor_flat, (self.sac_actor_floats(),), t.float32, "actor_flat")
         ret = t.empty(n, dtype=t.float64, device=self.device)
         length = t.empty(n, dtype=t.int32, device=self.device)
-        tr, rec = None, None
-        if trace:
-            T = int(max_steps) if max_steps is not None else (26 if self.kind == ENV_SWING else 1001)
-            f = dict(dtype=t.float32, device=self.device)
-            rec = dict(obs=t.zeros((T, n, self.obs_dim), **f), eps=t.zeros((T, n, self.act_dim), **f), actions=t.zeros((T, n, self.act_dim), **f),
-                       reward=t.zeros((T, n), **f), done=t.zeros((T, n), dtype=t.uint8, device=self.device))
-            tr = TbSacEvalTrace(ctypes.sizeof(TbSacEvalTrace), T, *(rec[k].data_ptr() for k in ("obs", "eps", "actions", "reward", "done")))
+        tr, rec = self._sac_eval_trace(trace, max_steps)
         _check(self.L, self.L.tb_sac_evaluate(self._h, w.data_ptr(), ret.data_ptr(), length.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                               1 if deterministic else 0, None if tr is None else ctypes.byref(tr), self._stream()), "tb_sac_evaluate")
         return (ret, length, rec) if trace else (ret, length)
+
+    def _sac_eval_trace(self, trace, max_steps):
+        """(TbSacEvalTrace or None, the dict of zeroed [T, N, ...] arrays it points into or None) for sac_evaluate / sac_evaluate_members"""
+        if not trace:
+            return None, None
+        t, n = self.torch, self.num_envs
+        T = int(max_steps) if max_steps is not None else (26 if self.kind == ENV_SWING else 1001)
+        f = dict(dtype=t.float32, device=self.device)
+        rec = dict(obs=t.zeros((T, n, self.obs_dim), **f), eps=t.zeros((T, n, self.act_dim), **f), actions=t.zeros((T, n, self.act_dim), **f),
+                   reward=t.zeros((T, n), **f), done=t.zeros((T, n), dtype=t.uint8, device=self.device))
+        return TbSacEvalTrace(ctypes.sizeof(TbSacEvalTrace), T, *(rec[k].data_ptr() for k in ("obs", "eps", "actions", "reward", "done"))), rec
+
+    def sac_evaluate_members(self, actors, envs_per_member, seed=0, deterministic=False, trace=False, max_steps=None):
+        """sac_evaluate for a population of actors in one launch (tb_sac_evaluate_members). actors: [M, stride] float32 on this
+        device, row m the flat TB_SAC_ACTOR vector of member m, stride a multiple of 4 and >= sac_actor_floats();
+        M * envs_per_member == num_envs and env i uses member i // envs_per_member; envs_per_member must be a multiple of
+        policy_member_granule(). A misaligned, non-contiguous or odd-stride input is re-packed first, as es_evaluate does. Sampling,
+        noise keys, the reset in front and the state afterwards are sac_evaluate's: row m is what sac_evaluate(actors[m]) gives on a
+        batch of envs_per_member envs at env_id_base + m * envs_per_member. Returns (returns float64 [M, R], lengths int32 [M, R]),
+        complete in stream order; with trace=True also sac_evaluate's dict, its rows [T, M * R, ...] in env order."""
+        t, n = self.torch, self.num_envs
+        actors, M, R = self._members_weights(actors, envs_per_member, self.sac_actor_floats(), "a flat SAC / TQC actor")
+        ret = t.empty(n, dtype=t.float64, device=self.device)
+        length = t.empty(n, dtype=t.int32, device=self.device)
+        tr, rec = self._sac_eval_trace(trace, max_steps)
+        _check(self.L, self.L.tb_sac_evaluate_members(self._h, actors.data_ptr(), M, actors.shape[1], R, ret.data_ptr(), length.data_ptr(),
+                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if deterministic else 0, None if tr is None else ctypes.byref(tr),
+                                                      self._stream()), "tb_sac_evaluate_members")
+        return (ret.view(M, R), length.view(M, R), rec) if trace else (ret.view(M, R), length.view(M, R))
 
     def sac_collect(self, actor_flat, n_steps, out_views, seed=0, uniform=False, eps=None):
         """n_steps agent steps of every env from where it stands, in one launch with the SAC / TQC actor inside, every transition

@@ -5,9 +5,12 @@
   python tools/rank_checkpoints.py model/rl_model_*_steps.pt model/best_model.pt
   python tools/rank_checkpoints.py --env Tennisbot-v0 --net tuned --episodes-per-member 1024 model/*.pt
   python tools/rank_checkpoints.py reference model/ppo_SwingRacket-v0.pt     # `reference`: tests/golden/ppo_swing_policy.npz
+  python tools/rank_checkpoints.py -s sac --env Tennisbot-v0 model/rl_model_*_steps.pt model/best_model.pt   # train_sac.py's files
 
 Checkpoints: what train_swing.py / train.py (PPO, TRPO) and train_es.py --policy mlp write (their "policy" entry), or an .npz of
-SB3-named arrays. All must hold the network --net names.
+SB3-named arrays. All must hold the network --net names. With -s sac / -s tqc: what train_sac.py / train_tqc.py write (their "actor"
+entry, the 256-wide actor the two share), every checkpoint one member of a BatchedEnv.sac_evaluate_members call
+(tb_sac_evaluate_members); all must be --env's actors.
 
 MEMBERS SEE DIFFERENT EPISODES. Resets and exploration noise are keyed by the global env id, and every member has env ids of its
 own, so no two checkpoints play the same balls: the table's means are estimates from independent samples, to be compared THROUGH
@@ -35,43 +38,85 @@ def plan(n_members, episodes_per_member, granule=GRANULE, max_envs=MAX_ENVS):
     return per_launch, -(-want // per_launch)
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("checkpoints", nargs="+", metavar="CKPT", help="checkpoint files; `reference`: the reference's shipped ppo_swing policy")
     ap.add_argument("--env", default="SwingRacket-v0", choices=["SwingRacket-v0", "Tennisbot-v0"])
-    ap.add_argument("--net", default="default", choices=["default", "tuned", "mlp64"], help="the network every checkpoint holds")
+    ap.add_argument("-s", "--select", default="ppo", choices=["ppo", "sac", "tqc"], help="what the checkpoints hold: `ppo` -- a fused MlpPolicy net (their "
+                    "\"policy\" entry, see --net); `sac` / `tqc` -- the 256-wide actor of train_sac.py / train_tqc.py (their \"actor\" entry)")
+    ap.add_argument("--net", default=None, choices=["default", "tuned", "mlp64"], help="-s ppo: the network every checkpoint holds (default: default)")
     ap.add_argument("--episodes-per-member", type=int, default=256, help="episodes per checkpoint (rounded up to whole launches; members see DIFFERENT "
                     "episodes: compare means through the sem column)")
     ap.add_argument("--deterministic", action="store_true", help="act on the mean action")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json", default=None, help="also write the table to this file")
+    return ap
+
+
+def parse(argv=None):
+    ap = parser()
     args = ap.parse_args(argv)
     if args.episodes_per_member < 1:
         ap.error("--episodes-per-member must be >= 1")
+    if args.select != "ppo" and args.net is not None:
+        ap.error("--net names a fused MlpPolicy net; -s %s checkpoints hold the 256-wide actor" % args.select)
+    if args.net is None:
+        args.net = "default"
+    return args
+
+
+def tournament_noise_seed(seed):
+    return (seed * 1000003 + 0x52414E4B) & 0xFFFFFFFFFFFFFFFF
+
+
+def load_actors(paths, env_id):
+    """[M, P] float32 on the CPU: every checkpoint's `actor` entry (train_sac.py / train_tqc.py: --save, best_model.pt,
+    rl_model_<n>_steps.pt) flattened in ACTOR_NAMES order, one row each. An actor of the other env's size is refused by file name."""
+    import torch
+    from tennisbot_rl_amd.sac import TB_SAC_ACTOR, flatten_actor
+    from tennisbot_rl_amd.stepper import ENV_IDS, load_library
+    P = int(load_library().tb_sac_param_floats(ENV_IDS[env_id], TB_SAC_ACTOR))
+    rows = []
+    for path in paths:
+        flat = flatten_actor(torch.load(path, map_location="cpu", weights_only=True)["actor"])
+        if len(flat) != P:
+            sys.exit("%s: the actor has %d parameters; %s's has %d (is --env right?)" % (path, len(flat), env_id, P))
+        rows.append(flat)
+    return torch.stack(rows)
+
+
+def main(argv=None):
+    args = parse(argv)
 
     import torch
     from tennisbot_rl_amd.evaluation import EVAL_ENV_ID_BASE
     from tennisbot_rl_amd.params import ENV_SWING, NET_NAMES
-    from tennisbot_rl_amd.policy_es import build_policy, load_init
-    from tennisbot_rl_amd.ppo import pack_policy
     from tennisbot_rl_amd.stepper import ENV_IDS, BatchedEnv, check_net
 
     kind = ENV_IDS[args.env]
-    net = check_net(kind, {v: k for k, v in NET_NAMES.items()}[args.net])
     dev = torch.device("cuda", 0)
-    blobs = []
-    for path in args.checkpoints:
-        src = os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz") if path == "reference" else path
-        blobs.append(pack_policy(load_init(build_policy(kind, net), src).to(dev)))
-    weights = torch.stack(blobs)
-    M = len(blobs)
+    if args.select == "ppo":
+        from tennisbot_rl_amd.policy_es import build_policy, load_init
+        from tennisbot_rl_amd.ppo import pack_policy
+        net = check_net(kind, {v: k for k, v in NET_NAMES.items()}[args.net])
+        blobs = []
+        for path in args.checkpoints:
+            src = os.path.join(ROOT, "tests", "golden", "ppo_swing_policy.npz") if path == "reference" else path
+            blobs.append(pack_policy(load_init(build_policy(kind, net), src).to(dev)))
+        weights = torch.stack(blobs)
+    else:
+        weights = load_actors(args.checkpoints, args.env).to(dev)
+    M = weights.shape[0]
     R, launches = plan(M, args.episodes_per_member)
     env = BatchedEnv(kind, M * R, device=dev, seed=args.seed, env_id_base=EVAL_ENV_ID_BASE, track_terminal_obs=False, pipeline=kind == ENV_SWING)
     assert R % env.policy_member_granule() == 0
-    noise_seed = (args.seed * 1000003 + 0x52414E4B) & 0xFFFFFFFFFFFFFFFF
+    noise_seed = tournament_noise_seed(args.seed)
     rets, lens = [], []
     for _ in range(launches):   # launch k is episode k of every env
-        r, ln = env.policy_evaluate_members(weights, R, seed=noise_seed, deterministic=args.deterministic, net=net)
+        if args.select == "ppo":
+            r, ln = env.policy_evaluate_members(weights, R, seed=noise_seed, deterministic=args.deterministic, net=net)
+        else:
+            r, ln = env.sac_evaluate_members(weights, R, seed=noise_seed, deterministic=args.deterministic)
         rets.append(r); lens.append(ln)
     ret, length = torch.cat(rets, dim=1), torch.cat(lens, dim=1).double()
     n = ret.shape[1]
@@ -79,7 +124,7 @@ def main(argv=None):
     env.close()
     rows = sorted(({"checkpoint": p, "mean": stats[0][m], "sem": stats[1][m], "mean_length": stats[2][m], "episodes": n} for m, p in enumerate(args.checkpoints)),
                   key=lambda r: -r["mean"])
-    print("%d checkpoints x %d episodes of %s (%s, %s), %d launch%s of %d envs" % (M, n, args.env, args.net, "deterministic" if args.deterministic else "stochastic",
+    print("%d checkpoints x %d episodes of %s (%s, %s), %d launch%s of %d envs" % (M, n, args.env, args.net if args.select == "ppo" else args.select, "deterministic" if args.deterministic else "stochastic",
                                                                                  launches, "" if launches == 1 else "es", M * R))
     print("members see DIFFERENT episodes: compare means through their standard errors (sem), not digit by digit")
     print("%4s  %12s  %10s  %11s  %s" % ("rank", "mean return", "sem", "mean length", "checkpoint"))

@@ -70,16 +70,11 @@ def report(out, env_id):
     return out
 
 
-def flatten_actor(torch, state_dict):
-    """a SAC / TQC trainer checkpoint's `actor` state dict as the flat TB_SAC_ACTOR vector (ACTOR_NAMES order)"""
-    from tennisbot_rl_amd.sac import ACTOR_NAMES
-    return torch.cat([state_dict[k].detach().reshape(-1).float() for k in ACTOR_NAMES]).contiguous()
-
-
 def validate_actor(args, torch, dev):
     from tennisbot_rl_amd.evaluation import ActorEvaluator
+    from tennisbot_rl_amd.sac import flatten_actor
     ck = torch.load(args.model_file, map_location="cpu", weights_only=True)
-    flat = flatten_actor(torch, ck["actor"]).to(dev)
+    flat = flatten_actor(ck["actor"]).to(dev)
     ev = ActorEvaluator(args.env, n_envs=args.num_envs, seed=args.seed, device=dev)
     if len(flat) != ev.env.sac_actor_floats():
         sys.exit("%s: the actor has %d parameters; %s's has %d (is --env right?)" % (args.model_file, len(flat), args.env, ev.env.sac_actor_floats()))

@@ -57,7 +57,9 @@ struct DeviceGuard {  // calls run on the handle's device without disturbing the
   int prev = -1;
   bool switched = false;
   hipError_t err = hipSuccess;
-  explicit DeviceGuard(int dev) {
+  DeviceGuard() = default;  // (no device yet: learner_device enters it once the index is known to exist)
+  explicit DeviceGuard(int dev) { enter(dev); }
+  void enter(int dev) {
     err = hipGetDevice(&prev);
     if (err == hipSuccess && prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess; }
   }
@@ -405,17 +407,22 @@ auto kernel_of_kind_rg(int kind, bool rg, F pick) {
   if (kind == TB_ENV_SWING) return rg ? pick(Int<TB_ENV_SWING>{}, std::true_type{}) : pick(Int<TB_ENV_SWING>{}, std::false_type{});
   return rg ? pick(Int<TB_ENV_TENNIS>{}, std::true_type{}) : pick(Int<TB_ENV_TENNIS>{}, std::false_type{});
 }
-// (kind, net, RG): tb_policy_evaluate_kernel, tb_policy_rollout_kernel. THE (kind, net) PAIRS THESE LAUNCHES ARE BUILT FOR: every kind's
-// own network, SwingRacket's [64, 64], Tennisbot's tuned one -- the pairs policy_net_ok lets through; any other is null, and its launch
-// a refusal.
+// THE (kind, net) PAIRS THE POLICY AND LEARNER KERNELS ARE BUILT FOR: every kind's own network, SwingRacket's [64, 64], Tennisbot's tuned
+// one. f(Int<KIND>{}, Int<NET>{}) for those -- a layout's constant, a kernel, a launch --, `otherwise` for any other pair. policy_net_ok
+// asks this table too, so what it lets through has an entry.
+template <class T, class F>
+T with_kind_net(int kind, int net, T otherwise, F f) {
+  if (kind == TB_ENV_SWING && net == TB_NET_DEFAULT) return f(Int<TB_ENV_SWING>{}, Int<TB_NET_DEFAULT>{});
+  if (kind == TB_ENV_SWING && net == TB_NET_MLP64) return f(Int<TB_ENV_SWING>{}, Int<TB_NET_MLP64>{});
+  if (kind == TB_ENV_TENNIS && net == TB_NET_DEFAULT) return f(Int<TB_ENV_TENNIS>{}, Int<TB_NET_DEFAULT>{});
+  if (kind == TB_ENV_TENNIS && net == TB_NET_TUNED) return f(Int<TB_ENV_TENNIS>{}, Int<TB_NET_TUNED>{});
+  return otherwise;
+}
+// (kind, net, RG): tb_policy_evaluate_kernel, tb_policy_rollout_kernel; null for a pair without an entry, and its launch a refusal
 template <class F>
-auto kernel_of_kind_net_rg(int kind, int net, bool rg, F pick) -> decltype(pick(Int<TB_ENV_SWING>{}, Int<TB_NET_DEFAULT>{}, std::false_type{})) {
-  const auto with_rg = [&](auto K, auto N) { return rg ? pick(K, N, std::true_type{}) : pick(K, N, std::false_type{}); };
-  if (kind == TB_ENV_SWING && net == TB_NET_DEFAULT) return with_rg(Int<TB_ENV_SWING>{}, Int<TB_NET_DEFAULT>{});
-  if (kind == TB_ENV_SWING && net == TB_NET_MLP64) return with_rg(Int<TB_ENV_SWING>{}, Int<TB_NET_MLP64>{});
-  if (kind == TB_ENV_TENNIS && net == TB_NET_DEFAULT) return with_rg(Int<TB_ENV_TENNIS>{}, Int<TB_NET_DEFAULT>{});
-  if (kind == TB_ENV_TENNIS && net == TB_NET_TUNED) return with_rg(Int<TB_ENV_TENNIS>{}, Int<TB_NET_TUNED>{});
-  return nullptr;
+auto kernel_of_kind_net_rg(int kind, int net, bool rg, F pick) {
+  using Kernel = decltype(pick(Int<TB_ENV_SWING>{}, Int<TB_NET_DEFAULT>{}, std::false_type{}));
+  return with_kind_net(kind, net, Kernel(nullptr), [&](auto K, auto N) -> Kernel { return rg ? pick(K, N, std::true_type{}) : pick(K, N, std::false_type{}); });
 }
 
 // the fast-forward family's one launch: one-wave workgroups on stream q
@@ -690,6 +697,21 @@ int refusal(int code, const char* who, const char* what) {
 }
 // the workgroups of the kernels whose env wave holds one slice of TB_POLICY_SLICE envs (their dynamic LDS: that wave's columns)
 dim3 slice_groups(const TbHandle* h) { return dim3((unsigned)((h->n + TB_POLICY_SLICE - 1) / TB_POLICY_SLICE)); }
+// A POPULATION over the handle's envs, n_members x envs_per_member of them, member m's floats in row m of `base`: what every entry
+// point that takes one refuses. granule: the envs that share a member's weights in one workgroup (TB_POLICY_SLICE; 1 for tb_es_evaluate)
+int members_refused(const char* who, const TbHandle* h, int n_members, int envs_per_member, int granule, size_t stride_floats, int min_floats, const void* base) {
+  char msg[160];
+  if (n_members < 1 || envs_per_member < 1 || envs_per_member % granule) {
+    snprintf(msg, sizeof msg, ": n_members must be >= 1 and envs_per_member a positive multiple of the member granule (%d)", granule);
+    return refusal(TB_E_INVAL, who, msg);
+  }
+  if ((long long)n_members * envs_per_member != h->n) return refusal(TB_E_INVAL, who, ": n_members * envs_per_member must equal n_envs");
+  if (stride_floats % 4 || stride_floats < (size_t)min_floats || reinterpret_cast<uintptr_t>(base) % 16) {
+    snprintf(msg, sizeof msg, ": the members' row stride must be a multiple of 4 floats and >= a member's %d, the base 16-byte aligned", min_floats);
+    return refusal(TB_E_INVAL, who, msg);
+  }
+  return TB_OK;
+}
 
 // WHOLE EPISODES of every env, one launch (tb_es_evaluate, tb_policy_evaluate, tb_sac_evaluate; `who` names the entry point, which has
 // checked its own arguments: nothing is allocated, reset or launched before this). Every env is reset, runs through its first `done`,
@@ -1147,9 +1169,9 @@ int tb_policy_floats(int env_kind) {
 }
 
 namespace {
-// the (kind, net) pairs the policy kernels are built for: every kind's own network, Tennisbot's tuned one, SwingRacket's [64, 64]
+// is (kind, net) a pair the policy kernels are built for (with_kind_net's table)? `who`'s refusal if not
 int policy_net_ok(int env_kind, int net, const char* who) {
-  if (net == TB_NET_DEFAULT || (net == TB_NET_TUNED && env_kind == TB_ENV_TENNIS) || (net == TB_NET_MLP64 && env_kind == TB_ENV_SWING)) return TB_OK;
+  if (with_kind_net(env_kind, net, false, [](auto, auto) { return true; })) return TB_OK;
   char msg[256];
   if (net == TB_NET_MLP64 && env_kind == TB_ENV_TENNIS)
     snprintf(msg, sizeof msg, "%s: TB_NET_MLP64 is SwingRacket-v0's; on Tennisbot-v0 TB_NET_DEFAULT is that net (pi = vf = [64, 64], tanh)", who);
@@ -1170,10 +1192,9 @@ int trpo_net_ok(int env_kind, int net, const char* who) {
 }  // namespace
 
 int tb_policy_blob_floats(int env_kind, int net) {
-  if (env_kind != TB_ENV_SWING && env_kind != TB_ENV_TENNIS) return TB_E_INVAL;
+  if (!kind_ok(env_kind)) return TB_E_INVAL;
   if (int rc = policy_net_ok(env_kind, net, "tb_policy_blob_floats")) return rc;
-  if (net == TB_NET_MLP64) return PolicyBlob<TB_ENV_SWING, TB_NET_MLP64>::TOTAL;
-  return net == TB_NET_TUNED ? PolicyBlob<TB_ENV_TENNIS, TB_NET_TUNED>::TOTAL : tb_policy_floats(env_kind);
+  return with_kind_net(env_kind, net, 0, [](auto K, auto N) { return (int)PolicyBlob<K.value, N.value>::TOTAL; });
 }
 
 int tb_policy_step_net(TbHandle* h, int net, const float* weights_dev, const float* obs_in_dev, float* actions_dev, float* raw_actions_dev, float* logp_dev,
@@ -1207,11 +1228,7 @@ int policy_rollout(const char* who, TbHandle* h, int net, int n_steps, const flo
   if (n_steps < 1) return refusal(TB_E_INVAL, who, ": n_steps must be >= 1");
   if (int rc = policy_net_ok(h->kind, net, who)) return rc;
   if (members) {
-    if (n_members < 1 || members->per_member < 1 || members->per_member % TB_POLICY_SLICE)
-      return refusal(TB_E_INVAL, who, ": n_members must be >= 1 and envs_per_member a positive multiple of tb_policy_member_granule() (16)");
-    if ((long long)n_members * members->per_member != h->n) return refusal(TB_E_INVAL, who, ": n_members * envs_per_member must equal n_envs");
-    if (members->stride % 4 || members->stride < (size_t)tb_policy_blob_floats(h->kind, net) || reinterpret_cast<uintptr_t>(weights_dev) % 16)
-      return refusal(TB_E_INVAL, who, ": the weights' row stride must be a multiple of 4 floats and >= tb_policy_blob_floats, the base 16-byte aligned");
+    if (int rc = members_refused(who, h, n_members, members->per_member, TB_POLICY_SLICE, members->stride, tb_policy_blob_floats(h->kind, net), weights_dev)) return rc;
   }
   if (int rc = refuse_steps_from_state(h, who)) return rc;
   const bool swing = h->kind == TB_ENV_SWING;
@@ -1263,10 +1280,7 @@ int tb_es_floats(int env_kind) {
 int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t weights_stride_floats, int envs_per_member, double* return_dev,
                    int32_t* length_dev, const TbEsTrace* trace, void* stream) {
   if (!h || !weights_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_es_evaluate: null argument");
-  if (n_members < 1 || envs_per_member < 1 || (long long)n_members * envs_per_member != h->n)
-    return fail(TB_E_INVAL, "tb_es_evaluate: n_members * envs_per_member must equal n_envs (both >= 1)");
-  if (weights_stride_floats % 4 || weights_stride_floats < (size_t)tb_es_floats(h->kind) || reinterpret_cast<uintptr_t>(weights_dev) % 16)
-    return fail(TB_E_INVAL, "tb_es_evaluate: the weights' row stride must be a multiple of 4 floats and >= tb_es_floats, the base 16-byte aligned");
+  if (int rc = members_refused("tb_es_evaluate", h, n_members, envs_per_member, 1, weights_stride_floats, tb_es_floats(h->kind), weights_dev)) return rc;
   EsArgs E;
   memset(&E, 0, sizeof E);
   E.weights = weights_dev; E.stride = weights_stride_floats; E.per_member = envs_per_member; E.ret = return_dev; E.len = length_dev;
@@ -1283,86 +1297,80 @@ int tb_es_evaluate(TbHandle* h, const float* weights_dev, int n_members, size_t 
   });
 }
 
-int tb_policy_evaluate(TbHandle* h, int net, const float* weights_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
-                       void* stream) {
-  if (!h || !weights_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_policy_evaluate: null argument");
-  if (int rc = policy_net_ok(h->kind, net, "tb_policy_evaluate")) return rc;
+namespace {
+// tb_policy_evaluate and tb_policy_evaluate_members (`who`; members: null, or the population whose blobs weights_dev holds: a
+// workgroup's 16 envs belong to one member, and the kernel's members form runs on the same grid, block and LDS)
+int policy_evaluate(const char* who, TbHandle* h, int net, const float* weights_dev, const PolicyMembers* members, int n_members, double* return_dev,
+                    int32_t* length_dev, uint64_t noise_seed, int deterministic, void* stream) {
+  if (!h || !weights_dev || !return_dev || !length_dev) return refusal(TB_E_INVAL, who, ": null argument");
+  if (int rc = policy_net_ok(h->kind, net, who)) return rc;
+  if (members) {
+    if (int rc = members_refused(who, h, n_members, members->per_member, TB_POLICY_SLICE, members->stride, tb_policy_blob_floats(h->kind, net), weights_dev)) return rc;
+  }
   PolicyIO pol = {};
   pol.weights = weights_dev; pol.seed = noise_seed; pol.deterministic = deterministic; pol.net = net;
-  return run_whole_episodes(h, "tb_policy_evaluate", &pol, return_dev, 0, nullptr, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
+  return run_whole_episodes(h, who, &pol, return_dev, 0, nullptr, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
+    const size_t lds = dyn_lds(policy_rollout_lds_words(h->kind, rg), 64);
+    if (members) {
+      const auto kern = kernel_of_kind_net_rg(h->kind, net, rg, [](auto K, auto N, auto R) { return tb_policy_evaluate_kernel<K.value, R.value, N.value, PolicyMembers>; });
+      if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_evaluate_kernel members instantiation for this variant");
+      return launch(kern, slice_groups(h), dim3(128), lds, s, a, return_dev, length_dev, *members);
+    }
     const auto kern = kernel_of_kind_net_rg(h->kind, net, rg, [](auto K, auto N, auto R) { return tb_policy_evaluate_kernel<K.value, R.value, N.value>; });
     if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_evaluate_kernel instantiation for this variant");
-    return launch(kern, slice_groups(h), dim3(128), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, return_dev, length_dev);
+    return launch(kern, slice_groups(h), dim3(128), lds, s, a, return_dev, length_dev);
   });
 }
-
-// a population of blobs through the same launch (tb_policy_evaluate_members_kernel): a workgroup's 16 envs belong to one member
+}  // namespace
+int tb_policy_evaluate(TbHandle* h, int net, const float* weights_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
+                       void* stream) {
+  return policy_evaluate("tb_policy_evaluate", h, net, weights_dev, nullptr, 0, return_dev, length_dev, noise_seed, deterministic, stream);
+}
 int tb_policy_member_granule(void) { return TB_POLICY_SLICE; }
 int tb_policy_evaluate_members(TbHandle* h, int net, const float* weights_dev, int n_members, size_t weights_stride_floats, int envs_per_member,
                                double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic, void* stream) {
-  if (!h || !weights_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_policy_evaluate_members: null argument");
-  if (int rc = policy_net_ok(h->kind, net, "tb_policy_evaluate_members")) return rc;
-  if (n_members < 1 || envs_per_member < 1 || envs_per_member % TB_POLICY_SLICE)
-    return fail(TB_E_INVAL, "tb_policy_evaluate_members: n_members must be >= 1 and envs_per_member a positive multiple of tb_policy_member_granule() (16)");
-  if ((long long)n_members * envs_per_member != h->n) return fail(TB_E_INVAL, "tb_policy_evaluate_members: n_members * envs_per_member must equal n_envs");
-  if (weights_stride_floats % 4 || weights_stride_floats < (size_t)tb_policy_blob_floats(h->kind, net) || reinterpret_cast<uintptr_t>(weights_dev) % 16)
-    return fail(TB_E_INVAL, "tb_policy_evaluate_members: the weights' row stride must be a multiple of 4 floats and >= tb_policy_blob_floats, the base 16-byte aligned");
-  PolicyIO pol = {};
-  pol.weights = weights_dev; pol.seed = noise_seed; pol.deterministic = deterministic; pol.net = net;
-  return run_whole_episodes(h, "tb_policy_evaluate_members", &pol, return_dev, 0, nullptr, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
-    const auto kern = kernel_of_kind_net_rg(h->kind, net, rg, [](auto K, auto N, auto R) { return tb_policy_evaluate_kernel<K.value, R.value, N.value, PolicyMembers>; });
-    if (!kern) return fail(TB_E_UNSUPPORTED, "no tb_policy_evaluate_kernel members instantiation for this variant");
-    return launch(kern, slice_groups(h), dim3(128), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, return_dev, length_dev,
-                  PolicyMembers{weights_stride_floats, envs_per_member});
-  });
+  const PolicyMembers members = {weights_stride_floats, envs_per_member};
+  return policy_evaluate("tb_policy_evaluate_members", h, net, weights_dev, &members, n_members, return_dev, length_dev, noise_seed, deterministic, stream);
 }
 
-// SAC's / TQC's actor inside the episode loop (tb_sac.hpp, tb_sac_evaluate_kernel), four waves per 16 envs. The kernel's arguments
-// from the caller's, the optional trace checked: ONE copy for tb_sac_evaluate and tb_sac_evaluate_members, `who` names the entry point
+// SAC's / TQC's actor inside the episode loop (tb_sac.hpp, tb_sac_evaluate_kernel), four waves per 16 envs: tb_sac_evaluate and
+// tb_sac_evaluate_members (`who`; members: null, or the population of actors, as in policy_evaluate). The optional trace is checked last
 namespace {
-int sac_eval_args(SacEvalArgs& S, const char* who, const float* actor_dev, double* return_dev, int32_t* length_dev, const TbSacEvalTrace* trace) {
+int sac_evaluate(const char* who, TbHandle* h, const float* actor_dev, const PolicyMembers* members, int n_members, double* return_dev, int32_t* length_dev,
+                 uint64_t noise_seed, int deterministic, const TbSacEvalTrace* trace, void* stream) {
+  if (!h || !actor_dev || !return_dev || !length_dev) return refusal(TB_E_INVAL, who, ": null argument");
+  if (members) {
+    if (int rc = members_refused(who, h, n_members, members->per_member, TB_POLICY_SLICE, members->stride, tb_sac_param_floats(h->kind, TB_SAC_ACTOR), actor_dev)) return rc;
+  }
+  SacEvalArgs S;
   memset(&S, 0, sizeof S);
   S.actor = actor_dev; S.ret = return_dev; S.len = length_dev;
-  if (!trace) return TB_OK;
-  if (trace->struct_size != sizeof(TbSacEvalTrace)) return refusal(TB_E_INVAL, who, ": TbSacEvalTrace.struct_size is not sizeof(TbSacEvalTrace)");
-  if (trace->max_steps > 0) {
-    if (!trace->obs || !trace->eps || !trace->actions || !trace->reward || !trace->done) return refusal(TB_E_INVAL, who, ": a TbSacEvalTrace array is null");
-    S.t_max = trace->max_steps; S.t_obs = trace->obs; S.t_eps = trace->eps; S.t_act = trace->actions; S.t_rew = trace->reward; S.t_done = trace->done;
+  if (trace) {
+    if (trace->struct_size != sizeof(TbSacEvalTrace)) return refusal(TB_E_INVAL, who, ": TbSacEvalTrace.struct_size is not sizeof(TbSacEvalTrace)");
+    if (trace->max_steps > 0) {
+      if (!trace->obs || !trace->eps || !trace->actions || !trace->reward || !trace->done) return refusal(TB_E_INVAL, who, ": a TbSacEvalTrace array is null");
+      S.t_max = trace->max_steps; S.t_obs = trace->obs; S.t_eps = trace->eps; S.t_act = trace->actions; S.t_rew = trace->reward; S.t_done = trace->done;
+    }
   }
-  return TB_OK;
+  PolicyIO pol = {};
+  pol.seed = noise_seed; pol.deterministic = deterministic;
+  return run_whole_episodes(h, who, &pol, return_dev, S.t_max, S.t_rew, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
+    const size_t lds = dyn_lds(policy_rollout_lds_words(h->kind, rg), 64);
+    if (members)
+      return launch(kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_sac_evaluate_kernel<K.value, R.value, PolicyMembers>; }), slice_groups(h), dim3(256), lds, s, a,
+                    S, *members);
+    return launch(kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_sac_evaluate_kernel<K.value, R.value>; }), slice_groups(h), dim3(256), lds, s, a, S);
+  });
 }
 }  // namespace
 int tb_sac_evaluate(TbHandle* h, const float* actor_dev, double* return_dev, int32_t* length_dev, uint64_t noise_seed, int deterministic,
                     const TbSacEvalTrace* trace, void* stream) {
-  if (!h || !actor_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_sac_evaluate: null argument");
-  SacEvalArgs S;
-  if (int rc = sac_eval_args(S, "tb_sac_evaluate", actor_dev, return_dev, length_dev, trace)) return rc;
-  PolicyIO pol = {};
-  pol.seed = noise_seed; pol.deterministic = deterministic;
-  return run_whole_episodes(h, "tb_sac_evaluate", &pol, return_dev, S.t_max, S.t_rew, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
-    const auto kern = kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_sac_evaluate_kernel<K.value, R.value>; });
-    return launch(kern, slice_groups(h), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S);
-  });
+  return sac_evaluate("tb_sac_evaluate", h, actor_dev, nullptr, 0, return_dev, length_dev, noise_seed, deterministic, trace, stream);
 }
-
-// a population of actors through the same launch (tb_sac_evaluate_kernel's members form): a workgroup's 16 envs belong to one member
 int tb_sac_evaluate_members(TbHandle* h, const float* actors_dev, int n_members, size_t actors_stride_floats, int envs_per_member, double* return_dev,
                             int32_t* length_dev, uint64_t noise_seed, int deterministic, const TbSacEvalTrace* trace, void* stream) {
-  if (!h || !actors_dev || !return_dev || !length_dev) return fail(TB_E_INVAL, "tb_sac_evaluate_members: null argument");
-  if (n_members < 1 || envs_per_member < 1 || envs_per_member % TB_POLICY_SLICE)
-    return fail(TB_E_INVAL, "tb_sac_evaluate_members: n_members must be >= 1 and envs_per_member a positive multiple of tb_policy_member_granule() (16)");
-  if ((long long)n_members * envs_per_member != h->n) return fail(TB_E_INVAL, "tb_sac_evaluate_members: n_members * envs_per_member must equal n_envs");
-  if (actors_stride_floats % 4 || actors_stride_floats < (size_t)tb_sac_param_floats(h->kind, TB_SAC_ACTOR) || reinterpret_cast<uintptr_t>(actors_dev) % 16)
-    return fail(TB_E_INVAL, "tb_sac_evaluate_members: the actors' row stride must be a multiple of 4 floats and >= tb_sac_param_floats(kind, 0), the base 16-byte aligned");
-  SacEvalArgs S;
-  if (int rc = sac_eval_args(S, "tb_sac_evaluate_members", actors_dev, return_dev, length_dev, trace)) return rc;
-  PolicyIO pol = {};
-  pol.seed = noise_seed; pol.deterministic = deterministic;
-  return run_whole_episodes(h, "tb_sac_evaluate_members", &pol, return_dev, S.t_max, S.t_rew, stream, [&](const KArgs& a, bool rg, hipStream_t s) {
-    const auto kern = kernel_of_kind_rg(h->kind, rg, [](auto K, auto R) { return tb_sac_evaluate_kernel<K.value, R.value, PolicyMembers>; });
-    return launch(kern, slice_groups(h), dim3(256), dyn_lds(policy_rollout_lds_words(h->kind, rg), 64), s, a, S,
-                  PolicyMembers{actors_stride_floats, envs_per_member});
-  });
+  const PolicyMembers members = {actors_stride_floats, envs_per_member};
+  return sac_evaluate("tb_sac_evaluate_members", h, actors_dev, &members, n_members, return_dev, length_dev, noise_seed, deterministic, trace, stream);
 }
 
 // tb_sac_collect_kernel (tb_sac.hpp): one launch, the caller's ring rows as outputs
@@ -1403,47 +1411,66 @@ int tb_ppo_param_floats(int env_kind) {
 }
 extern "C++" {
 namespace {
-// PpoLayout<KIND, NET> at run time, for the separate-tower nets: the flat vector's length and where its value slots lie. THE place
-// that maps a (kind, net) pair to a layout: a pair without an entry (the tuned net has TunedLayout, no critic-only range) gives P = 0.
-struct PpoDims { int P, VF, PI_HEAD, VF_HEAD; };
-template <int KIND, int NET> PpoDims ppo_dims_of() {
-  using L = PpoLayout<KIND, NET>;
-  return {L::P, L::VF, L::PI_HEAD, L::VF_HEAD};
-}
+// PpoLayout<KIND, NET> / TunedLayout at run time: the flat vector's length, the floats of one partial vector (the gradient and the two
+// statistics; the tuned net's also hold the vf waves' extractor share) and where the value slots lie -- zeros for the tuned net, whose
+// extractor is shared: it has no critic-only range. THE place that maps a (kind, net) pair to a layout; any other pair gives zeros.
+struct PpoDims { int P, STRIDE, VF, PI_HEAD, VF_HEAD; };
 PpoDims ppo_dims(int env_kind, int net) {
-  if (net == TB_NET_DEFAULT && env_kind == TB_ENV_SWING) return ppo_dims_of<TB_ENV_SWING, TB_NET_DEFAULT>();
-  if (net == TB_NET_DEFAULT && env_kind == TB_ENV_TENNIS) return ppo_dims_of<TB_ENV_TENNIS, TB_NET_DEFAULT>();
-  if (net == TB_NET_MLP64 && env_kind == TB_ENV_SWING) return ppo_dims_of<TB_ENV_SWING, TB_NET_MLP64>();
-  return {0, 0, 0, 0};
+  return with_kind_net(env_kind, net, PpoDims{}, [](auto K, auto N) -> PpoDims {
+    if constexpr (N.value == TB_NET_TUNED) return {TunedLayout::P, TunedLayout::STRIDE, 0, 0, 0};
+    else {
+      using L = PpoLayout<K.value, N.value>;
+      return {L::P, L::P + 2, L::VF, L::PI_HEAD, L::VF_HEAD};
+    }
+  });
+}
+size_t ppo_partials(int batch) { return 2 * (((size_t)batch + TB_PPO_SHARE - 1) / TB_PPO_SHARE); }
+constexpr size_t kPpoStatBytes = sizeof(double) * 2 * TB_PPO_STAT_BLOCKS;
+bool misaligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+
+// The learner calls name their device by index, and look it up only once every argument has passed: `who`'s refusal if there is no
+// device or no such index, else g makes it current for the rest of the call.
+int learner_device(DeviceGuard& g, int device, const char* who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TB_E_NODEVICE, "tb_ppo: no HIP device available (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev) return refusal(TB_E_NODEVICE, who, ": device index out of range");
+  g.enter(device);
+  return g.err == hipSuccess ? TB_OK : fail((int)g.err, "hipSetDevice");
+}
+// A rollout's rewards and dones, rows one step apart: their step strides in elements from the caller's in bytes (0: packed, n_envs)
+int step_strides(const char* who, int n_envs, size_t reward_bytes, size_t done_bytes, size_t* rs, size_t* ds) {
+  *rs = *ds = (size_t)n_envs;
+  if (reward_bytes) {
+    if (reward_bytes % sizeof(float) || reward_bytes < sizeof(float) * (size_t)n_envs)
+      return refusal(TB_E_INVAL, who, ": the rewards' step stride must be a multiple of 4 bytes and hold n_envs floats");
+    *rs = reward_bytes / sizeof(float);
+  }
+  if (done_bytes) {
+    if (done_bytes < (size_t)n_envs) return refusal(TB_E_INVAL, who, ": the dones' step stride is shorter than n_envs bytes");
+    *ds = done_bytes;
+  }
+  return TB_OK;
 }
 }  // namespace
 }  // extern "C++"
 int tb_ppo_param_floats_net(int env_kind, int net) {
   if (!kind_ok(env_kind)) return TB_E_INVAL;
   if (int rc = policy_net_ok(env_kind, net, "tb_ppo_param_floats_net")) return rc;
-  return net == TB_NET_TUNED ? TunedLayout::P : ppo_dims(env_kind, net).P;
+  return ppo_dims(env_kind, net).P;
 }
 int tb_ppo_rows_per_workgroup(void) { return TB_PPO_SHARE; }
-
-static size_t ppo_partials(int batch) { return 2 * (((size_t)batch + TB_PPO_SHARE - 1) / TB_PPO_SHARE); }
-static constexpr size_t kPpoStatBytes = sizeof(double) * 2 * TB_PPO_STAT_BLOCKS;
-// floats of one partial vector: the gradient and the two statistics; the tuned net's also hold the vf waves' extractor share
-static size_t ppo_partial_stride(int env_kind, int net) { return net == TB_NET_TUNED ? (size_t)TunedLayout::STRIDE : (size_t)tb_ppo_param_floats_net(env_kind, net) + 2; }
 
 long long tb_ppo_workspace_bytes_net(int env_kind, int net, int batch) {
   if (!kind_ok(env_kind) || batch < 2) return fail(TB_E_INVAL, "tb_ppo_workspace_bytes: unknown env kind, or batch < 2");
   if (int rc = policy_net_ok(env_kind, net, "tb_ppo_workspace_bytes_net")) return rc;
-  return (long long)(kPpoStatBytes + sizeof(float) * ppo_partials(batch) * ppo_partial_stride(env_kind, net));
+  return (long long)(kPpoStatBytes + sizeof(float) * ppo_partials(batch) * (size_t)ppo_dims(env_kind, net).STRIDE);
 }
 long long tb_ppo_workspace_bytes(int env_kind, int batch) { return tb_ppo_workspace_bytes_net(env_kind, TB_NET_DEFAULT, batch); }
-
-static int ppo_device(int device, const char* what) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TB_E_NODEVICE, "tb_ppo: no HIP device available (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(TB_E_NODEVICE, what);
-  return TB_OK;
+// a population's workspace: one learner's per member, a multiple of 8 bytes apart
+long long tb_ppo_members_workspace_stride_bytes(int env_kind, int net, int batch) {
+  const long long one = tb_ppo_workspace_bytes_net(env_kind, net, batch);
+  return one < 0 ? one : (one + 7) / 8 * 8;
 }
-static bool misaligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 int tb_ppo_gae(int env_kind, int device, void* stream, int n_steps, int n_envs, const float* rewards_dev, size_t reward_step_stride_bytes,
                const uint8_t* dones_dev, size_t done_step_stride_bytes, const float* values_dev, const float* last_value_dev, double gamma,
@@ -1453,22 +1480,127 @@ int tb_ppo_gae(int env_kind, int device, void* stream, int n_steps, int n_envs, 
   if (n_steps < 1 || n_envs < 1) return fail(TB_E_INVAL, "tb_ppo_gae: n_steps and n_envs must be >= 1");
   if (misaligned(rewards_dev, 4) || misaligned(values_dev, 4) || misaligned(last_value_dev, 4) || misaligned(adv_dev, 4) || misaligned(returns_dev, 4))
     return fail(TB_E_INVAL, "tb_ppo_gae: a float array is not 4-byte aligned");
-  size_t rs = (size_t)n_envs, ds = (size_t)n_envs;
-  if (reward_step_stride_bytes) {
-    if (reward_step_stride_bytes % sizeof(float) || reward_step_stride_bytes < sizeof(float) * (size_t)n_envs)
-      return fail(TB_E_INVAL, "tb_ppo_gae: the rewards' step stride must be a multiple of 4 bytes and hold n_envs floats");
-    rs = reward_step_stride_bytes / sizeof(float);
-  }
-  if (done_step_stride_bytes) {
-    if (done_step_stride_bytes < (size_t)n_envs) return fail(TB_E_INVAL, "tb_ppo_gae: the dones' step stride is shorter than n_envs bytes");
-    ds = done_step_stride_bytes;
-  }
-  if (int rc = ppo_device(device, "tb_ppo_gae: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  size_t rs, ds;
+  if (int rc = step_strides("tb_ppo_gae", n_envs, reward_step_stride_bytes, done_step_stride_bytes, &rs, &ds)) return rc;
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, "tb_ppo_gae")) return rc;
   return launch(tb_ppo_gae_kernel, dim3((unsigned)((n_envs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n_steps, n_envs, rewards_dev, rs, dones_dev, ds,
                 values_dev, last_value_dev, (float)gamma, (float)(gamma * gae_lambda), adv_dev, returns_dev);
 }
+
+// ---- a minibatch step, for one learner and for a population (tb_learner.hpp, "THE MEMBER AXIS": the same kernels with the member as a
+// second grid axis). Each stage is written once: mb is nothing, or the population's PpoMembers, which the kernels take the same way.
+extern "C++" {
+namespace {
+const PpoMembers* population() { return nullptr; }
+const PpoMembers* population(const PpoMembers& mb) { return &mb; }
+
+// What both stages refuse before the device is looked up (pop: null for one learner). First the pair: the kind, then the net
+// (TB_E_PARAMS). arrays_null: a population's null array is TB_E_INVAL whatever the pair; one learner's is, under a pair that is built ...
+int ppo_pair_refused(const char* who, int env_kind, int net, bool arrays_null) {
+  if (arrays_null) return refusal(TB_E_INVAL, who, ": null argument");
+  if (!kind_ok(env_kind)) return refusal(TB_E_INVAL, who, ": unknown env kind");
+  return policy_net_ok(env_kind, net, who);
+}
+// ... then the buffers. any_null, float_off, idx_off: over the stage's own arrays (null; not 4-byte aligned; idx not 8-byte aligned).
+// with_workspace: the call reads or writes the workspace (all but tb_ppo_apply without TB_PPO_REDUCE), so it and the batch are checked.
+int ppo_buffers_refused(const char* who, int env_kind, int net, int n_params, bool any_null, bool float_off, bool idx_off, bool with_workspace, int batch,
+                        const void* workspace_dev, size_t workspace_bytes, const PpoMembers* pop, int n_members) {
+  if (pop && (n_members < 1 || n_members > 65535)) return refusal(TB_E_INVAL, who, ": n_members must be in [1, 65535] (the member is a grid axis)");
+  if (with_workspace && batch < 2) return refusal(TB_E_INVAL, who, ": batch must be >= 2 (the unbiased std of one row is undefined)");
+  if (any_null || (with_workspace && !workspace_dev) || (pop && !pop->hp)) return refusal(TB_E_INVAL, who, ": null argument");
+  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return refusal(TB_E_INVAL, who, ": n_params is not tb_ppo_param_floats_net(env_kind, net)");
+  if (pop && pop->param_stride < (size_t)n_params) return refusal(TB_E_INVAL, who, ": param_stride_floats is shorter than n_params");
+  if (float_off) return refusal(TB_E_INVAL, who, ": a float array is not 4-byte aligned");
+  if (idx_off || (with_workspace && misaligned(workspace_dev, 8)) || (pop && misaligned(pop->hp, 8)))
+    return refusal(TB_E_INVAL, who, ": idx, hp and the workspace must be 8-byte aligned");
+  if (with_workspace && workspace_bytes / (size_t)(pop ? n_members : 1) < (pop ? pop->ws_stride : (size_t)tb_ppo_workspace_bytes_net(env_kind, net, batch)))
+    return refusal(TB_E_INVAL, who, ": the workspace is smaller than tb_ppo_workspace_bytes (a population's: n_members * tb_ppo_members_workspace_stride_bytes)");
+  return TB_OK;
+}
+
+// tb_ppo_grad_net and tb_ppo_grad_members (`who`). n_members: the grid's second axis, 1 for one learner; a population's clip_range and
+// vf_coef are each member's own, from hp
+template <class... MB>
+int ppo_grad(const char* who, int env_kind, int net, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev,
+             const float* adv_dev, const float* returns_dev, long long n_rows, const int64_t* idx_dev, int batch, int n_members, const float* params_dev, int n_params,
+             float clip_range, float vf_coef, void* workspace_dev, size_t workspace_bytes, const MB&... mb) {
+  const PpoMembers* const pop = population(mb...);
+  const bool any_null = !obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !returns_dev || !idx_dev || !params_dev;
+  if (int rc = ppo_pair_refused(who, env_kind, net, pop && any_null)) return rc;
+  if (int rc = ppo_buffers_refused(who, env_kind, net, n_params, any_null,
+                                   misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) ||
+                                       misaligned(returns_dev, 4) || misaligned(params_dev, 4),
+                                   misaligned(idx_dev, 8), true, batch, workspace_dev, workspace_bytes, pop, n_members))
+    return rc;
+  if (n_rows < 1) return refusal(TB_E_INVAL, who, ": n_rows must be >= 1");
+  if (pop && pop->idx_stride < (size_t)batch) return refusal(TB_E_INVAL, who, ": idx_stride is shorter than batch");
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, who)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  double* sums = (double*)workspace_dev;
+  const PpoGradArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, (const long long*)idx_dev, params_dev, sums,
+                         (float*)((char*)workspace_dev + kPpoStatBytes), n_rows, batch, clip_range, vf_coef};
+  const unsigned M = (unsigned)n_members;
+  if (int rc = launch(tb_ppo_adv_stats_kernel<MB...>, dim3(TB_PPO_STAT_BLOCKS, M), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums, mb...)) return rc;
+  const dim3 grid((unsigned)(ppo_partials(batch) / 2), M);
+  return with_kind_net(env_kind, net, TB_E_UNSUPPORTED, [&](auto K, auto N) {
+    if constexpr (N.value == TB_NET_TUNED) return launch(tb_ppo_grad_tuned_kernel<MB...>, grid, dim3(256), 0, s, a, mb...);
+    else return launch(tb_ppo_grad_kernel<K.value, N.value, MB...>, grid, dim3(256), 0, s, a, mb...);
+  });
+}
+
+// tb_ppo_apply_net and tb_ppo_apply_members (`who`): the reduce and the Adam step. A population runs both phases, never value-only, with
+// world = 1; its ent_coef and lr are each member's own, from hp
+template <class... MB>
+int ppo_apply(const char* who, int env_kind, int net, int device, void* stream, int phases, const void* workspace_dev, size_t workspace_bytes, int batch, int n_members,
+              float* params_dev, float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int n_params, float* stats_dev, float ent_coef, float max_grad_norm,
+              int world, float lr, float beta1, float beta2, float eps, long long step, const MB&... mb) {
+  const PpoMembers* const pop = population(mb...);
+  const bool reduce = (phases & TB_PPO_REDUCE) != 0, adam = (phases & TB_PPO_STEP) != 0;
+  const int value_only = (phases & TB_PPO_VALUE_ONLY) != 0;
+  const bool any_null = !params_dev || !grad_dev || (reduce && !stats_dev) || (adam && (!exp_avg_dev || !exp_avg_sq_dev));
+  if (int rc = ppo_pair_refused(who, env_kind, net, pop && any_null)) return rc;
+  if (net == TB_NET_TUNED && value_only)
+    return refusal(TB_E_UNSUPPORTED, who, ": TB_PPO_VALUE_ONLY is not offered for TB_NET_TUNED (the extractor is shared: there is no critic-only slot range)");
+  if (!(reduce || adam) || (phases & ~(TB_PPO_REDUCE | TB_PPO_STEP | TB_PPO_VALUE_ONLY)))
+    return refusal(TB_E_INVAL, who, ": phases must be TB_PPO_REDUCE, TB_PPO_STEP or both, with or without TB_PPO_VALUE_ONLY");
+  if (int rc = ppo_buffers_refused(who, env_kind, net, n_params, any_null,
+                                   misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) ||
+                                       misaligned(stats_dev, 4),
+                                   false, reduce, batch, workspace_dev, workspace_bytes, pop, n_members))
+    return rc;
+  if (adam && (world < 1 || step < 1)) return refusal(TB_E_INVAL, who, ": world and step must be >= 1");
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, who)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned M = (unsigned)n_members;
+  if (reduce) {
+    const float* partials = (const float*)((const char*)workspace_dev + kPpoStatBytes);
+    const float* params = params_dev;
+    const int n_part = (int)ppo_partials(batch);
+    const dim3 grid((unsigned)((n_params + 2 + 63) / 64), M);
+    // (the tuned net's reduce is its own kernel, without a value-only form)
+    if (int rc = with_kind_net(env_kind, net, TB_E_UNSUPPORTED, [&](auto K, auto N) {
+          if constexpr (N.value == TB_NET_TUNED) return launch(tb_ppo_reduce_tuned_kernel<MB...>, grid, dim3(256), 0, s, partials, n_part, batch, params, ent_coef, grad_dev, stats_dev, mb...);
+          else return launch(tb_ppo_reduce_kernel<K.value, N.value, MB...>, grid, dim3(256), 0, s, partials, n_part, batch, params, ent_coef, grad_dev, stats_dev, value_only, mb...);
+        }))
+      return rc;
+  }
+  if (adam) {
+    const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
+    int lo0 = 0, hi0 = n_params, lo1 = 0, hi1 = 0;
+    if (value_only) {  // the critic's slots alone
+      const PpoDims d = ppo_dims(env_kind, net);
+      lo0 = d.VF; hi0 = d.PI_HEAD; lo1 = d.VF_HEAD; hi1 = d.P;
+    }
+    return launch(tb_ppo_step_kernel<MB...>, dim3(M), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, (float)world, max_grad_norm, lr,
+                  beta1, beta2, eps, c1, c2, lo0, hi0, lo1, hi1, mb...);
+  }
+  return TB_OK;
+}
+}  // namespace
+}  // extern "C++"
 
 int tb_ppo_grad(int env_kind, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev, const float* adv_dev,
                 const float* returns_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* params_dev, int n_params, float clip_range,
@@ -1479,29 +1611,15 @@ int tb_ppo_grad(int env_kind, int device, void* stream, const float* obs_dev, co
 int tb_ppo_grad_net(int env_kind, int net, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev,
                     const float* adv_dev, const float* returns_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* params_dev, int n_params,
                     float clip_range, float vf_coef, void* workspace_dev, size_t workspace_bytes) {
-  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_ppo_grad: unknown env kind");
-  if (int rc = policy_net_ok(env_kind, net, "tb_ppo_grad")) return rc;
-  if (!obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !returns_dev || !idx_dev || !params_dev || !workspace_dev)
-    return fail(TB_E_INVAL, "tb_ppo_grad: null argument");
-  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_ppo_grad: n_params is not tb_ppo_param_floats_net(env_kind, net)");
-  if (n_rows < 1 || batch < 2) return fail(TB_E_INVAL, "tb_ppo_grad: n_rows must be >= 1 and batch >= 2 (the unbiased std of one row is undefined)");
-  if (misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) || misaligned(returns_dev, 4) ||
-      misaligned(params_dev, 4))
-    return fail(TB_E_INVAL, "tb_ppo_grad: a float array is not 4-byte aligned");
-  if (misaligned(idx_dev, 8) || misaligned(workspace_dev, 8)) return fail(TB_E_INVAL, "tb_ppo_grad: idx and the workspace must be 8-byte aligned");
-  if ((long long)workspace_bytes < tb_ppo_workspace_bytes_net(env_kind, net, batch)) return fail(TB_E_INVAL, "tb_ppo_grad: the workspace is smaller than tb_ppo_workspace_bytes");
-  if (int rc = ppo_device(device, "tb_ppo_grad: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  hipStream_t s = (hipStream_t)stream;
-  double* sums = (double*)workspace_dev;
-  PpoGradArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, (const long long*)idx_dev, params_dev, sums,
-                   (float*)((char*)workspace_dev + kPpoStatBytes), n_rows, batch, clip_range, vf_coef};
-  if (int rc = launch(tb_ppo_adv_stats_kernel<>, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
-  const dim3 grid((unsigned)(ppo_partials(batch) / 2));
-  if (net == TB_NET_TUNED) return launch(tb_ppo_grad_tuned_kernel<>, grid, dim3(256), 0, s, a);
-  if (net == TB_NET_MLP64) return launch(tb_ppo_grad_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, a);
-  return env_kind == TB_ENV_SWING ? launch(tb_ppo_grad_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a) : launch(tb_ppo_grad_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a);
+  return ppo_grad("tb_ppo_grad", env_kind, net, device, stream, obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, n_rows, idx_dev, batch, 1, params_dev,
+                  n_params, clip_range, vf_coef, workspace_dev, workspace_bytes);
+}
+int tb_ppo_grad_members(int env_kind, int net, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev,
+                        const float* adv_dev, const float* returns_dev, long long n_rows, const int64_t* idx_dev, size_t idx_stride, int batch, int n_members,
+                        const float* params_dev, size_t param_stride_floats, int n_params, const TbPpoMemberHp* hp_dev, void* workspace_dev, size_t workspace_bytes) {
+  const PpoMembers mb = {hp_dev, idx_stride, param_stride_floats, (size_t)tb_ppo_members_workspace_stride_bytes(env_kind, net, batch)};
+  return ppo_grad("tb_ppo_grad_members", env_kind, net, device, stream, obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, n_rows, idx_dev, batch, n_members,
+                  params_dev, n_params, 0.0f, 0.0f, workspace_dev, workspace_bytes, mb);
 }
 
 int tb_ppo_apply(int env_kind, int device, void* stream, int phases, const void* workspace_dev, size_t workspace_bytes, int batch, float* params_dev,
@@ -1513,135 +1631,15 @@ int tb_ppo_apply(int env_kind, int device, void* stream, int phases, const void*
 int tb_ppo_apply_net(int env_kind, int net, int device, void* stream, int phases, const void* workspace_dev, size_t workspace_bytes, int batch, float* params_dev,
                      float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int n_params, float* stats_dev, float ent_coef, float max_grad_norm, int world,
                      float lr, float beta1, float beta2, float eps, long long step) {
-  if (!kind_ok(env_kind)) return fail(TB_E_INVAL, "tb_ppo_apply: unknown env kind");
-  if (int rc = policy_net_ok(env_kind, net, "tb_ppo_apply")) return rc;
-  if (net == TB_NET_TUNED && (phases & TB_PPO_VALUE_ONLY))
-    return fail(TB_E_UNSUPPORTED, "tb_ppo_apply: TB_PPO_VALUE_ONLY is not offered for TB_NET_TUNED (the extractor is shared: there is no critic-only slot range)");
-  if (!(phases & (TB_PPO_REDUCE | TB_PPO_STEP)) || (phases & ~(TB_PPO_REDUCE | TB_PPO_STEP | TB_PPO_VALUE_ONLY)))
-    return fail(TB_E_INVAL, "tb_ppo_apply: phases must be TB_PPO_REDUCE, TB_PPO_STEP or both, with or without TB_PPO_VALUE_ONLY");
-  const int value_only = (phases & TB_PPO_VALUE_ONLY) != 0;
-  if (!params_dev || !grad_dev) return fail(TB_E_INVAL, "tb_ppo_apply: null argument");
-  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return fail(TB_E_INVAL, "tb_ppo_apply: n_params is not tb_ppo_param_floats_net(env_kind, net)");
-  if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(stats_dev, 4))
-    return fail(TB_E_INVAL, "tb_ppo_apply: a float array is not 4-byte aligned");
-  if (phases & TB_PPO_REDUCE) {
-    if (!workspace_dev || !stats_dev) return fail(TB_E_INVAL, "tb_ppo_apply: TB_PPO_REDUCE needs the workspace and stats_dev");
-    if (batch < 2 || misaligned(workspace_dev, 8) || (long long)workspace_bytes < tb_ppo_workspace_bytes_net(env_kind, net, batch))
-      return fail(TB_E_INVAL, "tb_ppo_apply: batch < 2, or the workspace is misaligned or smaller than tb_ppo_workspace_bytes");
-  }
-  if (phases & TB_PPO_STEP) {
-    if (!exp_avg_dev || !exp_avg_sq_dev) return fail(TB_E_INVAL, "tb_ppo_apply: TB_PPO_STEP needs both moments");
-    if (world < 1 || step < 1) return fail(TB_E_INVAL, "tb_ppo_apply: world and step must be >= 1");
-  }
-  if (int rc = ppo_device(device, "tb_ppo_apply: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  hipStream_t s = (hipStream_t)stream;
-  if (phases & TB_PPO_REDUCE) {
-    const float* partials = (const float*)((const char*)workspace_dev + kPpoStatBytes);
-    const int n_part = (int)ppo_partials(batch);
-    const dim3 grid((unsigned)((n_params + 2 + 63) / 64));
-    if (net == TB_NET_TUNED) {
-      if (int rc = launch(tb_ppo_reduce_tuned_kernel<>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev)) return rc;
-    } else if (net == TB_NET_MLP64) {
-      if (int rc = launch(tb_ppo_reduce_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only))
-        return rc;
-    } else if (int rc = env_kind == TB_ENV_SWING ? launch(tb_ppo_reduce_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only)
-                                          : launch(tb_ppo_reduce_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, partials, n_part, batch, (const float*)params_dev, ent_coef, grad_dev, stats_dev, value_only))
-      return rc;
-  }
-  if (phases & TB_PPO_STEP) {
-    const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
-    int lo0 = 0, hi0 = n_params, lo1 = 0, hi1 = 0;
-    if (value_only) {
-      const PpoDims d = ppo_dims(env_kind, net);
-      if (d.P != n_params) return fail(TB_E_UNSUPPORTED, "tb_ppo_apply: no critic-only slot range for this (kind, net) pair");
-      lo0 = d.VF; hi0 = d.PI_HEAD; lo1 = d.VF_HEAD; hi1 = d.P;
-    }
-    return launch(tb_ppo_step_kernel<>, dim3(1), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, (float)world, max_grad_norm, lr,
-                  beta1, beta2, eps, c1, c2, lo0, hi0, lo1, hi1);
-  }
-  return TB_OK;
+  return ppo_apply("tb_ppo_apply", env_kind, net, device, stream, phases, workspace_dev, workspace_bytes, batch, 1, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev,
+                   n_params, stats_dev, ent_coef, max_grad_norm, world, lr, beta1, beta2, eps, step);
 }
-
-// ---- a population's minibatch step (tb_learner.hpp, "THE MEMBER AXIS"): the same kernels with the member as a second grid axis
-long long tb_ppo_members_workspace_stride_bytes(int env_kind, int net, int batch) {
-  const long long one = tb_ppo_workspace_bytes_net(env_kind, net, batch);
-  return one < 0 ? one : (one + 7) / 8 * 8;
-}
-// what both calls refuse, before the device is looked up
-static int ppo_members_refused(const char* who, int env_kind, int net, int batch, int n_members, size_t param_stride_floats, int n_params, const void* hp_dev,
-                               const void* workspace_dev, size_t workspace_bytes) {
-  if (!kind_ok(env_kind)) return refusal(TB_E_INVAL, who, ": unknown env kind");
-  if (int rc = policy_net_ok(env_kind, net, who)) return rc;
-  if (n_members < 1 || n_members > 65535) return refusal(TB_E_INVAL, who, ": n_members must be in [1, 65535] (the member is a grid axis)");
-  if (batch < 2) return refusal(TB_E_INVAL, who, ": batch must be >= 2 (the unbiased std of one row is undefined)");
-  if (!hp_dev || !workspace_dev) return refusal(TB_E_INVAL, who, ": null argument");
-  if (n_params != tb_ppo_param_floats_net(env_kind, net)) return refusal(TB_E_INVAL, who, ": n_params is not tb_ppo_param_floats_net(env_kind, net)");
-  if (param_stride_floats < (size_t)n_params) return refusal(TB_E_INVAL, who, ": param_stride_floats is shorter than n_params");
-  if (misaligned(hp_dev, 8) || misaligned(workspace_dev, 8)) return refusal(TB_E_INVAL, who, ": idx, hp and the workspace must be 8-byte aligned");
-  if (workspace_bytes / (size_t)n_members < (size_t)tb_ppo_members_workspace_stride_bytes(env_kind, net, batch))
-    return refusal(TB_E_INVAL, who, ": the workspace is smaller than n_members * tb_ppo_members_workspace_stride_bytes");
-  return TB_OK;
-}
-
-int tb_ppo_grad_members(int env_kind, int net, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev,
-                        const float* adv_dev, const float* returns_dev, long long n_rows, const int64_t* idx_dev, size_t idx_stride, int batch, int n_members,
-                        const float* params_dev, size_t param_stride_floats, int n_params, const TbPpoMemberHp* hp_dev, void* workspace_dev, size_t workspace_bytes) {
-  const char* const who = "tb_ppo_grad_members";
-  if (!obs_dev || !raw_actions_dev || !old_logp_dev || !adv_dev || !returns_dev || !idx_dev || !params_dev) return refusal(TB_E_INVAL, who, ": null argument");
-  if (int rc = ppo_members_refused(who, env_kind, net, batch, n_members, param_stride_floats, n_params, hp_dev, workspace_dev, workspace_bytes)) return rc;
-  if (n_rows < 1) return refusal(TB_E_INVAL, who, ": n_rows must be >= 1");
-  if (idx_stride < (size_t)batch) return refusal(TB_E_INVAL, who, ": idx_stride is shorter than batch");
-  if (misaligned(obs_dev, 4) || misaligned(raw_actions_dev, 4) || misaligned(old_logp_dev, 4) || misaligned(adv_dev, 4) || misaligned(returns_dev, 4) ||
-      misaligned(params_dev, 4))
-    return refusal(TB_E_INVAL, who, ": a float array is not 4-byte aligned");
-  if (misaligned(idx_dev, 8)) return refusal(TB_E_INVAL, who, ": idx, hp and the workspace must be 8-byte aligned");
-  if (int rc = ppo_device(device, "tb_ppo_grad_members: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  hipStream_t s = (hipStream_t)stream;
-  double* sums = (double*)workspace_dev;
-  const PpoMembers mb = {hp_dev, idx_stride, param_stride_floats, (size_t)tb_ppo_members_workspace_stride_bytes(env_kind, net, batch)};
-  const PpoGradArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, returns_dev, (const long long*)idx_dev, params_dev, sums,
-                         (float*)((char*)workspace_dev + kPpoStatBytes), n_rows, batch, 0.0f, 0.0f};  // (clip_range, vf_coef: the member's, from hp)
-  const unsigned M = (unsigned)n_members;
-  if (int rc = launch(tb_ppo_adv_stats_kernel<PpoMembers>, dim3(TB_PPO_STAT_BLOCKS, M), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums, mb)) return rc;
-  const dim3 grid((unsigned)(ppo_partials(batch) / 2), M);
-  if (net == TB_NET_TUNED) return launch(tb_ppo_grad_tuned_kernel<PpoMembers>, grid, dim3(256), 0, s, a, mb);
-  if (net == TB_NET_MLP64) return launch(tb_ppo_grad_kernel<TB_ENV_SWING, TB_NET_MLP64, PpoMembers>, grid, dim3(256), 0, s, a, mb);
-  return env_kind == TB_ENV_SWING ? launch(tb_ppo_grad_kernel<TB_ENV_SWING, TB_NET_DEFAULT, PpoMembers>, grid, dim3(256), 0, s, a, mb)
-                                  : launch(tb_ppo_grad_kernel<TB_ENV_TENNIS, TB_NET_DEFAULT, PpoMembers>, grid, dim3(256), 0, s, a, mb);
-}
-
 int tb_ppo_apply_members(int env_kind, int net, int device, void* stream, const void* workspace_dev, size_t workspace_bytes, int batch, int n_members,
                          float* params_dev, float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, size_t param_stride_floats, int n_params, float* stats_dev,
                          const TbPpoMemberHp* hp_dev, float max_grad_norm, float beta1, float beta2, float eps, long long step) {
-  const char* const who = "tb_ppo_apply_members";
-  if (!params_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !stats_dev) return refusal(TB_E_INVAL, who, ": null argument");
-  if (int rc = ppo_members_refused(who, env_kind, net, batch, n_members, param_stride_floats, n_params, hp_dev, workspace_dev, workspace_bytes)) return rc;
-  if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(stats_dev, 4))
-    return refusal(TB_E_INVAL, who, ": a float array is not 4-byte aligned");
-  if (step < 1) return refusal(TB_E_INVAL, who, ": step must be >= 1");
-  if (int rc = ppo_device(device, "tb_ppo_apply_members: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
-  hipStream_t s = (hipStream_t)stream;
   const PpoMembers mb = {hp_dev, 0, param_stride_floats, (size_t)tb_ppo_members_workspace_stride_bytes(env_kind, net, batch)};
-  const float* partials = (const float*)((const char*)workspace_dev + kPpoStatBytes);
-  const int n_part = (int)ppo_partials(batch);
-  const unsigned M = (unsigned)n_members;
-  const dim3 grid((unsigned)((n_params + 2 + 63) / 64), M);
-  const float* params = params_dev;
-  int rc;
-  if (net == TB_NET_TUNED) rc = launch(tb_ppo_reduce_tuned_kernel<PpoMembers>, grid, dim3(256), 0, s, partials, n_part, batch, params, 0.0f, grad_dev, stats_dev, mb);
-  else if (net == TB_NET_MLP64) rc = launch(tb_ppo_reduce_kernel<TB_ENV_SWING, TB_NET_MLP64, PpoMembers>, grid, dim3(256), 0, s, partials, n_part, batch, params, 0.0f, grad_dev, stats_dev, 0, mb);
-  else if (env_kind == TB_ENV_SWING) rc = launch(tb_ppo_reduce_kernel<TB_ENV_SWING, TB_NET_DEFAULT, PpoMembers>, grid, dim3(256), 0, s, partials, n_part, batch, params, 0.0f, grad_dev, stats_dev, 0, mb);
-  else rc = launch(tb_ppo_reduce_kernel<TB_ENV_TENNIS, TB_NET_DEFAULT, PpoMembers>, grid, dim3(256), 0, s, partials, n_part, batch, params, 0.0f, grad_dev, stats_dev, 0, mb);
-  if (rc) return rc;
-  const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
-  return launch(tb_ppo_step_kernel<PpoMembers>, dim3(M), dim3(1024), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_params, 1.0f, max_grad_norm, 0.0f, beta1,
-                beta2, eps, c1, c2, 0, n_params, 0, 0, mb);
+  return ppo_apply("tb_ppo_apply_members", env_kind, net, device, stream, TB_PPO_REDUCE | TB_PPO_STEP, workspace_dev, workspace_bytes, batch, n_members, params_dev, grad_dev,
+                   exp_avg_dev, exp_avg_sq_dev, n_params, stats_dev, 0.0f, max_grad_norm, 1, 0.0f, beta1, beta2, eps, step, mb);
 }
 
 // ------------------------------------------------------------------------------------------- the TRPO learner (tb_trpo.hpp)
@@ -1649,6 +1647,16 @@ int tb_trpo_rows_per_workgroup(void) { return TB_PPO_SHARE; }
 int tb_trpo_search_rows_per_workgroup(void) { return TB_TRPO_SEARCH_SHARE; }
 
 static size_t trpo_search_shares(int batch) { return ((size_t)batch + TB_TRPO_SEARCH_SHARE - 1) / TB_TRPO_SEARCH_SHARE; }
+// the pairs the TRPO kernels are built for: with_kind_net's without the tuned network (trpo_net_ok has refused it by then)
+extern "C++" {
+template <class F>
+static int with_trpo_kind_net(int kind, int net, F f) {
+  return with_kind_net(kind, net, TB_E_UNSUPPORTED, [&](auto K, auto N) {
+    if constexpr (N.value == TB_NET_TUNED) return TB_E_UNSUPPORTED;
+    else return f(K, N);
+  });
+}
+}
 
 long long tb_trpo_fvp_workspace_bytes_net(int env_kind, int net, int n_idx) {
   if (!kind_ok(env_kind) || n_idx < 1) return fail(TB_E_INVAL, "tb_trpo_fvp_workspace_bytes: unknown env kind, or n_idx < 1");
@@ -1683,21 +1691,16 @@ int tb_trpo_fvp_net(int env_kind, int net, int device, void* stream, const float
   if (misaligned(idx_dev, 8) || misaligned(workspace_dev, 8)) return fail(TB_E_INVAL, "tb_trpo_fvp: idx and the workspace must be 8-byte aligned");
   if (vec_dev == out_dev) return fail(TB_E_INVAL, "tb_trpo_fvp: out_dev must not be vec_dev");
   if ((long long)workspace_bytes < tb_trpo_fvp_workspace_bytes_net(env_kind, net, n_idx)) return fail(TB_E_INVAL, "tb_trpo_fvp: the workspace is smaller than tb_trpo_fvp_workspace_bytes");
-  if (int rc = ppo_device(device, "tb_trpo_fvp: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, "tb_trpo_fvp")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int n_part = (int)ppo_partials(n_idx);
   TrpoFvpArgs a = {obs_dev, (const long long*)idx_dev, params_dev, vec_dev, (float*)workspace_dev, n_rows, n_idx};
   const dim3 grid((unsigned)(n_part / 2)), rgrid((unsigned)((n_params + 63) / 64));
-  if (net == TB_NET_MLP64) {
-    if (int rc = launch(tb_trpo_fvp_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(128), 0, s, a)) return rc;
-    return launch(tb_trpo_fvp_reduce_kernel<TB_ENV_SWING, TB_NET_MLP64>, rgrid, dim3(256), 0, s, (const float*)workspace_dev, n_part, n_idx, vec_dev, damping, out_dev);
-  }
-  const bool swing = env_kind == TB_ENV_SWING;
-  if (int rc = swing ? launch(tb_trpo_fvp_kernel<TB_ENV_SWING>, grid, dim3(128), 0, s, a) : launch(tb_trpo_fvp_kernel<TB_ENV_TENNIS>, grid, dim3(128), 0, s, a)) return rc;
-  return swing ? launch(tb_trpo_fvp_reduce_kernel<TB_ENV_SWING>, rgrid, dim3(256), 0, s, (const float*)workspace_dev, n_part, n_idx, vec_dev, damping, out_dev)
-               : launch(tb_trpo_fvp_reduce_kernel<TB_ENV_TENNIS>, rgrid, dim3(256), 0, s, (const float*)workspace_dev, n_part, n_idx, vec_dev, damping, out_dev);
+  return with_trpo_kind_net(env_kind, net, [&](auto K, auto N) {
+    if (int rc = launch(tb_trpo_fvp_kernel<K.value, N.value>, grid, dim3(128), 0, s, a)) return rc;
+    return launch(tb_trpo_fvp_reduce_kernel<K.value, N.value>, rgrid, dim3(256), 0, s, (const float*)workspace_dev, n_part, n_idx, vec_dev, damping, out_dev);
+  });
 }
 
 int tb_trpo_search(int env_kind, int device, void* stream, const float* obs_dev, const float* raw_actions_dev, const float* old_logp_dev, const float* adv_dev,
@@ -1723,9 +1726,8 @@ int tb_trpo_search_net(int env_kind, int net, int device, void* stream, const fl
     return fail(TB_E_INVAL, "tb_trpo_search: idx, out and the workspace must be 8-byte aligned");
   if ((long long)workspace_bytes < tb_trpo_search_workspace_bytes_net(env_kind, net, batch, n_candidates))
     return fail(TB_E_INVAL, "tb_trpo_search: the workspace is smaller than tb_trpo_search_workspace_bytes");
-  if (int rc = ppo_device(device, "tb_trpo_search: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, "tb_trpo_search")) return rc;
   hipStream_t s = (hipStream_t)stream;
   double* sums = (double*)workspace_dev;
   double* partials = (double*)((char*)workspace_dev + kPpoStatBytes);
@@ -1733,10 +1735,7 @@ int tb_trpo_search_net(int env_kind, int net, int device, void* stream, const fl
   TrpoSearchArgs a = {obs_dev, raw_actions_dev, old_logp_dev, adv_dev, (const long long*)idx_dev, params_dev, direction_dev, steps_dev, sums, partials, n_rows, batch};
   if (int rc = launch(tb_ppo_adv_stats_kernel<>, dim3(TB_PPO_STAT_BLOCKS), dim3(256), 0, s, adv_dev, (const long long*)idx_dev, batch, n_rows, sums)) return rc;
   const dim3 grid((unsigned)shares, (unsigned)n_candidates);
-  if (int rc = net == TB_NET_MLP64            ? launch(tb_trpo_search_kernel<TB_ENV_SWING, TB_NET_MLP64>, grid, dim3(256), 0, s, a)
-               : env_kind == TB_ENV_SWING ? launch(tb_trpo_search_kernel<TB_ENV_SWING>, grid, dim3(256), 0, s, a)
-                                          : launch(tb_trpo_search_kernel<TB_ENV_TENNIS>, grid, dim3(256), 0, s, a))
-    return rc;
+  if (int rc = with_trpo_kind_net(env_kind, net, [&](auto K, auto N) { return launch(tb_trpo_search_kernel<K.value, N.value>, grid, dim3(256), 0, s, a); })) return rc;
   return launch(tb_trpo_search_reduce_kernel, dim3((unsigned)n_candidates), dim3(256), 0, s, (const double*)partials, shares, batch, out_dev);
 }
 
@@ -1756,22 +1755,13 @@ int tb_trpo_returns(int env_kind, int device, void* stream, int n_steps, int n_e
   if (misaligned(rewards_dev, 4) || misaligned(returns_dev, 4)) return fail(TB_E_INVAL, "tb_trpo_returns: a float array is not 4-byte aligned");
   if (misaligned(idx_dev, 8) || misaligned(count_dev, 8) || misaligned(workspace_dev, 8))
     return fail(TB_E_INVAL, "tb_trpo_returns: idx, count and the workspace must be 8-byte aligned");
-  size_t rs = (size_t)n_envs, ds = (size_t)n_envs;
-  if (reward_step_stride_bytes) {
-    if (reward_step_stride_bytes % sizeof(float) || reward_step_stride_bytes < sizeof(float) * (size_t)n_envs)
-      return fail(TB_E_INVAL, "tb_trpo_returns: the rewards' step stride must be a multiple of 4 bytes and hold n_envs floats");
-    rs = reward_step_stride_bytes / sizeof(float);
-  }
-  if (done_step_stride_bytes) {
-    if (done_step_stride_bytes < (size_t)n_envs) return fail(TB_E_INVAL, "tb_trpo_returns: the dones' step stride is shorter than n_envs bytes");
-    ds = done_step_stride_bytes;
-  }
+  size_t rs, ds;
+  if (int rc = step_strides("tb_trpo_returns", n_envs, reward_step_stride_bytes, done_step_stride_bytes, &rs, &ds)) return rc;
   if ((long long)n_steps * trpo_return_chunks(n_envs) > 0x7fffffffLL) return fail(TB_E_INVAL, "tb_trpo_returns: n_steps * ceil(n_envs / 64) must be below 2^31");
   if ((long long)workspace_bytes < tb_trpo_returns_workspace_bytes(n_steps, n_envs))
     return fail(TB_E_INVAL, "tb_trpo_returns: the workspace is smaller than tb_trpo_returns_workspace_bytes");
-  if (int rc = ppo_device(device, "tb_trpo_returns: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, "tb_trpo_returns")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int chunks = (int)trpo_return_chunks(n_envs);
   const long long entries = (long long)n_steps * chunks;
@@ -1889,10 +1879,11 @@ int sac_fail(int code, const char* what, const char* words, const char* more = "
 }
 
 // What a stage refuses before its first launch, in this order: the env kind, the batch and the workspace; null pointers;
-// n_rows; alignment (wide8 names what must be 8-byte aligned); aliasing (aliased: the words of the refusal, or null); the device.
+// n_rows; alignment (wide8 names what must be 8-byte aligned); aliasing (aliased: the words of the refusal, or null); the device, which
+// g then makes current for the rest of the stage.
 template <class Algo>
 int sac_check(const char* what, int env_kind, int batch, const void* workspace_dev, size_t workspace_bytes, bool any_null, long long n_rows, bool any_misaligned,
-              const char* wide8, const char* aliased, int device) {
+              const char* wide8, const char* aliased, int device, DeviceGuard& g) {
   if (!kind_ok(env_kind)) return sac_fail(TB_E_INVAL, what, "unknown env kind");
   if (batch < 1) return sac_fail(TB_E_INVAL, what, "batch must be >= 1");
   if (!workspace_dev) return sac_fail(TB_E_INVAL, what, "null argument (the workspace)");
@@ -1902,9 +1893,7 @@ int sac_check(const char* what, int env_kind, int batch, const void* workspace_d
   if (n_rows < 1) return sac_fail(TB_E_INVAL, what, "n_rows must be >= 1");
   if (any_misaligned) return sac_fail(TB_E_INVAL, what, "a float array is not 4-byte aligned, or ", wide8);
   if (aliased) return sac_fail(TB_E_INVAL, what, aliased);
-  char msg[96];
-  snprintf(msg, sizeof msg, "%s: device index out of range", what);
-  return ppo_device(device, msg);
+  return learner_device(g, device, what);
 }
 template <class Algo> SacRun sac_run(int env_kind, void* stream, int batch, void* workspace_dev) {
   return {Algo::dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev, Algo::HEADS, Algo::HW};
@@ -1925,13 +1914,12 @@ template <class Algo>
 int sac_actor_forward(const char* what, int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* actor_dev,
                       const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes) {
   using Ws = typename Algo::Ws;
+  DeviceGuard g;
   if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes, !obs_dev || !idx_dev || !actor_dev || !eps_dev || !act_out_dev || !logp_out_dev, n_rows,
                                misaligned(obs_dev, 4) || misaligned(actor_dev, 4) || misaligned(eps_dev, 4) || misaligned(act_out_dev, 4) || misaligned(logp_out_dev, 4) ||
                                    misaligned(idx_dev, 8),
-                               "idx not 8-byte aligned", nullptr, device))
+                               "idx not 8-byte aligned", nullptr, device, g))
     return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
   const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
   if (int rc = r.gather(obs_dev, nullptr, idx_dev, n_rows, Ws::X0)) return rc;
   return r.actor(actor_dev, eps_dev, Ws::X0, Ws::H1, Ws::H2, Ws::ZH, Ws::XC, Ws::LP, act_out_dev, logp_out_dev);
@@ -1942,14 +1930,13 @@ int sac_targets(const char* what, int env_kind, int device, void* stream, const 
                 const int64_t* idx_dev, int batch, const float* actor_dev, const float* target_dev, const float* log_ent_coef_dev, const float* eps_next_dev, float gamma,
                 float* y_dev, void* workspace_dev, size_t workspace_bytes) {
   using Ws = typename Algo::Ws;
+  DeviceGuard g;
   if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes,
                                !next_obs_dev || !reward_dev || !done_dev || !idx_dev || !actor_dev || !target_dev || !log_ent_coef_dev || !eps_next_dev || !y_dev, n_rows,
                                misaligned(next_obs_dev, 4) || misaligned(reward_dev, 4) || misaligned(done_dev, 4) || misaligned(actor_dev, 4) || misaligned(target_dev, 4) ||
                                    misaligned(log_ent_coef_dev, 4) || misaligned(eps_next_dev, 4) || misaligned(y_dev, 4) || misaligned(idx_dev, 8),
-                               "idx not 8-byte aligned", nullptr, device))
+                               "idx not 8-byte aligned", nullptr, device, g))
     return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
   const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
   if (int rc = r.gather(next_obs_dev, nullptr, idx_dev, n_rows, Ws::NX0)) return rc;
   if (int rc = r.actor(actor_dev, eps_next_dev, Ws::NX0, Ws::NH1, Ws::NH2, Ws::NZH, Ws::NXC, Ws::NAL, nullptr, nullptr)) return rc;  // logp' in NAL
@@ -1961,13 +1948,12 @@ template <class Algo>
 int sac_critic_grad(const char* what, int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev, int batch,
                     const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
   using Ws = typename Algo::Ws;
+  DeviceGuard g;
   if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes, !obs_dev || !action_dev || !idx_dev || !critic_dev || !y_dev || !grad_dev || !stats_dev, n_rows,
                                misaligned(obs_dev, 4) || misaligned(action_dev, 4) || misaligned(critic_dev, 4) || misaligned(y_dev, 4) || misaligned(grad_dev, 4) ||
                                    misaligned(idx_dev, 8) || misaligned(stats_dev, 8),
-                               "idx / stats not 8-byte aligned", grad_dev == critic_dev ? "grad_dev must not be critic_dev" : nullptr, device))
+                               "idx / stats not 8-byte aligned", grad_dev == critic_dev ? "grad_dev must not be critic_dev" : nullptr, device, g))
     return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
   const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
   const SacDims& d = r.d;
   const long long BH = (long long)batch * SAC_H;
@@ -1984,14 +1970,13 @@ template <class Algo>
 int sac_actor_grad(const char* what, int env_kind, int device, void* stream, int batch, const float* actor_dev, const float* critic_dev, const float* log_ent_coef_dev,
                    const float* eps_dev, float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
   using Ws = typename Algo::Ws;
+  DeviceGuard g;
   if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes,
                                !actor_dev || !critic_dev || !log_ent_coef_dev || !eps_dev || !actor_grad_dev || !ent_grad_dev || !stats_dev, 1,
                                misaligned(actor_dev, 4) || misaligned(critic_dev, 4) || misaligned(log_ent_coef_dev, 4) || misaligned(eps_dev, 4) || misaligned(actor_grad_dev, 4) ||
                                    misaligned(ent_grad_dev, 4) || misaligned(stats_dev, 8),
-                               "stats not 8-byte aligned", actor_grad_dev == actor_dev ? "actor_grad_dev must not be actor_dev" : nullptr, device))
+                               "stats not 8-byte aligned", actor_grad_dev == actor_dev ? "actor_grad_dev must not be actor_dev" : nullptr, device, g))
     return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
   const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
   const SacDims& d = r.d;
   const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
@@ -2073,9 +2058,8 @@ int tb_sac_adam(int device, void* stream, float* params_dev, const float* grad_d
   if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(target_dev, 4))
     return fail(TB_E_INVAL, "tb_sac_adam: a float array is not 4-byte aligned");
   if (target_dev == params_dev) return fail(TB_E_INVAL, "tb_sac_adam: target_dev must not be params_dev");
-  if (int rc = ppo_device(device, "tb_sac_adam: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, "tb_sac_adam")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const float omt = (float)(1.0 - (double)tau);
   const dim3 grid(sac_blocks(n, 256));
@@ -2218,9 +2202,8 @@ int tb_render(int env_kind, int device, void* stream, const TbParams* params, co
     const bool in = i < params->n_hull;
     hull.e[i] = make_float4(in ? params->hull_edges[i][0] : 0.0f, in ? params->hull_edges[i][1] : 0.0f, in ? params->hull_edges[i][2] : 0.0f, in ? params->hull_edges[i][3] : 0.0f);
   }
-  if (int rc = ppo_device(device, "tb_render: device index out of range")) return rc;
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail((int)g.err, "hipSetDevice");
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, "tb_render")) return rc;
   const dim3 grid((unsigned)(tiles * n_images)), block(64);
   if (env_kind == TB_ENV_SWING)
     return launch(tb_render_kernel<TB_ENV_SWING>, grid, block, 0, (hipStream_t)stream, cam, sc, hull, words_dev, n_envs, env_idx_dev_or_null, width, height, tiles_x, tiles,

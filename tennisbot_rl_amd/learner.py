@@ -53,8 +53,44 @@ def flatten_parameters(policy):
     return flat
 
 
+# What every learner object (FusedLearner and FusedTRPO, PopulationPPO) needs around a library call; each takes them as methods: they
+# read self.torch, self.device and self.lib.
+def current_stream(self):
+    return self.torch.cuda.current_stream(self.device).cuda_stream
+
+
+def device_index(self):
+    return self.device.index if self.device.index is not None else self.torch.cuda.current_device()
+
+
+def grown_workspace(self, ws, need, what):
+    """`ws` if it holds `need` bytes (the answer of the C query `what`: a refusal raises), else a new zeroed float64 one that does"""
+    if need < 0:
+        _check(self.lib, int(need), what)
+    if ws is None or ws.numel() * 8 < need:
+        ws = self.torch.zeros((need + 7) // 8, dtype=self.torch.float64, device=self.device)
+    return ws
+
+
+def gae(self, rewards, dones, values, last_value):
+    """(adv, returns) float32 [T, n] of tb_ppo_gae with self.hp's gamma and gae_lambda. rewards float32 / dones uint8 [T, n] with
+    contiguous rows, which may be strided over steps (a packed rollout buffer's views); values [T, n] and last_value [n] contiguous."""
+    t = self.torch
+    T, n = values.shape
+    r_stride = 4 * rewards.stride(0) if T > 1 and rewards.stride(0) >= n else 0
+    d_stride = dones.stride(0) if T > 1 and dones.stride(0) >= n else 0
+    if T > 1 and (rewards.stride(0) < n or dones.stride(0) < n):
+        rewards, dones, r_stride, d_stride = rewards.contiguous(), dones.contiguous(), 0, 0
+    adv, returns = t.empty((T, n), dtype=t.float32, device=self.device), t.empty((T, n), dtype=t.float32, device=self.device)
+    _check(self.lib, self.lib.tb_ppo_gae(self.kind, self._dev(), self._stream(), T, n, rewards.data_ptr(), r_stride, dones.data_ptr(), d_stride,
+                                         values.data_ptr(), last_value.data_ptr(), float(self.hp["gamma"]), float(self.hp["gae_lambda"]),
+                                         adv.data_ptr(), returns.data_ptr()), "tb_ppo_gae")
+    return adv, returns
+
+
 class FusedLearner:
     """GAE and the PPO update on the device for one policy / optimiser pair. Needs no env."""
+    _stream, _dev, _grow = current_stream, device_index, grown_workspace
 
     def __init__(self, kind, policy, opt, hp, device):
         import torch
@@ -89,12 +125,6 @@ class FusedLearner:
             off += n
         self._ws = None
 
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
-
-    def _dev(self):
-        return self.device.index if self.device.index is not None else self.torch.cuda.current_device()
-
     def _float(self, x, name):
         t = self.torch
         if x.dtype != t.float32 or x.device != self.flat.device:
@@ -115,15 +145,7 @@ class FusedLearner:
             rewards = rewards.contiguous()
         if n > 1 and dones.stride(1) != 1:
             dones = dones.contiguous()
-        r_stride = 4 * rewards.stride(0) if T > 1 and rewards.stride(0) >= n else 0
-        d_stride = dones.stride(0) if T > 1 and dones.stride(0) >= n else 0
-        if T > 1 and (rewards.stride(0) < n or dones.stride(0) < n):
-            rewards, dones, r_stride, d_stride = rewards.contiguous(), dones.contiguous(), 0, 0
-        adv, returns = t.empty((T, n), dtype=t.float32, device=self.device), t.empty((T, n), dtype=t.float32, device=self.device)
-        _check(self.lib, self.lib.tb_ppo_gae(self.kind, self._dev(), self._stream(), T, n, rewards.data_ptr(), r_stride, dones.data_ptr(), d_stride,
-                                             values.data_ptr(), last_value.data_ptr(), float(self.hp["gamma"]), float(self.hp["gae_lambda"]),
-                                             adv.data_ptr(), returns.data_ptr()), "tb_ppo_gae")
-        return adv, returns
+        return gae(self, rewards, dones, values, last_value)
 
     # ------------------------------------------------------------------------------------------------------------- update
     def _adopt_optimizer_state(self):
@@ -149,11 +171,7 @@ class FusedLearner:
         return step
 
     def workspace(self, batch):
-        need = self.lib.tb_ppo_workspace_bytes_net(self.kind, self.net, int(batch))
-        if need < 0:
-            _check(self.lib, int(need), "tb_ppo_workspace_bytes_net")
-        if self._ws is None or self._ws.numel() * 8 < need:
-            self._ws = self.torch.zeros((need + 7) // 8, dtype=self.torch.float64, device=self.device)
+        self._ws = self._grow(self._ws, self.lib.tb_ppo_workspace_bytes_net(self.kind, self.net, int(batch)), "tb_ppo_workspace_bytes_net")
         return self._ws
 
     def minibatch(self, arrays, n_rows, idx_ptr, batch, step, world=1):

@@ -19,6 +19,7 @@ import math
 import os
 import time
 
+from .learner import current_stream, device_index, gae, grown_workspace
 from .params import ENV_SWING, ENV_TENNIS, NET_MLP64, NET_NAMES, NET_TUNED
 from .rollout import RolloutBuffer
 from .stepper import ENV_IDS, BatchedEnv, StepperError, _check, load_library
@@ -297,11 +298,7 @@ class PopulationPPO:
         self._ws = None
 
     # ------------------------------------------------------------------------------------------------------------ plumbing
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
-
-    def _dev(self):
-        return self.device.index if self.device.index is not None else self.torch.cuda.current_device()
+    _stream, _dev, _grow = current_stream, device_index, grown_workspace
 
     def pack(self):
         """flat -> blobs, one batched gather"""
@@ -334,14 +331,7 @@ class PopulationPPO:
 
     def advantages(self, last_value):
         """(adv, returns) [T, N]: one tb_ppo_gae call over all envs"""
-        t = self.torch
-        T, N = self.n_steps, self.num_envs
-        rew, done = self.buf.rewards, self.buf.dones
-        adv, returns = t.empty((T, N), dtype=t.float32, device=self.device), t.empty((T, N), dtype=t.float32, device=self.device)
-        _check(self.lib, self.lib.tb_ppo_gae(self.kind, self._dev(), self._stream(), T, N, rew.data_ptr(), 4 * rew.stride(0) if T > 1 else 0, done.data_ptr(),
-                                             done.stride(0) if T > 1 else 0, self.values.data_ptr(), last_value.data_ptr(), float(self.hp["gamma"]),
-                                             float(self.hp["gae_lambda"]), adv.data_ptr(), returns.data_ptr()), "tb_ppo_gae")
-        return adv, returns
+        return gae(self, self.buf.rewards, self.buf.dones, self.values, last_value)
 
     # -------------------------------------------------------------------------------------------------------------- update
     def draw_indices(self):
@@ -353,11 +343,7 @@ class PopulationPPO:
 
     def workspace(self, batch):
         stride = int(self.lib.tb_ppo_members_workspace_stride_bytes(self.kind, self.net, int(batch)))
-        if stride < 0:
-            _check(self.lib, stride, "tb_ppo_members_workspace_stride_bytes")
-        need = stride * self.M
-        if self._ws is None or self._ws.numel() * 8 < need:
-            self._ws = self.torch.zeros(need // 8, dtype=self.torch.float64, device=self.device)
+        self._ws = self._grow(self._ws, stride if stride < 0 else stride * self.M, "tb_ppo_members_workspace_stride_bytes")
         return self._ws
 
     def minibatch(self, arrays, n_rows, idx, offset, batch, step):

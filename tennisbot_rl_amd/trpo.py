@@ -184,13 +184,6 @@ class FusedTRPO(FusedLearner):
         self.net_mask = self.mask * (~self._log_std).float()
 
     # ----------------------------------------------------------------------------------------------------------- the kernels
-    def _grow(self, ws, need, what):
-        if need < 0:
-            _check(self.lib, int(need), what)
-        if ws is None or ws.numel() * 8 < need:
-            ws = self.torch.zeros((need + 7) // 8, dtype=self.torch.float64, device=self.device)
-        return ws
-
     def fvp(self, obs, idx_ptr, m, vec, out, damping=None):
         """out = F vec + damping vec over the rows idx[0 .. m) (a device pointer to int64) of obs; returns out"""
         obs, vec = self._float(obs, "obs"), self._float(vec, "vec")

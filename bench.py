@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: env steps/sec (whole node), SwingRacket-v0 @ 4096 envs/GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W            the headline figure and nothing else: set-up, warm-up, the K timed steps, one line
+  python bench.py --gpus N --steps K --warmup W --full     ... and every other measurement and check the line can carry (below)
   N > 1: either under the launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py
   --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or plain `python bench.py --gpus N`:
   the process then IS the launcher (self_launch: it starts the N ranks as children before anything touches a GPU,
@@ -28,18 +29,24 @@ after --settle-seconds of untimed replays (a fresh process replays ~8 % slower d
 about every second time), so that the same arguments give the same outputs (--dump-outputs).
 Inputs (state, synthetic U(-1,1) actions from PCG64) are resident in HBM before the timed region.
 
-Also in that line:
+Also in that line, from the timed steps themselves (no run of their own):
   roofline     -- HBM roofline of the step kernel: algorithmic bytes per launch (267 B/env Swing,
                   263 B/env Tennisbot: DESIGN.md) / average launch duration from HIP events on the
                   launch stream; `read_only` prices the same launch with the 145 / 117 B a step READS.
-                  Launch- and ALU-latency-bound at 4096 envs; `sweep` shows 4096 and
-                  1 M envs for both envs (--sweep: the whole 4096 .. 4 M ladder).
-  cpu_baseline -- the float32 CPU oracle (a port, not PyBullet, which is not installable here) timed on
-                  this host's cores on a bounded sample of the same workload (whole episodes: the same
-                  substeps per step), and `reference_record`: the wall-clock the reference's own PyBullet
-                  training run recorded (tests/golden/ppo_swing_reference_episodes.json).
-  exchange     -- N > 1: ranks_seen, bytes per rank, rollout_ms / exchange_ms measured apart, and what
-                  of the exchange stayed exposed in the timed region.
+                  Launch- and ALU-latency-bound at 4096 envs.
+  substeps_per_agent_step -- what the timed steps ran, held against the workload's (a run that did not hold it has no value).
+
+Only with --full (runs of their own, after the timed steps or untimed before them; none of them touches the timed region):
+  sweep        -- 4096 and 1 M envs for both envs, and BASELINE configs[1] as worded (--sweep: the whole
+                  4096 .. 4 M ladder of this env and the open-loop figure); --no-sweep leaves it out.
+  cpu_baseline -- the float32 CPU oracle (a port, not PyBullet) timed on the host's cores on a bounded sample
+                  of the same workload (whole episodes: the same substeps per step; a GPU leg that ran another
+                  workload than the CPU leg has no value), and `reference_record`: the wall-clock the
+                  reference's own PyBullet training run recorded (tests/golden/ppo_swing_reference_episodes.json);
+                  --no-cpu-baseline leaves it out.
+  exchange     -- N > 1: rollout_ms / exchange_ms measured apart, what of the exchange stayed exposed in the
+                  timed region, the single all-gather timed beside the default chunked form, and what the
+                  exchange should cost over xGMI (a plain run carries ranks_seen, bytes per rank and the form).
 """
 import argparse
 import json
@@ -99,10 +106,12 @@ def parse():
     ap.add_argument("--rolling-friction", action="store_true", help="also solve the rolling-friction rows of every ball contact (TbParams.roll_*, row f3; opt-in)")
     ap.add_argument("--magnus", type=float, default=0.0, help="BASELINE configs[4] extension: Magnus coefficient k_M in F = k_M w x v (0 = the reference)")
     ap.add_argument("--spin-max", type=float, default=0.0, help="BASELINE configs[4] extension: initial ball spin ~ U(-w, w)^3 rad/s at reset (0 = the reference)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, everything else the line can carry, each a run of its own outside the timed steps: the sweep over batch sizes and envs, "
+                    "the CPU baseline, and with N > 1 the rollout and the exchange measured apart and the single all-gather timed beside the chunked form (default: the headline figure only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU work per baseline leg (1 core, all cores)")
-    ap.add_argument("--sweep", action="store_true", help="the whole N ladder (4096 .. 4 M envs) for this env instead of the default 4096 + 1 M of both envs")
-    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--sweep", action="store_true", help="with --full: the whole N ladder (4096 .. 4 M envs) for this env instead of the default 4096 + 1 M of both envs")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: leave the sweep out")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gather-chunks", type=int, default=8, help="multi-rank exchange of the rollout: C > 1 (default 8) = C step-chunks, each chunk's all-gather issued on a high-priority side stream as soon as the chunk is final, overlapped with the later chunks' steps; 1 = ONE all-gather after the rollout")
     ap.add_argument("--no-graph", action="store_true", help="launch every step from the host instead of replaying one captured hipGraph per rollout")
@@ -114,6 +123,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.sweep and not args.full:
+        ap.error("--sweep is part of --full: pass both")
     if args.warmup is None:
         args.warmup = 52 if args.env == "swing" else 1040
     return args
@@ -717,15 +728,17 @@ def main():
     start = env.get_state_words()
     warmup_run += R.settle(args.settle_seconds) * T_roll + T_roll  # (+ the one untimed rollout of prepare())
     exch = None
-    if R.collective:  # measured apart, untimed: what the rollout and the exchange cost on their own
+    if R.collective:
         seen = torch.ones(1, device=dev)
         if dist_on:
             torch.distributed.all_reduce(seen)
-        r_wall, _ = R.timed(R.steps_only, 1)
-        x_wall, _ = R.timed(R.exchange_only, 1)
-        exch = {"ranks_seen": int(seen.item()), "bytes_per_rank": int(buf.nbytes), "rollout_ms": r_wall * 1e3, "exchange_ms": x_wall * 1e3,
-                "form": "%d step-chunks, each all-gathered on a high-priority side stream while later chunks step" % R.chunks if R.chunks > 1
-                        else "ONE all-gather after the rollout"}
+        exch = {"ranks_seen": int(seen.item()), "bytes_per_rank": int(buf.nbytes)}
+        if args.full:  # measured apart, untimed: what the rollout and the exchange cost on their own
+            r_wall, _ = R.timed(R.steps_only, 1)
+            x_wall, _ = R.timed(R.exchange_only, 1)
+            exch.update(rollout_ms=r_wall * 1e3, exchange_ms=x_wall * 1e3)
+        exch["form"] = ("%d step-chunks, each all-gathered on a high-priority side stream while later chunks step" % R.chunks if R.chunks > 1
+                        else "ONE all-gather after the rollout")
     R.prepare_rest(rest)
     warmup_run += rest
     env.set_state_words(*start)
@@ -741,7 +754,7 @@ def main():
     c = env.counters()
 
     single = None
-    if R.collective and R.chunks > 1:
+    if args.full and R.collective and R.chunks > 1:
         # north_star's wording of the exchange -- "a single RCCL all-gather at the PPO collect boundary" -- timed the same way next
         # to the default form: the same rollouts, then ONE all-gather of the whole rollout buffer, nothing overlapped
         R1 = Rollouts(env, buf, torch, dist_on, R.use_graph, 1, force_collective, exchange=True)
@@ -767,7 +780,7 @@ def main():
     wall_t = torch.tensor([wall], dtype=torch.float64, device=dev)
     if dist_on:
         torch.distributed.all_reduce(wall_t, op=torch.distributed.ReduceOp.MAX)
-    # Two complete forms of the same job were timed the same way (K steps each, barrier + synchronize on both sides, max over ranks):
+    # --full with N > 1: two complete forms of the same job were timed the same way (K steps each, barrier + synchronize on both sides, max over ranks):
     # `value` is ALWAYS the default (chunked) form's, named in config.workload and in exchange.timed_form; the single all-gather's
     # figures stay beside it (pick_exchange_form: only a chunked run whose shards failed their check gives way).
     picked_single = single is not None and pick_exchange_form(float(wall_t.item()), gather_ok, float(w1_t[0].item()), bool(ok1.item() > 0.5)) == "single_all_gather"
@@ -792,7 +805,8 @@ def main():
         cadence = None if (args.contact_off or args.racket_ground or args.rolling_friction) else cadence_profile(args.env, N)
         sps = timed_substeps / (world * N * steps_timed)
         if exch is not None:
-            exch["exposed_exchange_ms"] = max(0.0, wall_max * T_roll / steps_timed * 1e3 - exch["rollout_ms"])
+            if "rollout_ms" in exch:
+                exch["exposed_exchange_ms"] = max(0.0, wall_max * T_roll / steps_timed * 1e3 - exch["rollout_ms"])
             exch["note"] = R.note
             if single is not None:
                 single["exposed_exchange_ms"] = max(0.0, single["ms_per_rollout"] - single["rollout_ms"])
@@ -838,7 +852,7 @@ def main():
                          "algorithmic_bytes_per_env_step": ab["read"] + ab["write"],
                          "read_only": {"achieved": ab["read"] * N / launch_s / 1e9, "frac": ab["read"] * N / launch_s / 1e9 / HBM_PEAK_GBS,
                                        "algorithmic_bytes_per_env_step": ab["read"], "note": "the HBM-READ roofline north_star words its 40 % target on"},
-                         "note": "latency-bound at this batch size, not bandwidth-bound (see sweep / DESIGN.md)"},
+                         "note": "latency-bound at this batch size, not bandwidth-bound (see the sweep of --full / DESIGN.md)"},
             "parity": parity_text(),
         }
         if rest:
@@ -884,7 +898,7 @@ def main():
             result["invalid"] = "; ".join(invalid)
             result["value_refused"] = result["value"]
             result["value"] = None
-    if not dist_on and not args.no_sweep and not force_collective:
+    if args.full and not dist_on and not args.no_sweep and not force_collective:
         ladder = [(args.env, n, None) for n in (4096, 32768, 262144, 1048576, 4194304)] if args.sweep else \
                  [("swing", 4096, None), ("swing", 1048576, None), ("tennis", 4096, None), ("tennis", 1048576, None),
                   ("swing", 4096, "BASELINE configs[1] as worded: racket-only dynamics, racket<->ball contact off")]
@@ -899,7 +913,7 @@ def main():
             result["sweep"] = sweep
             if args.sweep:
                 result["open_loop"] = open_loop_rate(kind, N, flags, pipeline, dev, args.seed, torch)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # a reported baseline, timed once, next to the 1-GPU figure
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # a reported baseline, timed once, next to the 1-GPU figure
         cb = cpu_baseline(args.env, N, args.cpu_seconds, args.seed, flags)
         best = cb["allcores"]
         result["cpu_baseline"] = {

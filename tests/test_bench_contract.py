@@ -1,8 +1,10 @@
-"""bench.py prints ONE JSON line with the driver's contract keys (+ roofline, cpu_baseline)."""
+"""bench.py prints ONE JSON line with the driver's contract keys (+ roofline; with --full also sweep, cpu_baseline and the
+exchange's own measurements)."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -21,7 +23,7 @@ def run_bench(*extra):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("extra", [("--cpu-seconds", "1"), ("--env", "tennis", "--no-cpu-baseline", "--no-sweep"),
+@pytest.mark.parametrize("extra", [("--full", "--cpu-seconds", "1"), ("--env", "tennis", "--no-cpu-baseline", "--no-sweep"),
                                    ("--no-graph", "--no-pipeline", "--no-cpu-baseline", "--no-sweep", "--rollout-steps", "104")])
 def test_bench_json_contract(extra):
     d = run_bench(*extra)
@@ -48,13 +50,15 @@ def test_bench_json_contract(extra):
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12 and 0 < r["frac"] < 1
     assert 0 < r["read_only"]["frac"] < r["frac"]
+    full = "--full" in extra  # the sweep and the CPU baseline are runs of their own: only --full makes them
+    assert ("cpu_baseline" in d) == (full and "--no-cpu-baseline" not in extra) and ("sweep" in d) == (full and "--no-sweep" not in extra)
     if "cpu_baseline" in d:
         c = d["cpu_baseline"]
         assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c and c["unit"] == "env steps/s"
         assert abs(c["substeps_per_agent_step"] / d["substeps_per_agent_step"] - 1) < 0.05   # GPU and CPU legs run the same workload
         rr = c["reference_record"]
         assert 100 < rr["agent_steps_per_s_collect"] < 400 and rr["agent_steps_per_s_overall"] < rr["agent_steps_per_s_collect"]
-    if "--no-sweep" not in extra:
+    if "sweep" in d:
         sw = {(e["env"], e["envs"]): e for e in d["sweep"] if "variant" not in e}
         assert set(sw) == {("swing", 4096), ("swing", 1048576), ("tennis", 4096), ("tennis", 1048576)}
         lit = [e for e in d["sweep"] if "variant" in e]  # BASELINE configs[1] as worded (racket<->ball contact off), next to the full-contact headline
@@ -64,12 +68,54 @@ def test_bench_json_contract(extra):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean():
+    """`bench.py --gpus 1 --steps K --warmup W` does what its headline figure needs and nothing else: the contract's keys, the
+    roofline of the timed steps, no sweep, no CPU baseline, no open-loop figure -- and at most 30 s of the whole run, from the
+    start of the process to its exit, lie outside its K + W steps"""
+    t0 = time.perf_counter()
+    d = run_bench("--gpus", "1")
+    whole = time.perf_counter() - t0
+    for k, t in REQUIRED.items():
+        assert k in d and (isinstance(d[k], t) or (t is float and isinstance(d[k], int))), k
+    assert d["n_gpus"] == 1 and d["steps"] == 52 == d["steps_timed"] and d["warmup"] == 20 and "invalid" not in d
+    assert d["metric"] == "env steps/sec (whole node), SwingRacket-v0 @4096 envs/GPU" and d["unit"] == "env steps/s" and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert abs(d["substeps_per_agent_step"] / 5.09 - 1) < 0.05
+    assert not {"sweep", "cpu_baseline", "open_loop", "exchange"} & set(d)
+    outside = whole - (52 + 20) * d["ms_per_step"] * 1e-3
+    print("whole run %.1f s, outside its steps %.1f s" % (whole, outside))
+    assert outside <= 30.0, outside
+
+
+def test_bench_full_is_an_option_off_by_default(monkeypatch, capsys):
+    """--full is there and off by default; --sweep, --no-sweep and --no-cpu-baseline shape what --full runs, and --sweep alone
+    is refused instead of being dropped in silence"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert a.full is False and a.gpus == 1 and a.steps == 20 and a.warmup == 5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--sweep", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.sweep is True and a.no_cpu_baseline is True and a.no_sweep is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-sweep", "--no-cpu-baseline"])  # what older command lines pass: still accepted
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--sweep"])
+    with pytest.raises(SystemExit) as exc:
+        bench.parse()
+    assert exc.value.code == 2 and "--full" in capsys.readouterr().err
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("chunks", ["8", "1"])
 def test_bench_exchange_forms_with_one_rank(chunks):
     """the multi-rank exchange path rehearsed with a single rank (TB_BENCH_FORCE_COLLECTIVE=1: RCCL is initialised and every
-    collective is issued): the chunked, overlapped form (default) and the single all-gather, with the diagnostics an N > 1 line carries"""
+    collective is issued): the chunked, overlapped form (default) and the single all-gather, with the diagnostics an N > 1 line carries
+    under --full"""
     env = dict(os.environ, TB_BENCH_FORCE_COLLECTIVE="1", TB_BENCH_FAKE_GATHER_US="1000")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "208", "--rollout-steps", "208", "--warmup", "26", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "208", "--rollout-steps", "208", "--warmup", "26", "--full", "--no-cpu-baseline",
                           "--gather-chunks", chunks], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
@@ -77,6 +123,22 @@ def test_bench_exchange_forms_with_one_rank(chunks):
     assert d["value"] > 0 and "invalid" not in d and "all-gather" in w
     assert x["ranks_seen"] == 1 and x["bytes_per_rank"] >= 208 * 4096 * 53 and x["rollout_ms"] > 0 and x["exchange_ms"] > 0.9 and x["exposed_exchange_ms"] >= 0
     assert ("step-chunks" in x["form"]) == (chunks == "8") and not x["note"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_exchange_with_one_rank():
+    """the same rehearsal without --full: the rollouts are exchanged in the timed steps as before, and the line says in which form,
+    but neither the rollout and the exchange are measured apart nor is the single all-gather timed beside the chunked form"""
+    env = dict(os.environ, TB_BENCH_FORCE_COLLECTIVE="1")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "208", "--rollout-steps", "208", "--warmup", "26", "--settle-seconds", "0.2"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])  # (RCCL prints its version banner first)
+    x = d["exchange"]
+    assert d["value"] > 0 and "invalid" not in d and "all-gathered (RCCL) in 8 step-chunks" in d["config"]["workload"]
+    assert x["ranks_seen"] == 1 and x["bytes_per_rank"] >= 208 * 4096 * 53 and "step-chunks" in x["form"] and not x["note"]
+    assert not {"rollout_ms", "exchange_ms", "exposed_exchange_ms", "single_all_gather", "timed_form", "predicted"} & set(x)
+    assert "sweep" not in d and "cpu_baseline" not in d
 
 
 def test_bench_launches_its_own_ranks_dry():
@@ -112,7 +174,7 @@ def test_bench_launches_its_own_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["TB_BENCH_REHEARSAL"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "208", "--rollout-steps", "208", "--warmup", "26",
-                          "--settle-seconds", "0.2"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--settle-seconds", "0.2", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout

@@ -14,10 +14,10 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd $R || exit 1
 if [ "$PART" = "a" ]; then
-  python3 bench.py --steps 20 --warmup 5 > $OUT/bench_swing4096_driver_line.json 2> $OUT/bench_driver.err || exit 1
-  python3 bench.py --sweep > $OUT/bench_swing4096_sweep.json 2> $OUT/bench_swing.err || exit 1
-  python3 bench.py --env tennis --sweep --no-cpu-baseline > $OUT/bench_tennis4096_sweep.json 2> $OUT/bench_tennis.err || exit 1
-  TB_BENCH_REHEARSAL=1 python3 bench.py --gpus 2 --steps 20 --warmup 5 > $OUT/bench_two_rank_rehearsal_one_gpu.json 2> $OUT/bench_two_rank.err || exit 1
+  python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_swing4096_driver_line.json 2> $OUT/bench_driver.err || exit 1
+  python3 bench.py --full --sweep > $OUT/bench_swing4096_sweep.json 2> $OUT/bench_swing.err || exit 1
+  python3 bench.py --env tennis --full --sweep --no-cpu-baseline > $OUT/bench_tennis4096_sweep.json 2> $OUT/bench_tennis.err || exit 1
+  TB_BENCH_REHEARSAL=1 python3 bench.py --gpus 2 --steps 20 --warmup 5 --full > $OUT/bench_two_rank_rehearsal_one_gpu.json 2> $OUT/bench_two_rank.err || exit 1
   cd /tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o swing4096 -- python3 $R/bench.py --no-cpu-baseline --no-sweep > $OUT/prof_swing4096.log 2>&1 || exit 1
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o swing4096_contact_off -- python3 $R/bench.py --contact-off --no-cpu-baseline --no-sweep > $OUT/prof_swing4096_contact_off.log 2>&1 || exit 1

@@ -57,19 +57,113 @@ TB_DEV f32x4 ppo_transpose(const f32x4 c, float* buf, int lane) {
   return t;
 }
 
-// one nn.Linear of a tower for this lane: forward fragments, transposed fragments, bias, and the gradient accumulators
-// WB_REGS = false (the tuned net's extractor output layer and third tower layer: six layers' operands do not fit in 512 registers): the transposed fragments
-// live in the wave's own LDS instead (stage_wb / backward_input_lds)
-template <int IN, int OUT, bool FIRST, bool WB_REGS = true>
-struct PpoLayer {
+// ---------------------------------------------------------------------------------------------------------- the shared pieces
+// Blocks that the tile kernels of this file and of tb_trpo.hpp used to repeat, defined once. A kernel that calls one computes the
+// same float operations in the same order as every other caller.
+//   piece                        called by                                        order and precision
+//   PpoForward                   PpoLayer (so every tower), TrpoFwd               z = bias, then += W x chunk by chunk, c ascending: fp32 MFMA
+//   ppo_row, ppo_tile            tb_trpo_fvp_kernel, tb_trpo_search_kernel        entry min(i, B - 1) of the index vector, clamped to
+//                                (ppo_row alone: tb_ppo_adv_stats_kernel)         [0, n_rows); a slot past the batch repeats the last
+//                                                                                 entry and is masked by `valid`
+//   ppo_adv_norm                 tb_trpo_search_kernel                            the 64 float64 pairs in block order 0 .. 63; mean, variance
+//                                                                                 and sqrt in float64; then (float)mean, (float)std + 1e-8f
+//   ppo_backward (_head, _step,  tb_trpo_fvp_kernel                               dz = dh (1 - h^2); dh_in = W^T dz on the MFMA, (t, r)
+//   _first)                                                                       ascending; dW += dz^T h_in over the tile's rows, 4 per MFMA;
+//                                                                                 db as in PpoLayer::accumulate. Layers from the head down
+//   ppo_partial_run / _total     tb_ppo_reduce_kernel, tb_trpo_fvp_reduce_kernel  float64: four runs of n_part / 4 partial vectors in
+//                                                                                 order, then (0 + 1) + (2 + 3)
+// ppo_tower and ppo_tuned_tower do NOT call ppo_tile, ppo_adv_norm or ppo_backward, nor tb_ppo_reduce_tuned_kernel the partial sum:
+// they spell the same operations out themselves (see ppo_tower), and tests/test_gpu_learner_bits.py holds them and the callers above
+// to one set of recorded bits.
+
+// the clamped row of entry min(i, B - 1) of an index vector
+TB_DEV long long ppo_row(const long long* idx, int i, int B, long long n_rows) {
+  const long long row = idx[i < B ? i : B - 1];
+  return row < 0 ? 0 : row >= n_rows ? n_rows - 1 : row;
+}
+
+// the 16 rows i0 .. i0 + 15 of a tile for this lane (g, e): slot e's row (returned; `valid`: inside the batch) and its observation
+// as the first layer's k-chunks x0[c] = obs[row][4 c + g] ...
+template <int O, int NC>
+TB_DEV long long ppo_tile(const float* obs, const long long* idx, int i0, int B, long long n_rows, int lane, bool& valid, float (&x0)[NC]) {
+  const int g = lane >> 4, e = lane & 15;
+  valid = i0 + e < B;
+  const long long row = ppo_row(idx, i0 + e, B, n_rows);
+  const float* orow = obs + (size_t)row * O;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) x0[c] = 4 * c + g < O ? orow[4 * c + g] : 0.0f;
+  return row;
+}
+// ... and, for a backward pass, the observations in ppo_transpose's layout: obsT[0][c] = feature e of slot 4 c + g's row
+template <int O, int NC>
+TB_DEV long long ppo_tile(const float* obs, const long long* idx, int i0, int B, long long n_rows, int lane, bool& valid, float (&x0)[NC], f32x4 (&obsT)[1]) {
+  const int g = lane >> 4, e = lane & 15;
+  const long long row = ppo_tile<O>(obs, idx, i0, B, n_rows, lane, valid, x0);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) obsT[0][c] = e < O ? obs[(size_t)ppo_row(idx, i0 + 4 * c + g, B, n_rows) * O + e] : 0.0f;
+  return row;
+}
+
+// the minibatch's advantage mean and unbiased std + 1e-8 from tb_ppo_adv_stats_kernel's float64 sums
+struct PpoAdvNorm { float mean, den; };
+TB_DEV PpoAdvNorm ppo_adv_norm(const double* adv_sums, int B) {
+  double sx = 0.0, sq = 0.0;
+  for (int k = 0; k < TB_PPO_STAT_BLOCKS; ++k) { sx += adv_sums[2 * k]; sq += adv_sums[2 * k + 1]; }
+  const double mean = sx / (double)B, var = (sq - sx * mean) / (double)(B - 1);
+  return {(float)mean, (float)sqrt(var > 0.0 ? var : 0.0) + 1e-8f};
+}
+
+// The float64 sum over the n_part partial vectors of slot p by a 4 x 64 workgroup: thread (q, j) adds quarter q in order
+// (ppo_partial_run) into s_sum[q][j]; after a barrier the slot's total is (0 + 1) + (2 + 3) (ppo_partial_total).
+TB_DEV double ppo_partial_run(const float* partials, size_t stride, int p, int n_part, int q) {
+  const int per = (n_part + 3) / 4, lo = q * per, hi = lo + per < n_part ? lo + per : n_part;
+  double s = 0.0;
+  for (int k = lo; k < hi; ++k) s += (double)partials[(size_t)k * stride + p];
+  return s;
+}
+TB_DEV double ppo_partial_total(const double (&s_sum)[4][64], int j) { return (s_sum[0][j] + s_sum[1][j]) + (s_sum[2][j] + s_sum[3][j]); }
+
+// the forward half of one nn.Linear for this lane: forward fragments and bias
+template <int IN, int OUT, bool FIRST>
+struct PpoForward {
   // (a later layer's input is whole accumulator tiles: IN is a multiple of 16, or -- the tuned net's feature -- narrower than one tile,
   //  the tile's other rows being exact zeros that meet zero weights)
   static constexpr int NT = (OUT + 15) / 16, NTI = (IN + 15) / 16, NC = FIRST ? (IN + 3) / 4 : NTI * 4;
   static_assert(FIRST || IN % 16 == 0 || IN < 16, "hidden widths are multiples of 16");
   float wf[NT * NC];                   // (t, c): W[16 t + j][k(c, g)], k as in tb_policy.hpp
+  f32x4 bias[NT];
+  // z = bias + W x. The first layer takes its k-chunks as floats, the later ones the previous layer's C/D registers
+  TB_DEV void forward_first(const float (&x)[NC], f32x4 (&z)[NT]) const {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) z[t] = bias[t];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t * NC + c], x[c], z[t], 0, 0, 0);
+    }
+  }
+  TB_DEV void forward(const f32x4 (&h)[NTI], f32x4 (&z)[NT]) const {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) z[t] = bias[t];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t * NC + c], h[c >> 2][c & 3], z[t], 0, 0, 0);
+    }
+  }
+};
+
+// one nn.Linear of a tower for this lane: PpoForward, the transposed fragments, and the gradient accumulators
+// WB_REGS = false (the tuned net's extractor output layer and third tower layer: six layers' operands do not fit in 512 registers): the transposed fragments
+// live in the wave's own LDS instead (stage_wb / backward_input_lds)
+template <int IN, int OUT, bool FIRST, bool WB_REGS = true>
+struct PpoLayer : PpoForward<IN, OUT, FIRST> {
+  using Fwd = PpoForward<IN, OUT, FIRST>;
+  using Fwd::wf;
+  using Fwd::bias;
+  static constexpr int NT = Fwd::NT, NTI = Fwd::NTI, NC = Fwd::NC;
   static constexpr int NWB = NTI * NT * 4;
   float wb[FIRST || !WB_REGS ? 1 : NWB];  // (ti, t, r): W[16 t + 4 g + r][16 ti + j]
-  f32x4 bias[NT];
   f32x4 dw[NT * NTI];                  // (t, ti), C/D layout: dW[16 t + 4 g + r][16 ti + j]
   float db[NT];                        // feature 16 t + j, summed over the rows = g (mod 4) so far
 
@@ -130,25 +224,6 @@ struct PpoLayer {
 #pragma unroll
         for (int ti = 0; ti < NTI; ++ti) dh[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[((ti * NT + t) * 4 + r) * 64 + lane], dz[t][r], dh[ti], 0, 0, 0);
       }
-    }
-  }
-  // z = bias + W x. The first layer takes its k-chunks as floats, the later ones the previous layer's C/D registers
-  TB_DEV void forward_first(const float (&x)[NC], f32x4 (&z)[NT]) const {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) z[t] = bias[t];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t * NC + c], x[c], z[t], 0, 0, 0);
-    }
-  }
-  TB_DEV void forward(const f32x4 (&h)[NTI], f32x4 (&z)[NT]) const {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) z[t] = bias[t];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t * NC + c], h[c >> 2][c & 3], z[t], 0, 0, 0);
     }
   }
   // dh = W^T dz, in the C/D layout of this layer's input
@@ -221,6 +296,51 @@ TB_DEV void ppo_transpose_all(const f32x4 (&c)[NTILES], f32x4 (&t)[NTILES], floa
   for (int k = 0; k < NTILES; ++k) t[k] = ppo_transpose(c[k], buf + (k & 1) * 256, lane);
 }
 
+// The backward pass of one tile of a tanh tower, layer by layer from the head down. l: a PpoLayer; dz: the loss's derivative with
+// respect to its output; h_in / dh_in: its input and the derivative with respect to it (C/D layout); buf: ppo_transpose's 512 floats.
+// the head (no activation behind it; dz = dout): dh_in = W^T dz; dW += dz^T h_in; db += dz^T 1
+template <class LAYER>
+TB_DEV void ppo_backward_head(LAYER& l, const f32x4 (&dz)[1], const f32x4 (&h_in)[LAYER::NTI], f32x4 (&dh_in)[LAYER::NTI], float* buf, int lane) {
+  f32x4 dzT[1], hT[LAYER::NTI];
+  ppo_transpose_all(dz, dzT, buf, lane);
+  l.backward_input(dz, dh_in);
+  ppo_transpose_all(h_in, hT, buf, lane);
+  l.accumulate(dzT, hT);
+}
+// a hidden layer with output h = tanh(z): dz = dh (1 - h^2), then the same three
+template <class LAYER>
+TB_DEV void ppo_backward_step(LAYER& l, const f32x4 (&dh)[LAYER::NT], const f32x4 (&h)[LAYER::NT], const f32x4 (&h_in)[LAYER::NTI], f32x4 (&dh_in)[LAYER::NTI],
+                              float* buf, int lane) {
+  f32x4 dz[LAYER::NT], dzT[LAYER::NT], hT[LAYER::NTI];
+  ppo_dtanh(dh, h, dz);
+  l.backward_input(dz, dh_in);
+  ppo_transpose_all(dz, dzT, buf, lane); ppo_transpose_all(h_in, hT, buf, lane);
+  l.accumulate(dzT, hT);
+}
+// the first layer: nothing to send further back, and its input arrives transposed (ppo_tile's obsT)
+template <class LAYER>
+TB_DEV void ppo_backward_first(LAYER& l, const f32x4 (&dh)[LAYER::NT], const f32x4 (&h)[LAYER::NT], const f32x4 (&obsT)[1], float* buf, int lane) {
+  f32x4 dz[LAYER::NT], dzT[LAYER::NT];
+  ppo_dtanh(dh, h, dz);
+  ppo_transpose_all(dz, dzT, buf, lane);
+  l.accumulate(dzT, obsT);
+}
+// NH hidden layers (l2 and h2 are untouched when NH == 2): head, hidden layers, first layer
+template <int NH, class L0, class L1, class L2, class LH>
+TB_DEV void ppo_backward(L0& l0, L1& l1, L2& l2, LH& lh, const f32x4 (&dout)[1], const f32x4 (&obsT)[1], const f32x4 (&h0)[L0::NT], const f32x4 (&h1)[L1::NT],
+                         const f32x4 (&h2)[L2::NT], float* buf, int lane) {
+  f32x4 dh1[L1::NT], dh0[L0::NT];
+  if constexpr (NH == 3) {
+    f32x4 dh2[L2::NT];
+    ppo_backward_head(lh, dout, h2, dh2, buf, lane);
+    ppo_backward_step(l2, dh2, h2, h1, dh1, buf, lane);
+  } else {
+    ppo_backward_head(lh, dout, h1, dh1, buf, lane);
+  }
+  ppo_backward_step(l1, dh1, h1, h0, dh0, buf, lane);
+  ppo_backward_first(l0, dh0, h0, obsT, buf, lane);
+}
+
 struct PpoGradArgs {
   const float* obs;       // [N][O]
   const float* act;       // [N][A] the unclipped samples
@@ -264,9 +384,7 @@ __global__ __launch_bounds__(256) void tb_ppo_adv_stats_kernel(const float* adv,
   __shared__ double s_x[256], s_q[256];
   double x = 0.0, q = 0.0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < batch; i += TB_PPO_STAT_BLOCKS * 256) {
-    long long row = idx[i];
-    row = row < 0 ? 0 : row >= n_rows ? n_rows - 1 : row;
-    const double a = (double)adv[row];
+    const double a = (double)adv[ppo_row(idx, i, batch, n_rows)];
     x += a; q += a * a;
   }
   s_x[threadIdx.x] = x; s_q[threadIdx.x] = q;
@@ -278,7 +396,11 @@ __global__ __launch_bounds__(256) void tb_ppo_adv_stats_kernel(const float* adv,
   if (threadIdx.x == 0) { out[2 * blockIdx.x] = s_x[0]; out[2 * blockIdx.x + 1] = s_q[0]; }
 }
 
-// one tower of one half share. PI: the policy tower (logp, ratio, clipped surrogate, d log_std); else the value tower
+// one tower of one half share. PI: the policy tower (logp, ratio, clipped surrogate, d log_std); else the value tower.
+// This tower and ppo_tuned_tower keep their own text of the clamp, the tile gather, the advantage norm and the backward chain: the
+// max-ILP scheduler orders these two 500-register waves differently for any change of their source. With ppo_tile, a shared loss
+// head and ppo_backward tb_ppo_grad_kernel<SWING> ran 2.6 % slower, with ppo_row alone both towers' streams already differ; as they
+// stand all eight gradient kernels compile to the parent's instruction stream ("Shared learner pieces").
 template <int KIND, bool PI, int NET = TB_NET_DEFAULT>
 TB_DEV void ppo_tower(const PpoGradArgs& a, float* buf, int lane, int first, float* part) {
   using L = PpoLayout<KIND, NET>;
@@ -457,7 +579,7 @@ __global__ __launch_bounds__(256) void tb_ppo_grad_kernel(PpoGradArgs a, MEMBERS
   else ppo_tower<KIND, false, NET>(a, s_buf + wave * 512, lane, first, part);
 }
 
-// gradient[p] = sum of the partials in a fixed order (float64: four runs of n_part / 4, then (0 + 1) + (2 + 3)); log_std's
+// gradient[p] = sum of the partials in a fixed order (ppo_partial_run / ppo_partial_total); log_std's
 // entropy term; the minibatch's three statistics. 64 parameters per block. value_only: grad's policy slots (log_std, PI,
 // PI_HEAD) are left as they are.
 // the member's partials, parameter and gradient rows, statistics row, ent_coef
@@ -478,15 +600,10 @@ __global__ __launch_bounds__(256) void tb_ppo_reduce_kernel(const float* partial
   using L = PpoLayout<KIND, NET>;
   __shared__ double s_sum[4][64];
   const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;
-  double s = 0.0;
-  if (p < L::STRIDE) {
-    const int per = (n_part + 3) / 4, lo = q * per, hi = lo + per < n_part ? lo + per : n_part;
-    for (int k = lo; k < hi; ++k) s += (double)partials[(size_t)k * L::STRIDE + p];
-  }
-  s_sum[q][j] = s;
+  s_sum[q][j] = p < L::STRIDE ? ppo_partial_run(partials, L::STRIDE, p, n_part, q) : 0.0;
   __syncthreads();
   if (q == 0 && p < L::STRIDE) {
-    const double total = (s_sum[0][j] + s_sum[1][j]) + (s_sum[2][j] + s_sum[3][j]);
+    const double total = ppo_partial_total(s_sum, j);
     if (p < L::P) {
       const bool value_slot = (p >= L::VF && p < L::PI_HEAD) || p >= L::VF_HEAD;
       if (!value_only || value_slot) grad[p] = p < L::A ? (float)total - ent_coef : (float)total;
@@ -780,7 +897,9 @@ __global__ __launch_bounds__(256) void tb_ppo_grad_tuned_kernel(PpoGradArgs a, M
 }
 
 // tb_ppo_reduce_kernel for the tuned net: the same fixed-order float64 sums per slot; an extractor slot is (the sum of the pi
-// waves' shares) + (the sum of the vf waves' shares, from the partials' second extractor region)
+// waves' shares) + (the sum of the vf waves' shares, from the partials' second extractor region). Both runs of a thread sit under
+// one test and one barrier; written with ppo_partial_run / ppo_partial_total the kernel compiles to another stream, so it keeps
+// its own lines (the operations are those two functions')
 template <class... MEMBERS>
 __global__ __launch_bounds__(256) void tb_ppo_reduce_tuned_kernel(const float* partials, int n_part, int batch, const float* params, float ent_coef, float* grad,
                                                                   float* stats, MEMBERS... members) {

@@ -1,6 +1,6 @@
 // The TRPO learner's two kernels (tb_trpo_fvp, tb_trpo_search), built from the pieces of tb_learner.hpp (PpoLayout, PpoLayer,
-// ppo_transpose, ppo_tanh / ppo_dtanh, tb_ppo_adv_stats_kernel), and tb_trpo_returns' four at the end of the file, which need none
-// of them. Device code only; included by tb_stepper.hip after tb_learner.hpp.
+// ppo_transpose, ppo_tanh / ppo_dtanh, tb_ppo_adv_stats_kernel, and its shared pieces ppo_tile, ppo_adv_norm, ppo_backward,
+// ppo_partial_run / ppo_partial_total and PpoForward), and tb_trpo_returns' four at the end of the file, which need none of them. Device code only; included by tb_stepper.hip after tb_learner.hpp.
 // The rule is the reference's agent.py (TRPOAgent; cited by line in tennisbot_rl_amd/trpo.py). Policy tower only: the LOG_STD,
 // PI and PI_HEAD slots of the flat parameter vector. Every vector (v, F v, the search direction) is a full flat vector of
 // PpoLayout::P floats; the value slots are ignored on input and written as 0. Instantiated per (kind, net) like the learner's kernels:
@@ -9,14 +9,14 @@
 // tb_trpo_fvp_kernel: F v = (1/m) sum_rows J^T diag(sigma^-2) J v over m rows of an index vector, J = d mean / d theta -- the
 // Hessian of KL(old || new) at theta, which agent.py:144-167 obtains by double backprop (second-order and cross terms vanish at
 // the expansion point). A workgroup of two waves takes TB_PPO_SHARE = 256 consecutive entries of the index vector, a wave one
-// half, 16 rows per tile, as ppo_tower does; waves never talk to each other. Per tile:
+// half, 16 rows per tile (ppo_tile), the shares of ppo_tower; waves never talk to each other. Per tile:
 //   forward          h_l = tanh(W_l h_(l-1) + b_l)
 //   tangent forward  zdot_l = V_l h_(l-1) + vb_l + W_l hdot_(l-1),  hdot_l = (1 - h_l^2) zdot_l;  mudot = V_H h + vb_H + W_H hdot
 //                    (V, vb: v's slots of the layer, as weight fragments of their own beside W's. W's forward and transposed
 //                    fragments and the dW accumulators fill the 512 registers of a lone wave, so V's fragments live in LDS:
 //                    fragment f of lane l at [f][l], written and read by that lane alone -- no bank conflict, no barrier)
 //   head             dout = sigma^-2 mudot
-//   backward         PpoLayer::backward_input / accumulate, exactly the path of ppo_tower
+//   backward         ppo_backward: head, hidden layers, first layer (the operations of ppo_tower's own chain)
 // Each wave writes its dW / db sums (an fp32 chain of 128 rows at the most) as one partial vector; tb_trpo_fvp_reduce_kernel
 // adds the partials per parameter in float64 in a fixed order, divides by m and adds the damping. No float atomics.
 //
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(128) void tb_trpo_fvp_kernel(const TrpoFvpArgs a) {
   const int first = blockIdx.x * TB_PPO_SHARE + half * TB_PPO_HALF;
   float* part = a.partials + (size_t)(2 * blockIdx.x + half) * L::P;
   float* buf = s_buf + half * 512;
-  const int g = lane >> 4, e = lane & 15, B = a.m;
+  const int g = lane >> 4, B = a.m;
   const float* body = a.params + L::PI;
   const float* head = a.params + L::PI_HEAD;
   const float* vbody = a.vec + L::PI;
@@ -130,21 +130,10 @@ __global__ __launch_bounds__(128) void tb_trpo_fvp_kernel(const TrpoFvpArgs a) {
   for (int r = 0; r < 4; ++r) inv_var[r] = 4 * g + r < NA ? expf(-2.0f * a.params[L::LOG_STD + 4 * g + r]) : 0.0f;
 
   for (int i0 = first; i0 < first + TB_PPO_HALF && i0 < B; i0 += 16) {
-    const bool valid = i0 + e < B;
-    long long row = a.idx[valid ? i0 + e : B - 1];
-    row = row < 0 ? 0 : row >= a.n_rows ? a.n_rows - 1 : row;
+    bool valid;
     float x0[L0::NC];
-    const float* orow = a.obs + (size_t)row * O;
-#pragma unroll
-    for (int c = 0; c < L0::NC; ++c) x0[c] = 4 * c + g < O ? orow[4 * c + g] : 0.0f;
     f32x4 obsT[1];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int s = i0 + 4 * c + g;
-      long long rc = a.idx[s < B ? s : B - 1];
-      rc = rc < 0 ? 0 : rc >= a.n_rows ? a.n_rows - 1 : rc;
-      obsT[0][c] = e < O ? a.obs[(size_t)rc * O + e] : 0.0f;
-    }
+    ppo_tile<O>(a.obs, a.idx, i0, B, a.n_rows, lane, valid, x0, obsT);
     // forward and tangent forward, layer by layer
     f32x4 z0[L0::NT], h0[L0::NT], hd0[L0::NT], z1[L1::NT], h1[L1::NT], hd1[L1::NT], z2[L2::NT], h2[L2::NT], hd2[L2::NT], mud[1];
     l0.forward_first(x0, z0); ppo_tanh(z0, h0);
@@ -161,38 +150,7 @@ __global__ __launch_bounds__(128) void tb_trpo_fvp_kernel(const TrpoFvpArgs a) {
     f32x4 dout[1];
 #pragma unroll
     for (int r = 0; r < 4; ++r) dout[0][r] = (valid && 4 * g + r < NA) ? mud[0][r] * inv_var[r] : 0.0f;
-    // backward: the path of ppo_tower
-    f32x4 doutT[1];
-    ppo_transpose_all(dout, doutT, buf, lane);
-    if constexpr (NH == 3) {
-      f32x4 dh2[L2::NT], dz2[L2::NT], dz2T[L2::NT], h2T[L2::NT], dh1[L1::NT], dz1[L1::NT], dz1T[L1::NT], h1T[L1::NT], dh0[L0::NT], dz0[L0::NT], dz0T[L0::NT], h0T[L0::NT];
-      lh.backward_input(dout, dh2);
-      ppo_transpose_all(h2, h2T, buf, lane);
-      lh.accumulate(doutT, h2T);
-      ppo_dtanh(dh2, h2, dz2);
-      l2.backward_input(dz2, dh1);
-      ppo_transpose_all(dz2, dz2T, buf, lane); ppo_transpose_all(h1, h1T, buf, lane);
-      l2.accumulate(dz2T, h1T);
-      ppo_dtanh(dh1, h1, dz1);
-      l1.backward_input(dz1, dh0);
-      ppo_transpose_all(dz1, dz1T, buf, lane); ppo_transpose_all(h0, h0T, buf, lane);
-      l1.accumulate(dz1T, h0T);
-      ppo_dtanh(dh0, h0, dz0);
-      ppo_transpose_all(dz0, dz0T, buf, lane);
-      l0.accumulate(dz0T, obsT);
-    } else {
-      f32x4 dh1[L1::NT], dz1[L1::NT], dz1T[L1::NT], h1T[L1::NT], dh0[L0::NT], dz0[L0::NT], dz0T[L0::NT], h0T[L0::NT];
-      lh.backward_input(dout, dh1);
-      ppo_transpose_all(h1, h1T, buf, lane);
-      lh.accumulate(doutT, h1T);
-      ppo_dtanh(dh1, h1, dz1);
-      l1.backward_input(dz1, dh0);
-      ppo_transpose_all(dz1, dz1T, buf, lane); ppo_transpose_all(h0, h0T, buf, lane);
-      l1.accumulate(dz1T, h0T);
-      ppo_dtanh(dh0, h0, dz0);
-      ppo_transpose_all(dz0, dz0T, buf, lane);
-      l0.accumulate(dz0T, obsT);
-    }
+    ppo_backward<NH>(l0, l1, l2, lh, dout, obsT, h0, h1, h2, buf, lane);
   }
   float* gbody = part + L::PI;
   float* ghead = part + L::PI_HEAD;
@@ -202,8 +160,8 @@ __global__ __launch_bounds__(128) void tb_trpo_fvp_kernel(const TrpoFvpArgs a) {
   lh.store(ghead, ghead + NA * N::LAST, lane);
 }
 
-// out[p] = (float)(sum of the partials / m) + damping v[p] on the network's policy slots (float64 sum in the fixed order of
-// tb_ppo_reduce_kernel; the two float32 roundings of the damping term are separate: fvp(d) == fvp(0) + fl(d v) bit for bit),
+// out[p] = (float)(sum of the partials / m) + damping v[p] on the network's policy slots (ppo_partial_run / ppo_partial_total's float64 sum;
+// the two float32 roundings of the damping term are separate: fvp(d) == fvp(0) + fl(d v) bit for bit),
 // 2 v[p] + damping v[p] on log_std (the Gaussian's own Fisher block: exact), 0 on the value slots. 64 parameters per block.
 template <int KIND, int NET = TB_NET_DEFAULT>
 __global__ __launch_bounds__(256) void tb_trpo_fvp_reduce_kernel(const float* partials, int n_part, int m, const float* vec, float damping, float* out) {
@@ -211,15 +169,10 @@ __global__ __launch_bounds__(256) void tb_trpo_fvp_reduce_kernel(const float* pa
   __shared__ double s_sum[4][64];
   const int j = threadIdx.x & 63, q = threadIdx.x >> 6, p = blockIdx.x * 64 + j;
   const bool net = (p >= L::PI && p < L::VF) || (p >= L::PI_HEAD && p < L::VF_HEAD);
-  double s = 0.0;
-  if (net) {
-    const int per = (n_part + 3) / 4, lo = q * per, hi = lo + per < n_part ? lo + per : n_part;
-    for (int k = lo; k < hi; ++k) s += (double)partials[(size_t)k * L::P + p];
-  }
-  s_sum[q][j] = s;
+  s_sum[q][j] = net ? ppo_partial_run(partials, L::P, p, n_part, q) : 0.0;
   __syncthreads();
   if (q == 0 && p < L::P) {
-    const double total = (s_sum[0][j] + s_sum[1][j]) + (s_sum[2][j] + s_sum[3][j]);
+    const double total = ppo_partial_total(s_sum, j);
     const float v = vec[p];
     out[p] = net ? (float)(total / (double)m) + damping * v : p < L::A ? 2.0f * v + damping * v : 0.0f;
   }
@@ -228,10 +181,12 @@ __global__ __launch_bounds__(256) void tb_trpo_fvp_reduce_kernel(const float* pa
 // --------------------------------------------------------------------------------------------------------------- line search
 // forward fragments of theta + step * direction for one nn.Linear
 template <int IN, int OUT, bool FIRST>
-struct TrpoFwd {
-  static constexpr int NT = (OUT + 15) / 16, NTI = (IN + 15) / 16, NC = FIRST ? (IN + 3) / 4 : IN / 4;
-  float wf[NT * NC];
-  f32x4 bias[NT];
+struct TrpoFwd : PpoForward<IN, OUT, FIRST> {
+  using Fwd = PpoForward<IN, OUT, FIRST>;
+  using Fwd::wf;
+  using Fwd::bias;
+  static constexpr int NT = Fwd::NT, NC = Fwd::NC;
+  static_assert(FIRST || IN % 16 == 0, "the search is built for hidden widths that are whole tiles: NC = IN / 4");
   TB_DEV void load(const float* W, const float* b, const float* DW, const float* Db, float step, int lane) {
     const int g = lane >> 4, j = lane & 15;
 #pragma unroll
@@ -246,24 +201,6 @@ struct TrpoFwd {
         const int o = 16 * t + 4 * g + r;
         bias[t][r] = o < OUT ? b[o] + step * Db[o] : 0.0f;
       }
-    }
-  }
-  TB_DEV void forward_first(const float (&x)[NC], f32x4 (&z)[NT]) const {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) z[t] = bias[t];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t * NC + c], x[c], z[t], 0, 0, 0);
-    }
-  }
-  TB_DEV void forward(const f32x4 (&h)[NTI], f32x4 (&z)[NT]) const {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) z[t] = bias[t];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t * NC + c], h[c >> 2][c & 3], z[t], 0, 0, 0);
     }
   }
 };
@@ -323,16 +260,13 @@ __global__ __launch_bounds__(256) void tb_trpo_search_kernel(const TrpoSearchArg
   using L = PpoLayout<KIND, NET>;
   constexpr int O = L::O, NA = L::A;
   __shared__ double s_part[4][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, e = lane & 15, B = a.batch;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, B = a.batch;
   const int first = blockIdx.x * TB_TRPO_SEARCH_SHARE + wave * (TB_TRPO_SEARCH_SHARE / 4);
   const float step = a.steps[blockIdx.y];
   TrpoMean<KIND, NET> cur, cand;
   cur.load(a.params, a.dir, 0.0f, lane);
   cand.load(a.params, a.dir, step, lane);
-  double sx = 0.0, sq = 0.0;
-  for (int k = 0; k < TB_PPO_STAT_BLOCKS; ++k) { sx += a.adv_sums[2 * k]; sq += a.adv_sums[2 * k + 1]; }
-  const double mean = sx / (double)B, var = (sq - sx * mean) / (double)(B - 1);
-  const float adv_mean = (float)mean, adv_den = (float)sqrt(var > 0.0 ? var : 0.0) + 1e-8f;
+  const PpoAdvNorm norm = ppo_adv_norm(a.adv_sums, B);
   float dls[4], ls2[4], inv_std2[4], e2[4], inv_var2[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -346,13 +280,9 @@ __global__ __launch_bounds__(256) void tb_trpo_search_kernel(const TrpoSearchArg
   }
   double sum_l = 0.0, sum_kl = 0.0;  // this lane's rows (lanes of group 0 only)
   for (int i0 = first; i0 < first + TB_TRPO_SEARCH_SHARE / 4 && i0 < B; i0 += 16) {
-    const bool valid = i0 + e < B;
-    long long row = a.idx[valid ? i0 + e : B - 1];
-    row = row < 0 ? 0 : row >= a.n_rows ? a.n_rows - 1 : row;
+    bool valid;
     float x0[TrpoMean<KIND, NET>::L0::NC];
-    const float* orow = a.obs + (size_t)row * O;
-#pragma unroll
-    for (int c = 0; c < TrpoMean<KIND, NET>::L0::NC; ++c) x0[c] = 4 * c + g < O ? orow[4 * c + g] : 0.0f;
+    const long long row = ppo_tile<O>(a.obs, a.idx, i0, B, a.n_rows, lane, valid, x0);
     const f32x4 mu = cur.mean(x0), mu2 = cand.mean(x0);
     float lp = 0.0f, kl = 0.0f;
 #pragma unroll
@@ -367,7 +297,7 @@ __global__ __launch_bounds__(256) void tb_trpo_search_kernel(const TrpoSearchArg
     lp += __shfl_xor(lp, 16); lp += __shfl_xor(lp, 32);
     kl += __shfl_xor(kl, 16); kl += __shfl_xor(kl, 32);
     const float ratio = expf(lp - a.old_logp[row]);
-    const float an = (a.adv[row] - adv_mean) / adv_den;
+    const float an = (a.adv[row] - norm.mean) / norm.den;
     if (valid && g == 0) { sum_l += (double)(ratio * an); sum_kl += (double)kl; }
   }
 #pragma unroll

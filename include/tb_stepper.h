@@ -576,6 +576,13 @@ int tb_sac_collect(TbHandle *h, const float *actor_dev, int n_steps, int mode, u
  * factor min(1, max_grad_norm / (norm + 1e-6)); Adam (bias correction from `step`, the 1-based count of this step) updates
  * params_dev, exp_avg_dev and exp_avg_sq_dev in place. Both bits: the two in turn. With several ranks the caller all-reduces
  * (sums) grad_dev between the two phases; identical grad_dev, parameters and moments give identical bits on every rank.
+ * NON-FINITE GRADIENTS: the factor is torch's clamp(r, max = 1) of r = max_grad_norm / (norm + 1e-6), which KEEPS a NaN (r < 1 ?
+ * r : (r is NaN ? r : 1); not fminf, which drops it). A norm that is NaN, or inf under an infinite bound (inf / inf), therefore
+ * makes every participating slot of grad_dev, of both moments and of the parameters NaN, and an inf norm under a finite bound
+ * gives the factor 0 (the inf slot itself: inf * 0 = NaN) -- slot for slot what torch.nn.utils.clip_grad_norm_ followed by
+ * torch.optim.Adam leaves. The norm is the float32 rounding of the root of a float64 sum: a root beyond float32's range is inf,
+ * although the sum itself is finite. Slots outside the participating ranges (TB_PPO_VALUE_ONLY below) and other members' rows
+ * (tb_ppo_apply_members) are untouched, whatever the norm is.
  * TB_PPO_VALUE_ONLY, added to either phase: the critic alone. TB_PPO_REDUCE then writes only the value slots of grad_dev
  * (value_net_body, value_net); TB_PPO_STEP takes its norm over, clips and updates only those slots. The policy slots of the
  * parameters, the gradient and both moments are not written.

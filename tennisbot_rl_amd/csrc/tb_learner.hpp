@@ -646,7 +646,8 @@ __global__ __launch_bounds__(1024) void tb_ppo_step_kernel(float* params, float*
     __syncthreads();
   }
   const float norm = (float)sqrt(s_sq[0]);
-  const float coef = fminf(1.0f, max_norm / (norm + 1e-6f));
+  const float r = max_norm / (norm + 1e-6f);
+  const float coef = r < 1.0f ? r : (r != r ? r : 1.0f);  // torch's clamp(max = 1): a NaN stays (fminf would drop it)
   for (int p = threadIdx.x; p < P; p += 1024) {
     if (!((p >= lo0 && p < hi0) || (p >= lo1 && p < hi1))) continue;
     const float g = (world != 1.0f ? grad[p] / world : grad[p]) * coef;

@@ -11,7 +11,7 @@ The rule is SB3 1.8.0's PPO as the reference scripts configure it (train_swing.p
     a diagonal Gaussian with a state-independent log_std, the clipped surrogate, a plain mean squared value error, the
     Gaussian's entropy; its gradient with respect to every parameter by a hand-written backward pass through the tanh towers.
   * The optimiser: gradients averaged over the ranks, THEN clipped to a global norm (torch's clip_grad_norm_: factor
-    min(1, max_norm / (norm + 1e-6))), Adam with eps 1e-5 and betas 0.9 / 0.999. `replay_update` runs epochs x minibatches
+    min(1, max_norm / (norm + 1e-6)), a NaN kept), Adam with eps 1e-5 and betas 0.9 / 0.999. `replay_update` runs epochs x minibatches
     from recorded permutations, ragged tail included.
 
 Every function takes a `dtype`: with np.float32 it is the float32 twin of itself -- the same formulas with every
@@ -161,11 +161,14 @@ def global_norm(grads):
 
 
 def clip_global_norm(grads, max_norm, dtype=np.float64):
-    """torch.nn.utils.clip_grad_norm_: every gradient times min(1, max_norm / (norm + 1e-6)); returns (clipped, norm)"""
+    """torch.nn.utils.clip_grad_norm_: every gradient times clamp(max_norm / (norm + 1e-6), max=1), which keeps a NaN (Python's
+    min, like fminf, would drop it): a non-finite norm reaches every gradient. Returns (clipped, norm)"""
     dt = np.dtype(dtype).type
-    norm = dt(np.sqrt(sum((np.asarray(g).astype(dtype) ** 2).sum(dtype=dtype) for g in grads.values()), dtype=dtype))
-    coef = min(dt(1.0), dt(max_norm) / (norm + dt(NORM_EPS)))
-    return {k: np.asarray(g).astype(dtype) * dt(coef) for k, g in grads.items()}, float(norm)
+    with np.errstate(over="ignore", invalid="ignore"):
+        norm = dt(np.sqrt(sum((np.asarray(g).astype(dtype) ** 2).sum(dtype=dtype) for g in grads.values()), dtype=dtype))
+        r = dt(max_norm) / (norm + dt(NORM_EPS))
+        coef = r if r < dt(1.0) else (r if np.isnan(r) else dt(1.0))
+        return {k: np.asarray(g).astype(dtype) * dt(coef) for k, g in grads.items()}, float(norm)
 
 
 def adam_init(params, dtype=np.float64):

@@ -803,6 +803,79 @@ int tb_tqc_actor_grad(int env_kind, int device, void *stream, int batch, const f
                       double *stats_dev, void *workspace_dev, size_t workspace_bytes);
 
 /*
+ * One gradient step of a POPULATION of n_members SAC (or TQC) learners in the launches of ONE learner's step, whatever n_members
+ * is: the kernels of the tb_sac_* / tb_tqc_* stages above with the member as one more grid axis (csrc/tb_sac.hpp, "THE MEMBER
+ * AXIS"). The replay arrays obs / next_obs / action / reward / done of n_rows rows are SHARED. Everything else is per member, in
+ * rows a stride apart; member m reads and writes
+ *   its index row idx_dev + m * idx_stride (entries; idx_stride >= batch; values outside [0, n_rows) are clamped),
+ *   its parameter rows actor_dev + m * actor_stride_floats and critic_dev / target_dev + m * critic_stride_floats (each stride >=
+ *     tb_sac_param_floats / tb_tqc_param_floats of that vector; a gradient and both moments use their parameter's stride, the
+ *     target the critic's),
+ *   its noise row eps_dev + m * eps_stride_floats (>= batch * A), act_out_dev + m * act_stride_floats (>= batch * A), logp_out_dev
+ *     + m * logp_stride_floats (>= batch), y_dev + m * y_stride_floats (>= batch for SAC, batch * 46 for TQC),
+ *   log_ent_coef_dev[m], ent_grad_dev[m], its statistics row stats_dev + 4 m (doubles), its hyper-parameter row hp_dev[m],
+ *   its workspace region, tb_sac_members_workspace_stride_bytes(kind, batch) apart (tb_tqc_... for TQC): a multiple of 8, at least
+ *     the single-member query; workspace_bytes >= n_members * that stride.
+ * After a stage, member m's outputs are bit for bit what the single-member stage leaves, given that member's row of each array
+ * and its scalars (gamma in the targets; lr and tau in tb_sac_adam_members). Floats between rows are neither read nor written.
+ * tb_sac_adam_members is tb_sac_adam over [n_members] rows of n floats `stride_floats` apart (grad, both moments and the target
+ * included): lr is hp_dev[m]'s lr_actor, lr_critic or lr_ent as which_lr (TB_SAC_LR_*) names it, tau hp_dev[m].tau with 1 - tau
+ * formed as tb_sac_adam forms it; betas, eps and the step count are shared. target_dev may be null (no Polyak update); with
+ * grad and both moments null and target_dev set it is every member's Polyak update alone, as in tb_sac_adam. log_ent_coef's step is
+ * the call with n = 1 and stride_floats = 1. TQC uses it as it is.
+ * Refused before the device is looked up, with the entry point's name in tb_last_error: n_members outside [1, TB_SAC_MAX_MEMBERS]
+ * (the (member, net) pair is the grid's z axis: 2 * n_members <= 65535), batch < 1, a null pointer, a float array not 4-byte
+ * aligned, idx / stats / hp / the workspace not 8-byte aligned, a stride that is too short, a gradient row range that overlaps its
+ * parameter rows, an unknown env kind: TB_E_INVAL; workspace_bytes < n_members * the stride: TB_E_PARAMS.
+ */
+#define TB_SAC_MAX_MEMBERS 32767
+#define TB_SAC_LR_ACTOR 0
+#define TB_SAC_LR_CRITIC 1
+#define TB_SAC_LR_ENT 2
+typedef struct TbSacMemberHp { float lr_actor, lr_critic, lr_ent, gamma, tau, reserved[3]; } TbSacMemberHp;   /* 32 bytes, device array [M] */
+long long tb_sac_members_workspace_stride_bytes(int env_kind, int batch);
+long long tb_tqc_members_workspace_stride_bytes(int env_kind, int batch);
+int tb_sac_actor_forward_members(int env_kind, int device, void *stream, const float *obs_dev, long long n_rows, const int64_t *idx_dev,
+                                 size_t idx_stride, int batch, int n_members, const float *actor_dev, size_t actor_stride_floats,
+                                 const float *eps_dev, size_t eps_stride_floats, float *act_out_dev, size_t act_stride_floats,
+                                 float *logp_out_dev, size_t logp_stride_floats, void *workspace_dev, size_t workspace_bytes);
+int tb_sac_targets_members(int env_kind, int device, void *stream, const float *next_obs_dev, const float *reward_dev,
+                           const float *done_dev, long long n_rows, const int64_t *idx_dev, size_t idx_stride, int batch, int n_members,
+                           const float *actor_dev, size_t actor_stride_floats, const float *target_dev, size_t critic_stride_floats,
+                           const float *log_ent_coef_dev /* [M] */, const float *eps_next_dev, size_t eps_stride_floats,
+                           const TbSacMemberHp *hp_dev, float *y_dev, size_t y_stride_floats, void *workspace_dev, size_t workspace_bytes);
+int tb_sac_critic_grad_members(int env_kind, int device, void *stream, const float *obs_dev, const float *action_dev, long long n_rows,
+                               const int64_t *idx_dev, size_t idx_stride, int batch, int n_members, const float *critic_dev,
+                               size_t critic_stride_floats, const float *y_dev, size_t y_stride_floats, float *grad_dev,
+                               double *stats_dev /* [M][4] */, void *workspace_dev, size_t workspace_bytes);
+int tb_sac_actor_grad_members(int env_kind, int device, void *stream, int batch, int n_members, const float *actor_dev,
+                              size_t actor_stride_floats, const float *critic_dev, size_t critic_stride_floats,
+                              const float *log_ent_coef_dev /* [M] */, const float *eps_dev, size_t eps_stride_floats,
+                              float *actor_grad_dev, float *ent_grad_dev /* [M] */, double *stats_dev /* [M][4] */, void *workspace_dev,
+                              size_t workspace_bytes);
+int tb_tqc_actor_forward_members(int env_kind, int device, void *stream, const float *obs_dev, long long n_rows, const int64_t *idx_dev,
+                                 size_t idx_stride, int batch, int n_members, const float *actor_dev, size_t actor_stride_floats,
+                                 const float *eps_dev, size_t eps_stride_floats, float *act_out_dev, size_t act_stride_floats,
+                                 float *logp_out_dev, size_t logp_stride_floats, void *workspace_dev, size_t workspace_bytes);
+int tb_tqc_targets_members(int env_kind, int device, void *stream, const float *next_obs_dev, const float *reward_dev,
+                           const float *done_dev, long long n_rows, const int64_t *idx_dev, size_t idx_stride, int batch, int n_members,
+                           const float *actor_dev, size_t actor_stride_floats, const float *target_dev, size_t critic_stride_floats,
+                           const float *log_ent_coef_dev /* [M] */, const float *eps_next_dev, size_t eps_stride_floats,
+                           const TbSacMemberHp *hp_dev, float *y_dev, size_t y_stride_floats, void *workspace_dev, size_t workspace_bytes);
+int tb_tqc_critic_grad_members(int env_kind, int device, void *stream, const float *obs_dev, const float *action_dev, long long n_rows,
+                               const int64_t *idx_dev, size_t idx_stride, int batch, int n_members, const float *critic_dev,
+                               size_t critic_stride_floats, const float *y_dev, size_t y_stride_floats, float *grad_dev,
+                               double *stats_dev /* [M][4] */, void *workspace_dev, size_t workspace_bytes);
+int tb_tqc_actor_grad_members(int env_kind, int device, void *stream, int batch, int n_members, const float *actor_dev,
+                              size_t actor_stride_floats, const float *critic_dev, size_t critic_stride_floats,
+                              const float *log_ent_coef_dev /* [M] */, const float *eps_dev, size_t eps_stride_floats,
+                              float *actor_grad_dev, float *ent_grad_dev /* [M] */, double *stats_dev /* [M][4] */, void *workspace_dev,
+                              size_t workspace_bytes);
+int tb_sac_adam_members(int device, void *stream, float *params_dev, const float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
+                        long long n, size_t stride_floats, int n_members, const TbSacMemberHp *hp_dev, int which_lr, float beta1,
+                        float beta2, float eps, long long step, float *target_dev);
+
+/*
  * rgb_array frames of env states (csrc/tb_render.hpp states the whole rule: camera, primitives, shading, exceptional values): what
  * the reference's render() set out to do (tennisbot_env.py:263-288 builds a camera at the racket and leaves getCameraImage
  * commented out; validate.py / validate_swing.py open PyBullet's GUI). One launch casts one primary ray per pixel of every image

@@ -61,6 +61,25 @@ TB_DEV long long sac_row(const long long* idx, int b, long long n_rows) {
   return r < 0 ? 0 : r >= n_rows ? n_rows - 1 : r;
 }
 
+// ------------------------------------------------------------------------------------------------------------- THE MEMBER AXIS
+// A population of learners (tb_sac_*_members / tb_tqc_*_members) runs every kernel of the gradient step below with ONE more
+// argument in a trailing pack that is empty or holds that one, as PolicyMembers and PpoMembers are passed: with the pack empty a
+// kernel is what it was, argument list included. Members share the replay arrays and nothing else.
+//   tile kernels   SacMembers: blockIdx.z enumerates (member, net), member = z / nets. Operands in the workspace (X, H, dZ, dX, Y)
+//                  move by the member's workspace region `ws`, operands in a flat vector (W, bias, dW, db) by that vector's row
+//                  stride `ps`. The tile's chain is the same chain: a member changes base addresses, never an order or an operand.
+//   row kernels    SacRowMembers: the member is blockIdx.y (blockIdx.x in the one-workgroup reductions): its index row, its noise
+//                  row, log_ent_coef[m], hp[m].gamma, its y row, its statistics row [4], ent_grad[m], its workspace region.
+//   Adam / Polyak  SacAdamMembers: blockIdx.y; lr and tau from hp[m], 1 - tau formed as the host forms it for one learner.
+// No kernel reads or writes between two members' rows: every offset inside a row is the single-member offset.
+struct SacMembers { int nets; long long ws, ps; };  // floats
+struct SacRowMembers {
+  long long idx, eps, act, logp, y, ws;  // the rows' strides: idx in entries, the others in floats
+  const TbSacMemberHp* hp;
+};
+struct SacAdamMembers { long long stride; const TbSacMemberHp* hp; int which_lr; };
+template <class T> TB_DEV void sac_shift(T*& p, long long by) { if (p) p += by; }
+
 // ---------------------------------------------------------------------------------------------------------------- tile kernels
 struct SacFwdArgs {
   const float* x; int xs; long long xz;  // X[b][k] at x[z xz + b xs + k]
@@ -71,9 +90,17 @@ struct SacFwdArgs {
 };
 
 // grid (ceil(B / 64), ceil(M / 16), nets), 256 threads: wave w of block x takes rows 64 x + 16 w ..
-template <bool RELU>
-__global__ __launch_bounds__(256) void sac_forward_kernel(const SacFwdArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, e = lane & 15, z = blockIdx.z;
+template <bool RELU, class... MEMBERS>
+__global__ __launch_bounds__(256) void sac_forward_kernel(SacFwdArgs a, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacMembers");
+  int z = blockIdx.z;
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const SacMembers mb = (members, ...);
+    const int m = z / mb.nets;
+    z -= m * mb.nets;
+    a.x += m * mb.ws; a.y += m * mb.ws; a.w += m * mb.ps; a.bias += m * mb.ps;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, e = lane & 15;
   const int b0 = blockIdx.x * SAC_ROWS_PER_WG + 16 * wave, o0 = blockIdx.y * 16;
   if (b0 >= a.B) return;
   const float* x = a.x + z * a.xz;
@@ -120,9 +147,18 @@ struct SacBwdArgs {
 };
 
 // grid (ceil(B / 64), ceil(K / 16), nets), 256 threads
-template <bool MASK>
-__global__ __launch_bounds__(256) void sac_backward_kernel(const SacBwdArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, e = lane & 15, z = blockIdx.z;
+template <bool MASK, class... MEMBERS>
+__global__ __launch_bounds__(256) void sac_backward_kernel(SacBwdArgs a, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacMembers");
+  int z = blockIdx.z;
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const SacMembers mb = (members, ...);
+    const int m = z / mb.nets;
+    z -= m * mb.nets;
+    a.dz += m * mb.ws; a.dx += m * mb.ws; a.w += m * mb.ps;
+    if (MASK) a.h += m * mb.ws;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, e = lane & 15;
   const int b0 = blockIdx.x * SAC_ROWS_PER_WG + 16 * wave, k0 = blockIdx.y * 16;
   if (b0 >= a.B) return;
   const float* w = a.w + z * a.wz;
@@ -168,8 +204,17 @@ struct SacWgradArgs {
 };
 
 // grid (ceil(K / 64), ceil(M / 16), nets), 256 threads: wave w takes input columns 64 x + 16 w ..; the tile of column 0 also sums db
-__global__ __launch_bounds__(256) void sac_wgrad_kernel(const SacWgradArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, e = lane & 15, z = blockIdx.z;
+template <class... MEMBERS>
+__global__ __launch_bounds__(256) void sac_wgrad_kernel(SacWgradArgs a, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacMembers");
+  int z = blockIdx.z;
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const SacMembers mb = (members, ...);
+    const int m = z / mb.nets;
+    z -= m * mb.nets;
+    a.dz += m * mb.ws; a.h += m * mb.ws; a.gw += m * mb.ps; a.gb += m * mb.ps;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, e = lane & 15;
   const int k0 = blockIdx.x * 64 + 16 * wave, o0 = blockIdx.y * 16;
   if (k0 >= a.K) return;
   const float* dz = a.dz + z * a.dzz;
@@ -215,7 +260,14 @@ __global__ __launch_bounds__(256) void sac_wgrad_kernel(const SacWgradArgs a) {
 
 // ----------------------------------------------------------------------------------------------------------------- row kernels
 // out[b][0 .. 16) = obs[row][0 .. O) | act[row][0 .. A) (or nothing) | 0, row = the clamped idx[b]
-__global__ __launch_bounds__(256) void sac_gather_kernel(const float* obs, int O, const float* act, int A, const long long* idx, long long n_rows, int B, float* out) {
+template <class... MEMBERS>
+__global__ __launch_bounds__(256) void sac_gather_kernel(const float* obs, int O, const float* act, int A, const long long* idx, long long n_rows, int B, float* out,
+                                                         MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const SacRowMembers mb = (members, ...);
+    idx += blockIdx.y * mb.idx; out += blockIdx.y * mb.ws;
+  }
   const int i = blockIdx.x * 256 + threadIdx.x, b = i >> 4, c = i & 15;
   if (b >= B) return;
   const long long row = sac_row(idx, b, n_rows);
@@ -235,8 +287,16 @@ TB_DEV float sac_squash_sample(float mu, float log_std, float ep, float& ls) {
 
 // one thread per row: the squashed sample and its log-probability from the head's outputs zh[b] = mu [A] | log_std [A];
 // xc[b] = the row's observation | the sample | 0: the critics' input; lp[b][0] = logp. act_out / logp_out may be null
+template <class... MEMBERS>
 __global__ __launch_bounds__(256) void sac_sample_kernel(const float* x0, const float* zh, const float* eps, int O, int A, int B, float* act_out, float* logp_out, float* xc,
-                                                         float* lp) {
+                                                         float* lp, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const SacRowMembers mb = (members, ...);
+    const long long m = blockIdx.y;
+    x0 += m * mb.ws; zh += m * mb.ws; xc += m * mb.ws; lp += m * mb.ws; eps += m * mb.eps;
+    sac_shift(act_out, m * mb.act); sac_shift(logp_out, m * mb.logp);
+  }
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   const float* z = zh + (size_t)b * SAC_XW;
@@ -257,9 +317,23 @@ __global__ __launch_bounds__(256) void sac_sample_kernel(const float* x0, const 
   lp[(size_t)b * SAC_XW] = logp;
 }
 
+// what a member's target kernel reads and writes of its own (sac_target_kernel, tqc_target_kernel)
+TB_DEV void sac_member_target(const SacRowMembers& mb, long long m, const long long*& idx, const float*& qt, const float*& logp_next, const float*& log_ent_coef, float& gamma,
+                              float*& y) {
+  idx += m * mb.idx; qt += m * mb.ws; logp_next += m * mb.ws; log_ent_coef += m; gamma = mb.hp[m].gamma; y += m * mb.y;
+}
+// ... and its actor-loss kernel (sac_actor_loss_kernel, tqc_actor_loss_kernel)
+TB_DEV void sac_member_actor_loss(const SacRowMembers& mb, long long m, const float*& q, const float*& lp, const float*& log_ent_coef, float*& dq, float*& ent_grad,
+                                  double*& stats) {
+  q += m * mb.ws; lp += m * mb.ws; dq += m * mb.ws; log_ent_coef += m; ent_grad += m; stats += 4 * m;
+}
+
 // y = r + (1 - d) gamma (min(Q1t, Q2t) - alpha logp'); a terminal row is selected, not multiplied: y = r bit for bit
+template <class... MEMBERS>
 __global__ __launch_bounds__(256) void sac_target_kernel(const float* reward, const float* done, const long long* idx, long long n_rows, int B, const float* qt,
-                                                         const float* logp_next, const float* log_ent_coef, float gamma, float* y) {
+                                                         const float* logp_next, const float* log_ent_coef, float gamma, float* y, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) sac_member_target((members, ...), blockIdx.y, idx, qt, logp_next, log_ent_coef, gamma, y);
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   const long long row = sac_row(idx, b, n_rows);
@@ -283,7 +357,14 @@ TB_DEV double sac_block_sum(double v, double* s) {
 }
 
 // dq[n][b] = (Q_n(s, a)[b] - y[b]) / B; stats[0] = 0.5 (mean d1^2 + mean d2^2). One workgroup.
-__global__ __launch_bounds__(256) void sac_critic_loss_kernel(const float* q, const float* y, int B, float* dq, double* stats) {
+template <class... MEMBERS>
+__global__ __launch_bounds__(256) void sac_critic_loss_kernel(const float* q, const float* y, int B, float* dq, double* stats, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {  // one workgroup per member
+    const SacRowMembers mb = (members, ...);
+    const long long m = blockIdx.x;
+    q += m * mb.ws; dq += m * mb.ws; y += m * mb.y; stats += 4 * m;
+  }
   __shared__ double s[256];
   double sq = 0.0;
   const float inv = 1.0f / (float)B;
@@ -301,8 +382,11 @@ __global__ __launch_bounds__(256) void sac_critic_loss_kernel(const float* q, co
 // the actor loss mean(alpha logp - min(Q1, Q2)(s, a~)): dq[n][b] = -1 / B on the smaller critic, 0 on the other (Q1 on a tie);
 // stats[1] = the loss, stats[2] = mean logp, stats[3] = the gradient of log_ent_coef, -mean(logp + target_entropy), also
 // written as float32 to ent_grad. One workgroup.
+template <class... MEMBERS>
 __global__ __launch_bounds__(256) void sac_actor_loss_kernel(const float* q, const float* lp, const float* log_ent_coef, float target_entropy, int B, float* dq,
-                                                             float* ent_grad, double* stats) {
+                                                             float* ent_grad, double* stats, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) sac_member_actor_loss((members, ...), blockIdx.x, q, lp, log_ent_coef, dq, ent_grad, stats);  // one workgroup per member
   __shared__ double s[256];
   const float alpha = expf(log_ent_coef[0]), inv = 1.0f / (float)B;
   double sl = 0.0, sp = 0.0, se = 0.0;
@@ -327,8 +411,15 @@ __global__ __launch_bounds__(256) void sac_actor_loss_kernel(const float* q, con
 // one thread per (row, action): the loss's gradient with respect to the head's outputs, through a~ = tanh(g), g = mu + sigma eps:
 //   dL/dg = da (1 - a~^2) + c 2 a~ (1 - a~^2) / (1 - a~^2 + 1e-6),  c = alpha / B,  da = both critics' input gradients summed
 //   dL/dmu = dL/dg,  dL/dlog_std = dL/dg sigma eps - c, zero where the clamp binds (outside [-20, 2])
+template <class... MEMBERS>
 __global__ __launch_bounds__(256) void sac_head_backward_kernel(const float* zh, const float* xc, const float* dx, const float* eps, const float* log_ent_coef, int O,
-                                                                int A, int B, float* dhd) {
+                                                                int A, int B, float* dhd, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const SacRowMembers mb = (members, ...);
+    const long long m = blockIdx.y;
+    zh += m * mb.ws; xc += m * mb.ws; dx += m * mb.ws; dhd += m * mb.ws; eps += m * mb.eps; log_ent_coef += m;
+  }
   const int i = blockIdx.x * 256 + threadIdx.x, b = i >> 4, j = i & 15;
   if (b >= B) return;
   float* out = dhd + (size_t)b * SAC_XW;
@@ -346,10 +437,26 @@ __global__ __launch_bounds__(256) void sac_head_backward_kernel(const float* zh,
   out[A + j] = (raw < SAC_LOG_STD_MIN || raw > SAC_LOG_STD_MAX) ? 0.0f : dg * (expf(ls) * ep) - c;
 }
 
+// a member's target row and its tau (sac_adam_kernel, sac_polyak_kernel); 1 - tau as tb_sac_adam's host code forms it
+TB_DEV void sac_member_polyak(const SacAdamMembers& mb, long long k, float*& target, float& one_minus_tau, float& tau) {
+  sac_shift(target, k * mb.stride);
+  tau = mb.hp[k].tau;
+  one_minus_tau = (float)(1.0 - (double)tau);
+}
+
 // Adam (torch's: eps added to sqrt(v_hat)) on a flat vector, and the Polyak update of a target vector of the same length with
 // the NEW parameters: target = (1 - tau) target + tau p (two roundings, SB3's mul_ then add). target may be null.
+template <class... MEMBERS>
 __global__ __launch_bounds__(256) void sac_adam_kernel(float* params, const float* grad, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
-                                                       float c1, float c2, float* target, float one_minus_tau, float tau) {
+                                                       float c1, float c2, float* target, float one_minus_tau, float tau, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacAdamMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const SacAdamMembers mb = (members, ...);
+    const long long k = blockIdx.y, by = k * mb.stride;
+    params += by; grad += by; m += by; v += by;
+    lr = mb.which_lr == 0 ? mb.hp[k].lr_actor : mb.which_lr == 1 ? mb.hp[k].lr_critic : mb.hp[k].lr_ent;
+    sac_member_polyak(mb, k, target, one_minus_tau, tau);
+  }
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   const float g = grad[p];
@@ -362,7 +469,14 @@ __global__ __launch_bounds__(256) void sac_adam_kernel(float* params, const floa
 }
 
 // the Polyak update alone
-__global__ __launch_bounds__(256) void sac_polyak_kernel(const float* params, float* target, long long n, float one_minus_tau, float tau) {
+template <class... MEMBERS>
+__global__ __launch_bounds__(256) void sac_polyak_kernel(const float* params, float* target, long long n, float one_minus_tau, float tau, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacAdamMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {
+    const SacAdamMembers mb = (members, ...);
+    params += blockIdx.y * mb.stride;
+    sac_member_polyak(mb, blockIdx.y, target, one_minus_tau, tau);
+  }
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
   if (p < n) target[p] = one_minus_tau * target[p] + tau * params[p];
 }

@@ -1795,52 +1795,90 @@ template <int KIND> SacDims tqc_dims_of() {
 
 unsigned sac_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
+// A population's rows (tb_sac_*_members; null: one learner): strides in entries (idx) and floats, zero where a stage has no such array
+struct SacPop {
+  int M;
+  size_t idx, pi, q, eps, act, logp, y;
+  const TbSacMemberHp* hp;
+};
+
 struct SacRun {  // one stage's launches: the dims, the stream, the batch and the workspace's regions
   SacDims d;
   hipStream_t s;
   int B;
   float* ws;
   int heads, hw;  // a critic's outputs and the padded width of its head rows: 1 / 16 for SAC, 25 / 32 for TQC
-  float* at(int region) const { return ws + (size_t)region * (size_t)B; }
+  // a population: the members' count, the row strides of the workspace regions, the actor and the critic (floats), and what the
+  // row kernels take. One learner: pop is false, NM is 1, and every launch below is the launch it was.
+  bool pop;
+  int NM;
+  long long wss, pis, qs;
+  SacRowMembers rm;
+  float* at(int region) const { return ws + (size_t)region * (size_t)B; }  // (of member 0: the kernels add the member's region)
 
-  int forward(bool relu, const float* x, int xs, long long xz, const float* w, int wrs, long long wz, const float* bias, float* y, int ys, long long yz, int K, int M, int nets) const {
+  // ps: the row stride of the flat vector that holds w (pis or qs)
+  int forward(bool relu, const float* x, int xs, long long xz, const float* w, int wrs, long long wz, const float* bias, float* y, int ys, long long yz, int K, int M, int nets,
+              long long ps) const {
     SacFwdArgs a = {x, xs, xz, w, wrs, wz, bias, y, ys, yz, B, K, M};
-    const dim3 grid(sac_blocks(B, SAC_ROWS_PER_WG), sac_blocks(M, 16), (unsigned)nets);
+    const dim3 grid(sac_blocks(B, SAC_ROWS_PER_WG), sac_blocks(M, 16), (unsigned)(nets * NM));
+    if (pop) {
+      const SacMembers mb = {nets, wss, ps};
+      return relu ? launch(sac_forward_kernel<true, SacMembers>, grid, dim3(256), 0, s, a, mb) : launch(sac_forward_kernel<false, SacMembers>, grid, dim3(256), 0, s, a, mb);
+    }
     return relu ? launch(sac_forward_kernel<true>, grid, dim3(256), 0, s, a) : launch(sac_forward_kernel<false>, grid, dim3(256), 0, s, a);
   }
   int backward(const float* dz, int dzs, long long dzz, const float* w, int wrs, long long wz, int split, int extra, const float* h, int hs, long long hz, float* dx, int dxs,
-               long long dxz, int K, int M, int nets) const {
+               long long dxz, int K, int M, int nets, long long ps) const {
     SacBwdArgs a = {dz, dzs, dzz, w, wrs, wz, split, extra, h, hs, hz, dx, dxs, dxz, B, K, M};
-    const dim3 grid(sac_blocks(B, SAC_ROWS_PER_WG), sac_blocks(K, 16), (unsigned)nets);
+    const dim3 grid(sac_blocks(B, SAC_ROWS_PER_WG), sac_blocks(K, 16), (unsigned)(nets * NM));
+    if (pop) {
+      const SacMembers mb = {nets, wss, ps};
+      return h ? launch(sac_backward_kernel<true, SacMembers>, grid, dim3(256), 0, s, a, mb) : launch(sac_backward_kernel<false, SacMembers>, grid, dim3(256), 0, s, a, mb);
+    }
     return h ? launch(sac_backward_kernel<true>, grid, dim3(256), 0, s, a) : launch(sac_backward_kernel<false>, grid, dim3(256), 0, s, a);
   }
-  int wgrad(const float* dz, int dzs, long long dzz, const float* h, int hs, long long hz, float* gw, int wrs, long long wz, float* gb, int K, int M, int nets) const {
+  int wgrad(const float* dz, int dzs, long long dzz, const float* h, int hs, long long hz, float* gw, int wrs, long long wz, float* gb, int K, int M, int nets, long long ps) const {
     SacWgradArgs a = {dz, dzs, dzz, h, hs, hz, gw, wrs, wz, gb, B, K, M};
-    return launch(sac_wgrad_kernel, dim3(sac_blocks(K, 64), sac_blocks(M, 16), (unsigned)nets), dim3(256), 0, s, a);
+    const dim3 grid(sac_blocks(K, 64), sac_blocks(M, 16), (unsigned)(nets * NM));
+    if (pop) {
+      const SacMembers mb = {nets, wss, ps};
+      return launch(sac_wgrad_kernel<SacMembers>, grid, dim3(256), 0, s, a, mb);
+    }
+    return launch(sac_wgrad_kernel<>, grid, dim3(256), 0, s, a);
+  }
+  // a row kernel or a one-workgroup reduction: k1 for one learner; km for a population, the member as grid axis y (member_is_x: x)
+  template <class... P1, class... PM, class... A>
+  int rows(void (*k1)(P1...), void (*km)(PM...), dim3 grid, bool member_is_x, const A&... a) const {
+    if (!pop) return launch(k1, grid, dim3(256), 0, s, a...);
+    if (member_is_x) grid.x = (unsigned)NM;
+    else grid.y = (unsigned)NM;
+    return launch(km, grid, dim3(256), 0, s, a..., rm);
   }
   // rows idx of obs, and of action beside them where there is one, into the 16-wide rows of region x
   int gather(const float* obs, const float* action, const int64_t* idx, long long n_rows, int x) const {
-    return launch(sac_gather_kernel, dim3(sac_blocks((long long)B * 16, 256)), dim3(256), 0, s, obs, d.O, action, action ? d.A : 0, (const long long*)idx, n_rows, B, at(x));
+    return rows(sac_gather_kernel<>, sac_gather_kernel<SacRowMembers>, dim3(sac_blocks((long long)B * 16, 256)), false, obs, d.O, action, action ? d.A : 0, (const long long*)idx,
+                n_rows, B, at(x));
   }
   // the actor on the gathered rows x0: h1, h2, the head's outputs zh; then the sample: act / logp out, xc = obs | sample, lp
   int actor(const float* actor, const float* eps, int x0, int h1, int h2, int zh, int xc, int lp, float* act_out, float* logp_out) const {
-    if (int rc = forward(true, at(x0), SAC_XW, 0, actor + d.pi_w0, d.O, 0, actor + d.pi_b0, at(h1), SAC_H, 0, d.O, SAC_H, 1)) return rc;
-    if (int rc = forward(true, at(h1), SAC_H, 0, actor + d.pi_w1, SAC_H, 0, actor + d.pi_b1, at(h2), SAC_H, 0, SAC_H, SAC_H, 1)) return rc;
-    if (int rc = forward(false, at(h2), SAC_H, 0, actor + d.pi_head, SAC_H, d.pi_block, actor + d.pi_head + d.A * SAC_H, at(zh), SAC_XW, d.A, SAC_H, d.A, 2)) return rc;
-    return launch(sac_sample_kernel, dim3(sac_blocks(B, 256)), dim3(256), 0, s, (const float*)at(x0), (const float*)at(zh), eps, d.O, d.A, B, act_out, logp_out, at(xc), at(lp));
+    if (int rc = forward(true, at(x0), SAC_XW, 0, actor + d.pi_w0, d.O, 0, actor + d.pi_b0, at(h1), SAC_H, 0, d.O, SAC_H, 1, pis)) return rc;
+    if (int rc = forward(true, at(h1), SAC_H, 0, actor + d.pi_w1, SAC_H, 0, actor + d.pi_b1, at(h2), SAC_H, 0, SAC_H, SAC_H, 1, pis)) return rc;
+    if (int rc = forward(false, at(h2), SAC_H, 0, actor + d.pi_head, SAC_H, d.pi_block, actor + d.pi_head + d.A * SAC_H, at(zh), SAC_XW, d.A, SAC_H, d.A, 2, pis)) return rc;
+    return rows(sac_sample_kernel<>, sac_sample_kernel<SacRowMembers>, dim3(sac_blocks(B, 256)), false, (const float*)at(x0), (const float*)at(zh), eps, d.O, d.A, B, act_out,
+                logp_out, at(xc), at(lp));
   }
   // both nets of a critic vector on the rows xc: h1, h2 [2][B][256], q [2][B][hw] (columns 0 .. heads)
   int critics(const float* critic, int xc, int h1, int h2, int q) const {
     const long long BH = (long long)B * SAC_H;
-    if (int rc = forward(true, at(xc), SAC_XW, 0, critic + d.q_w0, d.C, d.q_one, critic + d.q_b0, at(h1), SAC_H, BH, d.C, SAC_H, 2)) return rc;
-    if (int rc = forward(true, at(h1), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, critic + d.q_b1, at(h2), SAC_H, BH, SAC_H, SAC_H, 2)) return rc;
-    return forward(false, at(h2), SAC_H, BH, critic + d.q_w2, SAC_H, d.q_one, critic + d.q_b2, at(q), hw, (long long)B * hw, SAC_H, heads, 2);
+    if (int rc = forward(true, at(xc), SAC_XW, 0, critic + d.q_w0, d.C, d.q_one, critic + d.q_b0, at(h1), SAC_H, BH, d.C, SAC_H, 2, qs)) return rc;
+    if (int rc = forward(true, at(h1), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, critic + d.q_b1, at(h2), SAC_H, BH, SAC_H, SAC_H, 2, qs)) return rc;
+    return forward(false, at(h2), SAC_H, BH, critic + d.q_w2, SAC_H, d.q_one, critic + d.q_b2, at(q), hw, (long long)B * hw, SAC_H, heads, 2, qs);
   }
   // dq [2][B][hw] back to dz2 and dz1 [2][B][256] through both nets, in the regions of the workspace layout Ws
   template <class Ws> int critics_backward(const float* critic) const {
     const long long BH = (long long)B * SAC_H;
-    if (int rc = backward(at(Ws::DQ), hw, (long long)B * hw, critic + d.q_w2, SAC_H, d.q_one, 1 << 30, 0, at(Ws::C2), SAC_H, BH, at(Ws::DZ2), SAC_H, BH, SAC_H, heads, 2)) return rc;
-    return backward(at(Ws::DZ2), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, 1 << 30, 0, at(Ws::C1), SAC_H, BH, at(Ws::DZ1), SAC_H, BH, SAC_H, SAC_H, 2);
+    if (int rc = backward(at(Ws::DQ), hw, (long long)B * hw, critic + d.q_w2, SAC_H, d.q_one, 1 << 30, 0, at(Ws::C2), SAC_H, BH, at(Ws::DZ2), SAC_H, BH, SAC_H, heads, 2, qs)) return rc;
+    return backward(at(Ws::DZ2), SAC_H, BH, critic + d.q_w1, SAC_H, d.q_one, 1 << 30, 0, at(Ws::C1), SAC_H, BH, at(Ws::DZ1), SAC_H, BH, SAC_H, SAC_H, 2, qs);
   }
 };
 
@@ -1849,27 +1887,36 @@ struct SacRun {  // one stage's launches: the dims, the stream, the batch and th
 // which the stage lists; the critic loss is one launch in SAC and two in TQC (the rows' sums into RL, then their sum).
 struct SacAlgo {
   using Ws = SacWs;
-  static constexpr int HEADS = 1, HW = SAC_XW;
+  static constexpr int HEADS = 1, HW = SAC_XW, Y_W = 1;  // Y_W: the floats of a row's target
   static constexpr const char* WS_QUERY = "tb_sac_workspace_bytes";
   static SacDims dims(int env_kind) { return env_kind == TB_ENV_SWING ? sac_dims_of<TB_ENV_SWING>() : sac_dims_of<TB_ENV_TENNIS>(); }
-  template <class... A> static int targets(const SacRun& r, const A&... a) { return launch(sac_target_kernel, dim3(sac_blocks(r.B, 256)), dim3(256), 0, r.s, a...); }
-  static int critic_loss(const SacRun& r, const float* y, double* stats) {
-    return launch(sac_critic_loss_kernel, dim3(1), dim3(256), 0, r.s, (const float*)r.at(Ws::Q), y, r.B, r.at(Ws::DQ), stats);
+  template <class... A> static int targets(const SacRun& r, const A&... a) {
+    return r.rows(sac_target_kernel<>, sac_target_kernel<SacRowMembers>, dim3(sac_blocks(r.B, 256)), false, a...);
   }
-  template <class... A> static int actor_loss(const SacRun& r, const A&... a) { return launch(sac_actor_loss_kernel, dim3(1), dim3(256), 0, r.s, a...); }  // the critics' min
+  static int critic_loss(const SacRun& r, const float* y, double* stats) {
+    return r.rows(sac_critic_loss_kernel<>, sac_critic_loss_kernel<SacRowMembers>, dim3(1), true, (const float*)r.at(Ws::Q), y, r.B, r.at(Ws::DQ), stats);
+  }
+  template <class... A> static int actor_loss(const SacRun& r, const A&... a) {  // the critics' min
+    return r.rows(sac_actor_loss_kernel<>, sac_actor_loss_kernel<SacRowMembers>, dim3(1), true, a...);
+  }
 };
 struct TqcAlgo {
   using Ws = TqcWs;
-  static constexpr int HEADS = TQC_Q, HW = TQC_HW;
+  static constexpr int HEADS = TQC_Q, HW = TQC_HW, Y_W = TQC_KEEP;
   static constexpr const char* WS_QUERY = "tb_tqc_workspace_bytes";
   static SacDims dims(int env_kind) { return env_kind == TB_ENV_SWING ? tqc_dims_of<TB_ENV_SWING>() : tqc_dims_of<TB_ENV_TENNIS>(); }
-  template <class... A> static int targets(const SacRun& r, const A&... a) { return launch(tqc_target_kernel, dim3(sac_blocks(r.B, 4)), dim3(256), 0, r.s, a...); }
+  template <class... A> static int targets(const SacRun& r, const A&... a) {
+    return r.rows(tqc_target_kernel<>, tqc_target_kernel<SacRowMembers>, dim3(sac_blocks(r.B, 4)), false, a...);
+  }
   static int critic_loss(const SacRun& r, const float* y, double* stats) {
     double* row_loss = reinterpret_cast<double*>(r.at(Ws::RL));
-    if (int rc = launch(tqc_critic_loss_kernel, dim3(sac_blocks(r.B, 4)), dim3(256), 0, r.s, (const float*)r.at(Ws::Q), y, r.B, r.at(Ws::DQ), row_loss)) return rc;
-    return launch(tqc_loss_sum_kernel, dim3(1), dim3(256), 0, r.s, (const double*)row_loss, r.B, stats);
+    if (int rc = r.rows(tqc_critic_loss_kernel<>, tqc_critic_loss_kernel<SacRowMembers>, dim3(sac_blocks(r.B, 4)), false, (const float*)r.at(Ws::Q), y, r.B, r.at(Ws::DQ), row_loss))
+      return rc;
+    return r.rows(tqc_loss_sum_kernel<>, tqc_loss_sum_kernel<SacRowMembers>, dim3(1), true, (const double*)row_loss, r.B, stats);
   }
-  template <class... A> static int actor_loss(const SacRun& r, const A&... a) { return launch(tqc_actor_loss_kernel, dim3(1), dim3(256), 0, r.s, a...); }  // their 50 quantiles' mean
+  template <class... A> static int actor_loss(const SacRun& r, const A&... a) {  // their 50 quantiles' mean
+    return r.rows(tqc_actor_loss_kernel<>, tqc_actor_loss_kernel<SacRowMembers>, dim3(1), true, a...);
+  }
 };
 
 int sac_fail(int code, const char* what, const char* words, const char* more = "") {
@@ -1880,23 +1927,48 @@ int sac_fail(int code, const char* what, const char* words, const char* more = "
 
 // What a stage refuses before its first launch, in this order: the env kind, the batch and the workspace; null pointers;
 // n_rows; alignment (wide8 names what must be 8-byte aligned); aliasing (aliased: the words of the refusal, or null); the device, which
-// g then makes current for the rest of the stage.
+// g then makes current for the rest of the stage. A population (pop: not null) adds its member count in front of the batch, asks
+// for n_members workspace regions, and refuses a stride shorter than what it strides over (short_stride: the stage's own verdict).
+template <class Algo> long long sac_members_workspace_stride(int batch) {
+  return ((long long)sizeof(float) * Algo::Ws::PER_ROW * (long long)batch + 7) / 8 * 8;
+}
 template <class Algo>
 int sac_check(const char* what, int env_kind, int batch, const void* workspace_dev, size_t workspace_bytes, bool any_null, long long n_rows, bool any_misaligned,
-              const char* wide8, const char* aliased, int device, DeviceGuard& g) {
+              const char* wide8, const char* aliased, int device, DeviceGuard& g, const SacPop* pop = nullptr, bool short_stride = false) {
   if (!kind_ok(env_kind)) return sac_fail(TB_E_INVAL, what, "unknown env kind");
+  if (pop && (pop->M < 1 || pop->M > TB_SAC_MAX_MEMBERS)) return sac_fail(TB_E_INVAL, what, "n_members must be in [1, 32767] (member and net share the grid's z axis)");
   if (batch < 1) return sac_fail(TB_E_INVAL, what, "batch must be >= 1");
   if (!workspace_dev) return sac_fail(TB_E_INVAL, what, "null argument (the workspace)");
   if (misaligned(workspace_dev, 8)) return sac_fail(TB_E_INVAL, what, "the workspace must be 8-byte aligned");
-  if ((long long)workspace_bytes < (long long)sizeof(float) * Algo::Ws::PER_ROW * (long long)batch) return sac_fail(TB_E_PARAMS, what, "the workspace is smaller than ", Algo::WS_QUERY);
+  if (pop) {
+    if ((long long)(workspace_bytes / (size_t)pop->M) < sac_members_workspace_stride<Algo>(batch))
+      return sac_fail(TB_E_PARAMS, what, "the workspace is smaller than n_members regions of the members_workspace_stride_bytes query");
+  } else if ((long long)workspace_bytes < (long long)sizeof(float) * Algo::Ws::PER_ROW * (long long)batch) {
+    return sac_fail(TB_E_PARAMS, what, "the workspace is smaller than ", Algo::WS_QUERY);
+  }
   if (any_null) return sac_fail(TB_E_INVAL, what, "null argument");
   if (n_rows < 1) return sac_fail(TB_E_INVAL, what, "n_rows must be >= 1");
   if (any_misaligned) return sac_fail(TB_E_INVAL, what, "a float array is not 4-byte aligned, or ", wide8);
+  if (short_stride) return sac_fail(TB_E_INVAL, what, "a member stride is shorter than the row it strides over");
   if (aliased) return sac_fail(TB_E_INVAL, what, aliased);
   return learner_device(g, device, what);
 }
-template <class Algo> SacRun sac_run(int env_kind, void* stream, int batch, void* workspace_dev) {
-  return {Algo::dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev, Algo::HEADS, Algo::HW};
+template <class Algo> SacRun sac_run(int env_kind, void* stream, int batch, void* workspace_dev, const SacPop* pop) {
+  SacRun r = {Algo::dims(env_kind), (hipStream_t)stream, batch, (float*)workspace_dev, Algo::HEADS, Algo::HW, false, 1, 0, 0, 0, {}};
+  if (pop) {
+    r.pop = true; r.NM = pop->M;
+    r.wss = sac_members_workspace_stride<Algo>(batch) / (long long)sizeof(float);
+    r.pis = (long long)pop->pi; r.qs = (long long)pop->q;
+    r.rm = {(long long)pop->idx, (long long)pop->eps, (long long)pop->act, (long long)pop->logp, (long long)pop->y, r.wss, pop->hp};
+  }
+  return r;
+}
+// the dims of a kind that may be unknown (then zeros: sac_check refuses the kind first)
+template <class Algo> SacDims sac_dims_or_zero(int env_kind) { return kind_ok(env_kind) ? Algo::dims(env_kind) : SacDims{}; }
+// a population's rows [M] of n floats, `stride` apart, from a and from b: do the two ranges share a float?
+bool sac_rows_overlap(const float* a, const float* b, size_t stride, int M, long long n) {
+  const uintptr_t span = ((uintptr_t)(M - 1) * stride + (uintptr_t)n) * sizeof(float), pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + span && pb < pa + span;
 }
 
 template <class Algo> int sac_param_floats(const char* what, int env_kind, int which) {
@@ -1912,15 +1984,18 @@ template <class Algo> long long sac_workspace_bytes(const char* what, int env_ki
 
 template <class Algo>
 int sac_actor_forward(const char* what, int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, int batch, const float* actor_dev,
-                      const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes) {
+                      const float* eps_dev, float* act_out_dev, float* logp_out_dev, void* workspace_dev, size_t workspace_bytes, const SacPop* pop = nullptr) {
   using Ws = typename Algo::Ws;
   DeviceGuard g;
+  const SacDims d0 = sac_dims_or_zero<Algo>(env_kind);
+  const size_t BA = (size_t)batch * (size_t)d0.A;
   if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes, !obs_dev || !idx_dev || !actor_dev || !eps_dev || !act_out_dev || !logp_out_dev, n_rows,
                                misaligned(obs_dev, 4) || misaligned(actor_dev, 4) || misaligned(eps_dev, 4) || misaligned(act_out_dev, 4) || misaligned(logp_out_dev, 4) ||
                                    misaligned(idx_dev, 8),
-                               "idx not 8-byte aligned", nullptr, device, g))
+                               "idx not 8-byte aligned", nullptr, device, g, pop,
+                               pop && (pop->idx < (size_t)batch || pop->pi < (size_t)d0.pi_p || pop->eps < BA || pop->act < BA || pop->logp < (size_t)batch)))
     return rc;
-  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
+  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev, pop);
   if (int rc = r.gather(obs_dev, nullptr, idx_dev, n_rows, Ws::X0)) return rc;
   return r.actor(actor_dev, eps_dev, Ws::X0, Ws::H1, Ws::H2, Ws::ZH, Ws::XC, Ws::LP, act_out_dev, logp_out_dev);
 }
@@ -1928,16 +2003,22 @@ int sac_actor_forward(const char* what, int env_kind, int device, void* stream, 
 template <class Algo>
 int sac_targets(const char* what, int env_kind, int device, void* stream, const float* next_obs_dev, const float* reward_dev, const float* done_dev, long long n_rows,
                 const int64_t* idx_dev, int batch, const float* actor_dev, const float* target_dev, const float* log_ent_coef_dev, const float* eps_next_dev, float gamma,
-                float* y_dev, void* workspace_dev, size_t workspace_bytes) {
+                float* y_dev, void* workspace_dev, size_t workspace_bytes, const SacPop* pop = nullptr) {
   using Ws = typename Algo::Ws;
   DeviceGuard g;
+  const SacDims d0 = sac_dims_or_zero<Algo>(env_kind);
   if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes,
-                               !next_obs_dev || !reward_dev || !done_dev || !idx_dev || !actor_dev || !target_dev || !log_ent_coef_dev || !eps_next_dev || !y_dev, n_rows,
+                               !next_obs_dev || !reward_dev || !done_dev || !idx_dev || !actor_dev || !target_dev || !log_ent_coef_dev || !eps_next_dev || !y_dev ||
+                                   (pop && !pop->hp),
+                               n_rows,
                                misaligned(next_obs_dev, 4) || misaligned(reward_dev, 4) || misaligned(done_dev, 4) || misaligned(actor_dev, 4) || misaligned(target_dev, 4) ||
-                                   misaligned(log_ent_coef_dev, 4) || misaligned(eps_next_dev, 4) || misaligned(y_dev, 4) || misaligned(idx_dev, 8),
-                               "idx not 8-byte aligned", nullptr, device, g))
+                                   misaligned(log_ent_coef_dev, 4) || misaligned(eps_next_dev, 4) || misaligned(y_dev, 4) || misaligned(idx_dev, 8) ||
+                                   (pop && misaligned(pop->hp, 8)),
+                               pop ? "idx / hp not 8-byte aligned" : "idx not 8-byte aligned", nullptr, device, g, pop,
+                               pop && (pop->idx < (size_t)batch || pop->pi < (size_t)d0.pi_p || pop->q < (size_t)d0.q_p || pop->eps < (size_t)batch * (size_t)d0.A ||
+                                       pop->y < (size_t)batch * (size_t)Algo::Y_W)))
     return rc;
-  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
+  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev, pop);
   if (int rc = r.gather(next_obs_dev, nullptr, idx_dev, n_rows, Ws::NX0)) return rc;
   if (int rc = r.actor(actor_dev, eps_next_dev, Ws::NX0, Ws::NH1, Ws::NH2, Ws::NZH, Ws::NXC, Ws::NAL, nullptr, nullptr)) return rc;  // logp' in NAL
   if (int rc = r.critics(target_dev, Ws::NXC, Ws::T1, Ws::T2, Ws::QT)) return rc;
@@ -1946,55 +2027,68 @@ int sac_targets(const char* what, int env_kind, int device, void* stream, const 
 
 template <class Algo>
 int sac_critic_grad(const char* what, int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev, int batch,
-                    const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+                    const float* critic_dev, const float* y_dev, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes, const SacPop* pop = nullptr) {
   using Ws = typename Algo::Ws;
   DeviceGuard g;
+  const SacDims d0 = sac_dims_or_zero<Algo>(env_kind);
+  const char* aliased = grad_dev == critic_dev ? "grad_dev must not be critic_dev" : nullptr;
+  if (pop && pop->M >= 1 && grad_dev && critic_dev && sac_rows_overlap(grad_dev, critic_dev, pop->q, pop->M, d0.q_p)) aliased = "the rows of grad_dev overlap the rows of critic_dev";
   if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes, !obs_dev || !action_dev || !idx_dev || !critic_dev || !y_dev || !grad_dev || !stats_dev, n_rows,
                                misaligned(obs_dev, 4) || misaligned(action_dev, 4) || misaligned(critic_dev, 4) || misaligned(y_dev, 4) || misaligned(grad_dev, 4) ||
                                    misaligned(idx_dev, 8) || misaligned(stats_dev, 8),
-                               "idx / stats not 8-byte aligned", grad_dev == critic_dev ? "grad_dev must not be critic_dev" : nullptr, device, g))
+                               "idx / stats not 8-byte aligned", aliased, device, g, pop,
+                               pop && (pop->idx < (size_t)batch || pop->q < (size_t)d0.q_p || pop->y < (size_t)batch * (size_t)Algo::Y_W)))
     return rc;
-  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
+  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev, pop);
   const SacDims& d = r.d;
   const long long BH = (long long)batch * SAC_H;
   if (int rc = r.gather(obs_dev, action_dev, idx_dev, n_rows, Ws::XSA)) return rc;
   if (int rc = r.critics(critic_dev, Ws::XSA, Ws::C1, Ws::C2, Ws::Q)) return rc;
   if (int rc = Algo::critic_loss(r, y_dev, stats_dev)) return rc;
   if (int rc = r.template critics_backward<Ws>(critic_dev)) return rc;
-  if (int rc = r.wgrad(r.at(Ws::DQ), r.hw, (long long)batch * r.hw, r.at(Ws::C2), SAC_H, BH, grad_dev + d.q_w2, SAC_H, d.q_one, grad_dev + d.q_b2, SAC_H, r.heads, 2)) return rc;
-  if (int rc = r.wgrad(r.at(Ws::DZ2), SAC_H, BH, r.at(Ws::C1), SAC_H, BH, grad_dev + d.q_w1, SAC_H, d.q_one, grad_dev + d.q_b1, SAC_H, SAC_H, 2)) return rc;
-  return r.wgrad(r.at(Ws::DZ1), SAC_H, BH, r.at(Ws::XSA), SAC_XW, 0, grad_dev + d.q_w0, d.C, d.q_one, grad_dev + d.q_b0, d.C, SAC_H, 2);
+  if (int rc = r.wgrad(r.at(Ws::DQ), r.hw, (long long)batch * r.hw, r.at(Ws::C2), SAC_H, BH, grad_dev + d.q_w2, SAC_H, d.q_one, grad_dev + d.q_b2, SAC_H, r.heads, 2, r.qs)) return rc;
+  if (int rc = r.wgrad(r.at(Ws::DZ2), SAC_H, BH, r.at(Ws::C1), SAC_H, BH, grad_dev + d.q_w1, SAC_H, d.q_one, grad_dev + d.q_b1, SAC_H, SAC_H, 2, r.qs)) return rc;
+  return r.wgrad(r.at(Ws::DZ1), SAC_H, BH, r.at(Ws::XSA), SAC_XW, 0, grad_dev + d.q_w0, d.C, d.q_one, grad_dev + d.q_b0, d.C, SAC_H, 2, r.qs);
 }
 
 template <class Algo>
 int sac_actor_grad(const char* what, int env_kind, int device, void* stream, int batch, const float* actor_dev, const float* critic_dev, const float* log_ent_coef_dev,
-                   const float* eps_dev, float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {
+                   const float* eps_dev, float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes, const SacPop* pop = nullptr) {
   using Ws = typename Algo::Ws;
   DeviceGuard g;
+  const SacDims d0 = sac_dims_or_zero<Algo>(env_kind);
+  const char* aliased = actor_grad_dev == actor_dev ? "actor_grad_dev must not be actor_dev" : nullptr;
+  if (pop && pop->M >= 1 && actor_grad_dev && actor_dev && sac_rows_overlap(actor_grad_dev, actor_dev, pop->pi, pop->M, d0.pi_p))
+    aliased = "the rows of actor_grad_dev overlap the rows of actor_dev";
   if (int rc = sac_check<Algo>(what, env_kind, batch, workspace_dev, workspace_bytes,
                                !actor_dev || !critic_dev || !log_ent_coef_dev || !eps_dev || !actor_grad_dev || !ent_grad_dev || !stats_dev, 1,
                                misaligned(actor_dev, 4) || misaligned(critic_dev, 4) || misaligned(log_ent_coef_dev, 4) || misaligned(eps_dev, 4) || misaligned(actor_grad_dev, 4) ||
                                    misaligned(ent_grad_dev, 4) || misaligned(stats_dev, 8),
-                               "stats not 8-byte aligned", actor_grad_dev == actor_dev ? "actor_grad_dev must not be actor_dev" : nullptr, device, g))
+                               "stats not 8-byte aligned", aliased, device, g, pop,
+                               pop && (pop->pi < (size_t)d0.pi_p || pop->q < (size_t)d0.q_p || pop->eps < (size_t)batch * (size_t)d0.A)))
     return rc;
-  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev);
+  const SacRun r = sac_run<Algo>(env_kind, stream, batch, workspace_dev, pop);
   const SacDims& d = r.d;
   const long long BH = (long long)batch * SAC_H, BX = (long long)batch * SAC_XW;
   // the critics as they are now on (s, a~), the algorithm's statistic of them, and back to their input
   if (int rc = r.critics(critic_dev, Ws::XC, Ws::C1, Ws::C2, Ws::Q)) return rc;
   if (int rc = Algo::actor_loss(r, (const float*)r.at(Ws::Q), (const float*)r.at(Ws::LP), log_ent_coef_dev, -(float)d.A, batch, r.at(Ws::DQ), ent_grad_dev, stats_dev)) return rc;
   if (int rc = r.template critics_backward<Ws>(critic_dev)) return rc;
-  if (int rc = r.backward(r.at(Ws::DZ1), SAC_H, BH, critic_dev + d.q_w0, d.C, d.q_one, 1 << 30, 0, nullptr, 0, 0, r.at(Ws::DX), SAC_XW, BX, d.C, SAC_H, 2)) return rc;
+  if (int rc = r.backward(r.at(Ws::DZ1), SAC_H, BH, critic_dev + d.q_w0, d.C, d.q_one, 1 << 30, 0, nullptr, 0, 0, r.at(Ws::DX), SAC_XW, BX, d.C, SAC_H, 2, r.qs)) return rc;
   // through tanh and logp to the head's outputs, then the actor's own backward pass
-  if (int rc = launch(sac_head_backward_kernel, dim3(sac_blocks((long long)batch * 16, 256)), dim3(256), 0, r.s, (const float*)r.at(Ws::ZH), (const float*)r.at(Ws::XC),
-                      (const float*)r.at(Ws::DX), eps_dev, log_ent_coef_dev, d.O, d.A, batch, r.at(Ws::DHD)))
+  if (int rc = r.rows(sac_head_backward_kernel<>, sac_head_backward_kernel<SacRowMembers>, dim3(sac_blocks((long long)batch * 16, 256)), false, (const float*)r.at(Ws::ZH),
+                      (const float*)r.at(Ws::XC), (const float*)r.at(Ws::DX), eps_dev, log_ent_coef_dev, d.O, d.A, batch, r.at(Ws::DHD)))
     return rc;
   float* gh = actor_grad_dev + d.pi_head;
-  if (int rc = r.wgrad(r.at(Ws::DHD), SAC_XW, d.A, r.at(Ws::H2), SAC_H, 0, gh, SAC_H, d.pi_block, gh + d.A * SAC_H, SAC_H, d.A, 2)) return rc;
-  if (int rc = r.backward(r.at(Ws::DHD), SAC_XW, 0, actor_dev + d.pi_head, SAC_H, 0, d.A, d.A, r.at(Ws::H2), SAC_H, 0, r.at(Ws::DA2), SAC_H, 0, SAC_H, 2 * d.A, 1)) return rc;
-  if (int rc = r.wgrad(r.at(Ws::DA2), SAC_H, 0, r.at(Ws::H1), SAC_H, 0, actor_grad_dev + d.pi_w1, SAC_H, 0, actor_grad_dev + d.pi_b1, SAC_H, SAC_H, 1)) return rc;
-  if (int rc = r.backward(r.at(Ws::DA2), SAC_H, 0, actor_dev + d.pi_w1, SAC_H, 0, 1 << 30, 0, r.at(Ws::H1), SAC_H, 0, r.at(Ws::DA1), SAC_H, 0, SAC_H, SAC_H, 1)) return rc;
-  return r.wgrad(r.at(Ws::DA1), SAC_H, 0, r.at(Ws::X0), SAC_XW, 0, actor_grad_dev + d.pi_w0, d.O, 0, actor_grad_dev + d.pi_b0, d.O, SAC_H, 1);
+  if (int rc = r.wgrad(r.at(Ws::DHD), SAC_XW, d.A, r.at(Ws::H2), SAC_H, 0, gh, SAC_H, d.pi_block, gh + d.A * SAC_H, SAC_H, d.A, 2, r.pis)) return rc;
+  if (int rc = r.backward(r.at(Ws::DHD), SAC_XW, 0, actor_dev + d.pi_head, SAC_H, 0, d.A, d.A, r.at(Ws::H2), SAC_H, 0, r.at(Ws::DA2), SAC_H, 0, SAC_H, 2 * d.A, 1, r.pis)) return rc;
+  if (int rc = r.wgrad(r.at(Ws::DA2), SAC_H, 0, r.at(Ws::H1), SAC_H, 0, actor_grad_dev + d.pi_w1, SAC_H, 0, actor_grad_dev + d.pi_b1, SAC_H, SAC_H, 1, r.pis)) return rc;
+  if (int rc = r.backward(r.at(Ws::DA2), SAC_H, 0, actor_dev + d.pi_w1, SAC_H, 0, 1 << 30, 0, r.at(Ws::H1), SAC_H, 0, r.at(Ws::DA1), SAC_H, 0, SAC_H, SAC_H, 1, r.pis)) return rc;
+  return r.wgrad(r.at(Ws::DA1), SAC_H, 0, r.at(Ws::X0), SAC_XW, 0, actor_grad_dev + d.pi_w0, d.O, 0, actor_grad_dev + d.pi_b0, d.O, SAC_H, 1, r.pis);
+}
+template <class Algo> long long sac_members_workspace_stride_bytes(const char* what, int env_kind, int batch) {
+  if (!kind_ok(env_kind) || batch < 1) return sac_fail(TB_E_INVAL, what, "unknown env kind, or batch < 1");
+  return sac_members_workspace_stride<Algo>(batch);
 }
 }  // namespace
 }  // extern "C++"
@@ -2047,6 +2141,68 @@ int tb_tqc_actor_grad(int env_kind, int device, void* stream, int batch, const f
                                  workspace_bytes);
 }
 
+// ---- the population's entry points: the same bodies with a SacPop
+#define TB_SAC_MEMBERS_ENTRIES(PREFIX, ALGO)                                                                                                                                   \
+  long long PREFIX##members_workspace_stride_bytes(int env_kind, int batch) { return sac_members_workspace_stride_bytes<ALGO>(__func__, env_kind, batch); }                   \
+  int PREFIX##actor_forward_members(int env_kind, int device, void* stream, const float* obs_dev, long long n_rows, const int64_t* idx_dev, size_t idx_stride, int batch,       \
+                                    int n_members, const float* actor_dev, size_t actor_stride_floats, const float* eps_dev, size_t eps_stride_floats, float* act_out_dev,      \
+                                    size_t act_stride_floats, float* logp_out_dev, size_t logp_stride_floats, void* workspace_dev, size_t workspace_bytes) {                    \
+    const SacPop pop = {n_members, idx_stride, actor_stride_floats, 0, eps_stride_floats, act_stride_floats, logp_stride_floats, 0, nullptr};                                   \
+    return sac_actor_forward<ALGO>(__func__, env_kind, device, stream, obs_dev, n_rows, idx_dev, batch, actor_dev, eps_dev, act_out_dev, logp_out_dev, workspace_dev,          \
+                                   workspace_bytes, &pop);                                                                                                                      \
+  }                                                                                                                                                                             \
+  int PREFIX##targets_members(int env_kind, int device, void* stream, const float* next_obs_dev, const float* reward_dev, const float* done_dev, long long n_rows,             \
+                              const int64_t* idx_dev, size_t idx_stride, int batch, int n_members, const float* actor_dev, size_t actor_stride_floats, const float* target_dev, \
+                              size_t critic_stride_floats, const float* log_ent_coef_dev, const float* eps_next_dev, size_t eps_stride_floats, const TbSacMemberHp* hp_dev,     \
+                              float* y_dev, size_t y_stride_floats, void* workspace_dev, size_t workspace_bytes) {                                                              \
+    const SacPop pop = {n_members, idx_stride, actor_stride_floats, critic_stride_floats, eps_stride_floats, 0, 0, y_stride_floats, hp_dev};                                    \
+    return sac_targets<ALGO>(__func__, env_kind, device, stream, next_obs_dev, reward_dev, done_dev, n_rows, idx_dev, batch, actor_dev, target_dev, log_ent_coef_dev,          \
+                             eps_next_dev, 0.0f, y_dev, workspace_dev, workspace_bytes, &pop);                                                                                  \
+  }                                                                                                                                                                             \
+  int PREFIX##critic_grad_members(int env_kind, int device, void* stream, const float* obs_dev, const float* action_dev, long long n_rows, const int64_t* idx_dev,             \
+                                  size_t idx_stride, int batch, int n_members, const float* critic_dev, size_t critic_stride_floats, const float* y_dev,                        \
+                                  size_t y_stride_floats, float* grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {                                    \
+    const SacPop pop = {n_members, idx_stride, 0, critic_stride_floats, 0, 0, 0, y_stride_floats, nullptr};                                                                     \
+    return sac_critic_grad<ALGO>(__func__, env_kind, device, stream, obs_dev, action_dev, n_rows, idx_dev, batch, critic_dev, y_dev, grad_dev, stats_dev, workspace_dev,       \
+                                 workspace_bytes, &pop);                                                                                                                        \
+  }                                                                                                                                                                             \
+  int PREFIX##actor_grad_members(int env_kind, int device, void* stream, int batch, int n_members, const float* actor_dev, size_t actor_stride_floats,                         \
+                                 const float* critic_dev, size_t critic_stride_floats, const float* log_ent_coef_dev, const float* eps_dev, size_t eps_stride_floats,           \
+                                 float* actor_grad_dev, float* ent_grad_dev, double* stats_dev, void* workspace_dev, size_t workspace_bytes) {                                  \
+    const SacPop pop = {n_members, 0, actor_stride_floats, critic_stride_floats, eps_stride_floats, 0, 0, 0, nullptr};                                                          \
+    return sac_actor_grad<ALGO>(__func__, env_kind, device, stream, batch, actor_dev, critic_dev, log_ent_coef_dev, eps_dev, actor_grad_dev, ent_grad_dev, stats_dev,          \
+                                workspace_dev, workspace_bytes, &pop);                                                                                                          \
+  }
+TB_SAC_MEMBERS_ENTRIES(tb_sac_, SacAlgo)
+TB_SAC_MEMBERS_ENTRIES(tb_tqc_, TqcAlgo)
+#undef TB_SAC_MEMBERS_ENTRIES
+
+int tb_sac_adam_members(int device, void* stream, float* params_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, long long n, size_t stride_floats,
+                        int n_members, const TbSacMemberHp* hp_dev, int which_lr, float beta1, float beta2, float eps, long long step, float* target_dev) {
+  const char* who = "tb_sac_adam_members";
+  if (n_members < 1 || n_members > TB_SAC_MAX_MEMBERS) return refusal(TB_E_INVAL, who, ": n_members must be in [1, 32767]");
+  if (!params_dev || !hp_dev) return refusal(TB_E_INVAL, who, ": null argument");
+  const bool polyak_only = !grad_dev && !exp_avg_dev && !exp_avg_sq_dev;
+  if (polyak_only && !target_dev) return refusal(TB_E_INVAL, who, ": null argument (neither a gradient with both moments nor a target)");
+  if (!polyak_only && (!grad_dev || !exp_avg_dev || !exp_avg_sq_dev)) return refusal(TB_E_INVAL, who, ": null argument (the gradient and both moments go together)");
+  if (n < 1) return refusal(TB_E_INVAL, who, ": n must be >= 1");
+  if (!polyak_only && step < 1) return refusal(TB_E_INVAL, who, ": step must be >= 1");
+  if (which_lr != TB_SAC_LR_ACTOR && which_lr != TB_SAC_LR_CRITIC && which_lr != TB_SAC_LR_ENT) return refusal(TB_E_INVAL, who, ": which_lr must be a TB_SAC_LR_* name");
+  if (misaligned(params_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) || misaligned(exp_avg_sq_dev, 4) || misaligned(target_dev, 4) || misaligned(hp_dev, 8))
+    return refusal(TB_E_INVAL, who, ": a float array is not 4-byte aligned, or hp not 8-byte aligned");
+  if (stride_floats < (size_t)n) return refusal(TB_E_INVAL, who, ": stride_floats is shorter than n");
+  if (!polyak_only && sac_rows_overlap(grad_dev, params_dev, stride_floats, n_members, n)) return refusal(TB_E_INVAL, who, ": the rows of grad_dev overlap the rows of params_dev");
+  if (target_dev && sac_rows_overlap(target_dev, params_dev, stride_floats, n_members, n)) return refusal(TB_E_INVAL, who, ": the rows of target_dev overlap the rows of params_dev");
+  DeviceGuard g;
+  if (int rc = learner_device(g, device, who)) return rc;
+  const SacAdamMembers mb = {(long long)stride_floats, hp_dev, which_lr};
+  const dim3 grid(sac_blocks(n, 256), (unsigned)n_members);
+  if (polyak_only) return launch(sac_polyak_kernel<SacAdamMembers>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)params_dev, target_dev, n, 0.0f, 0.0f, mb);
+  const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
+  return launch(sac_adam_kernel<SacAdamMembers>, grid, dim3(256), 0, (hipStream_t)stream, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n, 0.0f, beta1, beta2, eps, c1,
+                c2, target_dev, 0.0f, 0.0f, mb);
+}
+
 int tb_sac_adam(int device, void* stream, float* params_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, long long n, float lr, float beta1, float beta2,
                 float eps, long long step, float* target_dev, float tau) {
   if (!params_dev) return fail(TB_E_INVAL, "tb_sac_adam: null argument (params)");
@@ -2063,9 +2219,9 @@ int tb_sac_adam(int device, void* stream, float* params_dev, const float* grad_d
   hipStream_t s = (hipStream_t)stream;
   const float omt = (float)(1.0 - (double)tau);
   const dim3 grid(sac_blocks(n, 256));
-  if (polyak_only) return launch(sac_polyak_kernel, grid, dim3(256), 0, s, (const float*)params_dev, target_dev, n, omt, tau);
+  if (polyak_only) return launch(sac_polyak_kernel<>, grid, dim3(256), 0, s, (const float*)params_dev, target_dev, n, omt, tau);
   const float c1 = (float)(1.0 - pow((double)beta1, (double)step)), c2 = (float)(1.0 - pow((double)beta2, (double)step));
-  return launch(sac_adam_kernel, grid, dim3(256), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, c1, c2, target_dev, omt, tau);
+  return launch(sac_adam_kernel<>, grid, dim3(256), 0, s, params_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, c1, c2, target_dev, omt, tau);
 }
 
 int tb_rollout(TbHandle* h, int n_steps, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,

@@ -39,8 +39,11 @@ static_assert(TqcWs::RL % 2 == 0, "the row sums are 8-byte aligned");
 // l / 25; its rank is the number of lanes that precede it in the total order (is-NaN, value, lane), so equal values take
 // consecutive slots and a NaN sorts last, as torch.sort does. The other lanes' values come from v_readlane, lane by lane.
 // y[b][rank] = r + gamma (z - alpha logp') for rank < 46; a terminal row is selected, not multiplied: y = r bit for bit.
+template <class... MEMBERS>
 __global__ __launch_bounds__(256) void tqc_target_kernel(const float* reward, const float* done, const long long* idx, long long n_rows, int B, const float* qt,
-                                                         const float* logp_next, const float* log_ent_coef, float gamma, float* y) {
+                                                         const float* logp_next, const float* log_ent_coef, float gamma, float* y, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers (tb_sac.hpp, THE MEMBER AXIS)");
+  if constexpr (sizeof...(MEMBERS) != 0) sac_member_target((members, ...), blockIdx.y, idx, qt, logp_next, log_ent_coef, gamma, y);
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const bool live = lane < TQC_N;
@@ -67,7 +70,14 @@ __global__ __launch_bounds__(256) void tqc_target_kernel(const float* reward, co
 //   dq[n][b][i] = -(1 / (B 2300)) sum_j |tau_i - [delta < 0]| clamp(delta, -1, 1)
 // Lanes 50 .. 63 write the zeros of columns 25 .. 31 of both nets' rows. row_loss[b] = the row's 2300 terms: float64, the
 // lane's sum in j order, then the wave's xor tree.
-__global__ __launch_bounds__(256) void tqc_critic_loss_kernel(const float* q, const float* y, int B, float* dq, double* row_loss) {
+template <class... MEMBERS>
+__global__ __launch_bounds__(256) void tqc_critic_loss_kernel(const float* q, const float* y, int B, float* dq, double* row_loss, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {  // (row_loss lies in the member's workspace region, whose stride is a multiple of 8 bytes)
+    const SacRowMembers mb = (members, ...);
+    const long long m = blockIdx.y;
+    q += m * mb.ws; dq += m * mb.ws; row_loss += m * (mb.ws / 2); y += m * mb.y;
+  }
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const bool live = lane < TQC_N;
@@ -92,7 +102,13 @@ __global__ __launch_bounds__(256) void tqc_critic_loss_kernel(const float* q, co
 }
 
 // stats[0] = the mean of the B 2300 loss terms from the rows' sums. One workgroup.
-__global__ __launch_bounds__(256) void tqc_loss_sum_kernel(const double* row_loss, int B, double* stats) {
+template <class... MEMBERS>
+__global__ __launch_bounds__(256) void tqc_loss_sum_kernel(const double* row_loss, int B, double* stats, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) {  // one workgroup per member
+    const SacRowMembers mb = (members, ...);
+    row_loss += blockIdx.x * (mb.ws / 2); stats += 4 * blockIdx.x;
+  }
   __shared__ double s[256];
   double v = 0.0;
   for (int b = threadIdx.x; b < B; b += 256) v += row_loss[b];
@@ -103,8 +119,11 @@ __global__ __launch_bounds__(256) void tqc_loss_sum_kernel(const double* row_los
 // the actor loss mean_b(alpha logp - Qbar(s, a~)), Qbar the mean over a row's 50 head outputs (qf0's 25 in index order, then
 // qf1's): dq = -1 / (50 B) in the 25 live columns of both nets' rows, 0 in the padding; stats[1] = the loss, stats[2] = mean
 // logp, stats[3] = the gradient of log_ent_coef, -mean(logp + target_entropy), also written as float32 to ent_grad. One workgroup.
+template <class... MEMBERS>
 __global__ __launch_bounds__(256) void tqc_actor_loss_kernel(const float* q, const float* lp, const float* log_ent_coef, float target_entropy, int B, float* dq,
-                                                             float* ent_grad, double* stats) {
+                                                             float* ent_grad, double* stats, MEMBERS... members) {
+  static_assert(sizeof...(MEMBERS) <= 1, "no argument, or one SacRowMembers");
+  if constexpr (sizeof...(MEMBERS) != 0) sac_member_actor_loss((members, ...), blockIdx.x, q, lp, log_ent_coef, dq, ent_grad, stats);  // one workgroup per member
   __shared__ double s[256];
   const float alpha = expf(log_ent_coef[0]), each = -1.0f / ((float)TQC_N * (float)B);
   double sl = 0.0, sp = 0.0, se = 0.0;

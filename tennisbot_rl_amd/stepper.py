@@ -185,6 +185,18 @@ def load_library():
     for sac, tqc in ((L.tb_sac_actor_forward, L.tb_tqc_actor_forward), (L.tb_sac_targets, L.tb_tqc_targets), (L.tb_sac_critic_grad, L.tb_tqc_critic_grad),
                      (L.tb_sac_actor_grad, L.tb_tqc_actor_grad)):   # the same signatures
         tqc.argtypes, tqc.restype = sac.argtypes, i32
+    sz = ctypes.c_size_t
+    members = {"members_workspace_stride_bytes": ([i32, i32], i64),
+               "actor_forward_members": ([i32, i32, vp, vp, i64, vp, sz, i32, i32, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz], i32),
+               "targets_members": ([i32, i32, vp, vp, vp, vp, i64, vp, sz, i32, i32, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz], i32),
+               "critic_grad_members": ([i32, i32, vp, vp, vp, i64, vp, sz, i32, i32, vp, sz, vp, sz, vp, vp, vp, sz], i32),
+               "actor_grad_members": ([i32, i32, vp, i32, i32, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, sz], i32)}
+    for prefix in ("tb_sac_", "tb_tqc_"):   # the same signatures
+        for name, (argtypes, restype) in members.items():
+            f = getattr(L, prefix + name)
+            f.argtypes, f.restype = argtypes, restype
+    L.tb_sac_adam_members.argtypes = [i32, vp, vp, vp, vp, vp, i64, sz, i32, vp, i32, f32, f32, f32, i64, vp]
+    L.tb_sac_adam_members.restype = i32
     L.tb_render.argtypes = [i32, i32, vp, ctypes.POINTER(TbParams), vp, i32, vp, i32, ctypes.POINTER(TbCamera), i32, i32, vp, vp, vp]
     L.tb_render.restype = i32
     L.tb_swing_trace.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]

@@ -10,6 +10,14 @@ buffer_size 1e6, learning_starts 100). One vector step collects --num-envs trans
 (default: one per transition, the reference's update-to-data ratio); with --collect-form fused it is --collect-steps env steps in
 one launch and --gradient-steps gradient steps per env step. Checkpoints hold the learner, the replay ring AND the env
 batch state. One rank only. TQC (train_swing.py only) is train_tqc.py.
+
+  python train_sac.py --population 16 --num-envs 256 --member-lr 1e-4,3e-4,...   # 16 learners side by side, one set of launches
+
+--population M trains M learners on one GPU (tennisbot_rl_amd/sac_population.py): --num-envs stays the total, --total-timesteps
+and --learning-starts count each member's own timesteps, --gradient-steps defaults to the envs per member; --member-lr /
+--member-gamma / --member-tau give per-member values, --pbt-every K exploits and explores every K vector steps. It writes the
+population checkpoint to --save and the best member, in the trainer's own format, to best_model.pt beside it, at the end and
+every --save-freq of a member's timesteps (the same two files each time, not rl_model_<timesteps>_steps.pt).
 """
 import argparse
 import json
@@ -47,6 +55,8 @@ def off_policy_parser(description, algo, batch_help, total_default, total_help):
     ap.add_argument("--collect-form", choices=["torch", "fused"], default="torch", help="how transitions are collected: `torch` runs the torch actor between "
                     "single env steps; `fused` runs --collect-steps env steps in one launch with the actor inside, straight into the replay ring (tb_sac_collect)")
     ap.add_argument("--collect-steps", type=int, default=1, help="env steps per vector step with --collect-form fused (--gradient-steps stays per env step)")
+    from tennisbot_rl_amd.sac_population import add_population_arguments
+    add_population_arguments(ap)
     return ap
 
 
@@ -64,6 +74,14 @@ def off_policy_main(argv, script, algo, trainer, description, batch_help, total_
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("%s runs on one rank: multi-rank %s is not provided" % (script, algo))
 
+    from tennisbot_rl_amd.sac_population import population_keywords
+    try:
+        population = population_keywords(args)
+    except ValueError as e:
+        sys.exit("%s: %s" % (script, e))
+    if population is not None and (args.curri or args.eval_freq or args.collect_form != "torch" or args.collect_steps != 1 or args.load == "best"):
+        sys.exit("%s: --population takes no --curri, --eval-freq, --collect-form fused, --collect-steps or --load best (not provided for a population)" % script)
+
     import torch
 
     total = args.total_timesteps or total_by_env.get(args.env, 0)
@@ -71,8 +89,18 @@ def off_policy_main(argv, script, algo, trainer, description, batch_help, total_
     if args.racket_ground or args.rolling_friction:
         from tennisbot_rl_amd.params import F_DEFAULT, F_RACKET_GROUND, default_params, reference_rolling_friction
         params = default_params(flags=F_DEFAULT | (F_RACKET_GROUND if args.racket_ground else 0), **(reference_rolling_friction() if args.rolling_friction else {}))
-    tr = trainer()(args.env, params=params, device=torch.device("cuda", 0), **trainer_arguments(args))
     path = args.save or "./model/%s_%s.pt" % (algo.lower(), args.env)
+    if population is not None:
+        from tennisbot_rl_amd.sac_population import PopulationSAC, run_population
+        pop = PopulationSAC(args.env, algo=algo.lower(), batch_size=args.batch_size, gradient_steps=args.gradient_steps, buffer_size=args.buffer_size,
+                            learning_starts=args.learning_starts, seed=args.seed, params=params, device=torch.device("cuda", 0), **population)
+        if args.load:
+            pop.load(args.load)
+        history = run_population(pop, total, path, save_freq=int(args.save_freq))   # --save-freq: in a member's own timesteps, like --total-timesteps
+        if args.log_json:
+            json.dump(history, open(args.log_json, "w"))
+        return
+    tr = trainer()(args.env, params=params, device=torch.device("cuda", 0), **trainer_arguments(args))
     if args.load:
         tr.load(resolve_load(args.load, path))
     schedule = schedule_from_args(args, path)

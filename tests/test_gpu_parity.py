@@ -159,7 +159,9 @@ def test_contact_off_bench_mode(torch, n):
 def test_forced_contacts_exercise_the_solver(torch):
     """random policies rarely hit the ball; inject states where every lane is in contact
     (racket face, rim, ground, net, goal) so that the narrowphase sweep + impulse solver
-    are compared lane by lane"""
+    are compared lane by lane. Of the static shapes it covers the interior of the ground's top face, the net's two x faces and the
+    goal's top cap -- axis-aligned normals, one static row per lane, unpipelined tb_step; edges, corners, interiors, the goal's wall
+    and rim, several static rows in one solve and the other kernels are tests/test_gpu_static_contacts.py's."""
     n = 512
     rng = np.random.default_rng(21)
     p = default_params()

@@ -234,7 +234,9 @@ def test_fuzzed_states_around_the_racket_stay_bit_exact(torch, kind, rg, roll):
     one substep: Tennisbot's rackets hardly reach the court in those 4 steps (on the oracle, under random actions, none or one of
     the 2048 envs caches a racket<->court point), so for Tennisbot this case pins the RG instantiation in flight
     and on the ball. Racket, ball and court in one solve are test_gpu_tennis_extended_loops.py's: the same
-    builder with low_rackets, what it reaches pinned in test_tennis_contact_states.py."""
+    builder with low_rackets, what it reaches pinned in test_tennis_contact_states.py. The narrowphase region by region, with
+    exact ties and controlled numbers of asking lanes per wave: racket_contact_fixtures.py,
+    test_racket_contact_states.py and test_gpu_racket_contacts.py."""
     n = 2048 if rg else 16384
     rng = np.random.default_rng(97 + kind + 10 * rg + 100 * roll)
     over = reference_rolling_friction() if roll else {}

@@ -100,7 +100,11 @@ def torch():
 
 
 def params_of(variant):
-    """"default", "altered" (h: other restitution and friction on court and goal), "extended" (g: racket<->court contact + rolling rows)"""
+    """"default", "altered" (h: other restitution and friction on court and goal), "extended" (g: racket<->court contact + rolling rows),
+    or a TbParams of the caller's own (tests/test_gpu_racket_contacts.py: other outlines; for make_env, make_oracle and replay only --
+    yardstick() caches by the variant's name and takes the three names alone)"""
+    if not isinstance(variant, str):
+        return variant.copy()
     if variant == "extended":
         return default_params(flags=F_DEFAULT | F_RACKET_GROUND, **reference_rolling_friction())
     return cs.altered(default_params()) if variant == "altered" else default_params()
